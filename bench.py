@@ -10,8 +10,15 @@ Workload (BASELINE.json metric "queries/sec + p50 latency, top-10 over 10M x 768
 row-sharded over the N ranks; one STEP = one batch of 256 queries answered with their exact
 top-10 (shard-local search, one RCCL all_gather of the packed partials, integer merge).
 `value` = whole-job queries/s with queries and corpus already in HBM; results stay in HBM.
-The p50 single-query (B=1) latency, host wall clock including the D2H of the 10 results, is
-reported next to it.  Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.
+
+A plain run only sets up, warms up, times the K steps and prints the line.  --full adds what
+the headline figure does not need: the correctness gate (planted neighbours, filtered search
+bit-equal to the exact scan), the p50 single-query (B=1) latency (host wall clock including the
+D2H of the 10 results), the drop-in call's latency, the CPU comparators and, with more than one
+batch in flight, K more steps on one stream for the per-kernel figures.
+--dump-outputs DIR writes the last timed step's answer (distances.npy fp32, rows.npy fp64 [B,k]);
+the inputs are seeded, so the same arguments give the same arrays on every run.
 """
 
 from __future__ import annotations
@@ -46,8 +53,8 @@ def parse_args():
     p.add_argument("--cpu-sample-queries", type=int, default=256)
     p.add_argument("--cpu-seconds", type=float, default=10.0)
     p.add_argument("--hnsw-build-seconds", type=float, default=12.0, help="target build time of the HNSW comparator's sample")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--validate-before", action="store_true", help="run the correctness gate (64 exact scans) in front of the warm-up instead of behind the timed steps")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU comparators")
+    p.add_argument("--validate-before", action="store_true", help="--full: run the correctness gate (64 exact scans) in front of the warm-up instead of behind the timed steps")
     p.add_argument("--set", action="append", default=[], metavar="KEY=VALUE",
                    help="engine option for A/B runs (codd_knn_set_option), e.g. --set i8v2=2; recorded in the line")
     p.add_argument("--corpus", default="isotropic", choices=["isotropic", "clustered"],
@@ -59,6 +66,11 @@ def parse_args():
                    help="batches in flight on alternating HIP streams in the timed loop (0 = 1 on one GPU, 2 when sharded)")
     p.add_argument("--force-dist", action="store_true",
                    help="initialise RCCL and take the sharded code path even with one rank (rehearsal on a 1-GPU box)")
+    p.add_argument("--full", action="store_true",
+                   help="also run the correctness gate, the B=1 and drop-in latencies, the CPU comparators and (batches in flight > 1) "
+                        "the per-kernel event pass; a plain run times the steps only")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's results to DIR/distances.npy (fp32) and DIR/rows.npy (fp64), [batch, k] each")
     return p.parse_args()
 
 
@@ -319,6 +331,17 @@ def measured_traffic(kernel, dtype, dim, n_local):
     return None, None
 
 
+def dump_outputs(path, out):
+    """What a caller of the timed path receives for the last timed batch: distances fp32 [B,k] ascending and global row ids
+    [B,k] (-1 padded), the ids widened to fp64, which holds every row index exactly."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    dist, rows = out
+    np.save(os.path.join(path, "distances.npy"), dist.float().cpu().numpy())
+    np.save(os.path.join(path, "rows.npy"), rows.cpu().numpy().astype(np.float64))
+
+
 def main():
     args = parse_args()
     # stdout carries exactly ONE JSON line: library banners (RCCL prints its version to stdout) go to stderr
@@ -387,7 +410,7 @@ def main():
             torch.distributed.barrier()
         torch.cuda.synchronize()
 
-    # correctness gate inside the bench, outside the timed region: (a) the planted neighbours must come back, in order;
+    # correctness gate inside the bench (--full), outside the timed region: (a) the planted neighbours must come back, in order;
     # (b) on one GPU, ALL B queries of two batches must equal the exact scan of the same index (filter switched off) bit
     # for bit — ids and distances: a filter that drops true neighbours of ordinary queries cannot pass.
     # It runs AFTER the timed region (since round 3): its 64 exact scans stream 2 TB from HBM at full clock, and K steps
@@ -410,7 +433,7 @@ def main():
 
     validated_queries = 2 * B
     valid = None
-    if args.validate_before:
+    if args.full and args.validate_before:
         valid = validate()
     step(queries)  # (the first search of an index derives the int8 shadow from the rows: ingest work, not a step)
     barrier()
@@ -441,20 +464,21 @@ def main():
             return PendingSearch(side, out)
 
     apipe = searcher if searcher is not None else (_LocalAsync(depth) if depth > 1 else None)
+    out = None  # the last timed step's (dist, rows)
     if depth == 1:
         # one stream: the HIP events around every heavy launch are taken inside the timed region itself
         ix.set_option("profile", args.steps * launches_per_step + 8)
         barrier()
         t0 = time.perf_counter()
         for i in range(args.steps):
-            step(batches[i % n_batches])
+            out = step(batches[i % n_batches])
         barrier()
         elapsed = time.perf_counter() - t0
     else:
         # sharded: consecutive batches alternate between `depth` streams, so the small kernels, the all_gather and
         # the merge of batch i overlap the filter kernel of batch i+1.  Every one of the K batches is complete when
         # the closing barrier returns.  Event pairs on concurrent streams would also time the wait for the other
-        # stream's kernel, so the per-kernel durations come from K more steps on ONE stream right after.
+        # stream's kernel, so the per-kernel durations come from K more steps on ONE stream right after (--full).
         for _ in range(depth):
             apipe.search_async(queries, k, depth).result()
         barrier()
@@ -465,13 +489,16 @@ def main():
             if len(pending) >= depth:
                 pending.pop(0).result()
         for h in pending:
-            h.result()
+            out = h.result()
         barrier()
         elapsed = time.perf_counter() - t0
-        ix.set_option("profile", args.steps * launches_per_step + 8)
-        for i in range(args.steps):
-            step(batches[i % n_batches])
-        barrier()
+        if args.full:
+            ix.set_option("profile", args.steps * launches_per_step + 8)
+            for i in range(args.steps):
+                step(batches[i % n_batches])
+            barrier()
+    if args.dump_outputs and rank == 0 and out is not None:
+        dump_outputs(args.dump_outputs, out)
     kernels = {}
     for name in ("scan", "filter", "sample", "finalize"):
         ev = ix.stat(f"events:{name}")
@@ -481,7 +508,7 @@ def main():
     ix_shadow8_passes = ix.stat("shadow8_passes")
     ix_tile_passes = ix.stat("i8v2_passes")
     filter_stats = {key: ix.stat(key) for key in ("filter_passes", "fallback_queries", "filter_hits", "filter_survivors")}
-    if valid is None:
+    if args.full and valid is None:
         valid = validate()
 
     if use_dist:
@@ -492,7 +519,7 @@ def main():
     # p50 latency of a single query (B=1), host wall clock incl. D2H of the k results
     lat = []
     q1 = queries[:1].contiguous()
-    for i in range(args.latency_iters + 3):
+    for i in range(args.latency_iters + 3 if args.full else 0):
         barrier()
         t1 = time.perf_counter()
         dd, rr = step(q1)
@@ -503,7 +530,7 @@ def main():
     p50_ms = statistics.median(lat) if lat else None
 
     dropin = None
-    if world == 1 and not use_dist:
+    if args.full and world == 1 and not use_dist:
         try:
             dropin = dropin_call(ix, args, torch)
         except Exception as e:  # noqa: BLE001  (never takes the headline number down with it)
@@ -549,17 +576,20 @@ def main():
             **({"engine_options": args.set} if args.set else {}),
         },
         **({"rehearsal": "all ranks on cuda:0, gloo collective: code-path check, not a measurement"} if rehearsal else {}),
-        "p50_latency_ms_batch1": p50_ms,
-        "dropin_call": dropin,
-        "results_valid": valid,
-        # a SELF-comparison: filtered search vs the exact scan of the same engine (the exact scan itself is what the GPU test suite
-        # checks against the CPU oracle, tests/test_gpu_parity.py) — not an oracle check inside the bench
-        "results_validated": f"{validated_queries} queries (all queries of two batches: ids and distances of the filtered search bit-equal to the EXACT SCAN OF THE SAME "
-                             + ("INDEX" if searcher is None else "SHARDS, merged the same way") + " — a self-comparison: the exact scan itself is oracle-checked in the -m gpu suite, "
-                             "not in this run; planted neighbours in order)",
+        **({
+            "p50_latency_ms_batch1": p50_ms,
+            "dropin_call": dropin,
+            "results_valid": valid,
+            # a SELF-comparison: filtered search vs the exact scan of the same engine (the exact scan itself is what the GPU test suite
+            # checks against the CPU oracle, tests/test_gpu_parity.py) — not an oracle check inside the bench
+            "results_validated": f"{validated_queries} queries (all queries of two batches: ids and distances of the filtered search bit-equal to the EXACT SCAN OF THE SAME "
+                                 + ("INDEX" if searcher is None else "SHARDS, merged the same way") + " — a self-comparison: the exact scan itself is oracle-checked in the -m gpu suite, "
+                                 "not in this run; planted neighbours in order)",
+        } if args.full else {}),
         "query_batches": n_batches,
         "index_build_s": t_build,
-        "roofline": {
+        # null when no per-kernel events were taken (batches in flight > 1 without --full)
+        "roofline": None if dom is None else {
             "bound": "hbm",
             "kernel": KERNEL_NAMES.get(dom) + (" (int8 shadow)" if int8_batch else ""),
             "achieved": achieved,
@@ -595,7 +625,7 @@ def main():
         },
         "filter_stats": filter_stats,
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             line["cpu_baseline"] = cpu_baseline(ix, args, queries.cpu().numpy())
         except Exception as e:  # the baseline must never take the GPU number down with it
@@ -607,7 +637,7 @@ def main():
     if use_dist:
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()
-    if not valid:
+    if args.full and not valid:
         sys.exit(3)
 
 

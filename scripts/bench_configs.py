@@ -21,7 +21,7 @@ RUNS = [
 ]
 
 for name, extra in RUNS:
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--warmup", "3", *extra], capture_output=True, text=True, timeout=600)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--warmup", "3", *extra], capture_output=True, text=True, timeout=600)
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     if p.returncode != 0 or not lines:
         print(json.dumps({"run": name, "failed": p.stderr[-500:]}), flush=True)

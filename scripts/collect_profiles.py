@@ -43,7 +43,7 @@ def main():
     W, K = int(line["warmup"]), int(line["steps"])
     timed = durs[1 + W:1 + W + K]
     paired = {
-        "_what": "python3 bench.py --no-cpu-baseline under `rocprofv3 --kernel-trace --stats` (scripts/profile_round.sh): the bench line and, in "
+        "_what": "python3 bench.py --full --no-cpu-baseline under `rocprofv3 --kernel-trace --stats` (scripts/profile_round.sh): the bench line and, in "
                  f"profiles/{a.round}/final_kernel_stats.csv, the per-kernel durations of the SAME run.  {kname}: {f0['Calls']} calls, average "
                  f"{float(f0['AverageNs']):,.0f} ns in the trace (warm-up, priming and validation launches included) vs roofline.avg_launch_ms below "
                  "(HIP events inside bench.py over the timed steps).  rocprof_timed_launches: the same K launches picked out of the kernel trace by position "
@@ -81,7 +81,7 @@ def main():
             if traffic is None or v["FETCH_SIZE"] > traffic[1]:
                 traffic = (k, v["FETCH_SIZE"])
     with open(os.path.join(out, "i8_tile_pmc.txt"), "w") as f:
-        f.write("# rocprofv3 --pmc <counters> --kernel-trace -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --latency-iters 3   (scripts/pmc_round.sh; three separate\n"
+        f.write("# rocprofv3 --pmc <counters> --kernel-trace -- python3 bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --latency-iters 3   (scripts/pmc_round.sh; three separate\n"
                 "# passes: SQ set 1 | SQ set 2 | GRBM_GUI_ACTIVE + FETCH_SIZE).  10M x 768 fp32 corpus, B = 256 steps (+ B = 1 latency calls); means per launch.\n")
         f.write("\n".join(keep) + "\n# derived:\n" + "\n".join(notes) + "\n")
     if traffic:

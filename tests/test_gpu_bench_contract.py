@@ -1,5 +1,5 @@
 """bench.py's contract with the driver, on a small corpus: exactly ONE JSON line on stdout, the keys the driver and the
-judge read, a valid planted-neighbour check, the roofline and cpu_baseline objects."""
+judge read; with --full a valid planted-neighbour check, the roofline and cpu_baseline objects; --dump-outputs."""
 
 import json
 import os
@@ -23,7 +23,7 @@ def run_bench(*extra):
 
 
 def test_single_gpu_line():
-    line = run_bench()
+    line = run_bench("--full")
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
                 "config", "roofline", "cpu_baseline"):
         assert key in line, key
@@ -37,8 +37,33 @@ def test_single_gpu_line():
     assert c["kind"] == "port" and c["cores"] >= 1 and c["value"] > 0 and "sample" in c
 
 
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run times the steps and nothing else; --dump-outputs writes the last timed step's answer.  With 17 steps the
+    last one searches batch 0 again (16 query batches), whose first 4 queries have planted neighbours at known rows.  The
+    inputs are seeded, so a second run with the same arguments dumps the same arrays."""
+    import numpy as np
+
+    from bench import planted_row
+
+    n = 300000
+    line = run_bench("--steps", "17", "--dump-outputs", str(tmp_path / "a"))
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "config"):
+        assert key in line, key
+    for key in ("cpu_baseline", "results_valid", "p50_latency_ms_batch1", "dropin_call"):
+        assert key not in line, key
+    assert line["steps"] == 17 and line["query_batches"] == 16 and line["value"] > 0
+    assert abs(line["ms_per_step"] * line["value"] - 256e3) < 1e-6 * 256e3  # B queries per step
+    dist, rows = np.load(tmp_path / "a" / "distances.npy"), np.load(tmp_path / "a" / "rows.npy")
+    assert dist.dtype == np.float32 and rows.dtype == np.float64 and dist.shape == rows.shape == (256, 10)
+    assert np.all(np.diff(dist, axis=1) >= 0) and np.all((rows >= 0) & (rows < n))
+    assert np.array_equal(rows[:4], [[planted_row(b, j, n) for j in range(10)] for b in range(4)])
+    run_bench("--steps", "17", "--dump-outputs", str(tmp_path / "b"))
+    assert np.array_equal(np.load(tmp_path / "b" / "distances.npy"), dist)
+    assert np.array_equal(np.load(tmp_path / "b" / "rows.npy"), rows)
+
+
 def test_sharded_code_path_line():
-    line = run_bench("--force-dist", "--no-cpu-baseline", "--rows", "400000")
+    line = run_bench("--full", "--force-dist", "--no-cpu-baseline", "--rows", "400000")
     assert line["results_valid"] is True and line["config"]["batches_in_flight"] == 2
     assert line["roofline"]["events_from"].startswith("the same K steps")
 
@@ -59,7 +84,7 @@ def test_driver_command_shape_under_torch_distributed_run():
         env.pop(key, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port", str(port),
            os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--rows", "400000", "--steps", "4", "--warmup", "1", "--latency-iters", "3",
-           "--no-cpu-baseline"]
+           "--full", "--no-cpu-baseline"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.strip().startswith("{")]
