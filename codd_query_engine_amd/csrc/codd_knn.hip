@@ -201,7 +201,51 @@ __device__ __forceinline__ void scan_topk_body(const void* __restrict__ rows_, i
     for (int g0 = 0; g0 < total; g0 += NB) {
     const int nq = total - g0 < NB ? total - g0 : NB;
 
-    float qf[NB][NITER][E];
+    WaveTopK<SLOTS> L[NB];
+    if constexpr (NITER == kWideRows) {
+        // wide rows: the group's queries in LDS (where the block merge keeps its lists: the previous group is done with them),
+        // every row group walked segment by segment (wide_segment)
+        float* qs = reinterpret_cast<float*>(lds);
+        const int qstride = wide_qfloats(nchunks, E);
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+            const float* src = b < nq ? qn + (qlist ? (int64_t)qlist[g0 + b] : (int64_t)(g0 + b)) * dpad : nullptr;
+            wide_stage_query(qs + b * qstride, src, dpad, qstride, (int)threadIdx.x, NW * kWave);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int b = 0; b < NB; ++b) L[b].init();
+        const uint4* base = reinterpret_cast<const uint4*>(rows_);
+        const int64_t ngroups = (n + 3) >> 2;
+        const int64_t W = (int64_t)nblocks * NW;
+        const int nseg = wide_nseg(nchunks);
+        for (int64_t g = (int64_t)bid * NW + wave; g < ngroups; g += W) {
+            const uint4* p[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int64_t row = g * 4 + r < n ? g * 4 + r : n - 1;
+                p[r] = base + row * (int64_t)nchunks + lane;
+            }
+            float acc[NB][4];
+#pragma unroll
+            for (int b = 0; b < NB; ++b)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) acc[b][r] = 0.0f;
+            for (int s = 0; s < nseg; ++s) wide_segment<DT, NB, 4>(p, s, nchunks, lane, qs, qstride, acc);
+#pragma unroll
+            for (int b = 0; b < NB; ++b) {
+                const float y = butterfly_sum4(acc[b][0], acc[b][1], acc[b][2], acc[b][3], lane);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float s = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(y), 16 * r));
+                    const int64_t row = g * 4 + r;
+                    if (row < n) L[b].offer(make_key(s, row_base + (uint32_t)row), k, lane);
+                }
+            }
+        }
+        __syncthreads();  // every wave is done with the queries: the lists take their place
+    } else {
+    float qf[NB][NITER > 0 ? NITER : 1][E];
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
         const int64_t qi = b < nq ? (qlist ? (int64_t)qlist[g0 + b] : (int64_t)(g0 + b)) : 0;
@@ -214,7 +258,6 @@ __device__ __forceinline__ void scan_topk_body(const void* __restrict__ rows_, i
         }
     }
 
-    WaveTopK<SLOTS> L[NB];
 #pragma unroll
     for (int b = 0; b < NB; ++b) L[b].init();
 
@@ -222,7 +265,7 @@ __device__ __forceinline__ void scan_topk_body(const void* __restrict__ rows_, i
     const int64_t ngroups = (n + 3) >> 2;
     const int64_t W = (int64_t)nblocks * NW;
     for (int64_t g = (int64_t)bid * NW + wave; g < ngroups; g += W) {
-        float w[4][NITER][E];
+        float w[4][NITER > 0 ? NITER : 1][E];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             int64_t row = g * 4 + r;
@@ -256,6 +299,7 @@ __device__ __forceinline__ void scan_topk_body(const void* __restrict__ rows_, i
             }
         }
     }
+    }  // (NITER)
 
     // block merge through LDS: [wave][b][slot][lane]
 #pragma unroll
@@ -334,6 +378,24 @@ __global__ __launch_bounds__(256) void scan_topk_kernel(const void* __restrict__
     const int total = qcount_ptr ? (int)*qcount_ptr : nq_arg;
     scan_topk_body<DT, NB, NITER, SLOTS, 4>(rows_, n, dpad, qn, total, k, row_base, partial, partial_stride_q, qlist, qcount_ptr != nullptr, merge_done, merged_keys,
                                             merged_dist, merged_rows, count_total, (int)blockIdx.x, (int)gridDim.x, reinterpret_cast<u64*>(smem_raw));
+}
+
+// scan_topk_kernel's wide form (more than 4 chunks per lane): the NB queries' full rows are staged in LDS, up to 128 KiB, so ONE
+// workgroup of 8 waves per compute unit shares them (2 waves per SIMD, 8 row groups per LDS copy of the queries)
+constexpr int kWideScanWaves = 8;
+template <int DT, int NB, int SLOTS>
+__global__ __launch_bounds__(kWideScanWaves * kWave) void scan_topk_wide_kernel(const void* __restrict__ rows_, int64_t n, int dpad,
+                                                                                const float* __restrict__ qn, int nq_arg, int k,
+                                                                                uint32_t row_base, u64* __restrict__ partial,
+                                                                                int64_t partial_stride_q, const unsigned* __restrict__ qlist,
+                                                                                const unsigned* __restrict__ qcount_ptr, unsigned* __restrict__ merge_done,
+                                                                                u64* __restrict__ merged_keys, float* __restrict__ merged_dist,
+                                                                                int64_t* __restrict__ merged_rows, unsigned long long* __restrict__ count_total) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    const int total = qcount_ptr ? (int)*qcount_ptr : nq_arg;
+    scan_topk_body<DT, NB, kWideRows, SLOTS, kWideScanWaves>(rows_, n, dpad, qn, total, k, row_base, partial, partial_stride_q, qlist, qcount_ptr != nullptr,
+                                                             merge_done, merged_keys, merged_dist, merged_rows, count_total, (int)blockIdx.x, (int)gridDim.x,
+                                                             reinterpret_cast<u64*>(smem_raw));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -546,19 +608,32 @@ __global__ __launch_bounds__(256) void shadow8_from_rows_kernel(const void* __re
     __syncthreads();
     vmax = fmaxf(fmaxf(s_max[0], s_max[1]), fmaxf(s_max[2], s_max[3]));
     const float scale = vmax > 0.0f ? vmax / 127.0f : 1.0f, inv_scale = 1.0f / scale;
-    // pass 2: quantise (the rows come from L2 this time), 16 rows at a time, 4 rows per wave
+    // pass 2: quantise (the rows come from L2 this time), 16 rows at a time, 4 rows per wave; rows wider than the tile (2,048
+    // elements) in column slices of kTileDwords dwords.  The scale above and each row's error norm below span the WHOLE row.
+    constexpr int kTileDwords = 512;
     float wave_err = 0.0f;  // largest error norm among this wave's rows
     for (int half = 0; half < 2; ++half) {
         const int64_t row16 = row32 + 16 * half;
         float err2[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        for (int it = 0; it < nit; ++it) {
-            float v[4][4];
+        for (int c0 = 0; c0 < nch8; c0 += kTileDwords) {
+            const int it1 = (c0 + kTileDwords) / kWave < nit ? (c0 + kTileDwords) / kWave : nit;
+            for (int it = c0 / kWave; it < it1; ++it) {
+                float v[4][4];
 #pragma unroll
-            for (int rr = 0; rr < 4; ++rr) load_chunk(row16 + wave * 4 + rr, it, v[rr]);
-            const int j = lane + kWave * it;
+                for (int rr = 0; rr < 4; ++rr) load_chunk(row16 + wave * 4 + rr, it, v[rr]);
+                const int j = lane + kWave * it;
 #pragma unroll
-            for (int rr = 0; rr < 4; ++rr)
-                if (j < nch8) tile[(wave * 4 + rr) * kRowDwords + j] = quantize4(v[rr], inv_scale, scale, err2[rr]);  // (rows past n, chunks past the row: zeros)
+                for (int rr = 0; rr < 4; ++rr)
+                    if (j < nch8) tile[(wave * 4 + rr) * kRowDwords + (j - c0)] = quantize4(v[rr], inv_scale, scale, err2[rr]);  // (rows past n, chunks past the row: zeros)
+            }
+            __syncthreads();
+            // piece (c16, r) of the half block: 16 bytes of row r at byte 16*c16 (c16 counted from the slice's first piece)
+            const int npieces = (nch8 - c0 < kTileDwords ? nch8 - c0 : kTileDwords) >> 2;
+            for (int p = (int)threadIdx.x; p < 16 * npieces; p += 256) {
+                const int r = p & 15, c16 = p >> 4;
+                shadow8[codd::shadow_piece_index(row16 + r, (c0 >> 2) + c16, nsteps8)] = *reinterpret_cast<const uint4*>(&tile[r * kRowDwords + c16 * 4]);
+            }
+            __syncthreads();
         }
 #pragma unroll
         for (int rr = 0; rr < 4; ++rr) {
@@ -569,13 +644,6 @@ __global__ __launch_bounds__(256) void shadow8_from_rows_kernel(const void* __re
                 wave_err = fmaxf(wave_err, __builtin_sqrtf(e2) * 1.0001f + 1e-7f);  // inflated a little: the norm itself was accumulated in fp32
             }
         }
-        __syncthreads();
-        // piece (c16, r) of the half block: 16 bytes of row r at byte 16*c16
-        for (int p = (int)threadIdx.x; p < 16 * (dpad8 >> 4); p += 256) {
-            const int r = p & 15, c16 = p >> 4;
-            shadow8[codd::shadow_piece_index(row16 + r, c16, nsteps8)] = *reinterpret_cast<const uint4*>(&tile[r * kRowDwords + c16 * 4]);
-        }
-        __syncthreads();
     }
     // The block's meta data: its scale and the largest quantisation error norm |c - c~| among its rows.  The filter's bound is
     // evaluated PER BLOCK with this norm (round 2 folded every row's norm into one device-wide maximum that could only grow: one
@@ -911,16 +979,31 @@ __global__ __launch_bounds__(256) void ivf_scan_kernel(const void* __restrict__ 
         const int64_t begin = lo + (x % split) * part;
         const int64_t end = begin + part < hi ? begin + part : hi;
 
-        float qf[NITER][E];
+        const uint4* base = reinterpret_cast<const uint4*>(rows_);
+        if constexpr (NITER == kWideRows) {  // wide rows: the query in LDS, the rows walked segment by segment
+            __shared__ __attribute__((aligned(16))) float lds_q[kWideMaxFloats];
+            wide_stage_query(lds_q, qn + (int64_t)b * dpad, dpad, wide_qfloats(nchunks, E), (int)threadIdx.x, 256);
+            __syncthreads();
+            for (int64_t g = begin + wave * 4; g < end; g += 16) {
+                const uint4* p[4];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) p[r] = base + (g + r < end ? g + r : end - 1) * (int64_t)nchunks + lane;
+                float sc[1][4];
+                wide_scores<DT, 1>(p, nchunks, lane, lds_q, sc);
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (g + r < end) L.offer(make_key(sc[0][r], row_base + ids[g + r]), k, lane);
+            }
+        } else {
+        float qf[NITER > 0 ? NITER : 1][E];
 #pragma unroll
         for (int it = 0; it < NITER; ++it) {
             const int j = lane + kWave * it;
 #pragma unroll
             for (int e = 0; e < E; ++e) qf[it][e] = j < nchunks ? qn[(int64_t)b * dpad + (int64_t)j * E + e] : 0.0f;
         }
-        const uint4* base = reinterpret_cast<const uint4*>(rows_);
         for (int64_t g = begin + wave * 4; g < end; g += 16) {
-            float w[4][NITER][E];
+            float w[4][NITER > 0 ? NITER : 1][E];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int64_t row = g + r < end ? g + r : end - 1;
@@ -949,6 +1032,7 @@ __global__ __launch_bounds__(256) void ivf_scan_kernel(const void* __restrict__ 
                 if (g + r < end) L.offer(make_key(s, row_base + ids[g + r]), k, lane);
             }
         }
+        }  // (NITER)
     }
     __shared__ u64 lds[4 * SLOTS * kWave];
 #pragma unroll
@@ -1053,7 +1137,44 @@ __global__ __launch_bounds__(256) void ivf_scan_shared_kernel(const void* __rest
     const int wave = (int)(threadIdx.x >> 6);
     const int nchunks = dpad / E;
     unsigned pair[kIvfNB];
-    float qf[kIvfNB][NITER][E];
+    WaveTopK<SLOTS> L[kIvfNB];
+    const int64_t begin = offsets[list], end = offsets[list + 1];
+    const uint4* base = reinterpret_cast<const uint4*>(rows_);
+    if constexpr (NITER == kWideRows) {  // wide rows: the item's queries in LDS (64 KiB at most), the rows walked segment by segment
+        __shared__ __attribute__((aligned(16))) float lds_q[kIvfNB * kWideMaxFloats];
+        const int qstride = wide_qfloats(nchunks, E);
+#pragma unroll
+        for (int b = 0; b < kIvfNB; ++b) {
+            pair[b] = b < nq ? sorted_pairs[p0 + b] : 0u;
+            const float* src = b < nq ? qn + (int64_t)(pair[b] / (unsigned)nprobe) * dpad : nullptr;
+            wide_stage_query(lds_q + b * qstride, src, dpad, qstride, (int)threadIdx.x, 256);
+            L[b].init();
+        }
+        __syncthreads();
+        const int nseg = wide_nseg(nchunks);
+        for (int64_t g4 = begin + wave * 4; g4 < end; g4 += 16) {
+            const uint4* p[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) p[r] = base + (g4 + r < end ? g4 + r : end - 1) * (int64_t)nchunks + lane;
+            float a[kIvfNB][4];
+#pragma unroll
+            for (int b = 0; b < kIvfNB; ++b)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) a[b][r] = 0.0f;
+            for (int s = 0; s < nseg; ++s) wide_segment<DT, kIvfNB, 4>(p, s, nchunks, lane, lds_q, qstride, a);
+#pragma unroll
+            for (int b = 0; b < kIvfNB; ++b)
+                if (b < nq) {
+                    const float y = butterfly_sum4(a[b][0], a[b][1], a[b][2], a[b][3], lane);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const float sc = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(y), 16 * r));
+                        if (g4 + r < end) L[b].offer(make_key(sc, row_base + ids[g4 + r]), k, lane);
+                    }
+                }
+        }
+    } else {
+    float qf[kIvfNB][NITER > 0 ? NITER : 1][E];
 #pragma unroll
     for (int b = 0; b < kIvfNB; ++b) {
         pair[b] = b < nq ? sorted_pairs[p0 + b] : 0u;
@@ -1065,14 +1186,11 @@ __global__ __launch_bounds__(256) void ivf_scan_shared_kernel(const void* __rest
             for (int e = 0; e < E; ++e) qf[b][it][e] = (b < nq && j < nchunks) ? qn[qi * dpad + (int64_t)j * E + e] : 0.0f;
         }
     }
-    WaveTopK<SLOTS> L[kIvfNB];
 #pragma unroll
     for (int b = 0; b < kIvfNB; ++b) L[b].init();
-    const int64_t begin = offsets[list], end = offsets[list + 1];
-    const uint4* base = reinterpret_cast<const uint4*>(rows_);
     // the rows of step g4 + 16 are on their way while step g4 is scored (raw 16-byte chunks: half the registers of widened rows)
-    uint4 cur[4][NITER], nxt[4][NITER];
-    auto fetch = [&](int64_t g4, uint4 (&dst)[4][NITER]) {
+    uint4 cur[4][NITER > 0 ? NITER : 1], nxt[4][NITER > 0 ? NITER : 1];
+    auto fetch = [&](int64_t g4, uint4 (&dst)[4][NITER > 0 ? NITER : 1]) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             int64_t row = g4 + r < end ? g4 + r : end - 1;
@@ -1118,6 +1236,7 @@ __global__ __launch_bounds__(256) void ivf_scan_shared_kernel(const void* __rest
 #pragma unroll
             for (int it = 0; it < NITER; ++it) cur[r][it] = nxt[r][it];
     }
+    }  // (NITER)
     __shared__ u64 lds[4 * kIvfNB * SLOTS * kWave];
 #pragma unroll
     for (int b = 0; b < kIvfNB; ++b)
@@ -1312,6 +1431,9 @@ struct codd_knn_index : WorkBufs {
     int64_t ivf_epoch = -1, epoch = 0;  // epoch bumps on every row write; search requires ivf_epoch == epoch
 
     int64_t stat_searches = 0, stat_scan_launches = 0, stat_last_scan_blocks = 0;
+    int64_t stat_last_scan_group = 0;       // queries per pass over the rows of the last exact scan (1, 4 or 8; wide 2-byte rows: at most 4)
+    int64_t stat_last_finalize_parts = 0;   // workgroups per query of the last filter pass's finalize
+    int64_t stat_ivf_shared = 0;            // IVF searches that scanned each probed list once for all its queries (ivf_scan_shared_kernel)
     int64_t stat_filter_passes = 0;
 
     // optional HIP-event timing of the heavy kernels (bench.py's roofline figure): one (start, stop)
@@ -1511,6 +1633,10 @@ struct ScanArgs {
     unsigned long long* count_total = nullptr;
 };
 
+// the NITER values the wide forms serve: rows of 5 .. 16 chunks per lane (f32: 1,025 .. 4,096 elements; 2-byte: 2,049 .. 4,096)
+constexpr int kMaxNiter = 16;
+#define CODD_WIDE_NITER_CASES case 5: case 6: case 7: case 8: case 9: case 10: case 11: case 12: case 13: case 14: case 15: case 16
+
 template <int DT, int NB, int NITER>
 void launch_scan_slots(int slots, dim3 grid, size_t lds, hipStream_t st, const ScanArgs& a) {
     if (slots == 1)
@@ -1531,8 +1657,46 @@ int launch_scan_niter(int niter, int slots, dim3 grid, size_t lds, hipStream_t s
     return CODD_KNN_OK;
 }
 
+// rows of more than 4 chunks per lane: scan_topk_wide_kernel, one 8-wave workgroup per compute unit (scan_geometry sizes the grid)
+template <int DT, int NB, int SLOTS>
+int launch_scan_wide(dim3 grid, int dpad, hipStream_t st, const ScanArgs& a) {
+    constexpr int E = RowTraits<DT>::E;
+    const size_t qbytes = (size_t)NB * wide_qfloats(dpad / E, E) * sizeof(float);
+    const size_t lbytes = (size_t)kWideScanWaves * NB * SLOTS * kWave * sizeof(u64);
+    const size_t lds = qbytes > lbytes ? qbytes : lbytes;   // the lists take the queries' place once a group is scanned
+    // dynamic LDS above 64 KiB needs the opt-in, once per device (the caller's DeviceGuard has made the index's device current)
+    static std::atomic<uint64_t> attr_set{0};
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    const uint64_t bit = dev < 64 ? 1ull << dev : 0ull;
+    if (!bit || !(attr_set.load(std::memory_order_acquire) & bit)) {
+        HIP_TRY(hipFuncSetAttribute((const void*)&scan_topk_wide_kernel<DT, NB, SLOTS>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)((size_t)NB * kWideMaxFloats * sizeof(float))));
+        attr_set.fetch_or(bit, std::memory_order_acq_rel);
+    }
+    hipLaunchKernelGGL((scan_topk_wide_kernel<DT, NB, SLOTS>), grid, dim3(kWideScanWaves * kWave), lds, st, a.rows, a.n, a.dpad, a.qn, a.nq, a.k, a.row_base,
+                       a.partial, a.stride_q, a.qlist, a.qcount, a.merge_done, a.merged_keys, a.merged_dist, a.merged_rows, a.count_total);
+    return CODD_KNN_OK;
+}
+// queries per pass of the wide scan: 2-byte rows take at most 4 (8 would spill: the kernel walks a larger batch 4 queries at a time)
+constexpr int wide_scan_nb(int dt, int nb) { return dt == DT_F32 || nb < 4 ? nb : 4; }
+template <int DT, int NB>
+int launch_scan_wide_slots(int niter, int slots, dim3 grid, hipStream_t st, const ScanArgs& a) {
+    if (niter > kMaxNiter) return fail(CODD_KNN_ENOTSUP, "row too wide for the scan kernel%s");
+    constexpr int NBW = wide_scan_nb(DT, NB);
+    return slots == 1 ? launch_scan_wide<DT, NBW, 1>(grid, a.dpad, st, a) : launch_scan_wide<DT, NBW, 2>(grid, a.dpad, st, a);
+}
+
 template <int DT>
 int launch_scan_nb(int nb, int niter, int slots, dim3 grid, hipStream_t st, const ScanArgs& a) {
+    if (niter > 4) {
+        switch (nb) {
+            case 1: return launch_scan_wide_slots<DT, 1>(niter, slots, grid, st, a);
+            case 4: return launch_scan_wide_slots<DT, 4>(niter, slots, grid, st, a);
+            case 8: return launch_scan_wide_slots<DT, 8>(niter, slots, grid, st, a);
+            default: return fail(CODD_KNN_EINVAL, "bad query group%s");
+        }
+    }
     const size_t lds = (size_t)4 * nb * slots * kWave * sizeof(u64);
     switch (nb) {
         case 1: return launch_scan_niter<DT, 1>(niter, slots, grid, lds, st, a);
@@ -1559,8 +1723,14 @@ int launch_merge(const u64* in, int B, int64_t m, int64_t in_stride, int k, u64*
 int scan_geometry(const codd_knn_index* ix, int64_t n, int* niter, int64_t* blocks) {
     const int nchunks = ix->dpad / elems_per_chunk(ix->dtype);
     *niter = (nchunks + kWave - 1) / kWave;
-    if (*niter > 4) return fail(CODD_KNN_ENOTSUP, "dim too large for this dtype (f32 <= 1024, bf16/f16 <= 2048)%s");
+    if (*niter > kMaxNiter) return fail(CODD_KNN_ENOTSUP, "dim too large (<= 4096 elements)%s");
     const int64_t ngroups = (n + 3) / 4;
+    if (*niter > 4) {  // scan_topk_wide_kernel: workgroups of 8 waves, one per compute unit (its query block fills the LDS)
+        int64_t b = (ngroups + kWideScanWaves - 1) / kWideScanWaves;
+        if (b > ix->num_cus) b = ix->num_cus;
+        *blocks = b < 1 ? 1 : b;
+        return CODD_KNN_OK;
+    }
     int64_t b = (ngroups + 3) / 4;
     const int64_t cap_blocks = (int64_t)ix->num_cus * ix->scan_blocks_per_cu;
     if (b > cap_blocks) b = cap_blocks;
@@ -1586,6 +1756,7 @@ int exact_scan(codd_knn_index* ix, const float* qn, int nqueries, int k, uint32_
         // of 8 inside the kernel (small corpora stay L2-resident across the groups, and a batch costs one
         // launch instead of B/8)
         const int nb = nqueries == 1 ? 1 : (nqueries <= 4 ? 4 : 8);
+        ix->stat_last_scan_group = niter > 4 ? wide_scan_nb(ix->dtype, nb) : nb;
         ScanArgs a{ix->rows, n, ix->dpad, qn, nqueries, k, row_base, ix->partial, stride_q};
         const dim3 grid((unsigned)blocks);
         {
@@ -1653,6 +1824,7 @@ int launch_finalize(int niter, int slots, int B, hipStream_t st, const codd_knn_
         case 2: launch_finalize_slots<DT, 2>(slots, B, st, ix, qn, k, two_eps, row_base, out_keys, two_eps_q, nparts, part_keys, out_dist, out_rows); break;
         case 3: launch_finalize_slots<DT, 3>(slots, B, st, ix, qn, k, two_eps, row_base, out_keys, two_eps_q, nparts, part_keys, out_dist, out_rows); break;
         case 4: launch_finalize_slots<DT, 4>(slots, B, st, ix, qn, k, two_eps, row_base, out_keys, two_eps_q, nparts, part_keys, out_dist, out_rows); break;
+        CODD_WIDE_NITER_CASES: launch_finalize_slots<DT, kWideRows>(slots, B, st, ix, qn, k, two_eps, row_base, out_keys, two_eps_q, nparts, part_keys, out_dist, out_rows); break;
         default: return fail(CODD_KNN_ENOTSUP, "row too wide for the finalize kernel%s");
     }
     HIP_TRY(hipGetLastError());
@@ -1986,7 +2158,9 @@ int filter_pass(codd_knn_index* ix, const float* qn, int nq, int k, uint32_t row
         case 1: CODD_ANCHOR(DT, 1, SL); break;                 \
         case 2: CODD_ANCHOR(DT, 2, SL); break;                 \
         case 3: CODD_ANCHOR(DT, 3, SL); break;                 \
-        default: CODD_ANCHOR(DT, 4, SL); break;                \
+        case 4: CODD_ANCHOR(DT, 4, SL); break;                 \
+        CODD_WIDE_NITER_CASES: CODD_ANCHOR(DT, kWideRows, SL); break; \
+        default: return fail(CODD_KNN_ENOTSUP, "row too wide for the threshold kernel%s"); \
     }
         if (ix->dtype == DT_F32) { if (slots == 1) { CODD_ANCHOR_NI(DT_F32, 1) } else { CODD_ANCHOR_NI(DT_F32, 2) } }
         else if (ix->dtype == DT_BF16) { if (slots == 1) { CODD_ANCHOR_NI(DT_BF16, 1) } else { CODD_ANCHOR_NI(DT_BF16, 2) } }
@@ -2083,10 +2257,11 @@ int filter_pass(codd_knn_index* ix, const float* qn, int nq, int k, uint32_t row
     // the int8 filter leaves thousands of survivors per query and is only used for a handful of queries: share each
     // query's re-scoring out between several workgroups, then merge their lists
     const int nparts = use8 ? (nq <= 8 ? 16 : (nq <= 32 ? 8 : (nq <= 64 ? 4 : 1))) : 1;
+    ix->stat_last_finalize_parts = nparts;
     if (nparts > 1 && (rc = ensure_buf(&ix->partial, &ix->partial_cap, (int64_t)nq * nparts * k)) != 0) return rc;
     // one list slot per lane and one workgroup per query (the large batches): finalize and the exact-scan fallback share ONE
     // launch — the scan workgroups derive the queue from the hit counters and leave at once when it is empty
-    if (slots == 1 && nparts == 1 && ix->fuse_fallback && !(ix->dtype != DT_F32 && niter == 4)) {  // (2-byte rows above 1536 elements: the fused kernel spills)
+    if (slots == 1 && nparts == 1 && ix->fuse_fallback && niter <= 4 && !(ix->dtype != DT_F32 && niter == 4)) {  // (2-byte rows above 1536 elements: the fused kernel spills; wide rows take the separate fallback launch)
         int nit;
         int64_t blocks;
         if ((rc = scan_geometry(ix, n, &nit, &blocks)) != 0) return rc;
@@ -2409,7 +2584,7 @@ int search_impl(codd_knn_index* ix, const float* dev_queries, int B, int k, uint
 extern "C" {
 
 const char* codd_knn_version(void) {
-    return "codd_knn 0.6.0 gfx950"
+    return "codd_knn 0.7.0 gfx950"
 #if CODD_SHADOW_F16
            " shadow=f16"
 #else
@@ -2433,8 +2608,6 @@ int codd_knn_create(codd_knn_index** out, int device, int dim, int dtype, int me
     HIP_TRY(hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev) return fail(CODD_KNN_EINVAL, "no such device%s");
     const int dpad = (dim + 63) / 64 * 64;
-    const int niter = (dpad / elems_per_chunk(dtype) + kWave - 1) / kWave;
-    if (niter > 4) return fail(CODD_KNN_ENOTSUP, "dim too large for this dtype (f32 <= 1024, bf16/f16 <= 2048)%s");
     codd_knn_index* ix = new (std::nothrow) codd_knn_index();
     if (!ix) return fail(CODD_KNN_ENOMEM, "host allocation failed%s");
     ix->device = device;
@@ -2837,6 +3010,7 @@ int codd_knn_ivf_search(codd_knn_index* ix, const float* dev_queries, int B, int
     //     grouping launches are pure overhead — 12.5M x 1024 fp16, 2,048 lists, B = 256: nprobe 8 5.98 ms per pair vs 7.22 shared)
     if (ix->ivf_share && npairs >= 1024 && npairs >= 2 * (int64_t)ix->ivf_nlist && !(ix->dtype != DT_F32 && niter == 4)) {
         const int nlist = ix->ivf_nlist;
+        ix->stat_ivf_shared++;
         if ((rc = ensure_buf(&ix->ivf_group, &ix->ivf_group_cap, 3 * (int64_t)nlist + 2 + npairs)) != 0) return rc;
         if ((rc = ensure_buf(&ix->ivf_partial, &ix->ivf_partial_cap, npairs * k)) != 0) return rc;
         unsigned* cnt = ix->ivf_group;
@@ -2861,7 +3035,9 @@ int codd_knn_ivf_search(codd_knn_index* ix, const float* dev_queries, int B, int
         case 1: CODD_IVFS_LAUNCH(DT, 1, SL); break;                   \
         case 2: CODD_IVFS_LAUNCH(DT, 2, SL); break;                   \
         case 3: CODD_IVFS_LAUNCH(DT, 3, SL); break;                   \
-        default: CODD_IVFS_LAUNCH(DT, 4, SL); break;                  \
+        case 4: CODD_IVFS_LAUNCH(DT, 4, SL); break;                   \
+        CODD_WIDE_NITER_CASES: CODD_IVFS_LAUNCH(DT, kWideRows, SL); break; \
+        default: return fail(CODD_KNN_ENOTSUP, "row too wide for the IVF scan%s"); \
     }
         if (ix->dtype == DT_F32) { if (slots == 1) { CODD_IVFS_NITER(DT_F32, 1) } else { CODD_IVFS_NITER(DT_F32, 2) } }
         else if (ix->dtype == DT_BF16) { if (slots == 1) { CODD_IVFS_NITER(DT_BF16, 1) } else { CODD_IVFS_NITER(DT_BF16, 2) } }
@@ -2887,7 +3063,9 @@ int codd_knn_ivf_search(codd_knn_index* ix, const float* dev_queries, int B, int
         case 1: CODD_IVF_LAUNCH(DT, 1, SL); break;                    \
         case 2: CODD_IVF_LAUNCH(DT, 2, SL); break;                    \
         case 3: CODD_IVF_LAUNCH(DT, 3, SL); break;                    \
-        default: CODD_IVF_LAUNCH(DT, 4, SL); break;                   \
+        case 4: CODD_IVF_LAUNCH(DT, 4, SL); break;                    \
+        CODD_WIDE_NITER_CASES: CODD_IVF_LAUNCH(DT, kWideRows, SL); break; \
+        default: return fail(CODD_KNN_ENOTSUP, "row too wide for the IVF scan%s"); \
     }
     {
         EvScope ev(ix, EV_SCAN, st);
@@ -3082,6 +3260,9 @@ int codd_knn_get_stat(const codd_knn_index* ix, const char* key, int64_t* out) {
     if (strcmp(key, "searches") == 0) *out = ix->stat_searches;
     else if (strcmp(key, "scan_launches") == 0) *out = ix->stat_scan_launches;
     else if (strcmp(key, "last_scan_blocks") == 0) *out = ix->stat_last_scan_blocks;
+    else if (strcmp(key, "last_scan_group") == 0) *out = ix->stat_last_scan_group;
+    else if (strcmp(key, "last_finalize_parts") == 0) *out = ix->stat_last_finalize_parts;
+    else if (strcmp(key, "ivf_shared_searches") == 0) *out = ix->stat_ivf_shared;
     else if (strcmp(key, "filter_passes") == 0) *out = ix->stat_filter_passes;
     else if (strcmp(key, "shadow8_builds") == 0) *out = ix->stat_shadow8_builds;
     else if (strcmp(key, "shadow16_builds") == 0) *out = ix->stat_shadow_builds;

@@ -64,7 +64,11 @@ const char* codd_knn_last_error(void);
 /*
  * Replaces: client.get_or_create_collection(name=..., metadata={"hnsw:space":"cosine",...})
  *           (store.py:60-69) — the arithmetic half: an empty device-resident row store.
- * dim: embedding width (<= 4096; f32 rows <= 1024 in this release).
+ * dim: embedding width, 1 <= dim <= 4096 for every dtype (4097 and above: EINVAL).  Rows of up to
+ *      1024 (f32) / 2048 (bf16, f16) elements are scored with the query held in registers; wider
+ *      rows (1536 / 3072 / 4096-wide embedders) by the wide forms of the exact-score kernels — the
+ *      scan, finalize, the threshold anchors and the IVF scans — which stage the query in LDS and
+ *      walk the row in segments: the same canonical scores.
  */
 int codd_knn_create(codd_knn_index** out, int device, int dim, int dtype, int metric);
 int codd_knn_destroy(codd_knn_index* index);
@@ -212,7 +216,9 @@ int codd_knn_ivf_search(codd_knn_index* index, const float* dev_queries, int B, 
  *            "debug_fail_shadow_alloc" (tests: the next N allocations of the 2-byte shadow fail);
  *            "profile" = N keeps N (start, stop) HIP-event pairs, one per heavy-kernel launch,
  *            recorded on the launch stream (0 = off; resets the log)
- *   stats  : "searches", "scan_launches", "last_scan_blocks", "filter_passes",
+ *   stats  : "searches", "scan_launches", "last_scan_blocks", "last_scan_group" (queries per pass over the rows of the
+ *            last exact scan), "last_finalize_parts" (workgroups per query of the last filter pass's finalize),
+ *            "ivf_shared_searches" (IVF searches that scanned each probed list once for all its queries), "filter_passes",
  *            "fallback_queries", "filter_hits", "filter_survivors", "capacity_rows",
  *            "device_bytes", "num_cus", "workspaces" (stream workspaces in use), "shadow8_builds", "shadow8_passes", "i8v2_passes",
  *            "shadow16_builds" (the bf16 shadow is built lazily, by the first search that needs it), "all_normalized",
