@@ -23,6 +23,7 @@
 #include <atomic>
 #include <mutex>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include "codd_knn.h"
@@ -1592,23 +1593,110 @@ int ensure_buf(T** buf, int64_t* cap, int64_t need) {
     return CODD_KNN_OK;
 }
 
+// ---- kernel dispatch -------------------------------------------------------------------------
+// Each run-time choice of a template argument is made in one place: a with_* helper calls the generic lambda `f` with a
+// std::integral_constant of the chosen value (usable as a template argument inside f) and returns what f returns (a
+// CODD_KNN_* code).  A value no kernel is built for is an error.
+
+template <int V>
+using IntC = std::integral_constant<int, V>;
+
+// f(IntC<V>) for the V of Vs that equals v, else EINVAL with `unsupported` (a fail() format)
+template <int... Vs, typename F>
+int with_int(int v, const char* unsupported, F&& f) {
+    bool found = false;
+    int rc = CODD_KNN_OK;
+    ((v == Vs ? (found = true, rc = f(IntC<Vs>{})) : 0), ...);
+    return found ? rc : fail(CODD_KNN_EINVAL, unsupported);
+}
+
+template <typename F>
+int with_dtype(int dtype, F&& f) {
+    return with_int<DT_F32, DT_BF16, DT_F16>(dtype, "unknown dtype%s", f);
+}
+
+// the NITER values the wide forms serve: rows of 5 .. 16 chunks per lane (f32: 1,025 .. 4,096 elements; 2-byte: 2,049 .. 4,096)
+constexpr int kMaxNiter = 16;
+
+// chunks of the padded row per lane: the NITER of the exact-score row kernels
+int niter_of(const codd_knn_index* ix) { return (ix->dpad / elems_per_chunk(ix->dtype) + kWave - 1) / kWave; }
+
+// 1 .. 4 chunks per lane: NITER itself; 5 .. kMaxNiter: the wide form (kWideRows); wider: ENOTSUP with `too_wide`
+template <typename F>
+int with_niter(int niter, const char* too_wide, F&& f) {
+    switch (niter) {
+        case 1: return f(IntC<1>{});
+        case 2: return f(IntC<2>{});
+        case 3: return f(IntC<3>{});
+        case 4: return f(IntC<4>{});
+    }
+    if (niter > 4 && niter <= kMaxNiter) return f(IntC<kWideRows>{});
+    return fail(CODD_KNN_ENOTSUP, too_wide);
+}
+
+// list slots per lane of a top-k list: one for k <= 64, else two
+template <typename F>
+int with_slots(int k, F&& f) {
+    return k <= 64 ? f(IntC<1>{}) : f(IntC<2>{});
+}
+
+// 32-query blocks of a filter pass
+template <typename F>
+int with_nbq(int nbq, F&& f) {
+    return with_int<1, 2, 4, 8>(nbq, "bad query block count%s", f);
+}
+
+// f(DT, NITER, SLOTS): the form of an exact-score row kernel for the index's rows and k
+template <typename F>
+int with_row_form(const codd_knn_index* ix, int k, const char* too_wide, F&& f) {
+    return with_dtype(ix->dtype, [&](auto dt) {
+        return with_niter(niter_of(ix), too_wide, [&](auto ni) {
+            return with_slots(k, [&](auto sl) { return f(dt, ni, sl); });
+        });
+    });
+}
+
+// Dynamic LDS above 64 KiB needs the instantiation's opt-in, once per device (the caller's DeviceGuard has made the index's
+// device current).  `bytes` must be at least what any launch of `Kernel` asks for.
+template <auto Kernel>
+int opt_in_lds(size_t bytes) {
+    static std::atomic<uint64_t> done{0};  // one bit per device
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    const uint64_t bit = dev < 64 ? 1ull << dev : 0ull;
+    if (!bit || !(done.load(std::memory_order_acquire) & bit)) {
+        HIP_TRY(hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+        done.fetch_or(bit, std::memory_order_acq_rel);
+    }
+    return CODD_KNN_OK;
+}
+
+// dynamic LDS of a launch, and what its kernel opts in to when that is above 64 KiB (by default the same: a kernel launched
+// with one size only)
+struct Lds {
+    size_t bytes, opt_in;
+    Lds(size_t b) : bytes(b), opt_in(b) {}
+    Lds(size_t b, size_t most) : bytes(b), opt_in(most) {}
+};
+constexpr size_t kLdsNoOptIn = 64 * 1024;
+
+// every launch of a template kernel, and every launch with dynamic LDS; the caller checks hipGetLastError
+template <auto Kernel, typename... Args>
+int launch_kernel(dim3 grid, dim3 block, Lds lds, hipStream_t st, Args... args) {
+    int rc;
+    if (lds.bytes > kLdsNoOptIn && (rc = opt_in_lds<Kernel>(lds.opt_in)) != 0) return rc;
+    hipLaunchKernelGGL(Kernel, grid, block, lds.bytes, st, args...);
+    return CODD_KNN_OK;
+}
+
 int launch_normalize(int dtype, const float* in, int64_t n, int d, int dpad, int normalize, const int64_t* slots,
                      int64_t first_slot, void* out, uint2* shadow, hipStream_t st) {
     if (n <= 0) return CODD_KNN_OK;
     const dim3 grid((unsigned)((n + 3) / 4)), block(256);
-    switch (dtype) {
-        case DT_F32:
-            hipLaunchKernelGGL(normalize_rows_kernel<DT_F32>, grid, block, 0, st, in, n, d, dpad, normalize, slots, first_slot, out, shadow);
-            break;
-        case DT_BF16:
-            hipLaunchKernelGGL(normalize_rows_kernel<DT_BF16>, grid, block, 0, st, in, n, d, dpad, normalize, slots, first_slot, out, shadow);
-            break;
-        case DT_F16:
-            hipLaunchKernelGGL(normalize_rows_kernel<DT_F16>, grid, block, 0, st, in, n, d, dpad, normalize, slots, first_slot, out, shadow);
-            break;
-        default:
-            return fail(CODD_KNN_EINVAL, "unknown dtype%s");
-    }
+    const int rc = with_dtype(dtype, [&](auto dt) {
+        return launch_kernel<normalize_rows_kernel<dt>>(grid, block, 0, st, in, n, d, dpad, normalize, slots, first_slot, out, shadow);
+    });
+    if (rc != 0) return rc;
     HIP_TRY(hipGetLastError());
     return CODD_KNN_OK;
 }
@@ -1633,96 +1721,56 @@ struct ScanArgs {
     unsigned long long* count_total = nullptr;
 };
 
-// the NITER values the wide forms serve: rows of 5 .. 16 chunks per lane (f32: 1,025 .. 4,096 elements; 2-byte: 2,049 .. 4,096)
-constexpr int kMaxNiter = 16;
-#define CODD_WIDE_NITER_CASES case 5: case 6: case 7: case 8: case 9: case 10: case 11: case 12: case 13: case 14: case 15: case 16
-
-template <int DT, int NB, int NITER>
-void launch_scan_slots(int slots, dim3 grid, size_t lds, hipStream_t st, const ScanArgs& a) {
-    if (slots == 1)
-        hipLaunchKernelGGL((scan_topk_kernel<DT, NB, NITER, 1>), grid, dim3(256), lds, st, a.rows, a.n, a.dpad, a.qn, a.nq, a.k, a.row_base, a.partial, a.stride_q, a.qlist, a.qcount, a.merge_done, a.merged_keys, a.merged_dist, a.merged_rows, a.count_total);
-    else
-        hipLaunchKernelGGL((scan_topk_kernel<DT, NB, NITER, 2>), grid, dim3(256), lds, st, a.rows, a.n, a.dpad, a.qn, a.nq, a.k, a.row_base, a.partial, a.stride_q, a.qlist, a.qcount, a.merge_done, a.merged_keys, a.merged_dist, a.merged_rows, a.count_total);
-}
-
-template <int DT, int NB>
-int launch_scan_niter(int niter, int slots, dim3 grid, size_t lds, hipStream_t st, const ScanArgs& a) {
-    switch (niter) {
-        case 1: launch_scan_slots<DT, NB, 1>(slots, grid, lds, st, a); break;
-        case 2: launch_scan_slots<DT, NB, 2>(slots, grid, lds, st, a); break;
-        case 3: launch_scan_slots<DT, NB, 3>(slots, grid, lds, st, a); break;
-        case 4: launch_scan_slots<DT, NB, 4>(slots, grid, lds, st, a); break;
-        default: return fail(CODD_KNN_ENOTSUP, "row too wide for the scan kernel%s");
-    }
-    return CODD_KNN_OK;
-}
-
-// rows of more than 4 chunks per lane: scan_topk_wide_kernel, one 8-wave workgroup per compute unit (scan_geometry sizes the grid)
-template <int DT, int NB, int SLOTS>
-int launch_scan_wide(dim3 grid, int dpad, hipStream_t st, const ScanArgs& a) {
-    constexpr int E = RowTraits<DT>::E;
-    const size_t qbytes = (size_t)NB * wide_qfloats(dpad / E, E) * sizeof(float);
-    const size_t lbytes = (size_t)kWideScanWaves * NB * SLOTS * kWave * sizeof(u64);
-    const size_t lds = qbytes > lbytes ? qbytes : lbytes;   // the lists take the queries' place once a group is scanned
-    // dynamic LDS above 64 KiB needs the opt-in, once per device (the caller's DeviceGuard has made the index's device current)
-    static std::atomic<uint64_t> attr_set{0};
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    const uint64_t bit = dev < 64 ? 1ull << dev : 0ull;
-    if (!bit || !(attr_set.load(std::memory_order_acquire) & bit)) {
-        HIP_TRY(hipFuncSetAttribute((const void*)&scan_topk_wide_kernel<DT, NB, SLOTS>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)((size_t)NB * kWideMaxFloats * sizeof(float))));
-        attr_set.fetch_or(bit, std::memory_order_acq_rel);
-    }
-    hipLaunchKernelGGL((scan_topk_wide_kernel<DT, NB, SLOTS>), grid, dim3(kWideScanWaves * kWave), lds, st, a.rows, a.n, a.dpad, a.qn, a.nq, a.k, a.row_base,
-                       a.partial, a.stride_q, a.qlist, a.qcount, a.merge_done, a.merged_keys, a.merged_dist, a.merged_rows, a.count_total);
-    return CODD_KNN_OK;
-}
 // queries per pass of the wide scan: 2-byte rows take at most 4 (8 would spill: the kernel walks a larger batch 4 queries at a time)
 constexpr int wide_scan_nb(int dt, int nb) { return dt == DT_F32 || nb < 4 ? nb : 4; }
-template <int DT, int NB>
-int launch_scan_wide_slots(int niter, int slots, dim3 grid, hipStream_t st, const ScanArgs& a) {
-    if (niter > kMaxNiter) return fail(CODD_KNN_ENOTSUP, "row too wide for the scan kernel%s");
-    constexpr int NBW = wide_scan_nb(DT, NB);
-    return slots == 1 ? launch_scan_wide<DT, NBW, 1>(grid, a.dpad, st, a) : launch_scan_wide<DT, NBW, 2>(grid, a.dpad, st, a);
-}
 
-template <int DT>
-int launch_scan_nb(int nb, int niter, int slots, dim3 grid, hipStream_t st, const ScanArgs& a) {
-    if (niter > 4) {
-        switch (nb) {
-            case 1: return launch_scan_wide_slots<DT, 1>(niter, slots, grid, st, a);
-            case 4: return launch_scan_wide_slots<DT, 4>(niter, slots, grid, st, a);
-            case 8: return launch_scan_wide_slots<DT, 8>(niter, slots, grid, st, a);
-            default: return fail(CODD_KNN_EINVAL, "bad query group%s");
-        }
-    }
-    const size_t lds = (size_t)4 * nb * slots * kWave * sizeof(u64);
-    switch (nb) {
-        case 1: return launch_scan_niter<DT, 1>(niter, slots, grid, lds, st, a);
-        case 4: return launch_scan_niter<DT, 4>(niter, slots, grid, lds, st, a);
-        case 8: return launch_scan_niter<DT, 8>(niter, slots, grid, lds, st, a);
-        default: return fail(CODD_KNN_EINVAL, "bad query group%s");
-    }
+// one exact-scan launch, queries in groups of `nb` (1, 4 or 8) per pass over the rows
+int launch_scan(int dtype, int nb, int niter, dim3 grid, hipStream_t st, const ScanArgs& a) {
+    return with_dtype(dtype, [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        return with_int<1, 4, 8>(nb, "bad query group%s", [&](auto nbc) {
+            constexpr int NB = decltype(nbc)::value;
+            return with_slots(a.k, [&](auto sl) {
+                constexpr int SLOTS = decltype(sl)::value;
+                return with_niter(niter, "row too wide for the scan kernel%s", [&](auto ni) {
+                    constexpr int NITER = decltype(ni)::value;
+                    if constexpr (NITER == kWideRows) {
+                        // rows of more than 4 chunks per lane: scan_topk_wide_kernel, one 8-wave workgroup per compute unit (scan_geometry sizes the grid)
+                        constexpr int NBW = wide_scan_nb(DT, NB);
+                        constexpr int E = RowTraits<DT>::E;
+                        const size_t qbytes = (size_t)NBW * wide_qfloats(a.dpad / E, E) * sizeof(float);
+                        const size_t lbytes = (size_t)kWideScanWaves * NBW * SLOTS * kWave * sizeof(u64);
+                        const size_t lds = qbytes > lbytes ? qbytes : lbytes;   // the lists take the queries' place once a group is scanned
+                        return launch_kernel<scan_topk_wide_kernel<DT, NBW, SLOTS>>(
+                            grid, dim3(kWideScanWaves * kWave), Lds(lds, (size_t)NBW * kWideMaxFloats * sizeof(float)), st, a.rows, a.n, a.dpad, a.qn, a.nq,
+                            a.k, a.row_base, a.partial, a.stride_q, a.qlist, a.qcount, a.merge_done, a.merged_keys, a.merged_dist, a.merged_rows, a.count_total);
+                    } else {
+                        const size_t lds = (size_t)4 * NB * SLOTS * kWave * sizeof(u64);
+                        return launch_kernel<scan_topk_kernel<DT, NB, NITER, SLOTS>>(
+                            grid, dim3(256), lds, st, a.rows, a.n, a.dpad, a.qn, a.nq, a.k, a.row_base, a.partial, a.stride_q, a.qlist, a.qcount,
+                            a.merge_done, a.merged_keys, a.merged_dist, a.merged_rows, a.count_total);
+                    }
+                });
+            });
+        });
+    });
 }
 
 int launch_merge(const u64* in, int B, int64_t m, int64_t in_stride, int k, u64* out_keys, float* out_dist, int64_t* out_rows,
                  hipStream_t st, const unsigned* out_list = nullptr, const unsigned* count_ptr = nullptr,
                  unsigned long long* count_total = nullptr, int64_t seg_len = 0, int64_t seg_stride = 0) {
     if (seg_len <= 0) seg_len = m > 0 ? m : 1;
-    if (k <= 64)
-        hipLaunchKernelGGL(merge_keys_kernel<1>, dim3(B), dim3(256), 0, st, in, m, in_stride, seg_len, seg_stride, k, out_keys, out_dist, out_rows,
-                           out_list, count_ptr, count_total);
-    else
-        hipLaunchKernelGGL(merge_keys_kernel<2>, dim3(B), dim3(256), 0, st, in, m, in_stride, seg_len, seg_stride, k, out_keys, out_dist, out_rows,
-                           out_list, count_ptr, count_total);
+    const int rc = with_slots(k, [&](auto sl) {
+        return launch_kernel<merge_keys_kernel<sl>>(dim3(B), dim3(256), 0, st, in, m, in_stride, seg_len, seg_stride, k, out_keys, out_dist, out_rows,
+                                                    out_list, count_ptr, count_total);
+    });
+    if (rc != 0) return rc;
     HIP_TRY(hipGetLastError());
     return CODD_KNN_OK;
 }
 
 int scan_geometry(const codd_knn_index* ix, int64_t n, int* niter, int64_t* blocks) {
-    const int nchunks = ix->dpad / elems_per_chunk(ix->dtype);
-    *niter = (nchunks + kWave - 1) / kWave;
+    *niter = niter_of(ix);
     if (*niter > kMaxNiter) return fail(CODD_KNN_ENOTSUP, "dim too large (<= 4096 elements)%s");
     const int64_t ngroups = (n + 3) / 4;
     if (*niter > 4) {  // scan_topk_wide_kernel: workgroups of 8 waves, one per compute unit (its query block fills the LDS)
@@ -1748,7 +1796,6 @@ int exact_scan(codd_knn_index* ix, const float* qn, int nqueries, int k, uint32_
     int rc = scan_geometry(ix, n, &niter, &blocks);
     if (rc != 0) return rc;
     ix->stat_last_scan_blocks = blocks;
-    const int slots = k <= 64 ? 1 : 2;
     const int64_t stride_q = blocks * k;
     if ((rc = ensure_buf(&ix->partial, &ix->partial_cap, (int64_t)nqueries * stride_q)) != 0) return rc;
     {
@@ -1758,15 +1805,9 @@ int exact_scan(codd_knn_index* ix, const float* qn, int nqueries, int k, uint32_
         const int nb = nqueries == 1 ? 1 : (nqueries <= 4 ? 4 : 8);
         ix->stat_last_scan_group = niter > 4 ? wide_scan_nb(ix->dtype, nb) : nb;
         ScanArgs a{ix->rows, n, ix->dpad, qn, nqueries, k, row_base, ix->partial, stride_q};
-        const dim3 grid((unsigned)blocks);
         {
             EvScope ev(ix, EV_SCAN, st);
-            switch (ix->dtype) {
-                case DT_F32: rc = launch_scan_nb<DT_F32>(nb, niter, slots, grid, st, a); break;
-                case DT_BF16: rc = launch_scan_nb<DT_BF16>(nb, niter, slots, grid, st, a); break;
-                case DT_F16: rc = launch_scan_nb<DT_F16>(nb, niter, slots, grid, st, a); break;
-                default: rc = fail(CODD_KNN_EINVAL, "unknown dtype%s");
-            }
+            rc = launch_scan(ix->dtype, nb, niter, dim3((unsigned)blocks), st, a);
         }
         if (rc != 0) return rc;
         HIP_TRY(hipGetLastError());
@@ -1802,35 +1843,6 @@ float filter_eps(const codd_knn_index* ix) {
     return (rounding + subnormal + summation) * 1.001f;
 }
 
-template <int DT, int NITER>
-void launch_finalize_slots(int slots, int B, hipStream_t st, const codd_knn_index* ix, const float* qn, int k, float two_eps,
-                           uint32_t row_base, u64* out_keys, const float* two_eps_q, int nparts, u64* part_keys, float* out_dist, int64_t* out_rows) {
-    FilterCtl* c = ix->ctl;
-    const float2* bm = two_eps_q && (ix->per_block & 2) ? ix->bmeta : nullptr;  // (the int8 passes: slack per 32-row block)
-    if (slots == 1)
-        hipLaunchKernelGGL((finalize_kernel<DT, NITER, 1>), dim3(B, nparts), dim3(kFinThreads), 0, st, ix->rows, ix->dpad, qn, ix->hits, c->hit_cnt,
-                           ix->hit_cap_q, c->flags, k, two_eps, row_base, out_keys, &c->fb_count, c->fb_list, ix->dstats, two_eps_q, part_keys, out_dist, out_rows, bm);
-    else
-        hipLaunchKernelGGL((finalize_kernel<DT, NITER, 2>), dim3(B, nparts), dim3(kFinThreads), 0, st, ix->rows, ix->dpad, qn, ix->hits, c->hit_cnt,
-                           ix->hit_cap_q, c->flags, k, two_eps, row_base, out_keys, &c->fb_count, c->fb_list, ix->dstats, two_eps_q, part_keys, out_dist, out_rows, bm);
-}
-
-template <int DT>
-int launch_finalize(int niter, int slots, int B, hipStream_t st, const codd_knn_index* ix, const float* qn, int k, float two_eps,
-                    uint32_t row_base, u64* out_keys, const float* two_eps_q = nullptr, int nparts = 1, u64* part_keys = nullptr,
-                    float* out_dist = nullptr, int64_t* out_rows = nullptr) {
-    switch (niter) {
-        case 1: launch_finalize_slots<DT, 1>(slots, B, st, ix, qn, k, two_eps, row_base, out_keys, two_eps_q, nparts, part_keys, out_dist, out_rows); break;
-        case 2: launch_finalize_slots<DT, 2>(slots, B, st, ix, qn, k, two_eps, row_base, out_keys, two_eps_q, nparts, part_keys, out_dist, out_rows); break;
-        case 3: launch_finalize_slots<DT, 3>(slots, B, st, ix, qn, k, two_eps, row_base, out_keys, two_eps_q, nparts, part_keys, out_dist, out_rows); break;
-        case 4: launch_finalize_slots<DT, 4>(slots, B, st, ix, qn, k, two_eps, row_base, out_keys, two_eps_q, nparts, part_keys, out_dist, out_rows); break;
-        CODD_WIDE_NITER_CASES: launch_finalize_slots<DT, kWideRows>(slots, B, st, ix, qn, k, two_eps, row_base, out_keys, two_eps_q, nparts, part_keys, out_dist, out_rows); break;
-        default: return fail(CODD_KNN_ENOTSUP, "row too wide for the finalize kernel%s");
-    }
-    HIP_TRY(hipGetLastError());
-    return CODD_KNN_OK;
-}
-
 size_t filter_lds_bytes(int mode) {
     return (size_t)kLdsQBytes + kLdsWords * 4 + (mode == MODE_FILTER ? (size_t)kHitCap * 12 : 0);
 }
@@ -1848,29 +1860,6 @@ int ensure_filter_workspace(codd_knn_index* ix) {
     if (!ix->dstats) {
         HIP_TRY(hipMalloc((void**)&ix->dstats, 4 * sizeof(unsigned long long)));
         HIP_TRY(hipMemset(ix->dstats, 0, 4 * sizeof(unsigned long long)));
-    }
-    static std::atomic<bool> attr_set{false};  // dynamic LDS above 64 KiB needs the opt-in (idempotent)
-    if (!attr_set.load(std::memory_order_acquire)) {
-        const void* fns[] = {
-            (const void*)&gemm_filter_kernel<MODE_FILTER, 1>, (const void*)&gemm_filter_kernel<MODE_FILTER, 2>,
-            (const void*)&gemm_filter_kernel<MODE_FILTER, 4>, (const void*)&gemm_filter_kernel<MODE_FILTER, 8>,
-            (const void*)&gemm_filter_kernel<MODE_SAMPLE, 1>, (const void*)&gemm_filter_kernel<MODE_SAMPLE, 2>,
-            (const void*)&gemm_filter_kernel<MODE_SAMPLE, 4>, (const void*)&gemm_filter_kernel<MODE_SAMPLE, 8>,
-            (const void*)&gemm_filter_kernel<MODE_DUMP, 8>};
-        for (const void* fn : fns)
-            HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)filter_lds_bytes(MODE_FILTER)));
-        const void* tile_fns[] = {(const void*)&i8_tile_kernel<MODE_FILTER, 0>, (const void*)&i8_tile_kernel<MODE_FILTER, 1>, (const void*)&i8_tile_kernel<MODE_FILTER, 2>,
-                                  (const void*)&i8_tile_kernel<MODE_FILTER, 0, 8>, (const void*)&i8_tile_kernel<MODE_FILTER, 1, 8>, (const void*)&i8_tile_kernel<MODE_FILTER, 2, 8>,
-                                  (const void*)&i8_tile_kernel<MODE_FILTER, 3>, (const void*)&i8_tile_kernel<MODE_FILTER, 3, 8>,
-                                  (const void*)&i8_tile_kernel<MODE_FILTER, 2, 16, false, true>, (const void*)&i8_tile_kernel<MODE_FILTER, 3, 16, false, true>,
-                                  (const void*)&i8_tile_kernel<MODE_FILTER, 4, 16, false, true>,
-                                  (const void*)&i8_tile_kernel<MODE_FILTER, 1, 16, true>, (const void*)&i8_tile_kernel<MODE_FILTER, 0, 16, true>,
-                                  (const void*)&i8_tile_kernel<MODE_FILTER, 1, 8, true>, (const void*)&i8_tile_kernel<MODE_FILTER, 0, 8, true>};
-        for (const void* fn : tile_fns) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)i8_lds_bytes(MODE_FILTER)));
-        const void* tile_sample_fns[] = {(const void*)&i8_tile_kernel<MODE_SAMPLE, 0>, (const void*)&i8_tile_kernel<MODE_SAMPLE, 0, 8>,
-                                         (const void*)&i8_tile_kernel<MODE_SAMPLE, 0, 16, true>, (const void*)&i8_tile_kernel<MODE_SAMPLE, 0, 8, true>};
-        for (const void* fn : tile_sample_fns) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)i8_lds_bytes(MODE_SAMPLE)));
-        attr_set.store(true, std::memory_order_release);
     }
     return CODD_KNN_OK;
 }
@@ -1959,11 +1948,10 @@ int ensure_shadow(codd_knn_index* ix, hipStream_t st) {
     if (m > 0) {
         const dim3 grid((unsigned)((m + 3) / 4)), block(256);
         uint2* sh = reinterpret_cast<uint2*>(ix->shadow);
-        switch (ix->dtype) {
-            case DT_F32: hipLaunchKernelGGL(shadow_from_rows_kernel<DT_F32>, grid, block, 0, st, ix->rows, first, m, ix->dpad, sh); break;
-            case DT_BF16: hipLaunchKernelGGL(shadow_from_rows_kernel<DT_BF16>, grid, block, 0, st, ix->rows, first, m, ix->dpad, sh); break;
-            default: hipLaunchKernelGGL(shadow_from_rows_kernel<DT_F16>, grid, block, 0, st, ix->rows, first, m, ix->dpad, sh); break;
-        }
+        const int rc = with_dtype(ix->dtype, [&](auto dt) {
+            return launch_kernel<shadow_from_rows_kernel<dt>>(grid, block, 0, st, ix->rows, first, m, ix->dpad, sh);
+        });
+        if (rc != 0) return rc;
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipEventRecord(ix->shadow_ready, st));
@@ -2018,11 +2006,10 @@ int ensure_shadow8(codd_knn_index* ix, hipStream_t st) {
         m = (last + 31) / 32 * 32 - first;
         const dim3 grid((unsigned)(m / 32)), block(256);
         uint4* s8 = ix->shadow8;
-        switch (ix->dtype) {
-            case DT_F32: hipLaunchKernelGGL(shadow8_from_rows_kernel<DT_F32>, grid, block, 0, st, ix->rows, first, n, ix->dpad, dpad8, s8, ix->rscale, ix->bmeta); break;
-            case DT_BF16: hipLaunchKernelGGL(shadow8_from_rows_kernel<DT_BF16>, grid, block, 0, st, ix->rows, first, n, ix->dpad, dpad8, s8, ix->rscale, ix->bmeta); break;
-            default: hipLaunchKernelGGL(shadow8_from_rows_kernel<DT_F16>, grid, block, 0, st, ix->rows, first, n, ix->dpad, dpad8, s8, ix->rscale, ix->bmeta); break;
-        }
+        const int rc = with_dtype(ix->dtype, [&](auto dt) {
+            return launch_kernel<shadow8_from_rows_kernel<dt>>(grid, block, 0, st, ix->rows, first, n, ix->dpad, dpad8, s8, ix->rscale, ix->bmeta);
+        });
+        if (rc != 0) return rc;
         HIP_TRY(hipGetLastError());
         // the device-wide maximum of the block error norms, over the rows stored now (not a running maximum)
         hipLaunchKernelGGL(eps_max_kernel, dim3(1), dim3(1024), 0, st, ix->bmeta, (n + 31) / 32, ix->eps_r_bits, ix->shadow8_max_eps);
@@ -2050,6 +2037,150 @@ int ensure_shadow8(codd_knn_index* ix, hipStream_t st) {
     return CODD_KNN_OK;
 }
 
+// The program a filter pass runs, chosen once per pass (filter_program); its sample launch and its filter launch both read it.
+//   GEMM      gemm_filter_kernel<MODE, nbq, el, res>: el = 1 int8 operands; res = 1 the whole int8 query block resident in LDS,
+//             res = 2 two of its six slices (768 elements, 4 query blocks)
+//   TILE      i8_tile_kernel<MODE, ts, 2 * nbq, res> (filter_i8.h: the int8 tile program, 16-query blocks; res: the query block
+//             resident in LDS); the sample pass runs ts = 0
+//   TILE_F16  i8_tile_kernel<MODE_FILTER, ts, 16, false, true>: the same program on fp16 operands; the sample pass is GEMM's
+//             gemm_filter_kernel<MODE_SAMPLE, 8>
+struct FilterProgram {
+    enum Family { GEMM, TILE, TILE_F16 };
+    Family family = GEMM;
+    int nbq = 8;  // 32-query blocks the GEMM multiplies
+    int ts = 0, res = 0, el = 0;
+};
+
+FilterProgram filter_program(const codd_knn_index* ix, int nq, int nsteps, bool use8) {
+    FilterProgram p;
+    p.nbq = nq <= 32 ? 1 : (nq <= 64 ? 2 : (nq <= 128 ? 4 : 8));
+    p.el = use8 ? 1 : 0;
+    const bool resident = use8 && nsteps <= 4 && ix->resident_q;
+    // 65..128 queries only: with <= 64 the kernel is a byte stream (nothing to gain); with 8 query blocks the six-step body
+    // needs more than the 256 registers of a wave (hipcc spills, no gain measured)
+    const bool partial6 = use8 && nsteps == 6 && nq > 64 && nq <= 128 && ix->resident_q;
+    // full query blocks: the second-generation int8 kernel (filter_i8.h); rows whose query block fits the LDS keep the resident one
+    const bool tile_v2 = use8 && (p.nbq == 8 || (p.nbq == 4 && ix->i8v2_half)) && ((ix->i8v2 == 1 && !resident && nsteps >= 3) || (ix->i8v2 == 2 && nsteps >= 3));
+    // the 2-byte filter (dense clusters the int8 slack cannot separate, the int8 filter switched off): the same tile program on fp16 operands
+    const bool tile_f16 = CODD_SHADOW_F16 && CODD_MFMA16 && !use8 && p.nbq == 8 && nsteps % 6 == 0 && ix->f16_tile;
+    if (tile_f16) {
+        p.family = FilterProgram::TILE_F16;
+        // rows of 768 elements are 12 K-steps of 64, rows of 384 are 6: the static forms of the tile program ("i8_pair" = 2); 18, 24, ...: run-time cursors
+        if (nsteps == 12 && ix->i8_pair == 2) p.ts = 4;
+        else if (nsteps == 6 && ix->i8_pair == 2) p.ts = 3;
+        else p.ts = 2;
+    } else if (tile_v2) {
+        p.family = FilterProgram::TILE;
+        p.res = i8_tile_resident(nsteps, p.nbq) && ix->resident_q;  // the query block fits the four LDS slices: loaded once per workgroup
+        // tile structure: rows of 6, 12, ... K-steps (768 elements: the headline shape) run the staged program with one barrier
+        // per TWO K-steps; other multiples of 3 one per K-step; the rest the generic interval loop
+        // ("i8_pair" = 2, the default: rows of exactly 6 K-steps take that program with every cursor a compile-time constant)
+        const bool pair = nsteps % 6 == 0 && ix->i8_pair;
+        const bool static6 = nsteps == 6 && ix->i8_pair == 2;
+        if (p.res) p.ts = nsteps % 3 == 0 ? 1 : 0;
+        else if (static6) p.ts = 3;
+        else if (pair) p.ts = 2;
+        else p.ts = nsteps % 3 == 0 ? 1 : 0;
+    } else if (partial6) {  // 768 int8 elements: two of the six query slices stay in LDS
+        p.res = 2;
+    } else if (resident) {  // the whole int8 query block fits the LDS slices: loaded once per workgroup
+        p.res = 1;
+    }
+    return p;
+}
+
+// the arguments gemm_filter_kernel and i8_tile_kernel share, in their order; each launch expands them into its kernel's list
+struct FilterArgs {
+    const uint4* shadow;
+    const uint4* qfrag;
+    int64_t n;
+    int nsteps;
+    int64_t ntiles_run, tile_stride;
+    const float* thr;
+    u64* bucket_key;
+    u64* hits;
+    unsigned* hit_cnt;
+    int cap_q;
+    unsigned* flags;
+    const float* rscale;  // int8 operands only
+    const float* qscale;
+    const float2* bmeta;  // i8_tile_kernel only
+    float eb_scale;
+};
+
+// one launch of program `p` in pass MODE (MODE_SAMPLE or MODE_FILTER)
+template <int MODE>
+int launch_filter_program(const FilterProgram& p, dim3 grid, hipStream_t st, const FilterArgs& a) {
+    using No = std::false_type;
+    using Yes = std::true_type;
+    const dim3 block(kFilterThreads);
+    auto gemm = [&](auto nbq, auto el, auto res) {
+        return launch_kernel<gemm_filter_kernel<MODE, nbq, el, res>>(grid, block, filter_lds_bytes(MODE), st, a.shadow, a.qfrag, a.n, a.nsteps,
+                                                                     a.ntiles_run, a.tile_stride, a.thr, a.bucket_key, a.hits, a.hit_cnt, a.cap_q,
+                                                                     a.flags, (float*)nullptr, a.rscale, a.qscale);
+    };
+    auto tile = [&](auto ts, auto nqb, auto res, auto f16) {
+        return launch_kernel<i8_tile_kernel<MODE, ts, nqb, res, f16>>(grid, block, i8_lds_bytes(MODE), st, a.shadow, a.qfrag, a.n, a.nsteps,
+                                                                      a.ntiles_run, a.tile_stride, a.thr, a.bucket_key, a.hits, a.hit_cnt, a.cap_q,
+                                                                      a.flags, a.rscale, a.qscale, a.bmeta, a.eb_scale);
+    };
+    if (p.family == FilterProgram::TILE) {
+        return with_int<4, 8>(p.nbq, "bad query block count%s", [&](auto nbq) {
+            const IntC<2 * decltype(nbq)::value> nqb;
+            if constexpr (MODE == MODE_SAMPLE) {
+                // (the sample pass keeps the generic program: its tile-structured instantiations — the static six-step one too, tried in round 3 —
+                //  spill inside the loop: the fold's registers on top of two corpus ring slots in flight)
+                return p.res ? tile(IntC<0>{}, nqb, Yes{}, No{}) : tile(IntC<0>{}, nqb, No{}, No{});
+            } else if (p.res) {  // (the pair programs stage the query block)
+                return with_int<0, 1>(p.ts, "bad tile program%s", [&](auto ts) { return tile(ts, nqb, Yes{}, No{}); });
+            } else {
+                return with_int<0, 1, 2, 3>(p.ts, "bad tile program%s", [&](auto ts) { return tile(ts, nqb, No{}, No{}); });
+            }
+        });
+    }
+    if constexpr (MODE == MODE_FILTER) {
+        if (p.family == FilterProgram::TILE_F16)
+            return with_int<2, 3, 4>(p.ts, "bad tile program%s", [&](auto ts) { return tile(ts, IntC<16>{}, No{}, Yes{}); });
+    }
+    // GEMM (and TILE_F16's sample pass: 8 query blocks, 2-byte operands)
+    if (p.el == 0) return with_nbq(p.nbq, [&](auto nbq) { return gemm(nbq, IntC<0>{}, IntC<0>{}); });
+    if (p.res == 2) return gemm(IntC<4>{}, IntC<1>{}, IntC<2>{});
+    return with_nbq(p.nbq, [&](auto nbq) { return p.res ? gemm(nbq, IntC<1>{}, IntC<1>{}) : gemm(nbq, IntC<1>{}, IntC<0>{}); });
+}
+
+// The list-driven exact-scan fallback: at most one workgroup per compute unit (bounds the queue's partial buffer) and the
+// buffer of its per-block partials.
+int fallback_geometry(codd_knn_index* ix, int k, int64_t* blocks, int64_t* stride_q) {
+    int niter, rc;
+    if ((rc = scan_geometry(ix, ix->count, &niter, blocks)) != 0) return rc;
+    if (*blocks > ix->num_cus) *blocks = ix->num_cus;
+    *stride_q = *blocks * k;
+    return ensure_buf(&ix->fb_partial, &ix->fb_partial_cap, (int64_t)kTileQ * *stride_q);
+}
+
+// exact-scan fallback for the queries a pass queued (normally none), entirely on the device and in ONE launch: the scan walks
+// the queue (an empty queue costs one empty launch), its last block merges the per-block partials and writes each answer into
+// its query's slot.  No host round trip: the whole search stays asynchronous on `st`.
+int listed_fallback(codd_knn_index* ix, const float* qn, int k, uint32_t row_base, u64* keys_out, float* dist_out, int64_t* rows_out,
+                    hipStream_t st) {
+    int64_t blocks, stride_q;
+    int rc;
+    if ((rc = fallback_geometry(ix, k, &blocks, &stride_q)) != 0) return rc;
+    ScanArgs a{ix->rows, ix->count, ix->dpad, qn, 0, k, row_base, ix->fb_partial, stride_q, ix->ctl->fb_list, &ix->ctl->fb_count};
+    a.merge_done = &ix->ctl->fb_done;
+    a.merged_keys = keys_out;
+    a.merged_dist = dist_out;
+    a.merged_rows = rows_out;
+    a.count_total = &ix->dstats[2];
+    {
+        EvScope ev(ix, EV_SCAN, st);
+        rc = launch_scan(ix->dtype, 8, niter_of(ix), dim3((unsigned)blocks), st, a);
+    }
+    if (rc != 0) return rc;
+    HIP_TRY(hipGetLastError());
+    return CODD_KNN_OK;
+}
+
 // one pass of <= 256 queries through sample -> threshold -> filter -> finalize (+ exact fallback)
 // keys_out and / or (dist_out, rows_out): what the caller wants written per query (any may be null)
 int filter_pass(codd_knn_index* ix, const float* qn, int nq, int k, uint32_t row_base, u64* keys_out, float* dist_out, int64_t* rows_out,
@@ -2059,11 +2190,9 @@ int filter_pass(codd_knn_index* ix, const float* qn, int nq, int k, uint32_t row
     const uint4* shadow = use8 ? ix->shadow8 : ix->shadow;
     const uint4* qfrag = use8 ? ix->qfrag8 : ix->qfrag;
     const float* slack_q = use8 ? ix->qmeta + 256 : nullptr;  // int8: 2*eps per query, written by prep_queries8_kernel
+    const float* rscale = use8 ? ix->rscale : nullptr;
+    const float* qscale = use8 ? ix->qmeta : nullptr;
     if (use8) ix->stat_shadow8_passes++;
-    const bool resident = use8 && nsteps <= 4 && ix->resident_q;
-    // 65..128 queries only: with <= 64 the kernel is a byte stream (nothing to gain); with 8 query blocks the six-step body
-    // needs more than the 256 registers of a wave (hipcc spills, no gain measured)
-    const bool partial6 = use8 && nsteps == 6 && nq > 64 && nq <= 128 && ix->resident_q;
     const int64_t ntiles = (n + kTileRows - 1) / kTileRows;
     const int slots = k <= 64 ? 1 : 2;
     const float eps = filter_eps(ix);
@@ -2076,267 +2205,94 @@ int filter_pass(codd_knn_index* ix, const float* qn, int nq, int k, uint32_t row
         HIP_TRY(hipGetLastError());
     }
 
+    const FilterProgram prog = filter_program(ix, nq, nsteps, use8);
+    if (prog.family == FilterProgram::TILE) ix->stat_i8v2_passes++;
+    if (prog.family == FilterProgram::TILE_F16) ix->stat_f16_tile_passes++;
     // sample: every `stride`-th tile
-    const int nbq = nq <= 32 ? 1 : (nq <= 64 ? 2 : (nq <= 128 ? 4 : 8));  // 32-query blocks the GEMM multiplies
-    // full query blocks: the second-generation int8 kernel (filter_i8.h); rows whose query block fits the LDS keep the resident one
-    const bool tile_v2 = use8 && (nbq == 8 || (nbq == 4 && ix->i8v2_half)) && ((ix->i8v2 == 1 && !resident && nsteps >= 3) || (ix->i8v2 == 2 && nsteps >= 3));
-    if (tile_v2) ix->stat_i8v2_passes++;
-    // the 2-byte filter (dense clusters the int8 slack cannot separate, the int8 filter switched off): the same tile program on fp16 operands
-    const bool tile_f16 = CODD_SHADOW_F16 && CODD_MFMA16 && !use8 && nbq == 8 && nsteps % 6 == 0 && ix->f16_tile;
-    if (tile_f16) ix->stat_f16_tile_passes++;
-    const int64_t ts = sample_tile_count(ix, ntiles, k, use8, nbq);
+    const int64_t ts = sample_tile_count(ix, ntiles, k, use8, prog.nbq);
     const int64_t stride = ntiles / ts;
     {
         EvScope ev(ix, EV_SAMPLE, st);
-        const dim3 g((unsigned)(ts < ix->num_cus ? ts : ix->num_cus)), b(kFilterThreads);
-        const size_t lds = filter_lds_bytes(MODE_SAMPLE);
-#define CODD_LAUNCH_SAMPLE(NBQ)                                                                                              \
-    hipLaunchKernelGGL((gemm_filter_kernel<MODE_SAMPLE, NBQ>), g, b, lds, st, shadow, qfrag, n, nsteps, ts, stride, \
-                       nullptr, ix->bucket_max, nullptr, nullptr, 0, nullptr, nullptr)
-#define CODD_LAUNCH_SAMPLE8(NBQ)                                                                                             \
-    hipLaunchKernelGGL((gemm_filter_kernel<MODE_SAMPLE, NBQ, 1>), g, b, lds, st, shadow, qfrag, n, nsteps, ts, stride, \
-                       nullptr, ix->bucket_max, nullptr, nullptr, 0, nullptr, nullptr, ix->rscale, ix->qmeta)
-#define CODD_LAUNCH_SAMPLE8R(NBQ)                                                                                            \
-    hipLaunchKernelGGL((gemm_filter_kernel<MODE_SAMPLE, NBQ, 1, 1>), g, b, lds, st, shadow, qfrag, n, nsteps, ts, stride, \
-                       nullptr, ix->bucket_max, nullptr, nullptr, 0, nullptr, nullptr, ix->rscale, ix->qmeta)
-#define CODD_LAUNCH_SAMPLE8P(NBQ)                                                                                            \
-    hipLaunchKernelGGL((gemm_filter_kernel<MODE_SAMPLE, NBQ, 1, 2>), g, b, lds, st, shadow, qfrag, n, nsteps, ts, stride, \
-                       nullptr, ix->bucket_max, nullptr, nullptr, 0, nullptr, nullptr, ix->rscale, ix->qmeta)
-        if (tile_v2) {
-            // (the sample pass keeps the generic program: its tile-structured instantiations — the static six-step one too, tried in round 3 —
-            //  spill inside the loop: the fold's registers on top of two corpus ring slots in flight)
-#define CODD_LAUNCH_TILE8_SAMPLE(NQB, RES)                                                                                                    \
-    hipLaunchKernelGGL((i8_tile_kernel<MODE_SAMPLE, 0, NQB, RES>), g, b, i8_lds_bytes(MODE_SAMPLE), st, shadow, qfrag, n, nsteps, ts, stride, \
-                       nullptr, ix->bucket_max, nullptr, nullptr, 0, nullptr, ix->rscale, ix->qmeta)
-            const bool res = i8_tile_resident(nsteps, nbq) && ix->resident_q;  // the query block fits the four LDS slices: loaded once per workgroup
-            if (nbq == 8) {
-                if (res) CODD_LAUNCH_TILE8_SAMPLE(16, true);
-                else CODD_LAUNCH_TILE8_SAMPLE(16, false);
-            } else {  // 65..128 queries: half the query blocks
-                if (res) CODD_LAUNCH_TILE8_SAMPLE(8, true);
-                else CODD_LAUNCH_TILE8_SAMPLE(8, false);
-            }
-#undef CODD_LAUNCH_TILE8_SAMPLE
-        } else if (use8 && partial6) {  // 768 int8 elements: two of the six query slices stay in LDS
-            CODD_LAUNCH_SAMPLE8P(4);
-        } else if (use8 && resident) {  // the whole int8 query block fits the LDS slices: loaded once per workgroup
-            switch (nbq) {
-                case 1: CODD_LAUNCH_SAMPLE8R(1); break;
-                case 2: CODD_LAUNCH_SAMPLE8R(2); break;
-                case 4: CODD_LAUNCH_SAMPLE8R(4); break;
-                default: CODD_LAUNCH_SAMPLE8R(8); break;
-            }
-        } else if (use8) {
-            switch (nbq) {
-                case 1: CODD_LAUNCH_SAMPLE8(1); break;
-                case 2: CODD_LAUNCH_SAMPLE8(2); break;
-                case 4: CODD_LAUNCH_SAMPLE8(4); break;
-                default: CODD_LAUNCH_SAMPLE8(8); break;
-            }
-        } else
-        switch (nbq) {
-            case 1: CODD_LAUNCH_SAMPLE(1); break;
-            case 2: CODD_LAUNCH_SAMPLE(2); break;
-            case 4: CODD_LAUNCH_SAMPLE(4); break;
-            default: CODD_LAUNCH_SAMPLE(8); break;
-        }
-#undef CODD_LAUNCH_SAMPLE
-#undef CODD_LAUNCH_SAMPLE8
-#undef CODD_LAUNCH_SAMPLE8R
-#undef CODD_LAUNCH_SAMPLE8P
+        const dim3 g((unsigned)(ts < ix->num_cus ? ts : ix->num_cus));
+        const FilterArgs sa{shadow, qfrag, n, nsteps, ts, stride, nullptr, ix->bucket_max, nullptr, nullptr, 0, nullptr, rscale, qscale, nullptr, 1.0f};
+        if ((rc = launch_filter_program<MODE_SAMPLE>(prog, g, st, sa)) != 0) return rc;
     }
     HIP_TRY(hipGetLastError());
-    {
-        // thresholds anchored on the exact scores of the k best sampled rows (anchor_thr_kernel)
-        const int nch_t = ix->dpad / elems_per_chunk(ix->dtype);
-        const int niter_t = (nch_t + kWave - 1) / kWave;
-#define CODD_ANCHOR(DT, NI, SL)                                                                                                       \
-    hipLaunchKernelGGL((anchor_thr_kernel<DT, NI, SL>), dim3(kTileQ), dim3(kAnchorWaves * kWave), 0, st, ix->bucket_max, ts, nq, k, ix->rows, ix->dpad, qn, \
-                       eps, slack_q, ix->thr, use8 ? ix->thr + kTileQ : nullptr)
-#define CODD_ANCHOR_NI(DT, SL)                                \
-    switch (niter_t) {                                         \
-        case 1: CODD_ANCHOR(DT, 1, SL); break;                 \
-        case 2: CODD_ANCHOR(DT, 2, SL); break;                 \
-        case 3: CODD_ANCHOR(DT, 3, SL); break;                 \
-        case 4: CODD_ANCHOR(DT, 4, SL); break;                 \
-        CODD_WIDE_NITER_CASES: CODD_ANCHOR(DT, kWideRows, SL); break; \
-        default: return fail(CODD_KNN_ENOTSUP, "row too wide for the threshold kernel%s"); \
-    }
-        if (ix->dtype == DT_F32) { if (slots == 1) { CODD_ANCHOR_NI(DT_F32, 1) } else { CODD_ANCHOR_NI(DT_F32, 2) } }
-        else if (ix->dtype == DT_BF16) { if (slots == 1) { CODD_ANCHOR_NI(DT_BF16, 1) } else { CODD_ANCHOR_NI(DT_BF16, 2) } }
-        else { if (slots == 1) { CODD_ANCHOR_NI(DT_F16, 1) } else { CODD_ANCHOR_NI(DT_F16, 2) } }
-#undef CODD_ANCHOR_NI
-#undef CODD_ANCHOR
-    }
+    // thresholds anchored on the exact scores of the k best sampled rows (anchor_thr_kernel)
+    rc = with_row_form(ix, k, "row too wide for the threshold kernel%s", [&](auto dt, auto ni, auto sl) {
+        return launch_kernel<anchor_thr_kernel<dt, ni, sl>>(dim3(kTileQ), dim3(kAnchorWaves * kWave), 0, st, ix->bucket_max, ts, nq, k, ix->rows,
+                                                            ix->dpad, qn, eps, slack_q, ix->thr, use8 ? ix->thr + kTileQ : nullptr);
+    });
+    if (rc != 0) return rc;
     HIP_TRY(hipGetLastError());
     {
         EvScope ev(ix, EV_FILTER, st);
-        const dim3 g((unsigned)(ntiles < ix->num_cus ? ntiles : ix->num_cus)), b(kFilterThreads);
-        const size_t lds = filter_lds_bytes(MODE_FILTER);
-#define CODD_LAUNCH_FILTER(NBQ)                                                                                             \
-    hipLaunchKernelGGL((gemm_filter_kernel<MODE_FILTER, NBQ>), g, b, lds, st, shadow, qfrag, n, nsteps, ntiles,     \
-                       (int64_t)1, ix->thr, nullptr, ix->hits, ix->ctl->hit_cnt, ix->hit_cap_q, ix->ctl->flags, nullptr)
-#define CODD_LAUNCH_FILTER8(NBQ)                                                                                            \
-    hipLaunchKernelGGL((gemm_filter_kernel<MODE_FILTER, NBQ, 1>), g, b, lds, st, shadow, qfrag, n, nsteps, ntiles,  \
-                       (int64_t)1, ix->thr, nullptr, ix->hits, ix->ctl->hit_cnt, ix->hit_cap_q, ix->ctl->flags, nullptr, ix->rscale, ix->qmeta)
-#define CODD_LAUNCH_FILTER8R(NBQ)                                                                                           \
-    hipLaunchKernelGGL((gemm_filter_kernel<MODE_FILTER, NBQ, 1, 1>), g, b, lds, st, shadow, qfrag, n, nsteps, ntiles, \
-                       (int64_t)1, ix->thr, nullptr, ix->hits, ix->ctl->hit_cnt, ix->hit_cap_q, ix->ctl->flags, nullptr, ix->rscale, ix->qmeta)
-#define CODD_LAUNCH_FILTER8P(NBQ)                                                                                           \
-    hipLaunchKernelGGL((gemm_filter_kernel<MODE_FILTER, NBQ, 1, 2>), g, b, lds, st, shadow, qfrag, n, nsteps, ntiles, \
-                       (int64_t)1, ix->thr, nullptr, ix->hits, ix->ctl->hit_cnt, ix->hit_cap_q, ix->ctl->flags, nullptr, ix->rscale, ix->qmeta)
-        if (tile_f16) {
-            // (thr doubles as the 256 readable bytes the kernel's per-tile metadata request needs; fp16 operands carry no scales)
-            // rows of 768 elements are 12 K-steps of 64, rows of 384 are 6: the static forms of the tile program ("i8_pair" = 2); 18, 24, ...: run-time cursors
-#define CODD_LAUNCH_TILE16(S3)                                                                                                                            \
-    hipLaunchKernelGGL((i8_tile_kernel<MODE_FILTER, S3, 16, false, true>), g, b, i8_lds_bytes(MODE_FILTER), st, shadow, qfrag, n, nsteps, ntiles, (int64_t)1, \
-                       ix->thr, nullptr, ix->hits, ix->ctl->hit_cnt, ix->hit_cap_q, ix->ctl->flags, nullptr, nullptr, reinterpret_cast<const float2*>(ix->thr), 0.0f)
-            if (nsteps == 12 && ix->i8_pair == 2) CODD_LAUNCH_TILE16(4);
-            else if (nsteps == 6 && ix->i8_pair == 2) CODD_LAUNCH_TILE16(3);
-            else CODD_LAUNCH_TILE16(2);
-#undef CODD_LAUNCH_TILE16
-        } else if (tile_v2) {
+        const dim3 g((unsigned)(ntiles < ix->num_cus ? ntiles : ix->num_cus));
+        FilterArgs fa{shadow, qfrag, n, nsteps, ntiles, 1, ix->thr, nullptr, ix->hits, ix->ctl->hit_cnt, ix->hit_cap_q, ix->ctl->flags, rscale, qscale, nullptr, 0.0f};
+        if (prog.family == FilterProgram::TILE) {
+            // the per-block bound (per_block & 1): thr0[q] and the blocks' error norms
+            fa.thr = (ix->per_block & 1) ? ix->thr + kTileQ : ix->thr;
+            fa.bmeta = ix->bmeta;
+            fa.eb_scale = (ix->per_block & 1) ? 1.0f : 0.0f;
 #ifdef CODD_I8_EXP_STAMPS  // (diagnostic build: the filter pass writes its per-wave phase stamps over the sample's bucket keys, which anchor_thr has consumed)
-#define CODD_STAMP_BUF ix->bucket_max
-#else
-#define CODD_STAMP_BUF nullptr
+            fa.bucket_key = ix->bucket_max;
 #endif
-#define CODD_LAUNCH_TILE8(S3, NQB, RES)                                                                                                              \
-    hipLaunchKernelGGL((i8_tile_kernel<MODE_FILTER, S3, NQB, RES>), g, b, i8_lds_bytes(MODE_FILTER), st, shadow, qfrag, n, nsteps, ntiles, (int64_t)1, \
-                       (ix->per_block & 1) ? ix->thr + kTileQ : ix->thr, CODD_STAMP_BUF, ix->hits, ix->ctl->hit_cnt, ix->hit_cap_q, ix->ctl->flags, ix->rscale, ix->qmeta, \
-                       ix->bmeta, (ix->per_block & 1) ? 1.0f : 0.0f)
-            const bool res = i8_tile_resident(nsteps, nbq) && ix->resident_q;
-            // tile structure: rows of 6, 12, ... K-steps (768 elements: the headline shape) run the staged program with one barrier
-            // per TWO K-steps; other multiples of 3 one per K-step; the rest the generic interval loop
-            // ("i8_pair" = 2, the default: rows of exactly 6 K-steps take that program with every cursor a compile-time constant)
-            const bool pair = nsteps % 6 == 0 && ix->i8_pair;
-            const bool static6 = nsteps == 6 && ix->i8_pair == 2;
-            if (nbq == 8) {
-                if (res) { if (nsteps % 3 == 0) CODD_LAUNCH_TILE8(1, 16, true); else CODD_LAUNCH_TILE8(0, 16, true); }
-                else if (static6) CODD_LAUNCH_TILE8(3, 16, false);
-                else if (pair) CODD_LAUNCH_TILE8(2, 16, false);
-                else { if (nsteps % 3 == 0) CODD_LAUNCH_TILE8(1, 16, false); else CODD_LAUNCH_TILE8(0, 16, false); }
-            } else {
-                if (res) { if (nsteps % 3 == 0) CODD_LAUNCH_TILE8(1, 8, true); else CODD_LAUNCH_TILE8(0, 8, true); }
-                else if (static6) CODD_LAUNCH_TILE8(3, 8, false);
-                else if (pair) CODD_LAUNCH_TILE8(2, 8, false);
-                else { if (nsteps % 3 == 0) CODD_LAUNCH_TILE8(1, 8, false); else CODD_LAUNCH_TILE8(0, 8, false); }
-            }
-#undef CODD_LAUNCH_TILE8
-        } else if (use8 && partial6) {
-            CODD_LAUNCH_FILTER8P(4);
-        } else if (use8 && resident) {
-            switch (nbq) {
-                case 1: CODD_LAUNCH_FILTER8R(1); break;
-                case 2: CODD_LAUNCH_FILTER8R(2); break;
-                case 4: CODD_LAUNCH_FILTER8R(4); break;
-                default: CODD_LAUNCH_FILTER8R(8); break;
-            }
-        } else if (use8) {
-            switch (nbq) {
-                case 1: CODD_LAUNCH_FILTER8(1); break;
-                case 2: CODD_LAUNCH_FILTER8(2); break;
-                case 4: CODD_LAUNCH_FILTER8(4); break;
-                default: CODD_LAUNCH_FILTER8(8); break;
-            }
-        } else
-        switch (nbq) {
-            case 1: CODD_LAUNCH_FILTER(1); break;
-            case 2: CODD_LAUNCH_FILTER(2); break;
-            case 4: CODD_LAUNCH_FILTER(4); break;
-            default: CODD_LAUNCH_FILTER(8); break;
+        } else if (prog.family == FilterProgram::TILE_F16) {
+            // (thr doubles as the 256 readable bytes the kernel's per-tile metadata request needs; fp16 operands carry no scales)
+            fa.bmeta = reinterpret_cast<const float2*>(ix->thr);
         }
-#undef CODD_LAUNCH_FILTER
-#undef CODD_LAUNCH_FILTER8
-#undef CODD_LAUNCH_FILTER8R
-#undef CODD_LAUNCH_FILTER8P
+        if ((rc = launch_filter_program<MODE_FILTER>(prog, g, st, fa)) != 0) return rc;
     }
     HIP_TRY(hipGetLastError());
-    const int nchunks = ix->dpad / elems_per_chunk(ix->dtype);
-    const int niter = (nchunks + kWave - 1) / kWave;
+    const int niter = niter_of(ix);
     // the int8 filter leaves thousands of survivors per query and is only used for a handful of queries: share each
     // query's re-scoring out between several workgroups, then merge their lists
     const int nparts = use8 ? (nq <= 8 ? 16 : (nq <= 32 ? 8 : (nq <= 64 ? 4 : 1))) : 1;
     ix->stat_last_finalize_parts = nparts;
     if (nparts > 1 && (rc = ensure_buf(&ix->partial, &ix->partial_cap, (int64_t)nq * nparts * k)) != 0) return rc;
+    const float2* bm = slack_q && (ix->per_block & 2) ? ix->bmeta : nullptr;  // (the int8 passes: slack per 32-row block)
+    FilterCtl* c = ix->ctl;
     // one list slot per lane and one workgroup per query (the large batches): finalize and the exact-scan fallback share ONE
     // launch — the scan workgroups derive the queue from the hit counters and leave at once when it is empty
     if (slots == 1 && nparts == 1 && ix->fuse_fallback && niter <= 4 && !(ix->dtype != DT_F32 && niter == 4)) {  // (2-byte rows above 1536 elements: the fused kernel spills; wide rows take the separate fallback launch)
-        int nit;
-        int64_t blocks;
-        if ((rc = scan_geometry(ix, n, &nit, &blocks)) != 0) return rc;
-        if (blocks > ix->num_cus) blocks = ix->num_cus;  // bounds the queue's partial buffer
-        const int64_t stride_q = blocks * k;
-        if ((rc = ensure_buf(&ix->fb_partial, &ix->fb_partial_cap, (int64_t)kTileQ * stride_q)) != 0) return rc;
+        int64_t blocks, stride_q;
+        if ((rc = fallback_geometry(ix, k, &blocks, &stride_q)) != 0) return rc;
         EvScope ev(ix, EV_FINALIZE, st);
-        const float2* bm = slack_q && (ix->per_block & 2) ? ix->bmeta : nullptr;
-        FilterCtl* c = ix->ctl;
         const dim3 grid((unsigned)(nq + blocks), 1);
         const size_t lds = (size_t)(kFinThreads / kWave) * 4 * kWave * sizeof(u64);   // the scan role's lists: 8 waves x 4 queries x 64 keys
-#define CODD_FIN_FB(DT, NI)                                                                                                                                    \
-    hipLaunchKernelGGL((finalize_fb_kernel<DT, NI>), grid, dim3(kFinThreads), lds, st, ix->rows, ix->dpad, qn, ix->hits, c->hit_cnt, ix->hit_cap_q, c->flags, k, \
-                       2.0f * eps, row_base, keys_out, ix->dstats, slack_q, (u64*)nullptr, dist_out, rows_out, bm, nq, n, ix->fb_partial, stride_q, &c->fb_done)
-#define CODD_FIN_FB_NI(DT)                          \
-    switch (niter) {                                \
-        case 1: CODD_FIN_FB(DT, 1); break;          \
-        case 2: CODD_FIN_FB(DT, 2); break;          \
-        case 3: CODD_FIN_FB(DT, 3); break;          \
-        case 4: CODD_FIN_FB(DT, 4); break;          \
-        default: return fail(CODD_KNN_ENOTSUP, "row too wide for the finalize kernel%s"); \
-    }
-        if (ix->dtype == DT_F32) { CODD_FIN_FB_NI(DT_F32) }
-        else if (ix->dtype == DT_BF16) { CODD_FIN_FB_NI(DT_BF16) }
-        else { CODD_FIN_FB_NI(DT_F16) }
-#undef CODD_FIN_FB_NI
-#undef CODD_FIN_FB
+        rc = with_dtype(ix->dtype, [&](auto dt) {
+            return with_niter(niter, "row too wide for the finalize kernel%s", [&](auto ni) {
+                if constexpr (decltype(ni)::value == kWideRows) {
+                    return fail(CODD_KNN_ENOTSUP, "row too wide for the finalize kernel%s");
+                } else {
+                    return launch_kernel<finalize_fb_kernel<decltype(dt)::value, ni>>(
+                        grid, dim3(kFinThreads), lds, st, ix->rows, ix->dpad, qn, ix->hits, c->hit_cnt, ix->hit_cap_q, c->flags, k, 2.0f * eps, row_base,
+                        keys_out, ix->dstats, slack_q, (u64*)nullptr, dist_out, rows_out, bm, nq, n, ix->fb_partial, stride_q, &c->fb_done);
+                }
+            });
+        });
+        if (rc != 0) return rc;
         HIP_TRY(hipGetLastError());
         return CODD_KNN_OK;
     }
     {
         EvScope ev(ix, EV_FINALIZE, st);
-        switch (ix->dtype) {
-            case DT_F32: rc = launch_finalize<DT_F32>(niter, slots, nq, st, ix, qn, k, 2.0f * eps, row_base, keys_out, slack_q, nparts, ix->partial, dist_out, rows_out); break;
-            case DT_BF16: rc = launch_finalize<DT_BF16>(niter, slots, nq, st, ix, qn, k, 2.0f * eps, row_base, keys_out, slack_q, nparts, ix->partial, dist_out, rows_out); break;
-            default: rc = launch_finalize<DT_F16>(niter, slots, nq, st, ix, qn, k, 2.0f * eps, row_base, keys_out, slack_q, nparts, ix->partial, dist_out, rows_out); break;
-        }
+        rc = with_row_form(ix, k, "row too wide for the finalize kernel%s", [&](auto dt, auto ni, auto sl) {
+            return launch_kernel<finalize_kernel<dt, ni, sl>>(dim3(nq, nparts), dim3(kFinThreads), 0, st, ix->rows, ix->dpad, qn, ix->hits, c->hit_cnt,
+                                                              ix->hit_cap_q, c->flags, k, 2.0f * eps, row_base, keys_out, &c->fb_count, c->fb_list,
+                                                              ix->dstats, slack_q, ix->partial, dist_out, rows_out, bm);
+        });
     }
     if (rc != 0) return rc;
+    HIP_TRY(hipGetLastError());
     if (nparts > 1 && (rc = launch_merge(ix->partial, nq, (int64_t)nparts * k, (int64_t)nparts * k, k, keys_out, dist_out, rows_out, st)) != 0) return rc;
-
-    // exact-scan fallback for the queries finalize queued (normally none), entirely on the device and in ONE launch: the
-    // scan walks the queue (an empty queue costs one empty launch), its last block merges the per-block partials and
-    // writes each answer into its query's slot.  No host round trip: the whole search stays asynchronous on `st`.
-    {
-        int nit;
-        int64_t blocks;
-        if ((rc = scan_geometry(ix, n, &nit, &blocks)) != 0) return rc;
-        if (blocks > ix->num_cus) blocks = ix->num_cus;  // bounds the queue's partial buffer
-        const int64_t stride_q = blocks * k;
-        if ((rc = ensure_buf(&ix->fb_partial, &ix->fb_partial_cap, (int64_t)kTileQ * stride_q)) != 0) return rc;
-        ScanArgs a{ix->rows, n, ix->dpad, qn, 0, k, row_base, ix->fb_partial, stride_q, ix->ctl->fb_list, &ix->ctl->fb_count};
-        a.merge_done = &ix->ctl->fb_done;
-        a.merged_keys = keys_out;
-        a.merged_dist = dist_out;
-        a.merged_rows = rows_out;
-        a.count_total = &ix->dstats[2];
-        {
-            EvScope ev(ix, EV_SCAN, st);
-            switch (ix->dtype) {
-                case DT_F32: rc = launch_scan_nb<DT_F32>(8, nit, slots, dim3((unsigned)blocks), st, a); break;
-                case DT_BF16: rc = launch_scan_nb<DT_BF16>(8, nit, slots, dim3((unsigned)blocks), st, a); break;
-                default: rc = launch_scan_nb<DT_F16>(8, nit, slots, dim3((unsigned)blocks), st, a); break;
-            }
-        }
-        if (rc != 0) return rc;
-        HIP_TRY(hipGetLastError());
-    }
-    return CODD_KNN_OK;
+    return listed_fallback(ix, qn, k, row_base, keys_out, dist_out, rows_out, st);
 }
 
 // ---- one launch for a single query (small_batch_kernel) + the (normally empty) list-driven fallback scan ----
 template <int DT, int NS>
-void launch_small_batch(int64_t nunits, hipStream_t st, const codd_knn_index* ix, const float* dev_queries, int k, uint32_t row_base, u64* cand,
-                        u64* out_keys, float* out_dist, int64_t* out_rows) {
+int launch_small_batch(int64_t nunits, hipStream_t st, const codd_knn_index* ix, const float* dev_queries, int k, uint32_t row_base, u64* cand,
+                       u64* out_keys, float* out_dist, int64_t* out_rows) {
     constexpr int E = DT == DT_F32 ? 4 : 8;
     constexpr int NITER = (NS * 128 / E + kWave - 1) / kWave;  // chunks of the PADDED row per lane (dpad <= NS * 128)
     constexpr int kWavesPerWg = kSbThreads / kWave;
@@ -2354,20 +2310,9 @@ void launch_small_batch(int64_t nunits, hipStream_t st, const codd_knn_index* ix
     const dim3 grid((unsigned)G);
     u64* dropmax = cand + G * kWavesPerWg * kSbKeep;
     FilterCtl* c = ix->ctl;
-    hipLaunchKernelGGL((small_batch_kernel<DT, NITER, NS>), grid, dim3(kSbThreads), 0, st, ix->shadow8, ix->bmeta, ix->rows, ix->count, ix->dim, ix->dpad,
-                       dev_queries, k, row_base, ix->eps_r_bits, ix->qn, cand, dropmax, &c->sb_ticket, &c->fb_count, c->fb_list, out_keys, out_dist, out_rows,
-                       ix->dstats);
-}
-template <int DT>
-bool launch_small_batch_ns(int ns, int64_t nunits, hipStream_t st, const codd_knn_index* ix, const float* dev_queries, int k, uint32_t row_base, u64* cand,
-                           u64* out_keys, float* out_dist, int64_t* out_rows) {
-    switch (ns) {
-        case 3: launch_small_batch<DT, 3>(nunits, st, ix, dev_queries, k, row_base, cand, out_keys, out_dist, out_rows); return true;
-        case 4: launch_small_batch<DT, 4>(nunits, st, ix, dev_queries, k, row_base, cand, out_keys, out_dist, out_rows); return true;
-        case 6: launch_small_batch<DT, 6>(nunits, st, ix, dev_queries, k, row_base, cand, out_keys, out_dist, out_rows); return true;
-        case 8: launch_small_batch<DT, 8>(nunits, st, ix, dev_queries, k, row_base, cand, out_keys, out_dist, out_rows); return true;
-        default: return false;
-    }
+    return launch_kernel<small_batch_kernel<DT, NITER, NS>>(grid, dim3(kSbThreads), 0, st, ix->shadow8, ix->bmeta, ix->rows, ix->count, ix->dim, ix->dpad,
+                                                            dev_queries, k, row_base, ix->eps_r_bits, ix->qn, cand, dropmax, &c->sb_ticket, &c->fb_count,
+                                                            c->fb_list, out_keys, out_dist, out_rows, ix->dstats);
 }
 bool small_batch_applies(const codd_knn_index* ix, int B, int k) {
     const int ns = dpad8_of(ix) / 128;
@@ -2386,39 +2331,16 @@ int small_batch_search(codd_knn_index* ix, const float* dev_queries, int B, int 
     ix->stat_small_batch++;
     {
         EvScope ev(ix, EV_FILTER, st);
-        bool ok;
-        switch (ix->dtype) {
-            case DT_F32: ok = launch_small_batch_ns<DT_F32>(ns, nunits, st, ix, dev_queries, k, row_base, cand, out_keys, out_dist, out_rows); break;
-            case DT_BF16: ok = launch_small_batch_ns<DT_BF16>(ns, nunits, st, ix, dev_queries, k, row_base, cand, out_keys, out_dist, out_rows); break;
-            default: ok = launch_small_batch_ns<DT_F16>(ns, nunits, st, ix, dev_queries, k, row_base, cand, out_keys, out_dist, out_rows); break;
-        }
-        if (!ok) return fail(CODD_KNN_EINVAL, "small batch: unsupported row width%s");
+        rc = with_dtype(ix->dtype, [&](auto dt) {
+            return with_int<3, 4, 6, 8>(ns, "small batch: unsupported row width%s", [&](auto nsc) {
+                return launch_small_batch<decltype(dt)::value, nsc>(nunits, st, ix, dev_queries, k, row_base, cand, out_keys, out_dist, out_rows);
+            });
+        });
     }
+    if (rc != 0) return rc;
     HIP_TRY(hipGetLastError());
     // a query the margin test could not clear (normally none): the list-driven exact scan, its last block merges
-    {
-        int nit;
-        int64_t blocks;
-        if ((rc = scan_geometry(ix, n, &nit, &blocks)) != 0) return rc;
-        if (blocks > ix->num_cus) blocks = ix->num_cus;
-        const int64_t stride_q = blocks * k;
-        if ((rc = ensure_buf(&ix->fb_partial, &ix->fb_partial_cap, (int64_t)kTileQ * stride_q)) != 0) return rc;
-        ScanArgs a{ix->rows, n, ix->dpad, ix->qn, 0, k, row_base, ix->fb_partial, stride_q, ix->ctl->fb_list, &ix->ctl->fb_count};
-        a.merge_done = &ix->ctl->fb_done;
-        a.merged_keys = out_keys;
-        a.merged_dist = out_dist;
-        a.merged_rows = out_rows;
-        a.count_total = &ix->dstats[2];
-        EvScope ev(ix, EV_SCAN, st);
-        switch (ix->dtype) {
-            case DT_F32: rc = launch_scan_nb<DT_F32>(8, nit, 1, dim3((unsigned)blocks), st, a); break;
-            case DT_BF16: rc = launch_scan_nb<DT_BF16>(8, nit, 1, dim3((unsigned)blocks), st, a); break;
-            default: rc = launch_scan_nb<DT_F16>(8, nit, 1, dim3((unsigned)blocks), st, a); break;
-        }
-        if (rc != 0) return rc;
-        HIP_TRY(hipGetLastError());
-    }
-    return CODD_KNN_OK;
+    return listed_fallback(ix, ix->qn, k, row_base, out_keys, out_dist, out_rows, st);
 }
 
 bool filter_applies(const codd_knn_index* ix, int B, int k) {
@@ -2770,11 +2692,9 @@ int codd_knn_load_rows(codd_knn_index* ix, int64_t first_slot, const void* host_
     hipError_t e = hipMemset(dev_bits, 0, sizeof(unsigned));
     const dim3 grid((unsigned)((n + 3) / 4)), block(256);
     if (e == hipSuccess) {
-        switch (ix->dtype) {
-            case DT_F32: hipLaunchKernelGGL(row_norm_check_kernel<DT_F32>, grid, block, 0, nullptr, ix->rows, first_slot, n, ix->dpad, dev_bits); break;
-            case DT_BF16: hipLaunchKernelGGL(row_norm_check_kernel<DT_BF16>, grid, block, 0, nullptr, ix->rows, first_slot, n, ix->dpad, dev_bits); break;
-            default: hipLaunchKernelGGL(row_norm_check_kernel<DT_F16>, grid, block, 0, nullptr, ix->rows, first_slot, n, ix->dpad, dev_bits); break;
-        }
+        (void)with_dtype(ix->dtype, [&](auto dt) {
+            return launch_kernel<row_norm_check_kernel<dt>>(grid, block, 0, nullptr, ix->rows, first_slot, n, ix->dpad, dev_bits);
+        });
         e = hipGetLastError();
     }
     float worst = 0.0f;
@@ -2864,9 +2784,10 @@ int codd_knn_approx_scores(codd_knn_index* ix, const float* dev_queries, int B, 
                            (int)(sizeof(FilterCtl) / 4), 1.0f);
         const int64_t ntiles8 = (ix->count + kTileRows - 1) / kTileRows;
         const int64_t g8 = ntiles8 < ix->num_cus ? ntiles8 : ix->num_cus;
-        hipLaunchKernelGGL((gemm_filter_kernel<MODE_DUMP, 1, 1>), dim3((unsigned)g8), dim3(kFilterThreads), filter_lds_bytes(MODE_DUMP), st,
-                           ix->shadow8, ix->qfrag8, ix->count, dpad8 / 128, ntiles8, (int64_t)1, nullptr, nullptr, nullptr, nullptr, 0, nullptr,
-                           dev_scores, ix->rscale, ix->qmeta);
+        if ((rc = launch_kernel<gemm_filter_kernel<MODE_DUMP, 1, 1>>(dim3((unsigned)g8), dim3(kFilterThreads), filter_lds_bytes(MODE_DUMP), st,
+                                                                     ix->shadow8, ix->qfrag8, ix->count, dpad8 / 128, ntiles8, (int64_t)1, nullptr, nullptr,
+                                                                     nullptr, nullptr, 0, nullptr, dev_scores, ix->rscale, ix->qmeta)) != 0)
+            return rc;
         HIP_TRY(hipGetLastError());
         return CODD_KNN_OK;
     }
@@ -2876,8 +2797,10 @@ int codd_knn_approx_scores(codd_knn_index* ix, const float* dev_queries, int B, 
                        (unsigned*)nullptr, 0);
     const int64_t ntiles = (ix->count + kTileRows - 1) / kTileRows;
     const int64_t g = ntiles < ix->num_cus ? ntiles : ix->num_cus;
-    hipLaunchKernelGGL((gemm_filter_kernel<MODE_DUMP, 8>), dim3((unsigned)g), dim3(kFilterThreads), filter_lds_bytes(MODE_DUMP), st, ix->shadow,
-                       ix->qfrag, ix->count, ix->dpad / 64, ntiles, (int64_t)1, nullptr, nullptr, nullptr, nullptr, 0, nullptr, dev_scores);
+    if ((rc = launch_kernel<gemm_filter_kernel<MODE_DUMP, 8>>(dim3((unsigned)g), dim3(kFilterThreads), filter_lds_bytes(MODE_DUMP), st, ix->shadow,
+                                                              ix->qfrag, ix->count, ix->dpad / 64, ntiles, (int64_t)1, nullptr, nullptr, nullptr, nullptr, 0,
+                                                              nullptr, dev_scores, nullptr, nullptr)) != 0)
+        return rc;
     HIP_TRY(hipGetLastError());
     return CODD_KNN_OK;
 }
@@ -2893,11 +2816,10 @@ int codd_knn_copy_rows_f32(codd_knn_index* ix, int64_t first, int64_t n, float* 
     // writer on another stream is ordered behind it (reader_done)
     int rc;
     if ((rc = wait_rows(ix, st)) != 0) return rc;
-    switch (ix->dtype) {
-        case DT_F32: hipLaunchKernelGGL(widen_rows_kernel<DT_F32>, grid, block, 0, st, ix->rows, first, n, ix->dim, ix->dpad, dev_out); break;
-        case DT_BF16: hipLaunchKernelGGL(widen_rows_kernel<DT_BF16>, grid, block, 0, st, ix->rows, first, n, ix->dim, ix->dpad, dev_out); break;
-        default: hipLaunchKernelGGL(widen_rows_kernel<DT_F16>, grid, block, 0, st, ix->rows, first, n, ix->dim, ix->dpad, dev_out); break;
-    }
+    rc = with_dtype(ix->dtype, [&](auto dt) {
+        return launch_kernel<widen_rows_kernel<dt>>(grid, block, 0, st, ix->rows, first, n, ix->dim, ix->dpad, dev_out);
+    });
+    if (rc != 0) return rc;
     HIP_TRY(hipGetLastError());
     if (!ix->reader_done) HIP_TRY(hipEventCreateWithFlags(&ix->reader_done, hipEventDisableTiming));
     if (ix->reader_event_set && ix->reader_stream != st) HIP_TRY(hipStreamWaitEvent(st, ix->reader_done, 0));  // (one event: chain the readers too)
@@ -3000,9 +2922,7 @@ int codd_knn_ivf_search(codd_knn_index* ix, const float* dev_queries, int B, int
     if ((rc = launch_normalize(DT_F32, dev_queries, B, ix->dim, ix->dpad, 1, nullptr, 0, ix->qn, nullptr, st)) != 0) return rc;
     // 1. coarse: the nprobe best lists per query (exact scan of the centroids, tiny)
     if ((rc = exact_scan(ix->coarse, ix->qn, B, nprobe, 0u, ix->probe_keys, nullptr, nullptr, st)) != 0) return rc;
-    const int nchunks = ix->dpad / elems_per_chunk(ix->dtype);
-    const int niter = (nchunks + kWave - 1) / kWave;
-    const int slots = k <= 64 ? 1 : 2;
+    const int niter = niter_of(ix);
     // 2a. a batch with enough (query, list) pairs to fill the chip without splitting lists: group the pairs by list on the
     //     device and scan every probed list once per kIvfNB of its queries (ivf_scan_shared_kernel)
     const int64_t npairs = (int64_t)B * nprobe;
@@ -3027,23 +2947,12 @@ int codd_knn_ivf_search(codd_knn_index* ix, const float* dev_queries, int B, int
         hipLaunchKernelGGL(ivf_pair_scatter_kernel, dim3(pb), dim3(256), 0, st, ix->probe_keys, (int)npairs, pair_start, cnt, sorted_pairs);
         // work items <= sum over lists of ceil(pairs / kIvfNB) <= min(pairs, lists + pairs / kIvfNB): the grid covers the bound, surplus workgroups leave at once
         const int64_t bound = std::min<int64_t>(npairs, (int64_t)nlist + npairs / kIvfNB);
-#define CODD_IVFS_LAUNCH(DT, NI, SL)                                                                                              \
-    hipLaunchKernelGGL((ivf_scan_shared_kernel<DT, NI, SL>), dim3((unsigned)bound), dim3(256), 0, st, ix->rows_ivf, ix->ivf_ids, \
-                       ix->ivf_offsets, pair_start, item_start, sorted_pairs, nlist, nprobe, ix->dpad, ix->qn, k, row_base, ix->ivf_partial)
-#define CODD_IVFS_NITER(DT, SL)                                       \
-    switch (niter) {                                                  \
-        case 1: CODD_IVFS_LAUNCH(DT, 1, SL); break;                   \
-        case 2: CODD_IVFS_LAUNCH(DT, 2, SL); break;                   \
-        case 3: CODD_IVFS_LAUNCH(DT, 3, SL); break;                   \
-        case 4: CODD_IVFS_LAUNCH(DT, 4, SL); break;                   \
-        CODD_WIDE_NITER_CASES: CODD_IVFS_LAUNCH(DT, kWideRows, SL); break; \
-        default: return fail(CODD_KNN_ENOTSUP, "row too wide for the IVF scan%s"); \
-    }
-        if (ix->dtype == DT_F32) { if (slots == 1) { CODD_IVFS_NITER(DT_F32, 1) } else { CODD_IVFS_NITER(DT_F32, 2) } }
-        else if (ix->dtype == DT_BF16) { if (slots == 1) { CODD_IVFS_NITER(DT_BF16, 1) } else { CODD_IVFS_NITER(DT_BF16, 2) } }
-        else { if (slots == 1) { CODD_IVFS_NITER(DT_F16, 1) } else { CODD_IVFS_NITER(DT_F16, 2) } }
-#undef CODD_IVFS_NITER
-#undef CODD_IVFS_LAUNCH
+        rc = with_row_form(ix, k, "row too wide for the IVF scan%s", [&](auto dt, auto ni, auto sl) {
+            return launch_kernel<ivf_scan_shared_kernel<dt, ni, sl>>(dim3((unsigned)bound), dim3(256), 0, st, ix->rows_ivf, ix->ivf_ids, ix->ivf_offsets,
+                                                                     pair_start, item_start, sorted_pairs, nlist, nprobe, ix->dpad, ix->qn, k, row_base,
+                                                                     ix->ivf_partial);
+        });
+        if (rc != 0) return rc;
         HIP_TRY(hipGetLastError());
         }
         const int64_t ms = (int64_t)nprobe * k;
@@ -3055,26 +2964,14 @@ int codd_knn_ivf_search(codd_knn_index* ix, const float* dev_queries, int B, int
     const int64_t m = (int64_t)nprobe * split * k;
     if ((rc = ensure_buf(&ix->ivf_partial, &ix->ivf_partial_cap, (int64_t)B * m)) != 0) return rc;
     const dim3 grid((unsigned)(nprobe * split), (unsigned)B), block(256);
-#define CODD_IVF_LAUNCH(DT, NI, SL)                                                                                          \
-    hipLaunchKernelGGL((ivf_scan_kernel<DT, NI, SL>), grid, block, 0, st, ix->rows_ivf, ix->ivf_ids, ix->ivf_offsets,       \
-                       ix->probe_keys, nprobe, split, ix->dpad, ix->qn, k, row_base, ix->ivf_partial)
-#define CODD_IVF_NITER(DT, SL)                                       \
-    switch (niter) {                                                  \
-        case 1: CODD_IVF_LAUNCH(DT, 1, SL); break;                    \
-        case 2: CODD_IVF_LAUNCH(DT, 2, SL); break;                    \
-        case 3: CODD_IVF_LAUNCH(DT, 3, SL); break;                    \
-        case 4: CODD_IVF_LAUNCH(DT, 4, SL); break;                    \
-        CODD_WIDE_NITER_CASES: CODD_IVF_LAUNCH(DT, kWideRows, SL); break; \
-        default: return fail(CODD_KNN_ENOTSUP, "row too wide for the IVF scan%s"); \
-    }
     {
         EvScope ev(ix, EV_SCAN, st);
-        if (ix->dtype == DT_F32) { if (slots == 1) { CODD_IVF_NITER(DT_F32, 1) } else { CODD_IVF_NITER(DT_F32, 2) } }
-        else if (ix->dtype == DT_BF16) { if (slots == 1) { CODD_IVF_NITER(DT_BF16, 1) } else { CODD_IVF_NITER(DT_BF16, 2) } }
-        else { if (slots == 1) { CODD_IVF_NITER(DT_F16, 1) } else { CODD_IVF_NITER(DT_F16, 2) } }
+        rc = with_row_form(ix, k, "row too wide for the IVF scan%s", [&](auto dt, auto ni, auto sl) {
+            return launch_kernel<ivf_scan_kernel<dt, ni, sl>>(grid, block, 0, st, ix->rows_ivf, ix->ivf_ids, ix->ivf_offsets, ix->probe_keys, nprobe, split,
+                                                              ix->dpad, ix->qn, k, row_base, ix->ivf_partial);
+        });
     }
-#undef CODD_IVF_NITER
-#undef CODD_IVF_LAUNCH
+    if (rc != 0) return rc;
     HIP_TRY(hipGetLastError());
     // 3. top-k of the nprobe*split partial lists
     return launch_merge(ix->ivf_partial, B, m, m, k, (u64*)dev_keys, dev_dist, dev_rows, st);
