@@ -20,6 +20,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include <algorithm>
 #include <atomic>
 #include <mutex>
 #include <new>
@@ -1263,6 +1264,275 @@ __global__ __launch_bounds__(256) void ivf_scan_shared_kernel(const void* __rest
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Scopes: a 32-bit label per row slot, 0 = none.  A scoped query sees only the rows of its scope.
+//   scope_of[capacity]          the label of every slot (codd_knn_set_scopes_host)
+//   scope_perm[count]           row slots grouped by scope, scope_offsets[nlist + 1] where each group starts (nlist = highest
+//                               scope + 1; group 0 = the unlabelled rows).  Built lazily by the first scoped search after labels
+//                               or the row count changed: count, prefix sums, scatter.  The order inside a group is whatever the
+//                               atomics give: keys carry the row, so the top-k does not depend on it.
+//   scope_scan_kernel           (scope, up to NB of the batch's queries with that scope, one of `split` parts of its group):
+//                               gathers the group's rows from the ORIGINAL row store by slot and scores them with the canonical
+//                               expression; one partial list per (query, part), merge_keys_kernel behind it.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void scope_set_kernel(const int64_t* __restrict__ packed, int64_t n, uint32_t* __restrict__ scope_of) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + (int64_t)threadIdx.x;
+    if (i < n) scope_of[(uint32_t)(packed[i] & 0xffffffffll)] = (uint32_t)((u64)packed[i] >> 32);   // (slot in the low word, scope in the high one)
+}
+// A wave whose 64 rows carry one scope (labels assigned in runs, as the indexer job writes them) costs one atomic, not 64.
+__global__ __launch_bounds__(256) void scope_count_kernel(const uint32_t* __restrict__ scope_of, int64_t n, int nlist, unsigned* __restrict__ cnt) {
+    const int64_t r = (int64_t)blockIdx.x * 256 + (int64_t)threadIdx.x;
+    const bool valid = r < n;
+    uint32_t s = valid ? scope_of[r] : 0u;
+    if (s >= (uint32_t)nlist) s = 0u;   // (cannot happen: nlist covers every label ever set)
+    const uint32_t first = (uint32_t)__builtin_amdgcn_readfirstlane((int)s);
+    const u64 act = __ballot(valid), same = __ballot(valid && s == first);
+    if (same == act) {
+        if (lane_id() == 0 && act != 0ull) atomicAdd(&cnt[first], (unsigned)__popcll(act));
+    } else if (valid) {
+        atomicAdd(&cnt[s], 1u);
+    }
+}
+// one workgroup: start[l] = exclusive prefix sum of cnt[], the total at start[nlist]; cnt[] is cleared on the way (the scatter's fill counters)
+__global__ __launch_bounds__(1024) void scope_offsets_kernel(unsigned* __restrict__ cnt, int nlist, unsigned* __restrict__ start) {
+    __shared__ unsigned s_p[1024];
+    const int tid = (int)threadIdx.x;
+    const int per = (nlist + 1023) / 1024;
+    unsigned sp = 0;
+    for (int j = 0; j < per; ++j) {
+        const int l = tid * per + j;
+        sp += l < nlist ? cnt[l] : 0u;
+    }
+    s_p[tid] = sp;
+    __syncthreads();
+    for (int off = 1; off < 1024; off <<= 1) {   // Hillis-Steele inclusive scan
+        const unsigned a = tid >= off ? s_p[tid - off] : 0u;
+        __syncthreads();
+        s_p[tid] += a;
+        __syncthreads();
+    }
+    unsigned bp = s_p[tid] - sp;
+    for (int j = 0; j < per; ++j) {
+        const int l = tid * per + j;
+        if (l < nlist) {
+            const unsigned c = cnt[l];
+            start[l] = bp;
+            bp += c;
+            cnt[l] = 0u;
+        }
+    }
+    if (tid == 1023) start[nlist] = s_p[1023];
+}
+__global__ __launch_bounds__(256) void scope_scatter_kernel(const uint32_t* __restrict__ scope_of, int64_t n, int nlist, const unsigned* __restrict__ start,
+                                                            unsigned* __restrict__ fill, uint32_t* __restrict__ perm) {
+    const int64_t r = (int64_t)blockIdx.x * 256 + (int64_t)threadIdx.x;
+    const bool valid = r < n;
+    uint32_t s = valid ? scope_of[r] : 0u;
+    if (s >= (uint32_t)nlist) s = 0u;
+    const uint32_t first = (uint32_t)__builtin_amdgcn_readfirstlane((int)s);
+    const u64 act = __ballot(valid), same = __ballot(valid && s == first);
+    if (same == act) {   // (valid lanes are the wave's first ones: r grows with the lane)
+        unsigned base = 0u;
+        if (lane_id() == 0 && act != 0ull) base = atomicAdd(&fill[first], (unsigned)__popcll(act));
+        base = (unsigned)__builtin_amdgcn_readfirstlane((int)base);
+        if (valid) perm[start[first] + base + (unsigned)lane_id()] = (uint32_t)r;
+    } else if (valid) {
+        perm[start[s] + atomicAdd(&fill[s], 1u)] = (uint32_t)r;
+    }
+}
+// One workgroup groups the batch's queries by scope: position p of the order (scope, query) holds query sorted_q[p], the rank[p]-th of its
+// scope.  Counting ranks over LDS (B <= 1,024 broadcast reads per thread): the cost does not depend on how many scopes exist, where
+// the count / prefix-sum / scatter of ivf_pair_* would walk a table of up to 2^20 scopes per search.
+__global__ __launch_bounds__(1024) void scope_group_kernel(const uint32_t* __restrict__ scopes, int B, unsigned* __restrict__ sorted_q, unsigned* __restrict__ rank) {
+    __shared__ uint32_t s_sc[CODD_KNN_MAX_BATCH];
+    const int tid = (int)threadIdx.x;
+    const uint32_t mine = tid < B ? scopes[tid] : 0xffffffffu;
+    s_sc[tid] = mine;
+    __syncthreads();
+    if (tid >= B) return;
+    unsigned lower = 0u, before = 0u;   // queries of a lower scope; ... plus those of this scope that come earlier in the batch
+    for (int j = 0; j < B; ++j) {
+        const uint32_t sj = s_sc[j];
+        lower += sj < mine ? 1u : 0u;
+        before += (sj < mine || (sj == mine && j < tid)) ? 1u : 0u;
+    }
+    sorted_q[before] = (unsigned)tid;
+    rank[before] = before - lower;
+}
+
+// queries per work item: four, as in ivf_scan_shared_kernel; two for 2-byte rows of 4 chunks per lane (four queries' registers would spill)
+constexpr int scope_nb(int dt, int niter) { return (dt != DT_F32 && niter == 4) ? 2 : 4; }
+// rows per part: a whole number of workgroup steps (4 waves x 4 rows)
+__host__ __device__ constexpr int64_t scope_part_rows(int64_t len, int split) { return ((len + split - 1) / split + 15) / 16 * 16; }
+
+// grid (B, split): workgroup (p, part) serves the queries at positions p .. p + NB-1 of the grouped order when p opens a group of NB
+// (rank[p] % NB == 0) and leaves at once otherwise.
+template <int DT, int NITER, int SLOTS>
+__global__ __launch_bounds__(256) void scope_scan_kernel(const void* __restrict__ rows_, const uint32_t* __restrict__ perm, const unsigned* __restrict__ offsets,
+                                                         int64_t count, uint32_t max_scope, const uint32_t* __restrict__ scopes,
+                                                         const unsigned* __restrict__ sorted_q, const unsigned* __restrict__ rank, int B, int split, int dpad,
+                                                         const float* __restrict__ qn, int k, uint32_t row_base, u64* __restrict__ partial) {
+    typedef RowTraits<DT> RT;
+    constexpr int E = RT::E;
+    constexpr int NB = scope_nb(DT, NITER);
+    const int p0 = (int)blockIdx.x, part = (int)blockIdx.y;
+    const unsigned r0 = rank[p0];
+    if (r0 % NB != 0u) return;
+    int nq = 1;
+    while (nq < NB && p0 + nq < B && rank[p0 + nq] == r0 + (unsigned)nq) ++nq;   // (ranks count up inside a scope and restart at 0)
+    unsigned qi[NB];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) qi[b] = b < nq ? sorted_q[p0 + b] : 0u;
+    const uint32_t scope = scopes[qi[0]];
+    int64_t lo = 0, hi = 0;   // the scope's rows: scope_perm[lo, hi); scope 0 = every row; a scope nobody carries = none
+    if (scope == 0u) hi = count;
+    else if (scope <= max_scope) { lo = offsets[scope]; hi = offsets[scope + 1]; }
+    const int64_t per = scope_part_rows(hi - lo, split);
+    const int64_t begin = lo + part * per < hi ? lo + part * per : hi;
+    const int64_t end = begin + per < hi ? begin + per : hi;
+
+    const int lane = lane_id();
+    const int wave = (int)(threadIdx.x >> 6);
+    const int nchunks = dpad / E;
+    WaveTopK<SLOTS> L[NB];
+    const uint4* base = reinterpret_cast<const uint4*>(rows_);
+    auto load_ids = [&](int64_t g4, uint32_t (&dst)[4]) {   // (g4 < end)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) dst[r] = perm[g4 + r < end ? g4 + r : end - 1];
+    };
+    if constexpr (NITER == kWideRows) {  // wide rows: the item's queries in LDS, the rows walked segment by segment
+        __shared__ __attribute__((aligned(16))) float lds_q[NB * kWideMaxFloats];
+        const int qstride = wide_qfloats(nchunks, E);
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+            const float* src = b < nq ? qn + (int64_t)qi[b] * dpad : nullptr;
+            wide_stage_query(lds_q + b * qstride, src, dpad, qstride, (int)threadIdx.x, 256);
+            L[b].init();
+        }
+        __syncthreads();
+        const int nseg = wide_nseg(nchunks);
+        uint32_t id0[4] = {0u, 0u, 0u, 0u}, id1[4] = {0u, 0u, 0u, 0u};
+        if (begin + wave * 4 < end) load_ids(begin + wave * 4, id0);
+        for (int64_t g4 = begin + wave * 4; g4 < end; g4 += 16) {
+            if (g4 + 16 < end) load_ids(g4 + 16, id1);   // the next step's row slots are on their way while this step is scored
+            const uint4* p[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) p[r] = base + (int64_t)id0[r] * nchunks + lane;
+            float a[NB][4];
+#pragma unroll
+            for (int b = 0; b < NB; ++b)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) a[b][r] = 0.0f;
+            for (int s = 0; s < nseg; ++s) wide_segment<DT, NB, 4>(p, s, nchunks, lane, lds_q, qstride, a);
+#pragma unroll
+            for (int b = 0; b < NB; ++b)
+                if (b < nq) {
+                    const float y = butterfly_sum4(a[b][0], a[b][1], a[b][2], a[b][3], lane);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const float sc = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(y), 16 * r));
+                        if (g4 + r < end) L[b].offer(make_key(sc, row_base + id0[r]), k, lane);
+                    }
+                }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) id0[r] = id1[r];
+        }
+    } else {
+    float qf[NB][NITER > 0 ? NITER : 1][E];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+#pragma unroll
+        for (int it = 0; it < NITER; ++it) {
+            const int j = lane + kWave * it;
+#pragma unroll
+            for (int e = 0; e < E; ++e) qf[b][it][e] = (b < nq && j < nchunks) ? qn[(int64_t)qi[b] * dpad + (int64_t)j * E + e] : 0.0f;
+        }
+        L[b].init();
+    }
+    // Two steps of look-ahead: the row slots of step g4 + 32 and the rows of step g4 + 16 (whose slots arrived a step ago) are in
+    // flight while step g4 is scored (raw 16-byte chunks, as in ivf_scan_shared_kernel)
+    uint4 cur[4][NITER > 0 ? NITER : 1], nxt[4][NITER > 0 ? NITER : 1];
+    uint32_t id0[4] = {0u, 0u, 0u, 0u}, id1[4] = {0u, 0u, 0u, 0u};
+    auto fetch = [&](const uint32_t (&id)[4], uint4 (&dst)[4][NITER > 0 ? NITER : 1]) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const uint4* p = base + (int64_t)id[r] * nchunks + lane;
+#pragma unroll
+            for (int it = 0; it < NITER; ++it) dst[r][it] = (lane + kWave * it < nchunks) ? p[kWave * it] : make_uint4(0u, 0u, 0u, 0u);
+        }
+    };
+    const int64_t g0 = begin + wave * 4;
+    if (g0 < end) {
+        load_ids(g0, id0);
+        if (g0 + 16 < end) load_ids(g0 + 16, id1);
+        fetch(id0, cur);
+    }
+    for (int64_t g4 = g0; g4 < end; g4 += 16) {
+        uint32_t id2[4] = {0u, 0u, 0u, 0u};
+        if (g4 + 32 < end) load_ids(g4 + 32, id2);
+        if (g4 + 16 < end) fetch(id1, nxt);
+        float a[NB][4];
+#pragma unroll
+        for (int b = 0; b < NB; ++b)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) a[b][r] = 0.0f;
+#pragma unroll
+        for (int it = 0; it < NITER; ++it)   // (it-major: the canonical fma order per (row, query))
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                float w[E];
+                RT::widen(cur[r][it], w);
+#pragma unroll
+                for (int b = 0; b < NB; ++b)
+                    if (b < nq) {
+#pragma unroll
+                        for (int e = 0; e < E; ++e) a[b][r] = __builtin_fmaf(qf[b][it][e], w[e], a[b][r]);
+                    }
+            }
+#pragma unroll
+        for (int b = 0; b < NB; ++b)
+            if (b < nq) {
+                const float y = butterfly_sum4(a[b][0], a[b][1], a[b][2], a[b][3], lane);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float sc = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(y), 16 * r));
+                    if (g4 + r < end) L[b].offer(make_key(sc, row_base + id0[r]), k, lane);
+                }
+            }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+#pragma unroll
+            for (int it = 0; it < NITER; ++it) cur[r][it] = nxt[r][it];
+            id0[r] = id1[r];
+            id1[r] = id2[r];
+        }
+    }
+    }  // (NITER)
+    __shared__ u64 lds[4 * NB * SLOTS * kWave];
+#pragma unroll
+    for (int b = 0; b < NB; ++b)
+#pragma unroll
+        for (int sl = 0; sl < SLOTS; ++sl) lds[((wave * NB + b) * SLOTS + sl) * kWave + lane] = L[b].v[sl];
+    __syncthreads();
+    for (int b = wave; b < nq; b += 4) {
+        WaveTopK<SLOTS> M;
+        M.init();
+        for (int wv = 0; wv < 4; ++wv)
+#pragma unroll
+            for (int sl = 0; sl < SLOTS; ++sl) {
+                u64 cand = lds[((wv * NB + b) * SLOTS + sl) * kWave + lane];
+                if (sl * kWave + lane >= k) cand = 0ull;
+                M.offer_lanes(cand, k, lane);
+            }
+        u64* dst = partial + ((int64_t)sorted_q[p0 + b] * split + part) * k;   // [query][part][k]
+#pragma unroll
+        for (int sl = 0; sl < SLOTS; ++sl) {
+            const int rk = sl * kWave + lane;
+            if (rk < k) dst[rk] = M.v[sl];
+        }
+    }
+}
+
 }  // namespace
 
 // =============================================================================================
@@ -1304,6 +1574,7 @@ struct WorkBufs {
     u64* probe_keys = nullptr; int64_t probe_cap = 0;      // IVF: [B][nprobe] coarse keys
     u64* ivf_partial = nullptr; int64_t ivf_partial_cap = 0;
     unsigned* ivf_group = nullptr; int64_t ivf_group_cap = 0;  // IVF at batch: [nlist] counters, [nlist+1] pair starts, [nlist+1] item starts, [B*nprobe] pairs by list
+    unsigned* scope_group = nullptr; int64_t scope_group_cap = 0;  // scoped search: [B] queries in (scope, query) order, [B] their ranks inside the scope
 };
 constexpr int kMaxWork = 4;
 struct WorkSlot {
@@ -1430,6 +1701,17 @@ struct codd_knn_index : WorkBufs {
     int64_t ivf_count = 0;             // rows covered by the IVF layout (must equal count to be fresh)
     int ivf_nlist = 0;
     int64_t ivf_epoch = -1, epoch = 0;  // epoch bumps on every row write; search requires ivf_epoch == epoch
+
+    // scopes (optional): a label per row slot and, derived from it like the shadows, the row slots grouped by label
+    uint32_t* scope_of = nullptr;      int64_t scope_of_cap = 0;   // [capacity], 0 = no label; allocated by the first call that needs it
+    uint32_t* scope_perm = nullptr;    int64_t scope_perm_cap = 0; // [count] row slots grouped by scope
+    unsigned* scope_offsets = nullptr; int64_t scope_lists_cap = 0; // [nlist + 1] group starts, then [nlist] counters of the build
+    uint32_t max_scope = 0;            // highest label ever set
+    int64_t scope_gen = 0;             // bumps on every codd_knn_set_scopes_host
+    int64_t scope_built_gen = -1, scope_built_count = -1;  // what scope_perm / scope_offsets were built from
+    hipStream_t scope_stream = nullptr;  // the stream the last build ran on, and its completion
+    hipEvent_t scope_ready = nullptr;
+    int64_t stat_scoped_searches = 0, stat_scope_builds = 0;
 
     int64_t stat_searches = 0, stat_scan_launches = 0, stat_last_scan_blocks = 0;
     int64_t stat_last_scan_group = 0;       // queries per pass over the rows of the last exact scan (1, 4 or 8; wide 2-byte rows: at most 4)
@@ -1572,6 +1854,20 @@ int grow_rows(codd_knn_index* ix, int64_t need, bool exact) {
     if (e != hipSuccess) {
         (void)hipFree(fresh);
         return fail(CODD_KNN_EDEVICE, "row copy on growth failed: %s", hipGetErrorString(e));
+    }
+    if (ix->scope_of && ix->scope_of_cap < cap) {  // the labels grow with the row store: new slots start with scope 0
+        uint32_t* labels = nullptr;
+        e = hipMalloc((void**)&labels, (size_t)cap * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMemset(labels, 0, (size_t)cap * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMemcpy(labels, ix->scope_of, (size_t)ix->scope_of_cap * sizeof(uint32_t), hipMemcpyDeviceToDevice);
+        if (e != hipSuccess) {
+            if (labels) (void)hipFree(labels);
+            (void)hipFree(fresh);
+            return fail(e == hipErrorOutOfMemory ? CODD_KNN_ENOMEM : CODD_KNN_EDEVICE, "growing the scope labels failed: %s", hipGetErrorString(e));
+        }
+        (void)hipFree(ix->scope_of);
+        ix->scope_of = labels;
+        ix->scope_of_cap = cap;
     }
     if (ix->rows) (void)hipFree(ix->rows);
     ix->rows = fresh;
@@ -2501,6 +2797,75 @@ int search_impl(codd_knn_index* ix, const float* dev_queries, int B, int k, uint
     return after_filter_search(ix, B, use8, st);
 }
 
+// ---- scopes ----------------------------------------------------------------------------------
+
+// the label array, as long as the row store, zero (= no label) until codd_knn_set_scopes_host writes it.  Only ever called with
+// scope_of == nullptr or from an exclusive call: a live array is regrown by grow_rows alone.
+int ensure_scope_labels(codd_knn_index* ix, hipStream_t st) {
+    if (ix->scope_of && ix->scope_of_cap >= ix->count) return CODD_KNN_OK;
+    if (ix->scope_of) return fail(CODD_KNN_EDEVICE, "scope labels shorter than the row store%s");
+    const int64_t cap = ix->capacity > ix->count ? ix->capacity : ix->count;
+    if (cap < 1) return CODD_KNN_OK;
+    HIP_TRY(hipMalloc((void**)&ix->scope_of, (size_t)cap * sizeof(uint32_t)));
+    ix->scope_of_cap = cap;
+    HIP_TRY(hipMemsetAsync(ix->scope_of, 0, (size_t)cap * sizeof(uint32_t), st));
+    return CODD_KNN_OK;
+}
+
+// The scope lists are derived data like the shadows: (re)built from the labels on the searching stream by the first scoped search
+// after the labels or the row count changed.  Searches on other streams wait for the build on the device; the build waits for
+// what they have already enqueued (their scans may still read the lists it overwrites).
+int ensure_scope_lists(codd_knn_index* ix, hipStream_t st) {
+    const int64_t n = ix->count;
+    if (ix->scope_perm && ix->scope_built_gen == ix->scope_gen && ix->scope_built_count == n) {
+        if (ix->scope_stream != st) HIP_TRY(hipStreamWaitEvent(st, ix->scope_ready, 0));
+        return CODD_KNN_OK;
+    }
+    int rc;
+    if ((rc = ensure_scope_labels(ix, st)) != 0) return rc;
+    const int64_t nlist = (int64_t)ix->max_scope + 1;
+    if (n > ix->scope_perm_cap || 2 * nlist + 1 > ix->scope_lists_cap) {
+        if ((rc = wait_searching_streams(ix)) != 0) return rc;   // (growth is the one place where a search call blocks)
+        if (n > ix->scope_perm_cap) {
+            if (ix->scope_perm) (void)hipFree(ix->scope_perm);
+            ix->scope_perm = nullptr; ix->scope_perm_cap = 0;
+            const int64_t cap = ix->capacity > n ? ix->capacity : n;
+            HIP_TRY(hipMalloc((void**)&ix->scope_perm, (size_t)cap * sizeof(uint32_t)));
+            ix->scope_perm_cap = cap;
+        }
+        if (2 * nlist + 1 > ix->scope_lists_cap) {
+            if (ix->scope_offsets) (void)hipFree(ix->scope_offsets);
+            ix->scope_offsets = nullptr; ix->scope_lists_cap = 0;
+            int64_t cap = 2049;
+            while (cap < 2 * nlist + 1) cap = 2 * cap - 1;
+            HIP_TRY(hipMalloc((void**)&ix->scope_offsets, (size_t)cap * sizeof(unsigned)));
+            ix->scope_lists_cap = cap;
+        }
+    }
+    for (WorkSlot& w : ix->slots) {
+        if (!w.used || w.stream == st) continue;
+        if (!w.handover) HIP_TRY(hipEventCreateWithFlags(&w.handover, hipEventDisableTiming));
+        if (hipEventRecord(w.handover, w.stream) == hipSuccess) HIP_TRY(hipStreamWaitEvent(st, w.handover, 0));
+        else (void)hipGetLastError();  // (a stream that no longer exists has nothing in flight)
+    }
+    if (ix->scope_ready && ix->scope_stream != st && ix->scope_built_gen >= 0) HIP_TRY(hipStreamWaitEvent(st, ix->scope_ready, 0));
+    unsigned* start = ix->scope_offsets;
+    unsigned* fill = start + nlist + 1;
+    HIP_TRY(hipMemsetAsync(fill, 0, (size_t)nlist * sizeof(unsigned), st));
+    const unsigned rb = (unsigned)((n + 255) / 256);
+    hipLaunchKernelGGL(scope_count_kernel, dim3(rb), dim3(256), 0, st, ix->scope_of, n, (int)nlist, fill);
+    hipLaunchKernelGGL(scope_offsets_kernel, dim3(1), dim3(1024), 0, st, fill, (int)nlist, start);
+    hipLaunchKernelGGL(scope_scatter_kernel, dim3(rb), dim3(256), 0, st, ix->scope_of, n, (int)nlist, start, fill, ix->scope_perm);
+    HIP_TRY(hipGetLastError());
+    if (!ix->scope_ready) HIP_TRY(hipEventCreateWithFlags(&ix->scope_ready, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(ix->scope_ready, st));
+    ix->scope_stream = st;
+    ix->scope_built_gen = ix->scope_gen;
+    ix->scope_built_count = n;
+    ix->stat_scope_builds++;
+    return CODD_KNN_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2547,7 +2912,9 @@ int codd_knn_destroy(codd_knn_index* ix) {
     if (!ix) return CODD_KNN_OK;
     DeviceGuard guard(ix->device);
     (void)hipDeviceSynchronize();
-    void* bufs[] = {ix->rows, ix->shadow, ix->dstats, ix->rows_ivf, ix->ivf_ids, ix->ivf_offsets, ix->shadow8, ix->rscale, ix->bmeta, ix->eps_r_bits};
+    void* bufs[] = {ix->rows, ix->shadow, ix->dstats, ix->rows_ivf, ix->ivf_ids, ix->ivf_offsets, ix->shadow8, ix->rscale, ix->bmeta, ix->eps_r_bits,
+                    ix->scope_of, ix->scope_perm, ix->scope_offsets};
+    if (ix->scope_ready) (void)hipEventDestroy(ix->scope_ready);
     if (ix->shadow8_ready) (void)hipEventDestroy(ix->shadow8_ready);
     if (ix->shadow_ready) (void)hipEventDestroy(ix->shadow_ready);
     if (ix->rows_ready) (void)hipEventDestroy(ix->rows_ready);
@@ -2562,7 +2929,8 @@ int codd_knn_destroy(codd_knn_index* ix) {
         if (b) (void)hipFree(b);
     for (WorkSlot& w : ix->slots) {
         void* wb[] = {w.bufs.qn, w.bufs.partial, w.bufs.keys_tmp, w.bufs.qfrag, w.bufs.thr, w.bufs.bucket_max, w.bufs.hits, w.bufs.ctl,
-                      w.bufs.fb_partial, w.bufs.probe_keys, w.bufs.ivf_partial, w.bufs.ivf_group, w.bufs.qfrag8, w.bufs.qmeta, w.bufs.sb_cand};
+                      w.bufs.fb_partial, w.bufs.probe_keys, w.bufs.ivf_partial, w.bufs.ivf_group, w.bufs.qfrag8, w.bufs.qmeta, w.bufs.sb_cand,
+                      w.bufs.scope_group};
         for (void* b : wb)
             if (b) (void)hipFree(b);
         if (w.handover) (void)hipEventDestroy(w.handover);
@@ -2977,6 +3345,107 @@ int codd_knn_ivf_search(codd_knn_index* ix, const float* dev_queries, int B, int
     return launch_merge(ix->ivf_partial, B, m, m, k, (u64*)dev_keys, dev_dist, dev_rows, st);
 }
 
+int codd_knn_set_scopes_host(codd_knn_index* ix, const int64_t* host_slots, const uint32_t* host_scopes, int64_t n) {
+    if (!ix || n < 0 || (n > 0 && (!host_slots || !host_scopes))) return fail(CODD_KNN_EINVAL, "bad set_scopes arguments%s");
+    if (n == 0) return CODD_KNN_OK;
+    uint32_t top = 0;
+    bool increasing = true;
+    for (int64_t i = 0; i < n; ++i) {
+        if (host_slots[i] < 0 || host_slots[i] >= ix->count) return fail(CODD_KNN_EINVAL, "set_scopes: row slot outside [0, count)%s");
+        if (host_scopes[i] > CODD_KNN_MAX_SCOPE) return fail(CODD_KNN_EINVAL, "set_scopes: scope above CODD_KNN_MAX_SCOPE%s");
+        if (host_scopes[i] > top) top = host_scopes[i];
+        if (i > 0 && host_slots[i] <= host_slots[i - 1]) increasing = false;
+    }
+    // (slot, scope) packed into one word each; a slot listed more than once keeps its LAST label (the device writes in no order)
+    std::vector<int64_t> packed;
+    try {
+        packed.resize((size_t)n);
+        for (int64_t i = 0; i < n; ++i) packed[(size_t)i] = (int64_t)(((u64)host_scopes[i] << 32) | (u64)host_slots[i]);
+        if (!increasing) {
+            std::vector<int64_t> order((size_t)n);
+            for (int64_t i = 0; i < n; ++i) order[(size_t)i] = i;
+            std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return host_slots[a] < host_slots[b]; });
+            size_t m = 0;
+            for (int64_t i = 0; i < n; ++i)
+                if (i + 1 == n || host_slots[order[(size_t)i]] != host_slots[order[(size_t)i + 1]])
+                    packed[m++] = (int64_t)(((u64)host_scopes[order[(size_t)i]] << 32) | (u64)host_slots[order[(size_t)i]]);
+            packed.resize(m);
+        }
+    } catch (const std::bad_alloc&) {
+        return fail(CODD_KNN_ENOMEM, "host allocation failed%s");
+    }
+    DeviceGuard guard(ix->device);
+    HIP_TRY(hipDeviceSynchronize());
+    int rc;
+    if ((rc = ensure_scope_labels(ix, nullptr)) != 0) return rc;
+    if (ix->stage_slot_cap < 4096) {  // (the staging buffer codd_knn_upsert_host keeps between calls)
+        if (ix->stage_slot) (void)hipFree(ix->stage_slot);
+        ix->stage_slot = nullptr; ix->stage_slot_cap = 0;
+        HIP_TRY(hipMalloc((void**)&ix->stage_slot, (size_t)4096 * sizeof(int64_t)));
+        ix->stage_slot_cap = 4096;
+    }
+    const int64_t total = (int64_t)packed.size(), pn = ix->stage_slot_cap;
+    for (int64_t i0 = 0; i0 < total; i0 += pn) {
+        const int64_t m = total - i0 < pn ? total - i0 : pn;
+        HIP_TRY(hipMemcpy(ix->stage_slot, packed.data() + i0, (size_t)m * sizeof(int64_t), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(scope_set_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, nullptr, ix->stage_slot, m, ix->scope_of);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipDeviceSynchronize());  // (the staging buffer is reused by the next piece, and the call is synchronous by contract)
+    }
+    if (top > ix->max_scope) ix->max_scope = top;
+    ix->scope_gen++;
+    return CODD_KNN_OK;
+}
+
+int codd_knn_search_scoped(codd_knn_index* ix, const float* dev_queries, const uint32_t* dev_scopes, int B, int k, uint32_t row_base,
+                           uint64_t* dev_keys, float* dev_dist, int64_t* dev_rows, void* stream) {
+    if (!ix || !dev_queries) return fail(CODD_KNN_EINVAL, "null index or queries%s");
+    if (!dev_scopes) return fail(CODD_KNN_EINVAL, "null scopes%s");
+    if (B < 1 || B > CODD_KNN_MAX_BATCH) return fail(CODD_KNN_EINVAL, "B out of range [1,1024]%s");
+    if (k < 1 || k > CODD_KNN_MAX_K) return fail(CODD_KNN_EINVAL, "k out of range [1,128]%s");
+    if ((int64_t)row_base + ix->count >= 0xffffffffll) return fail(CODD_KNN_EINVAL, "global row ids must fit 32 bits%s");
+    DeviceGuard guard(ix->device);
+    hipStream_t st = (hipStream_t)stream;
+    WorkScope work(ix, st);
+    ix->stat_scoped_searches++;
+    const int64_t n = ix->count;
+    int rc;
+    if ((rc = wait_rows(ix, st)) != 0) return rc;
+    if (n == 0) {  // nothing stored: all-empty result, as codd_knn_search gives
+        if ((rc = ensure_buf(&ix->keys_tmp, &ix->keys_tmp_cap, (int64_t)B * k)) != 0) return rc;
+        u64* keys_dst = dev_keys ? (u64*)dev_keys : ix->keys_tmp;
+        HIP_TRY(hipMemsetAsync(keys_dst, 0, (size_t)B * k * sizeof(u64), st));
+        if (!dev_dist && !dev_rows) return CODD_KNN_OK;
+        return launch_merge(keys_dst, B, k, k, k, nullptr, dev_dist, dev_rows, st);
+    }
+    // enough work items to fill the chip whatever the batch: a scope's list is cut into `split` parts.  The batch has between
+    // ceil(B / 4) (one scope) and B (all different) groups of queries; the lower bound sizes the split, surplus workgroups are cheap.
+    const int64_t groups = (B + 3) / 4;
+    int split = (int)((4 * (int64_t)ix->num_cus + groups - 1) / groups);
+    split = split < 1 ? 1 : (split > 256 ? 256 : split);
+    const int64_t m = (int64_t)split * k;
+    if ((rc = ensure_buf(&ix->qn, &ix->qn_cap, (int64_t)B * ix->dpad)) != 0) return rc;
+    if ((rc = ensure_buf(&ix->partial, &ix->partial_cap, (int64_t)B * m)) != 0) return rc;
+    if ((rc = ensure_buf(&ix->scope_group, &ix->scope_group_cap, (int64_t)2 * CODD_KNN_MAX_BATCH)) != 0) return rc;
+    if ((rc = ensure_scope_lists(ix, st)) != 0) return rc;
+    if ((rc = launch_normalize(DT_F32, dev_queries, B, ix->dim, ix->dpad, 1, nullptr, 0, ix->qn, nullptr, st)) != 0) return rc;
+    unsigned* sorted_q = ix->scope_group;
+    unsigned* rank = sorted_q + CODD_KNN_MAX_BATCH;
+    hipLaunchKernelGGL(scope_group_kernel, dim3(1), dim3(1024), 0, st, dev_scopes, B, sorted_q, rank);
+    HIP_TRY(hipGetLastError());
+    {
+        EvScope ev(ix, EV_SCAN, st);
+        rc = with_row_form(ix, k, "row too wide for the scope scan%s", [&](auto dt, auto ni, auto sl) {
+            return launch_kernel<scope_scan_kernel<dt, ni, sl>>(dim3((unsigned)B, (unsigned)split), dim3(256), 0, st, ix->rows, ix->scope_perm,
+                                                                ix->scope_offsets, n, ix->max_scope, dev_scopes, sorted_q, rank, B, split, ix->dpad,
+                                                                ix->qn, k, row_base, ix->partial);
+        });
+    }
+    if (rc != 0) return rc;
+    HIP_TRY(hipGetLastError());
+    return launch_merge(ix->partial, B, m, m, k, (u64*)dev_keys, dev_dist, dev_rows, st);
+}
+
 #ifdef CODD_I8_EXP_STAMPS
 // diagnostic builds only (not in include/codd_knn.h): the per-wave phase stamps of the last i8_tile_kernel<FILTER> launch on `stream`'s
 // workspace — [workgroup][wave][8] u64: issue, corpus wait, MFMA phase, end-of-interval sync, epilogue, intervals, total, tiles
@@ -3160,6 +3629,9 @@ int codd_knn_get_stat(const codd_knn_index* ix, const char* key, int64_t* out) {
     else if (strcmp(key, "last_scan_group") == 0) *out = ix->stat_last_scan_group;
     else if (strcmp(key, "last_finalize_parts") == 0) *out = ix->stat_last_finalize_parts;
     else if (strcmp(key, "ivf_shared_searches") == 0) *out = ix->stat_ivf_shared;
+    else if (strcmp(key, "scoped_searches") == 0) *out = ix->stat_scoped_searches;
+    else if (strcmp(key, "scope_builds") == 0) *out = ix->stat_scope_builds;
+    else if (strcmp(key, "scopes") == 0) *out = (int64_t)ix->max_scope;
     else if (strcmp(key, "filter_passes") == 0) *out = ix->stat_filter_passes;
     else if (strcmp(key, "shadow8_builds") == 0) *out = ix->stat_shadow8_builds;
     else if (strcmp(key, "shadow16_builds") == 0) *out = ix->stat_shadow_builds;
@@ -3198,7 +3670,7 @@ int codd_knn_get_stat(const codd_knn_index* ix, const char* key, int64_t* out) {
     else if (strcmp(key, "num_cus") == 0) *out = ix->num_cus;
     else if (strcmp(key, "device_bytes") == 0) {
         int64_t b = ix->capacity * (int64_t)ix->dpad * (int64_t)elem_size(ix->dtype) + ix->shadow_rows * (int64_t)ix->dpad * 2 +
-                    ix->shadow8_rows * ((int64_t)dpad8_of(ix) + 4);
+                    ix->shadow8_rows * ((int64_t)dpad8_of(ix) + 4) + (ix->scope_of_cap + ix->scope_perm_cap + ix->scope_lists_cap) * 4;
         for (const WorkSlot& w : ix->slots)
             b += w.bufs.qn_cap * 4 + w.bufs.partial_cap * 8 + w.bufs.keys_tmp_cap * 8 + w.bufs.hits_cap * 8 + w.bufs.bucket_cap * 8 +
                  w.bufs.qfrag_cap * 16 + w.bufs.fb_partial_cap * 8 + w.bufs.probe_cap * 8 + w.bufs.ivf_partial_cap * 8;

@@ -71,6 +71,7 @@ class Collection:
         self._metadatas: list[Optional[dict]] = []
         self._dirty = False
         self._generation = 0
+        self._scope_of_namespace: dict[str, int] = {}  # namespace string -> scope label of the engine (from 1, first seen first)
 
     # ------------------------------------------------------------------ helpers
     def _engine_for(self, dim: int):
@@ -91,6 +92,44 @@ class Collection:
 
     def count(self) -> int:
         return len(self._ids)
+
+    # ------------------------------------------------------------------ namespaces -> scopes
+    def _scope_for(self, metadata: Optional[dict]) -> int:
+        """The engine's scope label of a row with this metadata: 0 without a "namespace" key."""
+        if not metadata or "namespace" not in metadata:
+            return 0
+        ns = metadata["namespace"]
+        scope = self._scope_of_namespace.get(ns)
+        if scope is None:
+            scope = len(self._scope_of_namespace) + 1
+            self._scope_of_namespace[ns] = scope
+        return scope
+
+    _WHERE_FORMS = 'where={"namespace": "x"}, where={"namespace": {"$eq": "x"}}, or a list of one such dict / None per query'
+
+    @classmethod
+    def _where_namespace(cls, where) -> Optional[str]:
+        if where is None:
+            return None
+        if isinstance(where, dict) and list(where) == ["namespace"]:
+            cond = where["namespace"]
+            if isinstance(cond, str):
+                return cond
+            if isinstance(cond, dict) and list(cond) == ["$eq"] and isinstance(cond["$eq"], str):
+                return cond["$eq"]
+        raise ValueError(f"unsupported where filter {where!r}; supported: {cls._WHERE_FORMS}")
+
+    def _where_scopes(self, where, B: int) -> Optional[np.ndarray]:
+        """Per-query scope labels of a `where` (None when no query is restricted); -1 marks a namespace nobody stored."""
+        if isinstance(where, (list, tuple)):
+            if len(where) != B:
+                raise ValueError(f"where has {len(where)} entries for {B} queries; supported: {self._WHERE_FORMS}")
+            names = [self._where_namespace(w) for w in where]
+        else:
+            names = [self._where_namespace(where)] * B
+        if all(ns is None for ns in names):
+            return None
+        return np.array([0 if ns is None else self._scope_of_namespace.get(ns, -1) for ns in names], dtype=np.int64)
 
     # ------------------------------------------------------------------ writes
     def upsert(self, ids: Sequence[str], embeddings=None, metadatas: Optional[Sequence[Optional[dict]]] = None,
@@ -139,6 +178,11 @@ class Collection:
             if metadatas is not None:
                 self._metadatas[slot] = dict(metadatas[i]) if metadatas[i] is not None else None
         self._dirty = True
+        # the rows' namespaces as scope labels of the engine (an engine without scoped search is not asked)
+        if metadatas is not None and hasattr(engine, "set_scopes"):
+            scopes = np.array([self._scope_for(md) for md in metadatas], dtype=np.uint32)
+            if scopes.any() or len(fresh) < n:  # (a new slot starts with scope 0; a rewritten one may have to lose its label)
+                engine.set_scopes(slots, scopes)
 
     def add(self, ids: Sequence[str], embeddings=None, metadatas=None, documents=None) -> None:
         """chromadb Collection.add: like upsert, but ids already present are left untouched."""
@@ -165,9 +209,14 @@ class Collection:
         }
 
     def query(self, query_texts: Optional[Sequence[str]] = None, query_embeddings=None, n_results: int = 10,
-              include: Sequence[str] = ("metadatas", "documents", "distances")) -> dict:
+              include: Sequence[str] = ("metadatas", "documents", "distances"), where=None) -> dict:
         """chromadb Collection.query: NESTED lists, one inner list per query, ascending
-        distance, min(n_results, count) hits each (store.py:314-329)."""
+        distance, min(n_results, count) hits each (store.py:314-329).
+
+        `where` restricts the search to one namespace (the metadata key every record of the path carries):
+        {"namespace": "x"} or {"namespace": {"$eq": "x"}}; as an extension a list of such dicts / None, one per
+        query.  The answer is the exact top-k among that namespace's rows (fewer when it holds fewer); a namespace
+        nobody stored gives an empty inner list.  Any other filter raises ValueError."""
         if (query_texts is None) == (query_embeddings is None):
             raise ValueError("give exactly one of query_texts / query_embeddings")
         if n_results < 1:
@@ -187,7 +236,17 @@ class Collection:
         if q.shape[1] != self._engine.dim:
             raise ValueError(f"query dimension {q.shape[1]} does not match collection dimension {self._engine.dim}")
         k = min(int(n_results), len(self._ids))
-        dist, rows = self._engine.search(q, k)
+        scopes = None if where is None else self._where_scopes(where, B)
+        if scopes is None:
+            dist, rows = self._engine.search(q, k)
+        else:
+            if not hasattr(self._engine, "search_scoped"):
+                raise NotImplementedError(f"{type(self._engine).__name__} has no scoped search: `where` needs an engine with search_scoped")
+            known = scopes >= 0
+            dist = np.full((B, k), np.inf, dtype=np.float32)
+            rows = np.full((B, k), -1, dtype=np.int64)
+            if known.any():
+                dist[known], rows[known] = self._engine.search_scoped(q[known], scopes[known].astype(np.uint32), k)
         out = empty
         for b in range(B):
             hit = [(int(r), float(d)) for r, d in zip(rows[b].tolist(), dist[b].tolist()) if r >= 0]
@@ -280,6 +339,11 @@ class Collection:
         self.metadata = dict(manifest.get("metadata") or {})
         self._ids, self._metadatas, self._documents = ids, metadatas, documents
         self._slot_of = {doc_id: i for i, doc_id in enumerate(ids)}
+        # namespaces -> scope labels, from the stored metadata (the on-disk format knows nothing of scopes)
+        self._scope_of_namespace = {}
+        scopes = np.array([self._scope_for(md) for md in metadatas], dtype=np.uint32)
+        if engine is not None and scopes.any() and hasattr(engine, "set_scopes"):
+            engine.set_scopes(np.arange(n, dtype=np.int64), scopes)
         self._generation = int(gen_name.split("-")[1])
         self._dirty = False
 

@@ -158,6 +158,57 @@ class DeviceKnnIndex:
         )
         return keys
 
+    # ------------------------------------------------------------------ scopes
+    def set_scopes(self, slots, scopes) -> None:
+        """Scope label (0 = none, <= native.MAX_SCOPE) of the given row slots; a slot keeps it when its vector is overwritten."""
+        slots = np.ascontiguousarray(slots, dtype=np.int64)
+        scopes = np.ascontiguousarray(scopes, dtype=np.uint32)
+        if slots.ndim != 1 or scopes.shape != slots.shape:
+            raise ValueError(f"expected slots [n] and scopes [n], got {slots.shape} / {scopes.shape}")
+        native.check(self._lib.codd_knn_set_scopes_host(self._h, slots.ctypes.data, scopes.ctypes.data, slots.shape[0]), "codd_knn_set_scopes_host")
+
+    def _scopes_tensor(self, scopes, B: int):
+        torch = _torch()
+        if isinstance(scopes, torch.Tensor):
+            s = scopes.to(device=self.device, dtype=torch.int32).contiguous()  # (uint32 bit patterns: labels are below 2^20)
+        else:
+            s = torch.from_numpy(np.ascontiguousarray(scopes, dtype=np.uint32).view(np.int32)).to(self.device)
+        if s.dim() != 1 or s.shape[0] != B:
+            raise ValueError(f"expected scopes [{B}], got {tuple(s.shape)}")
+        return s
+
+    def search_scoped_tensors(self, queries, scopes, k: int):
+        """search_tensors among the rows whose scope equals the query's (scope 0: every row)."""
+        torch = _torch()
+        q = self._queries_tensor(queries)
+        B = q.shape[0]
+        s = self._scopes_tensor(scopes, B)
+        dist = torch.empty((B, k), dtype=torch.float32, device=self.device)
+        rows = torch.empty((B, k), dtype=torch.int64, device=self.device)
+        native.check(
+            self._lib.codd_knn_search_scoped(self._h, q.data_ptr(), s.data_ptr(), B, int(k), 0, None, dist.data_ptr(), rows.data_ptr(), self._stream()),
+            "codd_knn_search_scoped",
+        )
+        return dist, rows
+
+    def search_scoped(self, queries, scopes, k: int):
+        """numpy in, numpy out (the façade's path for `where=`)."""
+        dist, rows = self.search_scoped_tensors(queries, scopes, k)
+        return dist.cpu().numpy(), rows.cpu().numpy()
+
+    def search_keys_scoped(self, queries, scopes, k: int, row_base: int = 0):
+        """search_keys among the rows whose scope equals the query's."""
+        torch = _torch()
+        q = self._queries_tensor(queries)
+        B = q.shape[0]
+        s = self._scopes_tensor(scopes, B)
+        keys = torch.empty((B, k), dtype=torch.int64, device=self.device)
+        native.check(
+            self._lib.codd_knn_search_scoped(self._h, q.data_ptr(), s.data_ptr(), B, int(k), int(row_base), keys.data_ptr(), None, None, self._stream()),
+            "codd_knn_search_scoped",
+        )
+        return keys
+
     def merge_keys(self, keys, k: int):
         """Top-k of [B,m] packed keys -> (keys [B,k], dist [B,k], rows [B,k]) on device."""
         return merge_keys(keys, k, self.device)

@@ -19,6 +19,7 @@ DTYPE_NAMES = {v: k for k, v in DTYPE_CODES.items()}
 METRIC_COSINE = 0
 MAX_K = 128
 MAX_BATCH = 1024
+MAX_SCOPE = 1048575
 
 # every symbol include/codd_knn.h declares: (name, restype, argtypes)
 _c_idx = ctypes.c_void_p
@@ -44,6 +45,8 @@ ABI = [
     ("codd_knn_copy_rows_f32", ctypes.c_int, [_c_idx, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
     ("codd_knn_ivf_install", ctypes.c_int, [_c_idx, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     ("codd_knn_ivf_search", ctypes.c_int, [_c_idx, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    ("codd_knn_set_scopes_host", ctypes.c_int, [_c_idx, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]),
+    ("codd_knn_search_scoped", ctypes.c_int, [_c_idx, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     ("codd_knn_set_option", ctypes.c_int, [_c_idx, ctypes.c_char_p, ctypes.c_int64]),
     ("codd_knn_get_stat", ctypes.c_int, [_c_idx, ctypes.c_char_p, _i64p]),
 ]

@@ -17,7 +17,7 @@ from __future__ import annotations
 
 import logging
 import re
-from typing import Any, Iterable
+from typing import Any, Iterable, Optional
 
 from .errors import ValidationError
 from .models import MetricMetadata
@@ -220,36 +220,48 @@ class MetricsSemanticMetadataStore:
             shaped.append({"metric_name": name, "similarity_score": 1.0 - distance, **stored})
         return shaped
 
-    def search_metadata(self, query: str, n_results: int = 10) -> list[dict]:
+    def search_metadata(self, query: str, n_results: int = 10, namespace: Optional[str] = None) -> list[dict]:
         """Metrics most similar to `query`, best first (reference store.py:266-341).
 
         Empty query -> []; query longer than 1000 chars after sanitising or n_results < 1 ->
-        ValidationError; n_results above 100 is capped with a warning.
+        ValidationError; n_results above 100 is capped with a warning.  `namespace` (extension) keeps the
+        search inside one namespace: the exact best matches among its metrics.
         """
         cleaned = self._clean_query(query)
         if cleaned is None:
             logger.debug("Empty query received, returning empty results")
             return []
         n_results = self._clamp_n_results(n_results)
-        results = self.collection.query(query_texts=[cleaned], n_results=n_results)
+        if namespace is None:
+            results = self.collection.query(query_texts=[cleaned], n_results=n_results)
+        else:
+            results = self.collection.query(query_texts=[cleaned], n_results=n_results, where={"namespace": namespace})
         if not results or not results.get("ids") or not results["ids"][0]:
             return []
         return self._shape_hits(
             results["ids"][0], results.get("metadatas", [[]])[0], results.get("distances", [[]])[0]
         )
 
-    def search_metadata_batch(self, queries: list[str], n_results: int = 10) -> list[list[dict]]:
+    def search_metadata_batch(self, queries: list[str], n_results: int = 10, namespace=None) -> list[list[dict]]:
         """Extension (the reference only ever sends one query): many queries, ONE engine call.
 
-        Same per-query rules as search_metadata; an empty query yields [] at its position.
+        Same per-query rules as search_metadata; an empty query yields [] at its position.  `namespace`: one
+        string for every query, or a list with a string / None per query.
         """
+        if isinstance(namespace, (list, tuple)) and len(namespace) != len(queries):
+            raise ValidationError(f"namespace has {len(namespace)} entries for {len(queries)} queries")
         cleaned = [self._clean_query(q) for q in queries]
         n_results = self._clamp_n_results(n_results)
         live = [i for i, c in enumerate(cleaned) if c is not None]
         out: list[list[dict]] = [[] for _ in queries]
         if not live:
             return out
-        results = self.collection.query(query_texts=[cleaned[i] for i in live], n_results=n_results)
+        if namespace is None:
+            results = self.collection.query(query_texts=[cleaned[i] for i in live], n_results=n_results)
+        else:
+            per_query = [namespace[i] for i in live] if isinstance(namespace, (list, tuple)) else [namespace] * len(live)
+            where = [None if ns is None else {"namespace": ns} for ns in per_query]
+            results = self.collection.query(query_texts=[cleaned[i] for i in live], n_results=n_results, where=where)
         if not results or not results.get("ids"):
             return out
         all_md = results.get("metadatas") or []

@@ -78,10 +78,12 @@ class ShardedSearcher:
         self._streams: list = []
         self._turn = 0
 
-    def search_keys_local(self, queries, k: int):
-        return self.engine.search_keys(queries, k, self.row_base)
+    def search_keys_local(self, queries, k: int, scopes=None):
+        if scopes is None:
+            return self.engine.search_keys(queries, k, self.row_base)
+        return self.engine.search_keys_scoped(queries, scopes, k, self.row_base)
 
-    def search_async(self, queries, k: int, depth: int = 2) -> "PendingSearch":
+    def search_async(self, queries, k: int, depth: int = 2, scopes=None) -> "PendingSearch":
         """Issue one batch on a side stream and return at once; `.result()` makes the caller's stream wait for it.
 
         Consecutive batches go to `depth` alternating HIP streams, so the small kernels, the all_gather and the merge
@@ -92,7 +94,7 @@ class ShardedSearcher:
 
         dev = getattr(queries, "device", None)
         if not (isinstance(queries, torch.Tensor) and dev is not None and dev.type == "cuda"):
-            return PendingSearch(None, self.search(queries, k))
+            return PendingSearch(None, self.search(queries, k, scopes))
         if len(self._streams) != depth:
             self._streams = [torch.cuda.Stream(device=dev) for _ in range(depth)]
             self._turn = 0
@@ -100,16 +102,18 @@ class ShardedSearcher:
         self._turn = (self._turn + 1) % depth
         side.wait_stream(torch.cuda.current_stream(dev))  # the queries are ready
         with torch.cuda.stream(side):
-            out = self.search(queries, k)
+            out = self.search(queries, k, scopes)
         queries.record_stream(side)
         return PendingSearch(side, out)
 
-    def search(self, queries, k: int):
-        """(dist [B,k], global rows [B,k]) — identical on every rank."""
+    def search(self, queries, k: int, scopes=None):
+        """(dist [B,k], global rows [B,k]) — identical on every rank.  `scopes` ([B] scope labels, the same on every
+        rank and the same labelling on every shard) restricts each query to its scope: the shards answer with
+        search_keys_scoped, the merge is the same."""
         import torch
         import torch.distributed as dist
 
-        local = self.search_keys_local(queries, k)  # [B,k] int64
+        local = self.search_keys_local(queries, k, scopes)  # [B,k] int64
         if self.world_size == 1 and not self.always_gather:
             _, d, r = self._merge(local, k)
             return d, r

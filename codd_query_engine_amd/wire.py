@@ -8,7 +8,7 @@ MCP host, HTTP clients, the CLI user) see no difference:
         (any exception -> HTTP 500 with the message; a missing `query` -> 422 from validation)
   MCP   search_relevant_metrics(problem_json: str, limit: int = 5) -> list[dict]
         codd_mcp_server/server.py:48-88  (POSTs to the service; ANY failure -> prints and returns [])
-  CLI   get-semantic-metrics QUERY --limit N   codd_cli/codd_cli/commands/metrics.py:26-67
+  CLI   get-semantic-metrics QUERY --limit N [--namespace NS]   codd_cli/codd_cli/commands/metrics.py:26-67
 
 These are plumbing, not the product: no server is started here, nothing is rebuilt from the
 reference's service/MCP/CLI packages beyond the one route, the one tool and the one command.
@@ -28,6 +28,7 @@ from .models import SearchResult
 class MetricsSearchRequest(BaseModel):
     query: str
     limit: int = 5
+    namespace: Optional[str] = None  # extension: search inside one namespace; absent = the reference's request
 
 
 class MetricsSearchResponse(BaseModel):
@@ -45,7 +46,10 @@ def create_app(get_search_client: Callable[[], MetricsSearchClient]):
     @router.post("/search", response_model=MetricsSearchResponse)
     async def search_metrics(request: MetricsSearchRequest):
         try:
-            results = get_search_client().search_relevant_metrics(request.query, limit=request.limit)
+            if request.namespace is None:
+                results = get_search_client().search_relevant_metrics(request.query, limit=request.limit)
+            else:
+                results = get_search_client().search_relevant_metrics(request.query, limit=request.limit, namespace=request.namespace)
             return MetricsSearchResponse(results=results, count=len(results))
         except Exception as exc:  # the reference maps every failure to a 500
             raise HTTPException(status_code=500, detail=str(exc))
@@ -75,9 +79,12 @@ def make_search_relevant_metrics_tool(post: Optional[Callable[[str, dict], dict]
     transport to the service; an in-process deployment can pass `lambda ep, js: app_call(js)`."""
     send = post or http_transport()
 
-    async def search_relevant_metrics(problem_json: str, limit: int = 5) -> list[dict[str, Any]]:
+    async def search_relevant_metrics(problem_json: str, limit: int = 5, namespace: Optional[str] = None) -> list[dict[str, Any]]:
         try:
-            response = send("/api/metrics/search", {"query": problem_json, "limit": limit})
+            body = {"query": problem_json, "limit": limit}
+            if namespace is not None:
+                body["namespace"] = namespace
+            response = send("/api/metrics/search", body)
             return response.get("results", [])
         except Exception as exc:
             print(f"Error searching metrics: {exc}")
@@ -109,6 +116,7 @@ def cli_main(argv: Optional[list[str]] = None, search_client: Optional[MetricsSe
     g.add_argument("query")
     g.add_argument("--limit", type=int, default=5)
     g.add_argument("--path", default=None, help="on-disk index written by the indexer job")
+    g.add_argument("--namespace", default=None, help="search inside this namespace only")
     args = p.parse_args(argv)
     try:
         if search_client is None:
@@ -116,7 +124,11 @@ def cli_main(argv: Optional[list[str]] = None, search_client: Optional[MetricsSe
             from .models import SemanticStoreConfig
 
             search_client = MetricsSearchClient(get_semantic_store(SemanticStoreConfig(chromadb_path=args.path)))
-        print(format_results_table(search_client.search_relevant_metrics(args.query, limit=args.limit)))
+        if args.namespace is None:
+            results = search_client.search_relevant_metrics(args.query, limit=args.limit)
+        else:
+            results = search_client.search_relevant_metrics(args.query, limit=args.limit, namespace=args.namespace)
+        print(format_results_table(results))
         return 0
     except Exception as exc:
         print(f"Error: {exc}")

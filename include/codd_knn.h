@@ -19,12 +19,12 @@
  *     the index owns its row storage and its workspaces.
  *   - `stream` is a hipStream_t passed as void* (NULL = the null stream).  Calls
  *     are asynchronous with respect to the host unless stated otherwise.
- *   - thread-safety: the search entry points (codd_knn_search, _search_keys,
+ *   - thread-safety: the search entry points (codd_knn_search, _search_keys, _search_scoped,
  *     _ivf_search, _approx_scores) may be called from several host threads and on
  *     several streams of one index: the index keeps one workspace per stream (up to
  *     4; a fifth stream takes over the least recently used one, ordered behind its
  *     previous owner on the device) and serialises only the enqueueing.  Searches on
- *     different streams then overlap on the GPU.  upsert/reserve/load/ivf_install
+ *     different streams then overlap on the GPU.  upsert/reserve/load/ivf_install/set_scopes
  *     are exclusive: no other call on the index may be in flight.
  *   - rows are stored L2-normalised, zero padded to a multiple of 64 elements.
  *     score = <q/|q|, c/|c|> evaluated in fp32 in the canonical order of
@@ -48,6 +48,7 @@ extern "C" {
 
 #define CODD_KNN_MAX_K 128        /* reference caps n_results at 100 (store.py:24) */
 #define CODD_KNN_MAX_BATCH 1024   /* queries per codd_knn_search call */
+#define CODD_KNN_MAX_SCOPE 1048575u /* highest scope label of codd_knn_set_scopes_host */
 
 #define CODD_KNN_OK 0
 #define CODD_KNN_EINVAL (-22)     /* bad argument */
@@ -178,6 +179,28 @@ int codd_knn_ivf_search(codd_knn_index* index, const float* dev_queries, int B, 
                         void* stream);
 
 /*
+ * Replaces: the `where={"namespace": ...}` of collection.query(query_texts=..., n_results=..., where=...) — the metadata
+ *           filter of ChromaDB's query, for the one key every record of the path carries (store.py:236-238 writes
+ *           "namespace" into each metadata).  Strings stay on the host: the façade numbers the namespaces, and the
+ *           number is the row slot's SCOPE, a 32-bit label; 0 = no label.
+ * set_scopes_host: the scope of n row slots (each < count; scope <= CODD_KNN_MAX_SCOPE, else EINVAL); 0 clears.  A slot listed
+ *           more than once keeps the last value.  Exclusive like upsert, synchronous.  A slot keeps its scope when its vector is
+ *           overwritten; a new slot starts with scope 0.
+ * search_scoped: like codd_knn_search / _search_keys, restricted per query: query q sees only the rows whose scope equals
+ *           dev_scopes[q] (device, B values) — the exact cosine top-k among them, the same scores, tie rule and padding.
+ *           dev_scopes[q] == 0 means "every row": bit-identical to codd_knn_search (so that one batch can mix scoped and
+ *           unscoped queries).  A scope no row carries, or a value above anything ever set, gives an empty result for that
+ *           query (all keys 0, rows -1, distances +inf), not an error.  Any of dev_keys / dev_dist / dev_rows may be NULL.
+ *           Asynchronous on `stream`, ordered against upserts like the other search entry points.  The rows of a scope are
+ *           found through lists (row slots grouped by scope) that the first scoped search after a change of scopes or of the
+ *           row count rebuilds on its stream; the scan reads rows_in_scope rows per group of up to four queries of that scope —
+ *           the tool for scopes that hold a small share of the index.
+ */
+int codd_knn_set_scopes_host(codd_knn_index* index, const int64_t* host_slots, const uint32_t* host_scopes, int64_t n);
+int codd_knn_search_scoped(codd_knn_index* index, const float* dev_queries, const uint32_t* dev_scopes, int B, int k,
+                           uint32_t row_base, uint64_t* dev_keys, float* dev_dist, int64_t* dev_rows, void* stream);
+
+/*
  * Tuning / introspection (never needed for correctness).
  *   options: "scan_blocks_per_cu" (1..8); "filter" (0/1: MFMA filter path for large batches);
  *            "filter_min_batch" (9), "filter_min_rows" (1: batches >= filter_min_batch always
@@ -218,7 +241,8 @@ int codd_knn_ivf_search(codd_knn_index* index, const float* dev_queries, int B, 
  *            recorded on the launch stream (0 = off; resets the log)
  *   stats  : "searches", "scan_launches", "last_scan_blocks", "last_scan_group" (queries per pass over the rows of the
  *            last exact scan), "last_finalize_parts" (workgroups per query of the last filter pass's finalize),
- *            "ivf_shared_searches" (IVF searches that scanned each probed list once for all its queries), "filter_passes",
+ *            "ivf_shared_searches" (IVF searches that scanned each probed list once for all its queries), "scoped_searches",
+ *            "scope_builds" (times the scope lists were rebuilt), "scopes" (highest scope label ever set), "filter_passes",
  *            "fallback_queries", "filter_hits", "filter_survivors", "capacity_rows",
  *            "device_bytes", "num_cus", "workspaces" (stream workspaces in use), "shadow8_builds", "shadow8_passes", "i8v2_passes",
  *            "shadow16_builds" (the bf16 shadow is built lazily, by the first search that needs it), "all_normalized",
