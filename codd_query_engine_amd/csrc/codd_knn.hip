@@ -185,12 +185,22 @@ __global__ __launch_bounds__(256) void shadow_from_rows_kernel(const void* __res
 // scan_topk_body: the scan as a workgroup of NW waves sees it — workgroup `bid` of `nblocks`, lds = NW * NB * SLOTS * 64 u64.
 // `total` queries, dense from qn (qlist == nullptr) or listed (qlist[i] = query slot; `listed` also selects the one-launch
 // hand-off to the last block, see below).  Shared by scan_topk_kernel and by the scan role of finalize_fb_kernel.
+// the tombstone bits of row group g (rows 4g .. 4g+3: one bitmap word, 4 | 32) in bits 0..3; 0 without a load while nothing was ever
+// deleted.  g is wave-uniform: said so to the compiler, the word is a scalar load into a scalar register, not one more vector register
+// in a loop that lives at the register limit.
+__device__ __forceinline__ uint32_t group_dead_bits(const uint32_t* __restrict__ dead, int64_t g) {
+    if (!dead) return 0u;
+    const uint32_t gu = (uint32_t)__builtin_amdgcn_readfirstlane((int)g);
+    return dead[gu >> 3] >> ((gu & 7u) * 4u);
+}
+
 template <int DT, int NB, int NITER, int SLOTS, int NW>
 __device__ __forceinline__ void scan_topk_body(const void* __restrict__ rows_, int64_t n, int dpad, const float* __restrict__ qn, int total, int k,
                                                uint32_t row_base, u64* __restrict__ partial, int64_t partial_stride_q,
                                                const unsigned* __restrict__ qlist, bool listed, unsigned* __restrict__ merge_done,
                                                u64* __restrict__ merged_keys, float* __restrict__ merged_dist, int64_t* __restrict__ merged_rows,
-                                               unsigned long long* __restrict__ count_total, int bid, int nblocks, u64* __restrict__ lds) {
+                                               unsigned long long* __restrict__ count_total, int bid, int nblocks, u64* __restrict__ lds,
+                                               const uint32_t* __restrict__ dead) {
     typedef RowTraits<DT> RT;
     constexpr int E = RT::E;
     const int lane = lane_id();
@@ -234,6 +244,7 @@ __device__ __forceinline__ void scan_topk_body(const void* __restrict__ rows_, i
 #pragma unroll
                 for (int r = 0; r < 4; ++r) acc[b][r] = 0.0f;
             for (int s = 0; s < nseg; ++s) wide_segment<DT, NB, 4>(p, s, nchunks, lane, qs, qstride, acc);
+            const uint32_t dm = group_dead_bits(dead, g);
 #pragma unroll
             for (int b = 0; b < NB; ++b) {
                 const float y = butterfly_sum4(acc[b][0], acc[b][1], acc[b][2], acc[b][3], lane);
@@ -241,7 +252,7 @@ __device__ __forceinline__ void scan_topk_body(const void* __restrict__ rows_, i
                 for (int r = 0; r < 4; ++r) {
                     const float s = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(y), 16 * r));
                     const int64_t row = g * 4 + r;
-                    if (row < n) L[b].offer(make_key(s, row_base + (uint32_t)row), k, lane);
+                    if (row < n && !((dm >> r) & 1u)) L[b].offer(make_key(s, row_base + (uint32_t)row), k, lane);
                 }
             }
         }
@@ -280,6 +291,7 @@ __device__ __forceinline__ void scan_topk_body(const void* __restrict__ rows_, i
                 RT::widen(c, w[r][it]);
             }
         }
+        const uint32_t dm = group_dead_bits(dead, g);
 #pragma unroll
         for (int b = 0; b < NB; ++b) {
             float a[4];
@@ -297,7 +309,7 @@ __device__ __forceinline__ void scan_topk_body(const void* __restrict__ rows_, i
             for (int r = 0; r < 4; ++r) {
                 const float s = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(y), 16 * r));
                 const int64_t row = g * 4 + r;
-                if (row < n) L[b].offer(make_key(s, row_base + (uint32_t)row), k, lane);
+                if (row < n && !((dm >> r) & 1u)) L[b].offer(make_key(s, row_base + (uint32_t)row), k, lane);
             }
         }
     }
@@ -375,11 +387,12 @@ __global__ __launch_bounds__(256) void scan_topk_kernel(const void* __restrict__
                                                         const unsigned* __restrict__ qcount_ptr, unsigned* __restrict__ merge_done = nullptr,
                                                         u64* __restrict__ merged_keys = nullptr, float* __restrict__ merged_dist = nullptr,
                                                         int64_t* __restrict__ merged_rows = nullptr,
-                                                        unsigned long long* __restrict__ count_total = nullptr) {
+                                                        unsigned long long* __restrict__ count_total = nullptr,
+                                                        const uint32_t* __restrict__ dead = nullptr) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int total = qcount_ptr ? (int)*qcount_ptr : nq_arg;
     scan_topk_body<DT, NB, NITER, SLOTS, 4>(rows_, n, dpad, qn, total, k, row_base, partial, partial_stride_q, qlist, qcount_ptr != nullptr, merge_done, merged_keys,
-                                            merged_dist, merged_rows, count_total, (int)blockIdx.x, (int)gridDim.x, reinterpret_cast<u64*>(smem_raw));
+                                            merged_dist, merged_rows, count_total, (int)blockIdx.x, (int)gridDim.x, reinterpret_cast<u64*>(smem_raw), dead);
 }
 
 // scan_topk_kernel's wide form (more than 4 chunks per lane): the NB queries' full rows are staged in LDS, up to 128 KiB, so ONE
@@ -392,12 +405,13 @@ __global__ __launch_bounds__(kWideScanWaves * kWave) void scan_topk_wide_kernel(
                                                                                 int64_t partial_stride_q, const unsigned* __restrict__ qlist,
                                                                                 const unsigned* __restrict__ qcount_ptr, unsigned* __restrict__ merge_done,
                                                                                 u64* __restrict__ merged_keys, float* __restrict__ merged_dist,
-                                                                                int64_t* __restrict__ merged_rows, unsigned long long* __restrict__ count_total) {
+                                                                                int64_t* __restrict__ merged_rows, unsigned long long* __restrict__ count_total,
+                                                                                const uint32_t* __restrict__ dead) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int total = qcount_ptr ? (int)*qcount_ptr : nq_arg;
     scan_topk_body<DT, NB, kWideRows, SLOTS, kWideScanWaves>(rows_, n, dpad, qn, total, k, row_base, partial, partial_stride_q, qlist, qcount_ptr != nullptr,
                                                              merge_done, merged_keys, merged_dist, merged_rows, count_total, (int)blockIdx.x, (int)gridDim.x,
-                                                             reinterpret_cast<u64*>(smem_raw));
+                                                             reinterpret_cast<u64*>(smem_raw), dead);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -416,7 +430,8 @@ __global__ __launch_bounds__(kFinThreads) void finalize_fb_kernel(const void* __
                                                                    uint32_t row_base, u64* __restrict__ out_keys, unsigned long long* __restrict__ stats,
                                                                    const float* __restrict__ two_eps_q, u64* __restrict__ part_keys, float* __restrict__ out_dist,
                                                                    int64_t* __restrict__ out_rows, const float2* __restrict__ bmeta, int nq, int64_t n,
-                                                                   u64* __restrict__ fb_partial, int64_t fb_stride_q, unsigned* __restrict__ fb_done) {
+                                                                   u64* __restrict__ fb_partial, int64_t fb_stride_q, unsigned* __restrict__ fb_done,
+                                                                   const uint32_t* __restrict__ dead) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     constexpr int kWavesHere = kFinThreads / kWave;
     if ((int)blockIdx.x < nq) {
@@ -431,7 +446,7 @@ __global__ __launch_bounds__(kFinThreads) void finalize_fb_kernel(const void* __
         const float bq = bmeta ? two_eps_q[512 + q] : 0.0f;
         finalize_body<DT, NITER, 1>(rows_, dpad, qn + (int64_t)q * dpad, hits + (int64_t)q * cap_q, total, part, nparts, k, eps1, bq, bmeta, row_base,
                                     out_keys ? out_keys + (int64_t)q * k : nullptr, out_dist ? out_dist + (int64_t)q * k : nullptr,
-                                    out_rows ? out_rows + (int64_t)q * k : nullptr, part_keys ? part_keys + ((int64_t)q * nparts + part) * k : nullptr, stats);
+                                    out_rows ? out_rows + (int64_t)q * k : nullptr, part_keys ? part_keys + ((int64_t)q * nparts + part) * k : nullptr, stats, dead);
         return;
     }
     if (blockIdx.y != 0) return;
@@ -453,7 +468,7 @@ __global__ __launch_bounds__(kFinThreads) void finalize_fb_kernel(const void* __
     __syncthreads();
     // (4 queries per pass over the rows, not 8: the role is rare, and its query registers must not push the finalize role into scratch)
     scan_topk_body<DT, 4, NITER, 1, kWavesHere>(rows_, n, dpad, qn, (int)total, k, row_base, fb_partial, fb_stride_q, s_fb, true, fb_done, out_keys, out_dist, out_rows,
-                                                 stats ? stats + 2 : nullptr, (int)blockIdx.x - nq, (int)gridDim.x - nq, reinterpret_cast<u64*>(smem_raw));
+                                                 stats ? stats + 2 : nullptr, (int)blockIdx.x - nq, (int)gridDim.x - nq, reinterpret_cast<u64*>(smem_raw), dead);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -771,7 +786,8 @@ __global__ __launch_bounds__(kSbThreads) void small_batch_kernel(const uint4* __
                                                                   const unsigned* __restrict__ eps_r_bits, float* __restrict__ qn, u64* __restrict__ cand,
                                                                   u64* __restrict__ dropmax, unsigned* __restrict__ ticket, unsigned* __restrict__ fb_count,
                                                                   unsigned* __restrict__ fb_list, u64* __restrict__ out_keys, float* __restrict__ out_dist,
-                                                                  int64_t* __restrict__ out_rows, unsigned long long* __restrict__ stats) {
+                                                                  int64_t* __restrict__ out_rows, unsigned long long* __restrict__ stats,
+                                                                  const uint32_t* __restrict__ dead) {
     constexpr int kWaves = kSbThreads / kWave;
     constexpr int kDpad8 = NS * 128;
     typedef unsigned sb_u32x4 __attribute__((ext_vector_type(4)));
@@ -859,7 +875,9 @@ __global__ __launch_bounds__(kSbThreads) void small_batch_kernel(const uint4* __
         const int64_t block = uu >> 1;
         const int64_t row = (block << 5) + 16 * (uu & 1) + r;
         const float score = (float)acc * scale * qscale;
-        const u64 key = (lane < 16 && row < n) ? make_key(score, (uint32_t)row) : 0ull;
+        // (a deleted row is no candidate: it would only crowd the wave's kSbKeep published keys and trip the margin test)
+        const bool live = lane < 16 && row < n && !(dead && row_dead(dead, (uint32_t)row));
+        const u64 key = live ? make_key(score, (uint32_t)row) : 0ull;
 #ifdef CODD_SB_EXP_NOOFFER
         asm volatile("" ::"v"(key));  // diagnostic: scores computed, no top-k insert
 #else
@@ -901,7 +919,7 @@ __global__ __launch_bounds__(kSbThreads) void small_batch_kernel(const uint4* __
     }
     __syncthreads();
     finalize_body<DT, NITER, 1>(rows_, dpad, qn, cand, (unsigned)(W * kSbKeep), 0u, 1u, k, s_eps, 0.0f, nullptr, row_base, out_keys, out_dist, out_rows, nullptr, stats,
-                                &s_lo);
+                                dead, &s_lo);
     // margin test: could a wave have kept a row to itself that belongs among the survivors?
     const float lo = s_lo;
     unsigned bad = 0;
@@ -962,7 +980,8 @@ template <int DT, int NITER, int SLOTS>
 __global__ __launch_bounds__(256) void ivf_scan_kernel(const void* __restrict__ rows_, const uint32_t* __restrict__ ids,
                                                        const int64_t* __restrict__ offsets, const u64* __restrict__ probe_keys,
                                                        int nprobe, int split, int dpad, const float* __restrict__ qn, int k,
-                                                       uint32_t row_base, u64* __restrict__ partial) {
+                                                       uint32_t row_base, u64* __restrict__ partial, const uint32_t* __restrict__ dead) {
+    // dead: the tombstone bits of the ORIGINAL row slots (ids[] carries them), null = none: a delete leaves the list layout valid
     typedef RowTraits<DT> RT;
     constexpr int E = RT::E;
     const int lane = lane_id();
@@ -994,7 +1013,7 @@ __global__ __launch_bounds__(256) void ivf_scan_kernel(const void* __restrict__ 
                 wide_scores<DT, 1>(p, nchunks, lane, lds_q, sc);
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
-                    if (g + r < end) L.offer(make_key(sc[0][r], row_base + ids[g + r]), k, lane);
+                    if (g + r < end && !(dead && row_dead(dead, ids[g + r]))) L.offer(make_key(sc[0][r], row_base + ids[g + r]), k, lane);
             }
         } else {
         float qf[NITER > 0 ? NITER : 1][E];
@@ -1031,7 +1050,7 @@ __global__ __launch_bounds__(256) void ivf_scan_kernel(const void* __restrict__ 
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const float s = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(y), 16 * r));
-                if (g + r < end) L.offer(make_key(s, row_base + ids[g + r]), k, lane);
+                if (g + r < end && !(dead && row_dead(dead, ids[g + r]))) L.offer(make_key(s, row_base + ids[g + r]), k, lane);
             }
         }
         }  // (NITER)
@@ -1121,7 +1140,8 @@ template <int DT, int NITER, int SLOTS>
 __global__ __launch_bounds__(256) void ivf_scan_shared_kernel(const void* __restrict__ rows_, const uint32_t* __restrict__ ids, const int64_t* __restrict__ offsets,
                                                               const unsigned* __restrict__ pair_start, const unsigned* __restrict__ item_start,
                                                               const unsigned* __restrict__ sorted_pairs, int nlist, int nprobe, int dpad,
-                                                              const float* __restrict__ qn, int k, uint32_t row_base, u64* __restrict__ partial) {
+                                                              const float* __restrict__ qn, int k, uint32_t row_base, u64* __restrict__ partial,
+                                                              const uint32_t* __restrict__ dead) {
     typedef RowTraits<DT> RT;
     constexpr int E = RT::E;
     const unsigned item = blockIdx.x;
@@ -1171,7 +1191,7 @@ __global__ __launch_bounds__(256) void ivf_scan_shared_kernel(const void* __rest
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const float sc = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(y), 16 * r));
-                        if (g4 + r < end) L[b].offer(make_key(sc, row_base + ids[g4 + r]), k, lane);
+                        if (g4 + r < end && !(dead && row_dead(dead, ids[g4 + r]))) L[b].offer(make_key(sc, row_base + ids[g4 + r]), k, lane);
                     }
                 }
         }
@@ -1230,7 +1250,7 @@ __global__ __launch_bounds__(256) void ivf_scan_shared_kernel(const void* __rest
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const float sc = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(y), 16 * r));
-                    if (g4 + r < end) L[b].offer(make_key(sc, row_base + ids[g4 + r]), k, lane);
+                    if (g4 + r < end && !(dead && row_dead(dead, ids[g4 + r]))) L[b].offer(make_key(sc, row_base + ids[g4 + r]), k, lane);
                 }
             }
 #pragma unroll
@@ -1280,9 +1300,11 @@ __global__ __launch_bounds__(256) void scope_set_kernel(const int64_t* __restric
     if (i < n) scope_of[(uint32_t)(packed[i] & 0xffffffffll)] = (uint32_t)((u64)packed[i] >> 32);   // (slot in the low word, scope in the high one)
 }
 // A wave whose 64 rows carry one scope (labels assigned in runs, as the indexer job writes them) costs one atomic, not 64.
-__global__ __launch_bounds__(256) void scope_count_kernel(const uint32_t* __restrict__ scope_of, int64_t n, int nlist, unsigned* __restrict__ cnt) {
+// (dead: the tombstone bits, null = none: deleted rows are left out of the lists, so scope_scan_kernel needs no mask of its own)
+__global__ __launch_bounds__(256) void scope_count_kernel(const uint32_t* __restrict__ scope_of, int64_t n, int nlist, unsigned* __restrict__ cnt,
+                                                          const uint32_t* __restrict__ dead) {
     const int64_t r = (int64_t)blockIdx.x * 256 + (int64_t)threadIdx.x;
-    const bool valid = r < n;
+    const bool valid = r < n && !(dead && row_dead(dead, (uint32_t)r));
     uint32_t s = valid ? scope_of[r] : 0u;
     if (s >= (uint32_t)nlist) s = 0u;   // (cannot happen: nlist covers every label ever set)
     const uint32_t first = (uint32_t)__builtin_amdgcn_readfirstlane((int)s);
@@ -1324,18 +1346,18 @@ __global__ __launch_bounds__(1024) void scope_offsets_kernel(unsigned* __restric
     if (tid == 1023) start[nlist] = s_p[1023];
 }
 __global__ __launch_bounds__(256) void scope_scatter_kernel(const uint32_t* __restrict__ scope_of, int64_t n, int nlist, const unsigned* __restrict__ start,
-                                                            unsigned* __restrict__ fill, uint32_t* __restrict__ perm) {
+                                                            unsigned* __restrict__ fill, uint32_t* __restrict__ perm, const uint32_t* __restrict__ dead) {
     const int64_t r = (int64_t)blockIdx.x * 256 + (int64_t)threadIdx.x;
-    const bool valid = r < n;
+    const bool valid = r < n && !(dead && row_dead(dead, (uint32_t)r));
     uint32_t s = valid ? scope_of[r] : 0u;
     if (s >= (uint32_t)nlist) s = 0u;
     const uint32_t first = (uint32_t)__builtin_amdgcn_readfirstlane((int)s);
     const u64 act = __ballot(valid), same = __ballot(valid && s == first);
-    if (same == act) {   // (valid lanes are the wave's first ones: r grows with the lane)
+    if (same == act) {   // (a valid lane's place: its rank among the valid lanes — deleted rows leave gaps)
         unsigned base = 0u;
         if (lane_id() == 0 && act != 0ull) base = atomicAdd(&fill[first], (unsigned)__popcll(act));
         base = (unsigned)__builtin_amdgcn_readfirstlane((int)base);
-        if (valid) perm[start[first] + base + (unsigned)lane_id()] = (uint32_t)r;
+        if (valid) perm[start[first] + base + (unsigned)__popcll(act & ((1ull << lane_id()) - 1ull))] = (uint32_t)r;
     } else if (valid) {
         perm[start[s] + atomicAdd(&fill[s], 1u)] = (uint32_t)r;
     }
@@ -1384,7 +1406,7 @@ __global__ __launch_bounds__(256) void scope_scan_kernel(const void* __restrict_
 #pragma unroll
     for (int b = 0; b < NB; ++b) qi[b] = b < nq ? sorted_q[p0 + b] : 0u;
     const uint32_t scope = scopes[qi[0]];
-    int64_t lo = 0, hi = 0;   // the scope's rows: scope_perm[lo, hi); scope 0 = every row; a scope nobody carries = none
+    int64_t lo = 0, hi = 0;   // the scope's rows: scope_perm[lo, hi); scope 0 = every listed row (`count`: the live rows); a scope nobody carries = none
     if (scope == 0u) hi = count;
     else if (scope <= max_scope) { lo = offsets[scope]; hi = offsets[scope + 1]; }
     const int64_t per = scope_part_rows(hi - lo, split);
@@ -1531,6 +1553,59 @@ __global__ __launch_bounds__(256) void scope_scan_kernel(const void* __restrict_
             if (rk < k) dst[rk] = M.v[sl];
         }
     }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Tombstones and compaction.
+//   dead_set_kernel        sets the bits of n row slots (vector atomics: several slots may share a word)
+//   live_prefix_kernel     per bitmap word: the live slots of its 256-word block that lie below it (popcount, Hillis-Steele scan
+//                          in LDS), and the block's total; scope_offsets_kernel turns the totals into block bases.  New slot of a
+//                          live row r = base[block] + prefix[word] + live bits of its word below r: its rank among the live rows.
+//   compact_gather_kernel  one wave per source row of a chunk [s0, s1), whole 16-byte pieces as gather_rows_kernel moves them: a
+//                          live row goes to the bounce buffer at (new slot - dbase), dbase = the chunk's first destination; its
+//                          scope label goes along.  The host then copies the bounce buffer to rows [dbase, dbase + live rows of
+//                          the chunk): rows only move down, and that range ends at or before s1, the next chunk's first source.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void dead_set_kernel(const int64_t* __restrict__ slots, int64_t n, uint32_t* __restrict__ dead) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + (int64_t)threadIdx.x;
+    if (i < n) atomicOr(&dead[slots[i] >> 5], 1u << (uint32_t)(slots[i] & 31));
+}
+// live slots of bitmap word w among rows [0, n)
+__device__ __forceinline__ uint32_t live_bits(const uint32_t* __restrict__ dead, int64_t w, int64_t n) {
+    const int64_t left = n - w * 32;
+    const uint32_t in_range = left >= 32 ? 0xffffffffu : (left > 0 ? (1u << (uint32_t)left) - 1u : 0u);
+    return ~dead[w] & in_range;
+}
+__global__ __launch_bounds__(256) void live_prefix_kernel(const uint32_t* __restrict__ dead, int64_t n, int64_t nwords, unsigned* __restrict__ prefix,
+                                                          unsigned* __restrict__ block_total) {
+    __shared__ unsigned s_p[256];
+    const int tid = (int)threadIdx.x;
+    const int64_t w = (int64_t)blockIdx.x * 256 + tid;
+    const unsigned mine = w < nwords ? (unsigned)__popc(live_bits(dead, w, n)) : 0u;
+    s_p[tid] = mine;
+    __syncthreads();
+    for (int off = 1; off < 256; off <<= 1) {   // Hillis-Steele inclusive scan
+        const unsigned a = tid >= off ? s_p[tid - off] : 0u;
+        __syncthreads();
+        s_p[tid] += a;
+        __syncthreads();
+    }
+    if (w < nwords) prefix[w] = s_p[tid] - mine;
+    if (tid == 255) block_total[blockIdx.x] = s_p[255];
+}
+__global__ __launch_bounds__(256) void compact_gather_kernel(const uint4* __restrict__ rows, const uint32_t* __restrict__ dead, int64_t n,
+                                                             const unsigned* __restrict__ prefix, const unsigned* __restrict__ block_base,
+                                                             const uint32_t* __restrict__ scope_of, int64_t s0, int64_t s1, int64_t dbase,
+                                                             int64_t bounce_rows, int chunks_per_row, uint4* __restrict__ bounce,
+                                                             uint32_t* __restrict__ bounce_scope) {
+    const int lane = lane_id();
+    const int64_t r = s0 + (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= s1 || row_dead(dead, (uint32_t)r)) return;
+    const int64_t w = r >> 5;
+    const int64_t to = (int64_t)block_base[w >> 8] + prefix[w] + __popc(live_bits(dead, w, n) & ((1u << (uint32_t)(r & 31)) - 1u)) - dbase;
+    if (to < 0 || to >= bounce_rows) return;   // (cannot happen: the host sized the chunk from the same bits)
+    for (int j = lane; j < chunks_per_row; j += kWave) bounce[to * chunks_per_row + j] = rows[r * chunks_per_row + j];
+    if (lane == 0 && scope_of) bounce_scope[to] = scope_of[r];
 }
 
 }  // namespace
@@ -1713,6 +1788,16 @@ struct codd_knn_index : WorkBufs {
     hipEvent_t scope_ready = nullptr;
     int64_t stat_scoped_searches = 0, stat_scope_builds = 0;
 
+    // tombstones: one bit per row slot, set = deleted.  Null until the first codd_knn_delete_host — the kernels
+    // take a null pointer as "nothing was ever deleted" and load nothing.  The host keeps a mirror: the write paths refuse dead
+    // slots from it and compaction derives the row mapping from it, so nothing is ever read back.
+    uint32_t* dead_bits = nullptr;     int64_t dead_words_cap = 0;  // [ceil(capacity / 32)] device words
+    std::vector<uint32_t> dead_host;                                // the same bits
+    int64_t dead_count = 0;                                         // dead slots below `count`
+    int64_t first_dead = INT64_MAX;                                 // lowest dead slot
+    int64_t compact_chunk_rows = 0;                                 // "compact_chunk_rows" option: source rows per compaction chunk (0 = what 64 MiB hold)
+    int64_t stat_delete_calls = 0, stat_compactions = 0;
+
     int64_t stat_searches = 0, stat_scan_launches = 0, stat_last_scan_blocks = 0;
     int64_t stat_last_scan_group = 0;       // queries per pass over the rows of the last exact scan (1, 4 or 8; wide 2-byte rows: at most 4)
     int64_t stat_last_finalize_parts = 0;   // workgroups per query of the last filter pass's finalize
@@ -1837,6 +1922,8 @@ struct WorkScope {
 size_t elem_size(int dtype) { return dtype == DT_F32 ? 4 : 2; }
 int elems_per_chunk(int dtype) { return dtype == DT_F32 ? 4 : 8; }
 
+int grow_dead_bits(codd_knn_index* ix, int64_t slots);
+
 // (re)allocate row storage for at least `need` slots, preserving contents (the shadows are derived data with their own
 // allocations: ensure_shadow / ensure_shadow8)
 int grow_rows(codd_knn_index* ix, int64_t need, bool exact) {
@@ -1869,10 +1956,60 @@ int grow_rows(codd_knn_index* ix, int64_t need, bool exact) {
         ix->scope_of = labels;
         ix->scope_of_cap = cap;
     }
+    if (ix->dead_bits) {  // ... and so do the tombstone bits, once they exist
+        const int rc = grow_dead_bits(ix, cap);
+        if (rc != 0) {
+            (void)hipFree(fresh);
+            return rc;
+        }
+    }
     if (ix->rows) (void)hipFree(ix->rows);
     ix->rows = fresh;
     ix->capacity = cap;
     return CODD_KNN_OK;
+}
+
+// the tombstone bits cover `slots` row slots (device words and host mirror; contents kept, new words zero).  Exclusive callers only.
+int grow_dead_bits(codd_knn_index* ix, int64_t slots) {
+    const int64_t words = (slots + 31) / 32;
+    if (words <= ix->dead_words_cap) return CODD_KNN_OK;
+    try {
+        ix->dead_host.resize((size_t)words, 0u);
+    } catch (const std::bad_alloc&) {
+        return fail(CODD_KNN_ENOMEM, "host allocation failed%s");
+    }
+    uint32_t* fresh = nullptr;
+    hipError_t e = hipMalloc((void**)&fresh, (size_t)words * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemset(fresh, 0, (size_t)words * sizeof(uint32_t));
+    if (e == hipSuccess && ix->dead_bits) e = hipMemcpy(fresh, ix->dead_bits, (size_t)ix->dead_words_cap * sizeof(uint32_t), hipMemcpyDeviceToDevice);
+    if (e != hipSuccess) {
+        if (fresh) (void)hipFree(fresh);
+        return fail(e == hipErrorOutOfMemory ? CODD_KNN_ENOMEM : CODD_KNN_EDEVICE, "growing the tombstone bits failed: %s", hipGetErrorString(e));
+    }
+    if (ix->dead_bits) (void)hipFree(ix->dead_bits);
+    ix->dead_bits = fresh;
+    ix->dead_words_cap = words;
+    return CODD_KNN_OK;
+}
+
+bool slot_dead(const codd_knn_index* ix, int64_t slot) {
+    return ix->dead_count > 0 && slot >= 0 && (slot >> 5) < (int64_t)ix->dead_host.size() && ((ix->dead_host[(size_t)(slot >> 5)] >> (slot & 31)) & 1u);
+}
+// any dead slot in [lo, hi)?  (the write paths: a dead slot stays dead until codd_knn_compact)
+bool range_has_dead(const codd_knn_index* ix, int64_t lo, int64_t hi) {
+    if (ix->dead_count == 0 || hi <= ix->first_dead) return false;
+    for (int64_t r = lo > ix->first_dead ? lo : ix->first_dead; r < hi && r < ix->count; ++r)
+        if (slot_dead(ix, r)) return true;
+    return false;
+}
+// live slots in [lo, hi), from the host mirror
+int64_t live_in_range(const codd_knn_index* ix, int64_t lo, int64_t hi) {
+    int64_t dead = 0;
+    for (int64_t r = lo; r < hi;) {
+        if ((r & 31) == 0 && r + 32 <= hi) { dead += __builtin_popcount(ix->dead_host[(size_t)(r >> 5)]); r += 32; }
+        else { dead += (ix->dead_host[(size_t)(r >> 5)] >> (r & 31)) & 1u; ++r; }
+    }
+    return (hi - lo) - dead;
 }
 
 template <typename T>
@@ -2015,6 +2152,7 @@ struct ScanArgs {
     float* merged_dist = nullptr;
     int64_t* merged_rows = nullptr;
     unsigned long long* count_total = nullptr;
+    const uint32_t* dead = nullptr;    // tombstone bits (null: nothing was ever deleted)
 };
 
 // queries per pass of the wide scan: 2-byte rows take at most 4 (8 would spill: the kernel walks a larger batch 4 queries at a time)
@@ -2039,12 +2177,12 @@ int launch_scan(int dtype, int nb, int niter, dim3 grid, hipStream_t st, const S
                         const size_t lds = qbytes > lbytes ? qbytes : lbytes;   // the lists take the queries' place once a group is scanned
                         return launch_kernel<scan_topk_wide_kernel<DT, NBW, SLOTS>>(
                             grid, dim3(kWideScanWaves * kWave), Lds(lds, (size_t)NBW * kWideMaxFloats * sizeof(float)), st, a.rows, a.n, a.dpad, a.qn, a.nq,
-                            a.k, a.row_base, a.partial, a.stride_q, a.qlist, a.qcount, a.merge_done, a.merged_keys, a.merged_dist, a.merged_rows, a.count_total);
+                            a.k, a.row_base, a.partial, a.stride_q, a.qlist, a.qcount, a.merge_done, a.merged_keys, a.merged_dist, a.merged_rows, a.count_total, a.dead);
                     } else {
                         const size_t lds = (size_t)4 * NB * SLOTS * kWave * sizeof(u64);
                         return launch_kernel<scan_topk_kernel<DT, NB, NITER, SLOTS>>(
                             grid, dim3(256), lds, st, a.rows, a.n, a.dpad, a.qn, a.nq, a.k, a.row_base, a.partial, a.stride_q, a.qlist, a.qcount,
-                            a.merge_done, a.merged_keys, a.merged_dist, a.merged_rows, a.count_total);
+                            a.merge_done, a.merged_keys, a.merged_dist, a.merged_rows, a.count_total, a.dead);
                     }
                 });
             });
@@ -2101,6 +2239,7 @@ int exact_scan(codd_knn_index* ix, const float* qn, int nqueries, int k, uint32_
         const int nb = nqueries == 1 ? 1 : (nqueries <= 4 ? 4 : 8);
         ix->stat_last_scan_group = niter > 4 ? wide_scan_nb(ix->dtype, nb) : nb;
         ScanArgs a{ix->rows, n, ix->dpad, qn, nqueries, k, row_base, ix->partial, stride_q};
+        a.dead = ix->dead_bits;
         {
             EvScope ev(ix, EV_SCAN, st);
             rc = launch_scan(ix->dtype, nb, niter, dim3((unsigned)blocks), st, a);
@@ -2218,6 +2357,7 @@ int ensure_shadow(codd_knn_index* ix, hipStream_t st) {
     }
     const int64_t need = (n + kTileRows - 1) / kTileRows * kTileRows;
     int64_t first = ix->dirty16_lo, m = ix->dirty16_hi - ix->dirty16_lo;
+    if (first + m > n) m = n > first ? n - first : 0;  // (never past the count: the allocation below is only checked against it)
     if (need > ix->shadow_rows) {
         // A failed allocation is remembered until rows change (no multi-GB hipMalloc retried by every search); the caller
         // answers the search another way (search_impl: the int8 filter or the exact scan).
@@ -2269,6 +2409,7 @@ int ensure_shadow8(codd_knn_index* ix, hipStream_t st) {
     }
     const int64_t need = (n + kTileRows - 1) / kTileRows * kTileRows;
     int64_t first = ix->dirty_lo, m = ix->dirty_hi - ix->dirty_lo;  // rows to (re)quantise
+    if (first + m > n) m = n > first ? n - first : 0;  // (never past the count: the allocation below is only checked against it)
     if (!ix->eps_r_bits) {
         HIP_TRY(hipMalloc((void**)&ix->eps_r_bits, 2 * sizeof(unsigned)));
         HIP_TRY(hipMemsetAsync(ix->eps_r_bits, 0, 2 * sizeof(unsigned), st));
@@ -2468,6 +2609,7 @@ int listed_fallback(codd_knn_index* ix, const float* qn, int k, uint32_t row_bas
     a.merged_dist = dist_out;
     a.merged_rows = rows_out;
     a.count_total = &ix->dstats[2];
+    a.dead = ix->dead_bits;
     {
         EvScope ev(ix, EV_SCAN, st);
         rc = launch_scan(ix->dtype, 8, niter_of(ix), dim3((unsigned)blocks), st, a);
@@ -2517,7 +2659,7 @@ int filter_pass(codd_knn_index* ix, const float* qn, int nq, int k, uint32_t row
     // thresholds anchored on the exact scores of the k best sampled rows (anchor_thr_kernel)
     rc = with_row_form(ix, k, "row too wide for the threshold kernel%s", [&](auto dt, auto ni, auto sl) {
         return launch_kernel<anchor_thr_kernel<dt, ni, sl>>(dim3(kTileQ), dim3(kAnchorWaves * kWave), 0, st, ix->bucket_max, ts, nq, k, ix->rows,
-                                                            ix->dpad, qn, eps, slack_q, ix->thr, use8 ? ix->thr + kTileQ : nullptr);
+                                                            ix->dpad, qn, eps, slack_q, ix->thr, use8 ? ix->thr + kTileQ : nullptr, ix->dead_bits);
     });
     if (rc != 0) return rc;
     HIP_TRY(hipGetLastError());
@@ -2563,7 +2705,7 @@ int filter_pass(codd_knn_index* ix, const float* qn, int nq, int k, uint32_t row
                 } else {
                     return launch_kernel<finalize_fb_kernel<decltype(dt)::value, ni>>(
                         grid, dim3(kFinThreads), lds, st, ix->rows, ix->dpad, qn, ix->hits, c->hit_cnt, ix->hit_cap_q, c->flags, k, 2.0f * eps, row_base,
-                        keys_out, ix->dstats, slack_q, (u64*)nullptr, dist_out, rows_out, bm, nq, n, ix->fb_partial, stride_q, &c->fb_done);
+                        keys_out, ix->dstats, slack_q, (u64*)nullptr, dist_out, rows_out, bm, nq, n, ix->fb_partial, stride_q, &c->fb_done, ix->dead_bits);
                 }
             });
         });
@@ -2576,7 +2718,7 @@ int filter_pass(codd_knn_index* ix, const float* qn, int nq, int k, uint32_t row
         rc = with_row_form(ix, k, "row too wide for the finalize kernel%s", [&](auto dt, auto ni, auto sl) {
             return launch_kernel<finalize_kernel<dt, ni, sl>>(dim3(nq, nparts), dim3(kFinThreads), 0, st, ix->rows, ix->dpad, qn, ix->hits, c->hit_cnt,
                                                               ix->hit_cap_q, c->flags, k, 2.0f * eps, row_base, keys_out, &c->fb_count, c->fb_list,
-                                                              ix->dstats, slack_q, ix->partial, dist_out, rows_out, bm);
+                                                              ix->dstats, slack_q, ix->partial, dist_out, rows_out, bm, ix->dead_bits);
         });
     }
     if (rc != 0) return rc;
@@ -2608,7 +2750,7 @@ int launch_small_batch(int64_t nunits, hipStream_t st, const codd_knn_index* ix,
     FilterCtl* c = ix->ctl;
     return launch_kernel<small_batch_kernel<DT, NITER, NS>>(grid, dim3(kSbThreads), 0, st, ix->shadow8, ix->bmeta, ix->rows, ix->count, ix->dim, ix->dpad,
                                                             dev_queries, k, row_base, ix->eps_r_bits, ix->qn, cand, dropmax, &c->sb_ticket, &c->fb_count,
-                                                            c->fb_list, out_keys, out_dist, out_rows, ix->dstats);
+                                                            c->fb_list, out_keys, out_dist, out_rows, ix->dstats, ix->dead_bits);
 }
 bool small_batch_applies(const codd_knn_index* ix, int B, int k) {
     const int ns = dpad8_of(ix) / 128;
@@ -2853,9 +2995,9 @@ int ensure_scope_lists(codd_knn_index* ix, hipStream_t st) {
     unsigned* fill = start + nlist + 1;
     HIP_TRY(hipMemsetAsync(fill, 0, (size_t)nlist * sizeof(unsigned), st));
     const unsigned rb = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL(scope_count_kernel, dim3(rb), dim3(256), 0, st, ix->scope_of, n, (int)nlist, fill);
+    hipLaunchKernelGGL(scope_count_kernel, dim3(rb), dim3(256), 0, st, ix->scope_of, n, (int)nlist, fill, ix->dead_bits);
     hipLaunchKernelGGL(scope_offsets_kernel, dim3(1), dim3(1024), 0, st, fill, (int)nlist, start);
-    hipLaunchKernelGGL(scope_scatter_kernel, dim3(rb), dim3(256), 0, st, ix->scope_of, n, (int)nlist, start, fill, ix->scope_perm);
+    hipLaunchKernelGGL(scope_scatter_kernel, dim3(rb), dim3(256), 0, st, ix->scope_of, n, (int)nlist, start, fill, ix->scope_perm, ix->dead_bits);
     HIP_TRY(hipGetLastError());
     if (!ix->scope_ready) HIP_TRY(hipEventCreateWithFlags(&ix->scope_ready, hipEventDisableTiming));
     HIP_TRY(hipEventRecord(ix->scope_ready, st));
@@ -2913,7 +3055,7 @@ int codd_knn_destroy(codd_knn_index* ix) {
     DeviceGuard guard(ix->device);
     (void)hipDeviceSynchronize();
     void* bufs[] = {ix->rows, ix->shadow, ix->dstats, ix->rows_ivf, ix->ivf_ids, ix->ivf_offsets, ix->shadow8, ix->rscale, ix->bmeta, ix->eps_r_bits,
-                    ix->scope_of, ix->scope_perm, ix->scope_offsets};
+                    ix->scope_of, ix->scope_perm, ix->scope_offsets, ix->dead_bits};
     if (ix->scope_ready) (void)hipEventDestroy(ix->scope_ready);
     if (ix->shadow8_ready) (void)hipEventDestroy(ix->shadow8_ready);
     if (ix->shadow_ready) (void)hipEventDestroy(ix->shadow_ready);
@@ -2956,6 +3098,7 @@ int codd_knn_upsert_host(codd_knn_index* ix, const int64_t* host_slots, const fl
     int64_t max_slot = -1, min_slot = INT64_MAX;
     for (int64_t i = 0; i < n; ++i) {
         if (host_slots[i] < 0 || host_slots[i] >= 0xfffffffell) return fail(CODD_KNN_EINVAL, "row slot out of range%s");
+        if (slot_dead(ix, host_slots[i])) return fail(CODD_KNN_EINVAL, "upsert into a deleted row slot (it stays dead until codd_knn_compact)%s");
         if (host_slots[i] > max_slot) max_slot = host_slots[i];
         if (host_slots[i] < min_slot) min_slot = host_slots[i];
     }
@@ -3010,6 +3153,7 @@ int codd_knn_upsert_device(codd_knn_index* ix, int64_t first_slot, const float* 
     if (!ix || n < 0 || first_slot < 0 || (n > 0 && !dev_vecs)) return fail(CODD_KNN_EINVAL, "bad upsert arguments%s");
     if (n == 0) return CODD_KNN_OK;
     if (first_slot + n >= 0xffffffffll) return fail(CODD_KNN_EINVAL, "row slots must fit 32 bits%s");
+    if (range_has_dead(ix, first_slot, first_slot + n)) return fail(CODD_KNN_EINVAL, "upsert into a deleted row slot (it stays dead until codd_knn_compact)%s");
     DeviceGuard guard(ix->device);
     if (first_slot + n > ix->capacity) {
         HIP_TRY(hipDeviceSynchronize());
@@ -3047,6 +3191,7 @@ int codd_knn_load_rows(codd_knn_index* ix, int64_t first_slot, const void* host_
     if (!ix || first_slot < 0 || n < 0 || (n > 0 && !host_rows)) return fail(CODD_KNN_EINVAL, "bad load_rows arguments%s");
     if (n == 0) return CODD_KNN_OK;
     if (first_slot + n >= 0xffffffffll) return fail(CODD_KNN_EINVAL, "row slots must fit 32 bits%s");
+    if (range_has_dead(ix, first_slot, first_slot + n)) return fail(CODD_KNN_EINVAL, "load_rows into a deleted row slot (it stays dead until codd_knn_compact)%s");
     DeviceGuard guard(ix->device);
     HIP_TRY(hipDeviceSynchronize());
     int rc = grow_rows(ix, first_slot + n, /*exact=*/false);
@@ -3318,7 +3463,7 @@ int codd_knn_ivf_search(codd_knn_index* ix, const float* dev_queries, int B, int
         rc = with_row_form(ix, k, "row too wide for the IVF scan%s", [&](auto dt, auto ni, auto sl) {
             return launch_kernel<ivf_scan_shared_kernel<dt, ni, sl>>(dim3((unsigned)bound), dim3(256), 0, st, ix->rows_ivf, ix->ivf_ids, ix->ivf_offsets,
                                                                      pair_start, item_start, sorted_pairs, nlist, nprobe, ix->dpad, ix->qn, k, row_base,
-                                                                     ix->ivf_partial);
+                                                                     ix->ivf_partial, ix->dead_bits);
         });
         if (rc != 0) return rc;
         HIP_TRY(hipGetLastError());
@@ -3336,7 +3481,7 @@ int codd_knn_ivf_search(codd_knn_index* ix, const float* dev_queries, int B, int
         EvScope ev(ix, EV_SCAN, st);
         rc = with_row_form(ix, k, "row too wide for the IVF scan%s", [&](auto dt, auto ni, auto sl) {
             return launch_kernel<ivf_scan_kernel<dt, ni, sl>>(grid, block, 0, st, ix->rows_ivf, ix->ivf_ids, ix->ivf_offsets, ix->probe_keys, nprobe, split,
-                                                              ix->dpad, ix->qn, k, row_base, ix->ivf_partial);
+                                                              ix->dpad, ix->qn, k, row_base, ix->ivf_partial, ix->dead_bits);
         });
     }
     if (rc != 0) return rc;
@@ -3352,6 +3497,7 @@ int codd_knn_set_scopes_host(codd_knn_index* ix, const int64_t* host_slots, cons
     bool increasing = true;
     for (int64_t i = 0; i < n; ++i) {
         if (host_slots[i] < 0 || host_slots[i] >= ix->count) return fail(CODD_KNN_EINVAL, "set_scopes: row slot outside [0, count)%s");
+        if (slot_dead(ix, host_slots[i])) return fail(CODD_KNN_EINVAL, "set_scopes: deleted row slot (it stays dead until codd_knn_compact)%s");
         if (host_scopes[i] > CODD_KNN_MAX_SCOPE) return fail(CODD_KNN_EINVAL, "set_scopes: scope above CODD_KNN_MAX_SCOPE%s");
         if (host_scopes[i] > top) top = host_scopes[i];
         if (i > 0 && host_slots[i] <= host_slots[i - 1]) increasing = false;
@@ -3437,13 +3583,183 @@ int codd_knn_search_scoped(codd_knn_index* ix, const float* dev_queries, const u
         EvScope ev(ix, EV_SCAN, st);
         rc = with_row_form(ix, k, "row too wide for the scope scan%s", [&](auto dt, auto ni, auto sl) {
             return launch_kernel<scope_scan_kernel<dt, ni, sl>>(dim3((unsigned)B, (unsigned)split), dim3(256), 0, st, ix->rows, ix->scope_perm,
-                                                                ix->scope_offsets, n, ix->max_scope, dev_scopes, sorted_q, rank, B, split, ix->dpad,
+                                                                ix->scope_offsets, n - ix->dead_count, ix->max_scope, dev_scopes, sorted_q, rank, B, split, ix->dpad,
                                                                 ix->qn, k, row_base, ix->partial);
         });
     }
     if (rc != 0) return rc;
     HIP_TRY(hipGetLastError());
     return launch_merge(ix->partial, B, m, m, k, (u64*)dev_keys, dev_dist, dev_rows, st);
+}
+
+int codd_knn_delete_host(codd_knn_index* ix, const int64_t* host_slots, int64_t n) {
+    if (!ix || n < 0 || (n > 0 && !host_slots)) return fail(CODD_KNN_EINVAL, "bad delete arguments%s");
+    for (int64_t i = 0; i < n; ++i)
+        if (host_slots[i] < 0 || host_slots[i] >= ix->count) return fail(CODD_KNN_EINVAL, "delete: row slot outside [0, count)%s");
+    if (n == 0) return CODD_KNN_OK;
+    DeviceGuard guard(ix->device);
+    HIP_TRY(hipDeviceSynchronize());
+    int rc;
+    if ((rc = grow_dead_bits(ix, ix->capacity)) != 0) return rc;
+    // the slots that are not dead yet, each once (an already-dead or repeated slot is a no-op): marked in the host mirror first,
+    // taken back if the device cannot follow
+    std::vector<int64_t> fresh;
+    try {
+        for (int64_t i = 0; i < n; ++i) {
+            uint32_t& word = ix->dead_host[(size_t)(host_slots[i] >> 5)];
+            const uint32_t bit = 1u << (uint32_t)(host_slots[i] & 31);
+            if (word & bit) continue;
+            fresh.push_back(host_slots[i]);
+            word |= bit;
+        }
+    } catch (const std::bad_alloc&) {
+        for (int64_t slot : fresh) ix->dead_host[(size_t)(slot >> 5)] &= ~(1u << (uint32_t)(slot & 31));
+        return fail(CODD_KNN_ENOMEM, "host allocation failed%s");
+    }
+    auto undo = [&]() {
+        for (int64_t slot : fresh) ix->dead_host[(size_t)(slot >> 5)] &= ~(1u << (uint32_t)(slot & 31));
+        if (ix->dead_bits) (void)hipMemcpy(ix->dead_bits, ix->dead_host.data(), (size_t)ix->dead_words_cap * sizeof(uint32_t), hipMemcpyHostToDevice);
+    };
+    // the staging buffer codd_knn_upsert_host keeps between calls, grown once to hold the call's slots (at most 1M of them, 8 MiB:
+    // a piece costs a copy, a launch and a synchronisation — 5M slots through 4,096-slot pieces were 1,221 such round trips)
+    const int64_t total = (int64_t)fresh.size();
+    const int64_t want = total < 4096 ? 4096 : (total < (1ll << 20) ? total : (1ll << 20));
+    if (ix->stage_slot_cap < want) {
+        if (ix->stage_slot) (void)hipFree(ix->stage_slot);
+        ix->stage_slot = nullptr; ix->stage_slot_cap = 0;
+        if (hipMalloc((void**)&ix->stage_slot, (size_t)want * sizeof(int64_t)) != hipSuccess) {
+            (void)hipGetLastError();
+            undo();
+            return fail(CODD_KNN_ENOMEM, "delete: staging buffer%s");
+        }
+        ix->stage_slot_cap = want;
+    }
+    const int64_t pn = ix->stage_slot_cap;
+    for (int64_t i0 = 0; i0 < total; i0 += pn) {
+        const int64_t m = total - i0 < pn ? total - i0 : pn;
+        hipError_t e = hipMemcpy(ix->stage_slot, fresh.data() + i0, (size_t)m * sizeof(int64_t), hipMemcpyHostToDevice);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(dead_set_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, nullptr, ix->stage_slot, m, ix->dead_bits);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipDeviceSynchronize();  // (the staging buffer is reused by the next piece, and the call is synchronous by contract)
+        if (e != hipSuccess) {
+            undo();
+            return fail(CODD_KNN_EDEVICE, "delete: setting the tombstone bits failed: %s", hipGetErrorString(e));
+        }
+    }
+    ix->stat_delete_calls++;
+    if (total == 0) return CODD_KNN_OK;
+    ix->dead_count += total;
+    for (int64_t slot : fresh)
+        if (slot < ix->first_dead) ix->first_dead = slot;
+    ix->scope_gen++;  // the scope lists leave dead rows out: rebuilt by the next scoped search, like after a label change
+    // (no epoch bump: the stored rows and both shadows are what they were, and an installed IVF layout stays valid — its scans
+    //  mask by the original row slot)
+    return CODD_KNN_OK;
+}
+
+int codd_knn_live_count(const codd_knn_index* ix, int64_t* out) {
+    if (!ix || !out) return fail(CODD_KNN_EINVAL, "bad live_count arguments%s");
+    *out = ix->count - ix->dead_count;
+    return CODD_KNN_OK;
+}
+
+int codd_knn_compact(codd_knn_index* ix, int64_t* new_count) {
+    if (!ix) return fail(CODD_KNN_EINVAL, "null index%s");
+    if (ix->dead_count == 0) {
+        if (new_count) *new_count = ix->count;
+        return CODD_KNN_OK;
+    }
+    DeviceGuard guard(ix->device);
+    HIP_TRY(hipDeviceSynchronize());
+    const int64_t n = ix->count, live = n - ix->dead_count, first = ix->first_dead;
+    const size_t row_bytes = (size_t)ix->dpad * elem_size(ix->dtype);
+    const int cpr = (int)(row_bytes / 16);
+    // source rows per chunk: what the bounce buffer (the staging buffer of codd_knn_upsert_host, at most 64 MiB) holds
+    int64_t chunk = ix->compact_chunk_rows > 0 ? ix->compact_chunk_rows : (int64_t)((64ull << 20) / row_bytes);
+    if (chunk > n - first) chunk = n - first;
+    if (chunk < 1) chunk = 1;
+    const int64_t bounce_floats = (chunk * (int64_t)row_bytes + 3) / 4;
+    if (bounce_floats > ix->stage_vec_cap) {
+        if (ix->stage_vec) (void)hipFree(ix->stage_vec);
+        ix->stage_vec = nullptr; ix->stage_vec_cap = 0;
+        const int64_t want = bounce_floats < 65536 ? 65536 : bounce_floats;
+        HIP_TRY(hipMalloc((void**)&ix->stage_vec, (size_t)want * sizeof(float)));
+        ix->stage_vec_cap = want;
+    }
+    if ((chunk + 1) / 2 > ix->stage_slot_cap) {  // the chunk's scope labels, 4 bytes each
+        if (ix->stage_slot) (void)hipFree(ix->stage_slot);
+        ix->stage_slot = nullptr; ix->stage_slot_cap = 0;
+        const int64_t want = (chunk + 1) / 2 < 4096 ? 4096 : (chunk + 1) / 2;
+        HIP_TRY(hipMalloc((void**)&ix->stage_slot, (size_t)want * sizeof(int64_t)));
+        ix->stage_slot_cap = want;
+    }
+    // new slot of a live row = its rank among the live rows: prefix sums over the bitmap, on the device
+    const int64_t nwords = (n + 31) / 32, nblocks = (nwords + 255) / 256;
+    unsigned* sums = nullptr;   // [nwords] per-word prefix, [nblocks] block totals, [nblocks + 1] block bases
+    HIP_TRY(hipMalloc((void**)&sums, (size_t)(nwords + 2 * nblocks + 1) * sizeof(unsigned)));
+    unsigned* prefix = sums;
+    unsigned* block_total = prefix + nwords;
+    unsigned* block_base = block_total + nblocks;
+    hipLaunchKernelGGL(live_prefix_kernel, dim3((unsigned)nblocks), dim3(256), 0, nullptr, ix->dead_bits, n, nwords, prefix, block_total);
+    hipLaunchKernelGGL(scope_offsets_kernel, dim3(1), dim3(1024), 0, nullptr, block_total, (int)nblocks, block_base);
+    hipError_t e = hipGetLastError();
+    // ascending chunks of source rows from the first dead slot on (the rows below it stay where they are), ordered on one stream
+    uint4* rows4 = reinterpret_cast<uint4*>(ix->rows);
+    uint4* bounce = reinterpret_cast<uint4*>(ix->stage_vec);
+    uint32_t* bounce_scope = reinterpret_cast<uint32_t*>(ix->stage_slot);
+    int64_t dbase = first;  // every slot below the first dead one is live
+    for (int64_t s0 = first; s0 < n && e == hipSuccess; s0 += chunk) {
+        const int64_t s1 = s0 + chunk < n ? s0 + chunk : n;
+        const int64_t moved = live_in_range(ix, s0, s1);
+        if (moved == 0) continue;
+        hipLaunchKernelGGL(compact_gather_kernel, dim3((unsigned)((s1 - s0 + 3) / 4)), dim3(256), 0, nullptr, rows4, ix->dead_bits, n, prefix, block_base,
+                           ix->scope_of, s0, s1, dbase, chunk, cpr, bounce, bounce_scope);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync((char*)ix->rows + (size_t)dbase * row_bytes, bounce, (size_t)moved * row_bytes, hipMemcpyDeviceToDevice, nullptr);
+        if (e == hipSuccess && ix->scope_of)
+            e = hipMemcpyAsync(ix->scope_of + dbase, bounce_scope, (size_t)moved * sizeof(uint32_t), hipMemcpyDeviceToDevice, nullptr);
+        dbase += moved;
+    }
+    // the slots past the live rows are new slots again: no label, no tombstone; the int8 shadow's scales there read "no such row"
+    if (e == hipSuccess && ix->scope_of) e = hipMemsetAsync(ix->scope_of + live, 0, (size_t)(n - live) * sizeof(uint32_t), nullptr);
+    if (e == hipSuccess) e = hipMemsetAsync(ix->dead_bits, 0, (size_t)ix->dead_words_cap * sizeof(uint32_t), nullptr);
+    if (e == hipSuccess && ix->rscale) {
+        const int64_t hi = n < ix->shadow8_rows ? n : ix->shadow8_rows;
+        if (hi > live) e = hipMemsetD32Async((hipDeviceptr_t)(ix->rscale + live), (int)0x7fc00000, (size_t)(hi - live), nullptr);
+        const int64_t b0 = (live + 31) / 32, b1 = (hi + 31) / 32;
+        if (e == hipSuccess && b1 > b0) e = hipMemsetD32Async((hipDeviceptr_t)(ix->bmeta + b0), (int)0x7fc00000, (size_t)(b1 - b0) * 2, nullptr);
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    (void)hipFree(sums);
+    // A device failure in the middle leaves rows partly moved under an unchanged bitmap and count: the index is unusable from
+    // then on (destroy it and rebuild the collection), as the header says.  Nothing short of a device error gets here.
+    if (e != hipSuccess) return fail(CODD_KNN_EDEVICE, "compaction failed, the index is unusable: %s", hipGetErrorString(e));
+    if (dbase != live) return fail(CODD_KNN_EDEVICE, "compaction: the host's row mapping disagrees with its dead count%s");
+    std::fill(ix->dead_host.begin(), ix->dead_host.end(), 0u);
+    ix->count = live;
+    ix->dead_count = 0;
+    ix->first_dead = INT64_MAX;
+    ix->rows_event_set = false;  // (everything is complete on the device)
+    ix->reader_event_set = false;
+    // both shadows are dirty from the first dead slot on (and the last live row's 32-row block is quantised again: its scale
+    // spanned rows that are gone); the epoch bump makes an installed IVF layout stale, as after an upsert
+    // A dirty range still pending from earlier upserts may reach past the new count (the count never shrank before compaction
+    // existed): cut it back first — a shadow build over rows past the count would write past a shadow sized for the count.
+    // Every pending dirty row at or behind `first` has moved to a slot in [first, live): the widened range below covers it.
+    auto cut = [&](int64_t& dlo, int64_t& dhi) {
+        if (dhi > live) dhi = live;
+        if (dlo > dhi) dlo = dhi;
+    };
+    cut(ix->dirty_lo, ix->dirty_hi);
+    cut(ix->dirty16_lo, ix->dirty16_hi);
+    const int64_t lo = live > 0 ? (first < live - 1 ? first : live - 1) : 0;
+    rows_written(ix, lo, live);
+    ix->scope_gen++;
+    ix->stat_compactions++;
+    if (new_count) *new_count = live;
+    return CODD_KNN_OK;
 }
 
 #ifdef CODD_I8_EXP_STAMPS
@@ -3575,6 +3891,11 @@ int codd_knn_set_option(codd_knn_index* ix, const char* key, int64_t value) {
         ix->sample_div = (int)value;
         return CODD_KNN_OK;
     }
+    if (strcmp(key, "compact_chunk_rows") == 0) {
+        if (value < 0 || value > (1ll << 32)) return fail(CODD_KNN_EINVAL, "compact_chunk_rows must be in [0,2^32]%s");
+        ix->compact_chunk_rows = value;
+        return CODD_KNN_OK;
+    }
     if (strcmp(key, "hit_cap") == 0) {
         if (value < 16 || value > (1 << 20)) return fail(CODD_KNN_EINVAL, "hit_cap must be in [16,2^20]%s");
         ix->hit_cap_q = (int)value;
@@ -3632,6 +3953,9 @@ int codd_knn_get_stat(const codd_knn_index* ix, const char* key, int64_t* out) {
     else if (strcmp(key, "scoped_searches") == 0) *out = ix->stat_scoped_searches;
     else if (strcmp(key, "scope_builds") == 0) *out = ix->stat_scope_builds;
     else if (strcmp(key, "scopes") == 0) *out = (int64_t)ix->max_scope;
+    else if (strcmp(key, "dead_rows") == 0) *out = ix->dead_count;
+    else if (strcmp(key, "delete_calls") == 0) *out = ix->stat_delete_calls;
+    else if (strcmp(key, "compactions") == 0) *out = ix->stat_compactions;
     else if (strcmp(key, "filter_passes") == 0) *out = ix->stat_filter_passes;
     else if (strcmp(key, "shadow8_builds") == 0) *out = ix->stat_shadow8_builds;
     else if (strcmp(key, "shadow16_builds") == 0) *out = ix->stat_shadow_builds;
@@ -3670,7 +3994,7 @@ int codd_knn_get_stat(const codd_knn_index* ix, const char* key, int64_t* out) {
     else if (strcmp(key, "num_cus") == 0) *out = ix->num_cus;
     else if (strcmp(key, "device_bytes") == 0) {
         int64_t b = ix->capacity * (int64_t)ix->dpad * (int64_t)elem_size(ix->dtype) + ix->shadow_rows * (int64_t)ix->dpad * 2 +
-                    ix->shadow8_rows * ((int64_t)dpad8_of(ix) + 4) + (ix->scope_of_cap + ix->scope_perm_cap + ix->scope_lists_cap) * 4;
+                    ix->shadow8_rows * ((int64_t)dpad8_of(ix) + 4) + (ix->scope_of_cap + ix->scope_perm_cap + ix->scope_lists_cap + ix->dead_words_cap) * 4;
         for (const WorkSlot& w : ix->slots)
             b += w.bufs.qn_cap * 4 + w.bufs.partial_cap * 8 + w.bufs.keys_tmp_cap * 8 + w.bufs.hits_cap * 8 + w.bufs.bucket_cap * 8 +
                  w.bufs.qfrag_cap * 16 + w.bufs.fb_partial_cap * 8 + w.bufs.probe_cap * 8 + w.bufs.ivf_partial_cap * 8;

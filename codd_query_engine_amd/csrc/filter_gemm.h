@@ -887,13 +887,17 @@ __device__ __forceinline__ void wide_scores(const uint4* const (&p)[4 * G], int 
 //   eps1 : the slack between an approximate and an exact score — the whole of it, or (bmeta != nullptr, the int8 filter) its
 //          block-independent part A(q), with bq = B(q): eps(q, block) = A + B e_block, e_block = bmeta[row / 32].y
 //   out_*_q / part_keys_q : where this query's k results go (any may be null)
+//   dead : the tombstone bits (null: no row was ever deleted).  A dead hit is dropped BEFORE the k best approximate hits are
+//          chosen — L' must be the smallest exact score of k LIVE rows, or rows between a dead anchor's score and the live
+//          k-th best would be cut off — and it is never re-scored into the answer.
 // Shared by finalize_kernel and by the last workgroup of small_batch_kernel (codd_knn.hip).
 template <int DT, int NITER, int SLOTS>
 __device__ __forceinline__ void finalize_body(const void* __restrict__ rows_, int dpad, const float* __restrict__ qn_q, const u64* __restrict__ my,
                                               unsigned total, unsigned part, unsigned nparts, int k, float eps1, float bq,
                                               const float2* __restrict__ bmeta, uint32_t row_base, u64* __restrict__ out_keys_q,
                                               float* __restrict__ out_dist_q, int64_t* __restrict__ out_rows_q, u64* __restrict__ part_keys_q,
-                                              unsigned long long* __restrict__ stats, float* lo_out = nullptr) {
+                                              unsigned long long* __restrict__ stats, const uint32_t* __restrict__ dead,
+                                              float* lo_out = nullptr) {
     typedef RowTraits<DT> RT;
     constexpr int E = RT::E;
     __shared__ u64 lds_list[kFinWaves * SLOTS * kWave];
@@ -926,7 +930,9 @@ __device__ __forceinline__ void finalize_body(const void* __restrict__ rows_, in
     L.init();
     for (unsigned i0 = wave * kWave; i0 < total; i0 += kFinThreads) {
         const unsigned i = i0 + lane;
-        L.offer_lanes(i < total ? my[i] : 0ull, k, lane);
+        u64 key = i < total ? my[i] : 0ull;
+        if (dead && key && row_dead(dead, key_row(key))) key = 0ull;
+        L.offer_lanes(key, k, lane);
     }
 #pragma unroll
     for (int s = 0; s < SLOTS; ++s) lds_list[(wave * SLOTS + s) * kWave + lane] = L.v[s];
@@ -1030,7 +1036,7 @@ __device__ __forceinline__ void finalize_body(const void* __restrict__ rows_, in
         for (unsigned i = b0 + tid; i < b1; i += kFinThreads) {
             const u64 key = my[i];
             const float slack_b = bmeta ? bq * bmeta[key_row(key) >> 5].y : 0.0f;
-            if (key_score(key) + slack_b >= lo) lds_surv[atomicAdd(&lds_n, 1u)] = key_row(key);
+            if (key_score(key) + slack_b >= lo && !(dead && row_dead(dead, key_row(key)))) lds_surv[atomicAdd(&lds_n, 1u)] = key_row(key);
         }
         __syncthreads();
         const unsigned ns = lds_n;
@@ -1108,7 +1114,8 @@ __global__ __launch_bounds__(kFinThreads) void finalize_kernel(const void* __res
                                                        unsigned* __restrict__ fb_count, unsigned* __restrict__ fb_list,
                                                        unsigned long long* __restrict__ stats, const float* __restrict__ two_eps_q = nullptr,
                                                        u64* __restrict__ part_keys = nullptr, float* __restrict__ out_dist = nullptr,
-                                                       int64_t* __restrict__ out_rows = nullptr, const float2* __restrict__ bmeta = nullptr) {
+                                                       int64_t* __restrict__ out_rows = nullptr, const float2* __restrict__ bmeta = nullptr,
+                                                       const uint32_t* __restrict__ dead = nullptr) {
     // bmeta (int8 filter; two_eps_q = qmeta + 256): the slack is evaluated per 32-row block, eps(q, block) = A(q) + B(q) e_block
     // (A at two_eps_q[256 + q], B at two_eps_q[512 + q], e_block = bmeta[row / 32].y): a hit survives iff
     // approx + B e_block >= L' - A.  Valid whichever kernel wrote the hit list (every kernel's list holds these rows).
@@ -1129,7 +1136,7 @@ __global__ __launch_bounds__(kFinThreads) void finalize_kernel(const void* __res
     const float bq = bmeta ? two_eps_q[512 + q] : 0.0f;
     finalize_body<DT, NITER, SLOTS>(rows_, dpad, qn + (int64_t)q * dpad, hits + (int64_t)q * cap_q, total, part, nparts, k, eps1, bq, bmeta, row_base,
                                     out_keys ? out_keys + (int64_t)q * k : nullptr, out_dist ? out_dist + (int64_t)q * k : nullptr,
-                                    out_rows ? out_rows + (int64_t)q * k : nullptr, part_keys ? part_keys + ((int64_t)q * nparts + part) * k : nullptr, stats);
+                                    out_rows ? out_rows + (int64_t)q * k : nullptr, part_keys ? part_keys + ((int64_t)q * nparts + part) * k : nullptr, stats, dead);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1139,13 +1146,16 @@ __global__ __launch_bounds__(kFinThreads) void finalize_kernel(const void* __res
 // score >= L - eps.  thr[q] = L - eps(q); -inf when fewer than k buckets hold a row; +inf for padding queries.
 // (Anchoring on exact scores costs k row reads per query and saves one eps of slack against the k-th largest
 // *approximate* bucket maximum: a third fewer hits for the bf16 filter, 6x fewer for the int8 one.)
+// dead (tombstone bits, null: none): a bucket whose best row is deleted is no anchor — its score bounds nothing a live row
+// reaches.  Fewer than k live anchors: thr = -inf as above, every row becomes a hit and the query is answered by finalize over
+// all of them or, past the candidate capacity, by the exact-scan fallback queue; never a threshold from fewer than k rows.
 // ---------------------------------------------------------------------------------------------
 constexpr int kAnchorWaves = 4;  // waves per query: the bucket scan and the k row reads are shared out (one wave: 19 us of a 430 us shard step)
 template <int DT, int NITER, int SLOTS>
 __global__ __launch_bounds__(kAnchorWaves * kWave) void anchor_thr_kernel(const u64* __restrict__ bucket_key, int64_t nbuckets, int B, int k,
                                                                           const void* __restrict__ rows_, int dpad, const float* __restrict__ qn, float eps,
                                                                           const float* __restrict__ two_eps_q, float* __restrict__ thr,
-                                                                          float* __restrict__ thr0 = nullptr) {
+                                                                          float* __restrict__ thr0 = nullptr, const uint32_t* __restrict__ dead = nullptr) {
     // thr0 (int8 filter, with two_eps_q = qmeta + 256): L - A(q), the block-independent part of the per-block threshold
     // L - A(q) - B(q) e_block that i8_tile_kernel evaluates (A at two_eps_q[256 + q])
     typedef RowTraits<DT> RT;
@@ -1180,7 +1190,9 @@ __global__ __launch_bounds__(kAnchorWaves * kWave) void anchor_thr_kernel(const 
     L.init();
     for (int64_t i0 = (int64_t)wave * kWave; i0 < nbuckets; i0 += kAnchorWaves * kWave) {
         const int64_t i = i0 + lane;
-        L.offer_lanes(i < nbuckets ? bucket_key[(int64_t)q * nbuckets + i] : 0ull, k, lane);
+        u64 key = i < nbuckets ? bucket_key[(int64_t)q * nbuckets + i] : 0ull;
+        if (dead && key && row_dead(dead, key_row(key))) key = 0ull;
+        L.offer_lanes(key, k, lane);
     }
 #pragma unroll
     for (int s = 0; s < SLOTS; ++s) lds_list[(wave * SLOTS + s) * kWave + lane] = L.v[s];

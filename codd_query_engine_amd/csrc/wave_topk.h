@@ -28,6 +28,13 @@ __device__ __forceinline__ u64 make_key(float score, uint32_t row) {
 __device__ __forceinline__ float key_score(u64 key) { return unord_f32((uint32_t)(key >> 32)); }
 __device__ __forceinline__ uint32_t key_row(u64 key) { return 0xffffffffu - (uint32_t)(key & 0xffffffffull); }
 
+// ---- tombstones: one bit per row slot, set = deleted ------------------------------
+// `dead` is null until the first codd_knn_delete_host: every kernel tests the pointer before it calls this
+// (wave-uniform, outside its per-row work), so an index nobody deleted from issues no extra load.
+__device__ __forceinline__ bool row_dead(const uint32_t* __restrict__ dead, uint32_t row) {
+    return ((dead[row >> 5] >> (row & 31u)) & 1u) != 0u;
+}
+
 // ---- cross-lane moves of 64-bit values -----------------------------------------------------
 __device__ __forceinline__ u64 shfl_up1_u64(u64 v) {
     const uint32_t lo = __shfl_up((uint32_t)v, 1), hi = __shfl_up((uint32_t)(v >> 32), 1);

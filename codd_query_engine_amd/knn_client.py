@@ -24,6 +24,7 @@ share a directory.  Layout per collection:
                                /ids.json, metadatas.jsonl, documents.jsonl
 
 `persist()` writes a new generation and flips CURRENT; `reload()` picks up a newer generation.
+Deleted records never reach the disk: `persist()` compacts a collection before it writes it.
 """
 
 from __future__ import annotations
@@ -54,9 +55,14 @@ def _default_engine_factory(device: str, dtype: str) -> Callable[[int], Any]:
 class Collection:
     """One named set of (id, document, metadata, embedding) rows.
 
-    Row slots are assigned in first-insertion order and never move, so "ties -> lower row"
-    means "ties -> the id inserted first".
+    Row slots are assigned in first-insertion order, so "ties -> lower row" means "ties -> the id
+    inserted first".  A deleted record's slot becomes a tombstone (its id is None in the host lists, the
+    engine never returns it) and is not reused: an id that is deleted and upserted again takes a fresh
+    slot at the end, a new insertion for the tie rule.  compact() squeezes the tombstones out; the live
+    rows keep their relative order, so the tie rule survives it.
     """
+
+    AUTO_COMPACT_SHARE = 0.5  # compact() runs by itself once dead slots exceed this share of all slots
 
     def __init__(self, name: str, metadata: Optional[dict], embedding_function: EmbeddingFunction,
                  engine_factory: Callable[[int], Any]):
@@ -65,7 +71,7 @@ class Collection:
         self._embed = embedding_function
         self._engine_factory = engine_factory
         self._engine = None
-        self._ids: list[str] = []
+        self._ids: list[Optional[str]] = []  # by row slot; None = deleted (tombstone until compact())
         self._slot_of: dict[str, int] = {}
         self._documents: list[Optional[str]] = []
         self._metadatas: list[Optional[dict]] = []
@@ -91,7 +97,8 @@ class Collection:
         return np.ascontiguousarray(m)
 
     def count(self) -> int:
-        return len(self._ids)
+        """Live records (deleted ones do not count)."""
+        return len(self._slot_of)
 
     # ------------------------------------------------------------------ namespaces -> scopes
     def _scope_for(self, metadata: Optional[dict]) -> int:
@@ -184,6 +191,54 @@ class Collection:
             if scopes.any() or len(fresh) < n:  # (a new slot starts with scope 0; a rewritten one may have to lose its label)
                 engine.set_scopes(slots, scopes)
 
+    def delete(self, ids: Optional[Sequence[str]] = None, where=None) -> None:
+        """chromadb Collection.delete: forget records by id and / or by namespace.
+
+        ids: unknown ids are ignored.  where: the forms `query` accepts for one query ({"namespace": "x"} or
+        {"namespace": {"$eq": "x"}}): every record of that namespace.  Both: the intersection.  Neither: ValueError.
+        The engine is told first (the rows become tombstones no search returns), then the host lists follow."""
+        if ids is None and where is None:
+            raise ValueError("delete needs ids and / or where")
+        if ids is not None:
+            ids = list(ids)
+            if any(not isinstance(i, str) or not i for i in ids):
+                raise ValueError("ids must be non-empty strings")
+        namespace = self._where_namespace(where)
+        if self._engine is not None and not hasattr(self._engine, "delete"):
+            raise NotImplementedError(f"{type(self._engine).__name__} has no delete: Collection.delete needs an engine with delete / live_count / compact")
+        if ids is None:
+            slots = [s for s, md in enumerate(self._metadatas) if self._ids[s] is not None and md and md.get("namespace") == namespace]
+        else:
+            slots = sorted({self._slot_of[i] for i in ids if i in self._slot_of})
+            if where is not None:
+                slots = [s for s in slots if self._metadatas[s] and self._metadatas[s].get("namespace") == namespace]
+        if not slots:
+            return
+        self._engine.delete(np.asarray(slots, dtype=np.int64))  # device first: host bookkeeping only changes if it succeeded
+        for s in slots:
+            del self._slot_of[self._ids[s]]
+            self._ids[s] = None
+            self._documents[s] = None
+            self._metadatas[s] = None
+        self._dirty = True
+        if len(self._ids) - len(self._slot_of) > self.AUTO_COMPACT_SHARE * len(self._ids):
+            self.compact()
+
+    def compact(self) -> int:
+        """Squeeze the tombstones out: the engine moves the live rows to slots 0 .. live-1 in slot order and the host lists are
+        renumbered by the same mapping.  Answers do not change.  Returns the number of slots (= live records) afterwards."""
+        if len(self._slot_of) == len(self._ids):
+            return len(self._ids)
+        new_count = self._engine.compact()
+        keep = [s for s, doc_id in enumerate(self._ids) if doc_id is not None]
+        if new_count != len(keep):
+            raise RuntimeError(f"engine compacted to {new_count} rows, the host lists hold {len(keep)} live records")
+        self._ids = [self._ids[s] for s in keep]
+        self._documents = [self._documents[s] for s in keep]
+        self._metadatas = [self._metadatas[s] for s in keep]
+        self._slot_of = {doc_id: i for i, doc_id in enumerate(self._ids)}
+        return new_count
+
     def add(self, ids: Sequence[str], embeddings=None, metadatas=None, documents=None) -> None:
         """chromadb Collection.add: like upsert, but ids already present are left untouched."""
         keep = [i for i, d in enumerate(ids) if d not in self._slot_of]
@@ -198,7 +253,8 @@ class Collection:
             include: Sequence[str] = ("metadatas", "documents")) -> dict:
         """chromadb Collection.get: FLAT lists; unknown ids are skipped (store.py:260-261)."""
         if ids is None:
-            slots = list(range(len(self._ids)))[offset : (None if limit is None else offset + limit)]
+            live = [s for s, doc_id in enumerate(self._ids) if doc_id is not None]
+            slots = live[offset : (None if limit is None else offset + limit)]
         else:
             slots = [self._slot_of[i] for i in ids if i in self._slot_of]
         return {
@@ -231,11 +287,11 @@ class Collection:
         empty = {"ids": [[] for _ in range(B)], "distances": [[] for _ in range(B)] if "distances" in include else None,
                  "metadatas": [[] for _ in range(B)] if "metadatas" in include else None,
                  "documents": [[] for _ in range(B)] if "documents" in include else None, "embeddings": None}
-        if self._engine is None or len(self._ids) == 0 or B == 0:
+        if self._engine is None or len(self._slot_of) == 0 or B == 0:
             return empty
         if q.shape[1] != self._engine.dim:
             raise ValueError(f"query dimension {q.shape[1]} does not match collection dimension {self._engine.dim}")
-        k = min(int(n_results), len(self._ids))
+        k = min(int(n_results), len(self._slot_of))  # (the live count: deleted records are never returned)
         scopes = None if where is None else self._where_scopes(where, B)
         if scopes is None:
             dist, rows = self._engine.search(q, k)
@@ -263,6 +319,7 @@ class Collection:
     # ------------------------------------------------------------------ persistence
     def _write_generation(self, directory: str) -> None:
         """Write gen-<n+1> under `directory`, then flip CURRENT (atomic rename)."""
+        self.compact()  # a generation on disk holds live rows only (the format knows nothing of tombstones)
         gen = self._generation + 1
         name = f"gen-{gen:08d}"
         tmp = os.path.join(directory, f".{name}.tmp-{os.getpid()}")

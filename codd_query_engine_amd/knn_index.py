@@ -34,7 +34,8 @@ class DeviceKnnIndex:
     """Device-resident, L2-normalised row store with exact cosine top-k search.
 
     Engine protocol consumed by knn_client.Collection:
-        count() / upsert(slots, vecs) / search(queries, k) -> (dist, rows) as numpy.
+        count() / upsert(slots, vecs) / search(queries, k) -> (dist, rows) as numpy;
+        optionally set_scopes / search_scoped (`where=`) and delete / live_count / compact (`Collection.delete`).
     """
 
     def __init__(self, dim: int, dtype: str = "f32", device: str = "cuda:0"):
@@ -166,6 +167,27 @@ class DeviceKnnIndex:
         if slots.ndim != 1 or scopes.shape != slots.shape:
             raise ValueError(f"expected slots [n] and scopes [n], got {slots.shape} / {scopes.shape}")
         native.check(self._lib.codd_knn_set_scopes_host(self._h, slots.ctypes.data, scopes.ctypes.data, slots.shape[0]), "codd_knn_set_scopes_host")
+
+    # ------------------------------------------------------------------ deletes
+    def delete(self, slots) -> None:
+        """Tombstone the given row slots (each < count(); repeats and already-dead slots are no-ops).  No search returns a dead
+        row; the slot stays dead, and cannot be written, until compact()."""
+        slots = np.ascontiguousarray(slots, dtype=np.int64)
+        if slots.ndim != 1:
+            raise ValueError(f"expected slots [n], got {slots.shape}")
+        native.check(self._lib.codd_knn_delete_host(self._h, slots.ctypes.data, slots.shape[0]), "codd_knn_delete_host")
+
+    def live_count(self) -> int:
+        """Row slots in use minus the dead ones (count() stays highest written slot + 1)."""
+        out = ctypes.c_int64()
+        native.check(self._lib.codd_knn_live_count(self._h, ctypes.byref(out)), "codd_knn_live_count")
+        return out.value
+
+    def compact(self) -> int:
+        """Move the live rows to slots 0 .. live-1 in slot order (scopes move along) and return the new count()."""
+        out = ctypes.c_int64()
+        native.check(self._lib.codd_knn_compact(self._h, ctypes.byref(out)), "codd_knn_compact")
+        return out.value
 
     def _scopes_tensor(self, scopes, B: int):
         torch = _torch()

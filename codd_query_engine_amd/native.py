@@ -47,6 +47,9 @@ ABI = [
     ("codd_knn_ivf_search", ctypes.c_int, [_c_idx, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     ("codd_knn_set_scopes_host", ctypes.c_int, [_c_idx, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]),
     ("codd_knn_search_scoped", ctypes.c_int, [_c_idx, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    ("codd_knn_delete_host", ctypes.c_int, [_c_idx, ctypes.c_void_p, ctypes.c_int64]),
+    ("codd_knn_live_count", ctypes.c_int, [_c_idx, _i64p]),
+    ("codd_knn_compact", ctypes.c_int, [_c_idx, _i64p]),
     ("codd_knn_set_option", ctypes.c_int, [_c_idx, ctypes.c_char_p, ctypes.c_int64]),
     ("codd_knn_get_stat", ctypes.c_int, [_c_idx, ctypes.c_char_p, _i64p]),
 ]

@@ -10,7 +10,8 @@ The client object is duck-typed exactly as the reference duck-types chromadb: an
 `get_or_create_collection(name=, metadata=)` returning an object with upsert / get / query.
 In this build that object is codd_query_engine_amd.knn_client.KnnClient (HIP engine).
 
-One extension, needed for batched configs: `search_metadata_batch`.
+Extensions beyond the reference: `search_metadata_batch` (batched configs), `namespace=` on the searches,
+`delete_metadata` / `delete_namespace` (metrics are renamed and retired, namespaces decommissioned).
 """
 
 from __future__ import annotations
@@ -205,6 +206,36 @@ class MetricsSemanticMetadataStore:
         except Exception as exc:
             logger.warning(f"Error checking if metric exists: {exc}")
             return False
+
+    # ------------------------------------------------------------------ deletes (extensions beyond the reference, like namespace=)
+    def delete_metadata(self, namespace: str, metric_name: str) -> bool:
+        """Extension (the reference never forgets a metric): remove `namespace#metric_name`, the id index_metadata
+        builds.  True when the record existed.  A bad metric name raises the same ValidationError as index_metadata."""
+        metric_name = str(metric_name)
+        self._validate_metric_name(metric_name)
+        document_id = f"{namespace}#{metric_name}"
+        try:
+            found = self.collection.get(ids=[document_id])
+            if not (found and found.get("ids")):
+                return False
+            self.collection.delete(ids=[document_id])
+        except Exception as exc:
+            logger.error(f"Failed to delete metric '{document_id}': {exc}")
+            raise
+        logger.debug(f"Deleted metric: {document_id}")
+        return True
+
+    def delete_namespace(self, namespace: str) -> int:
+        """Extension: remove every record of one namespace (a decommissioned cluster).  Returns how many were removed."""
+        try:
+            before = self.collection.count()
+            self.collection.delete(where={"namespace": namespace})
+            removed = before - self.collection.count()
+        except Exception as exc:
+            logger.error(f"Failed to delete namespace '{namespace}': {exc}")
+            raise
+        logger.debug(f"Deleted {removed} metrics of namespace '{namespace}'")
+        return removed
 
     # ------------------------------------------------------------------ search
     @staticmethod

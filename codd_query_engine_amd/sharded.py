@@ -55,6 +55,11 @@ class ShardedSearcher:
     engine's device; merge(keys [B,m], k) -> (keys, dist, rows).  Products pass a
     DeviceKnnIndex and leave `merge` unset (HIP merge kernel); the gloo tests pass the
     checker engine and its merge.
+
+    Deletes need nothing here: tombstones are shard-local (engine.delete) and the keys carry
+    global rows.  Compacting ONE shard (engine.compact) changes its local slots, so the
+    caller's row_base bookkeeping must follow: a global row is row_base + local slot, and
+    whatever maps global rows to records has to be renumbered for that shard.
     """
 
     def __init__(self, engine: Any, row_base: int, group: Optional[Any] = None,

@@ -24,11 +24,15 @@
  *     several streams of one index: the index keeps one workspace per stream (up to
  *     4; a fifth stream takes over the least recently used one, ordered behind its
  *     previous owner on the device) and serialises only the enqueueing.  Searches on
- *     different streams then overlap on the GPU.  upsert/reserve/load/ivf_install/set_scopes
- *     are exclusive: no other call on the index may be in flight.
+ *     different streams then overlap on the GPU.  upsert/reserve/load/ivf_install/set_scopes/
+ *     delete/compact are exclusive: no other call on the index may be in flight.
  *   - rows are stored L2-normalised, zero padded to a multiple of 64 elements.
  *     score = <q/|q|, c/|c|> evaluated in fp32 in the canonical order of
  *     DESIGN.md §3; distance = 1 - score (fp32); ties -> lower row.
+ *   - a row slot can be deleted (codd_knn_delete_host): it becomes a tombstone that no search entry
+ *     point returns and no write accepts, until codd_knn_compact moves the live rows down over it
+ *     (stable: slot order kept).  An index nobody deleted from behaves, and runs, exactly as before
+ *     (DESIGN.md §14).
  */
 #ifndef CODD_KNN_H
 #define CODD_KNN_H
@@ -112,7 +116,7 @@ int codd_knn_count(const codd_knn_index* index, int64_t* out);
 int codd_knn_dim(const codd_knn_index* index, int* dim, int* padded_dim, int* dtype);
 
 /* Copy stored rows [first, first+n) back to the host, in storage dtype, padded width.
- * (persistence + tests).  Synchronous. */
+ * (persistence + tests).  Synchronous.  Slot-addressed: a deleted slot's contents are returned as they are. */
 int codd_knn_read_rows(const codd_knn_index* index, int64_t first, int64_t n, void* host_out);
 
 /*
@@ -201,6 +205,30 @@ int codd_knn_search_scoped(codd_knn_index* index, const float* dev_queries, cons
                            uint32_t row_base, uint64_t* dev_keys, float* dev_dist, int64_t* dev_rows, void* stream);
 
 /*
+ * Replaces: collection.delete(ids=..., where=...) — the row half (ChromaDB's own call; the reference never deletes).
+ * delete_host: tombstones n row slots.  A slot outside [0, count) gives EINVAL and changes nothing; a slot that is dead already,
+ *           or listed twice, is a no-op.  Exclusive like upsert, synchronous.  From then on NO search entry point returns the row:
+ *           codd_knn_search, _search_keys, _search_scoped and _ivf_search give each query the exact canonical top-k among the LIVE
+ *           rows it may see — same scores, tie rule and padding, min(k, live rows) hits.  An installed IVF layout stays valid (its
+ *           scans mask by the original row slot); the scope lists are rebuilt by the next scoped search.  Both MFMA filters keep
+ *           scoring dead rows (their shadows are untouched); the threshold anchors and the exact re-scoring drop them.
+ *           A dead slot stays dead until codd_knn_compact: upsert_host, upsert_device, load_rows and set_scopes_host return EINVAL
+ *           for it (no reuse: "ties -> the row inserted first" would break).  The slot-addressed readers — codd_knn_read_rows,
+ *           _copy_rows_f32, _approx_scores — keep returning a dead slot's contents.  codd_knn_count keeps its meaning.
+ * live_count: row slots in use minus the dead ones.
+ * compact:  moves the live rows to slots 0 .. live-1 IN SLOT ORDER (new slot = live slots below the old one; the caller renumbers
+ *           its own tables by the same rule), their scopes with them; clears the tombstones; count shrinks to the live count
+ *           (*new_count, may be NULL), capacity is kept.  In place, through the bounded staging buffer of codd_knn_upsert_host —
+ *           no second copy of the row store.  Both shadows are brought up to date by the next search that needs them, from the
+ *           first moved row on; an installed IVF layout becomes stale, as after an upsert.  No dead row: a no-op that returns the
+ *           count.  Exclusive, synchronous.  EDEVICE from compact means a HIP error struck while rows were being moved: the rows
+ *           are then partly moved under the old tombstones and count, and the index must be destroyed and rebuilt.
+ */
+int codd_knn_delete_host(codd_knn_index* index, const int64_t* host_slots, int64_t n);
+int codd_knn_live_count(const codd_knn_index* index, int64_t* out);
+int codd_knn_compact(codd_knn_index* index, int64_t* new_count);
+
+/*
  * Tuning / introspection (never needed for correctness).
  *   options: "scan_blocks_per_cu" (1..8); "filter" (0/1: MFMA filter path for large batches);
  *            "filter_min_batch" (9), "filter_min_rows" (1: batches >= filter_min_batch always
@@ -236,13 +264,15 @@ int codd_knn_search_scoped(codd_knn_index* index, const float* dev_queries, cons
  *            DESIGN.md §12, hence off), "f16_tile" (1: the 2-byte filter of 129..256 queries on rows of 384 / 768 / 1152 ... elements runs
  *            csrc/filter_i8.h's tile program on fp16 operands; 0: the first-generation kernel), "ivf_share" (1: codd_knn_ivf_search scans a probed list once for all queries of the
  *            batch that probe it, from 1,024 (query, list) pairs on; 0: once per pair),
+ *            "compact_chunk_rows" (0: codd_knn_compact moves as many source rows per step as 64 MiB hold; N: N rows — tests),
  *            "debug_fail_shadow_alloc" (tests: the next N allocations of the 2-byte shadow fail);
  *            "profile" = N keeps N (start, stop) HIP-event pairs, one per heavy-kernel launch,
  *            recorded on the launch stream (0 = off; resets the log)
  *   stats  : "searches", "scan_launches", "last_scan_blocks", "last_scan_group" (queries per pass over the rows of the
  *            last exact scan), "last_finalize_parts" (workgroups per query of the last filter pass's finalize),
  *            "ivf_shared_searches" (IVF searches that scanned each probed list once for all its queries), "scoped_searches",
- *            "scope_builds" (times the scope lists were rebuilt), "scopes" (highest scope label ever set), "filter_passes",
+ *            "scope_builds" (times the scope lists were rebuilt), "scopes" (highest scope label ever set), "dead_rows" (tombstones below count),
+ *            "delete_calls", "compactions" (codd_knn_compact calls that moved rows), "filter_passes",
  *            "fallback_queries", "filter_hits", "filter_survivors", "capacity_rows",
  *            "device_bytes", "num_cus", "workspaces" (stream workspaces in use), "shadow8_builds", "shadow8_passes", "i8v2_passes",
  *            "shadow16_builds" (the bf16 shadow is built lazily, by the first search that needs it), "all_normalized",
