@@ -32,6 +32,7 @@
 #ifndef CODD_EXPERIMENTS
 #define CODD_EXPERIMENTS 0  // 1 (build_variant only): the diagnostic switches that can return wrong results exist
 #endif
+#include "exact_score.h"
 #include "filter_gemm.h"
 #include "filter_i8.h"
 #include "row_traits.h"
@@ -246,97 +247,55 @@ __device__ __forceinline__ void scan_topk_body(const void* __restrict__ rows_, i
             for (int s = 0; s < nseg; ++s) wide_segment<DT, NB, 4>(p, s, nchunks, lane, qs, qstride, acc);
             const uint32_t dm = group_dead_bits(dead, g);
 #pragma unroll
-            for (int b = 0; b < NB; ++b) {
-                const float y = butterfly_sum4(acc[b][0], acc[b][1], acc[b][2], acc[b][3], lane);
+            for (int b = 0; b < NB; ++b) {   // (one query's tail and offers at a time: NB x 4 scores at once spill scalar registers)
+                const float y = packed4(acc[b], lane);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const float s = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(y), 16 * r));
                     const int64_t row = g * 4 + r;
-                    if (row < n && !((dm >> r) & 1u)) L[b].offer(make_key(s, row_base + (uint32_t)row), k, lane);
+                    if (row < n && !((dm >> r) & 1u)) L[b].offer(make_key(packed_score(y, r), row_base + (uint32_t)row), k, lane);
                 }
             }
         }
         __syncthreads();  // every wave is done with the queries: the lists take their place
     } else {
-    float qf[NB][NITER > 0 ? NITER : 1][E];
+    float qf[NB][NITER][E];
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
-        const int64_t qi = b < nq ? (qlist ? (int64_t)qlist[g0 + b] : (int64_t)(g0 + b)) : 0;
-#pragma unroll
-        for (int it = 0; it < NITER; ++it) {
-            const int j = lane + kWave * it;
-#pragma unroll
-            for (int e = 0; e < E; ++e)
-                qf[b][it][e] = (b < nq && j < nchunks) ? qn[qi * dpad + (int64_t)j * E + e] : 0.0f;
-        }
+        load_query_frags(b < nq ? qn + (qlist ? (int64_t)qlist[g0 + b] : (int64_t)(g0 + b)) * dpad : nullptr, nchunks, lane, qf[b]);
+        L[b].init();
     }
-
-#pragma unroll
-    for (int b = 0; b < NB; ++b) L[b].init();
 
     const uint4* base = reinterpret_cast<const uint4*>(rows_);
     const int64_t ngroups = (n + 3) >> 2;
     const int64_t W = (int64_t)nblocks * NW;
     for (int64_t g = (int64_t)bid * NW + wave; g < ngroups; g += W) {
-        float w[4][NITER > 0 ? NITER : 1][E];
+        const uint4* p[4];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            int64_t row = g * 4 + r;
-            row = row < n ? row : n - 1;
-            const uint4* p = base + row * (int64_t)nchunks + lane;
-#pragma unroll
-            for (int it = 0; it < NITER; ++it) {
-                uint4 c = make_uint4(0u, 0u, 0u, 0u);
-                if (lane + kWave * it < nchunks) c = p[kWave * it];
-                RT::widen(c, w[r][it]);
-            }
-        }
+        for (int r = 0; r < 4; ++r) p[r] = base + (g * 4 + r < n ? g * 4 + r : n - 1) * (int64_t)nchunks + lane;
+        float w[4][NITER][E];
+        fetch4_widened<DT>(p, nchunks, lane, w);
         const uint32_t dm = group_dead_bits(dead, g);
 #pragma unroll
-        for (int b = 0; b < NB; ++b) {
-            float a[4];
+        for (int b = 0; b < NB; ++b) {   // (an absent query's fragments are zeros: its list is never read)
+            const float y = score4_one(w, qf[b], lane);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                float acc = 0.0f;
-#pragma unroll
-                for (int it = 0; it < NITER; ++it)
-#pragma unroll
-                    for (int e = 0; e < E; ++e) acc = __builtin_fmaf(qf[b][it][e], w[r][it][e], acc);
-                a[r] = acc;
-            }
-            const float y = butterfly_sum4(a[0], a[1], a[2], a[3], lane);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float s = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(y), 16 * r));
                 const int64_t row = g * 4 + r;
-                if (row < n && !((dm >> r) & 1u)) L[b].offer(make_key(s, row_base + (uint32_t)row), k, lane);
+                if (row < n && !((dm >> r) & 1u)) L[b].offer(make_key(packed_score(y, r), row_base + (uint32_t)row), k, lane);
             }
         }
     }
     }  // (NITER)
 
-    // block merge through LDS: [wave][b][slot][lane]
+    // block merge through LDS: wave b collects query b's list
 #pragma unroll
-    for (int b = 0; b < NB; ++b)
-#pragma unroll
-        for (int s = 0; s < SLOTS; ++s) lds[((wave * NB + b) * SLOTS + s) * kWave + lane] = L[b].v[s];
+    for (int b = 0; b < NB; ++b) store_list(lds, wave, NB, b, lane, L[b]);
     __syncthreads();
     for (int b = wave; b < nq; b += NW) {
         WaveTopK<SLOTS> M;
         M.init();
-        for (int wv = 0; wv < NW; ++wv)
-#pragma unroll
-            for (int s = 0; s < SLOTS; ++s) {
-                u64 cand = lds[((wv * NB + b) * SLOTS + s) * kWave + lane];
-                if (s * kWave + lane >= k) cand = 0ull;
-                M.offer_lanes(cand, k, lane);
-            }
-        u64* dst = partial + (int64_t)(g0 + b) * partial_stride_q + (int64_t)bid * k;
-#pragma unroll
-        for (int s = 0; s < SLOTS; ++s) {
-            const int rank = s * kWave + lane;
-            if (rank < k) dst[rank] = M.v[s];
-        }
+        merge_lists(M, lds, 0, NW, NB, b, k, lane);
+        write_keys(M, k, lane, partial + (int64_t)(g0 + b) * partial_stride_q + (int64_t)bid * k);
     }
     __syncthreads();  // the LDS lists are rewritten by the next group
     }  // group loop
@@ -365,16 +324,7 @@ __device__ __forceinline__ void scan_topk_body(const void* __restrict__ rows_, i
                 M.offer_lanes(i < m ? src[i] : 0ull, k, lane);
             }
             const int64_t o = (int64_t)qlist[qi] * k;
-#pragma unroll
-            for (int s2 = 0; s2 < SLOTS; ++s2) {
-                const int rank = s2 * kWave + lane;
-                if (rank < k) {
-                    const u64 key = M.v[s2];
-                    if (merged_keys) merged_keys[o + rank] = key;
-                    if (merged_dist) merged_dist[o + rank] = key ? 1.0f - key_score(key) : INFINITY;
-                    if (merged_rows) merged_rows[o + rank] = key ? (int64_t)key_row(key) : (int64_t)-1;
-                }
-            }
+            write_ranks(M, k, lane, merged_keys ? merged_keys + o : nullptr, merged_dist ? merged_dist + o : nullptr, merged_rows ? merged_rows + o : nullptr);
         }
     }
 }
@@ -502,28 +452,12 @@ __global__ __launch_bounds__(256) void merge_keys_kernel(const u64* __restrict__
         L.offer_lanes(cand, k, lane);
     }
     __shared__ u64 lds[4 * SLOTS * kWave];
-#pragma unroll
-    for (int s = 0; s < SLOTS; ++s) lds[(wave * SLOTS + s) * kWave + lane] = L.v[s];
+    store_list(lds, wave, 1, 0, lane, L);
     __syncthreads();
     if (wave != 0) return;
-    for (int wv = 1; wv < 4; ++wv)
-#pragma unroll
-        for (int s = 0; s < SLOTS; ++s) {
-            u64 cand = lds[(wv * SLOTS + s) * kWave + lane];
-            if (s * kWave + lane >= k) cand = 0ull;
-            L.offer_lanes(cand, k, lane);
-        }
-#pragma unroll
-    for (int s = 0; s < SLOTS; ++s) {
-        const int rank = s * kWave + lane;
-        if (rank < k) {
-            const u64 key = L.v[s];
-            const int64_t o = oblock * k + rank;
-            if (out_keys) out_keys[o] = key;
-            if (out_dist) out_dist[o] = key ? 1.0f - key_score(key) : INFINITY;
-            if (out_rows) out_rows[o] = key ? (int64_t)key_row(key) : (int64_t)-1;
-        }
-    }
+    merge_lists(L, lds, 1, 4, 1, 0, k, lane);
+    const int64_t o = oblock * k;
+    write_ranks(L, k, lane, out_keys ? out_keys + o : nullptr, out_dist ? out_dist + o : nullptr, out_rows ? out_rows + o : nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1001,77 +935,39 @@ __global__ __launch_bounds__(256) void ivf_scan_kernel(const void* __restrict__ 
         const int64_t end = begin + part < hi ? begin + part : hi;
 
         const uint4* base = reinterpret_cast<const uint4*>(rows_);
-        if constexpr (NITER == kWideRows) {  // wide rows: the query in LDS, the rows walked segment by segment
-            __shared__ __attribute__((aligned(16))) float lds_q[kWideMaxFloats];
+        [[maybe_unused]] float qf[1][NITER > 0 ? NITER : 1][E];
+        [[maybe_unused]] float* lds_q = nullptr;
+        if constexpr (NITER == kWideRows) {  // wide rows: the query in LDS
+            __shared__ __attribute__((aligned(16))) float lds_qw[kWideMaxFloats];
+            lds_q = lds_qw;
             wide_stage_query(lds_q, qn + (int64_t)b * dpad, dpad, wide_qfloats(nchunks, E), (int)threadIdx.x, 256);
             __syncthreads();
-            for (int64_t g = begin + wave * 4; g < end; g += 16) {
-                const uint4* p[4];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) p[r] = base + (g + r < end ? g + r : end - 1) * (int64_t)nchunks + lane;
-                float sc[1][4];
-                wide_scores<DT, 1>(p, nchunks, lane, lds_q, sc);
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    if (g + r < end && !(dead && row_dead(dead, ids[g + r]))) L.offer(make_key(sc[0][r], row_base + ids[g + r]), k, lane);
-            }
         } else {
-        float qf[NITER > 0 ? NITER : 1][E];
-#pragma unroll
-        for (int it = 0; it < NITER; ++it) {
-            const int j = lane + kWave * it;
-#pragma unroll
-            for (int e = 0; e < E; ++e) qf[it][e] = j < nchunks ? qn[(int64_t)b * dpad + (int64_t)j * E + e] : 0.0f;
+            load_query_frags(qn + (int64_t)b * dpad, nchunks, lane, qf[0]);
         }
         for (int64_t g = begin + wave * 4; g < end; g += 16) {
-            float w[4][NITER > 0 ? NITER : 1][E];
+            const uint4* p[4];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int64_t row = g + r < end ? g + r : end - 1;
-                const uint4* p = base + row * (int64_t)nchunks + lane;
-#pragma unroll
-                for (int it = 0; it < NITER; ++it) {
-                    uint4 c = make_uint4(0u, 0u, 0u, 0u);
-                    if (lane + kWave * it < nchunks) c = p[kWave * it];
-                    RT::widen(c, w[r][it]);
-                }
+            for (int r = 0; r < 4; ++r) p[r] = base + (g + r < end ? g + r : end - 1) * (int64_t)nchunks + lane;
+            float sc[1][4];
+            if constexpr (NITER == kWideRows) {
+                wide_scores<DT, 1, 1>(p, nchunks, lane, lds_q, 0, 1, sc);
+            } else {
+                uint4 c[4][NITER];
+                fetch4(p, nchunks, lane, c);
+                score4<DT, 1, NITER>(c, qf, 1, lane, sc);
             }
-            float a[4];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                float acc = 0.0f;
-#pragma unroll
-                for (int it = 0; it < NITER; ++it)
-#pragma unroll
-                    for (int e = 0; e < E; ++e) acc = __builtin_fmaf(qf[it][e], w[r][it][e], acc);
-                a[r] = acc;
-            }
-            const float y = butterfly_sum4(a[0], a[1], a[2], a[3], lane);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float s = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(y), 16 * r));
-                if (g + r < end && !(dead && row_dead(dead, ids[g + r]))) L.offer(make_key(s, row_base + ids[g + r]), k, lane);
-            }
+            for (int r = 0; r < 4; ++r)
+                if (g + r < end && !(dead && row_dead(dead, ids[g + r]))) L.offer(make_key(sc[0][r], row_base + ids[g + r]), k, lane);
         }
-        }  // (NITER)
     }
     __shared__ u64 lds[4 * SLOTS * kWave];
-#pragma unroll
-    for (int s = 0; s < SLOTS; ++s) lds[(wave * SLOTS + s) * kWave + lane] = L.v[s];
+    store_list(lds, wave, 1, 0, lane, L);
     __syncthreads();
     if (wave != 0) return;
-    for (int wv = 1; wv < 4; ++wv)
-#pragma unroll
-        for (int s = 0; s < SLOTS; ++s) {
-            u64 cand = lds[(wv * SLOTS + s) * kWave + lane];
-            if (s * kWave + lane >= k) cand = 0ull;
-            L.offer_lanes(cand, k, lane);
-        }
-#pragma unroll
-    for (int s = 0; s < SLOTS; ++s) {
-        const int rank = s * kWave + lane;
-        if (rank < k) dst[rank] = L.v[s];
-    }
+    merge_lists(L, lds, 1, 4, 1, 0, k, lane);
+    write_keys(L, k, lane, dst);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1135,6 +1031,120 @@ __global__ __launch_bounds__(256) void ivf_pair_scatter_kernel(const u64* __rest
     const uint32_t l = key_row(probe_keys[p]);
     sorted_pairs[pair_start[l] + atomicAdd(&fill[l], 1u)] = (unsigned)p;
 }
+// list_scan_body: one workgroup of 4 waves scores positions [begin, end) of a row list against up to NB queries (q[b]: the query's
+// normalised row, null = absent) and writes query b's k best keys to dst_of(b); a wave owns 4 positions per step.
+//   GATHER = false (IVF): position i IS row i of the regrouped store and reports ids[i]; the next step's rows are on their way while
+//                  this step is scored (raw 16-byte chunks: half the registers of widened rows)
+//   GATHER = true (scopes): position i names row ids[i] of the original store and reports it.  Two steps of look-ahead: the row
+//                  slots of step g + 32 and the rows of step g + 16 (whose slots arrived a step ago) are in flight
+//   dead: the tombstone bits of the reported ids, null = no mask
+template <int DT, int NB, int NITER, int SLOTS, bool GATHER, class DstOf>
+__device__ __forceinline__ void list_scan_body(const void* __restrict__ rows_, const uint32_t* __restrict__ ids, int64_t begin, int64_t end, int dpad,
+                                               const float* const (&q)[NB], int nq, int k, uint32_t row_base, const uint32_t* __restrict__ dead,
+                                               DstOf dst_of) {
+    typedef RowTraits<DT> RT;
+    constexpr int E = RT::E;
+    const int lane = lane_id();
+    const int wave = (int)(threadIdx.x >> 6);
+    const int nchunks = dpad / E;
+    const uint4* base = reinterpret_cast<const uint4*>(rows_);
+    WaveTopK<SLOTS> L[NB];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) L[b].init();
+    auto load_ids = [&](int64_t g, uint32_t (&dst)[4]) {   // (g < end)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) dst[r] = ids[g + r < end ? g + r : end - 1];
+    };
+    // where the rows of step g are: by position (clamped into the list), or by the slots `id` that load_ids(g) brought
+    auto row_ptrs = [&](int64_t g, const uint32_t (&id)[4], const uint4* (&p)[4]) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            int64_t row = id[r];
+            if constexpr (!GATHER) {
+                row = g + r < end ? g + r : end - 1;
+                row = row < begin ? begin : row;
+            }
+            p[r] = base + row * (int64_t)nchunks + lane;
+        }
+    };
+    auto offer4 = [&](int64_t g, const uint32_t (&id)[4], const float (&sc)[NB][4]) {
+#pragma unroll
+        for (int b = 0; b < NB; ++b)
+            if (b < nq) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    if constexpr (GATHER) {
+                        if (g + r < end && !(dead && row_dead(dead, id[r]))) L[b].offer(make_key(sc[b][r], row_base + id[r]), k, lane);
+                    } else {
+                        if (g + r < end && !(dead && row_dead(dead, ids[g + r]))) L[b].offer(make_key(sc[b][r], row_base + ids[g + r]), k, lane);
+                    }
+                }
+            }
+    };
+    const int64_t g0 = begin + wave * 4;
+    uint32_t id0[4] = {0u, 0u, 0u, 0u}, id1[4] = {0u, 0u, 0u, 0u};
+    if constexpr (NITER == kWideRows) {  // wide rows: the queries in LDS (64 KiB at most); the next step's row slots on their way
+        __shared__ __attribute__((aligned(16))) float lds_q[NB * kWideMaxFloats];
+        const int qstride = wide_qfloats(nchunks, E);
+#pragma unroll
+        for (int b = 0; b < NB; ++b) wide_stage_query(lds_q + b * qstride, q[b], dpad, qstride, (int)threadIdx.x, 256);
+        __syncthreads();
+        if (GATHER && g0 < end) load_ids(g0, id0);
+        for (int64_t g = g0; g < end; g += 16) {
+            if (GATHER && g + 16 < end) load_ids(g + 16, id1);
+            const uint4* p[4];
+            row_ptrs(g, id0, p);
+            float sc[NB][4];
+            wide_scores<DT, NB, 1>(p, nchunks, lane, lds_q, qstride, nq, sc);
+            offer4(g, id0, sc);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) id0[r] = id1[r];
+        }
+    } else {
+        float qf[NB][NITER][E];
+#pragma unroll
+        for (int b = 0; b < NB; ++b) load_query_frags(q[b], nchunks, lane, qf[b]);
+        uint4 cur[4][NITER], nxt[4][NITER];
+        const uint4* p[4];
+        if (g0 < end) {
+            if constexpr (GATHER) {
+                load_ids(g0, id0);
+                if (g0 + 16 < end) load_ids(g0 + 16, id1);
+            }
+            row_ptrs(g0, id0, p);
+            fetch4(p, nchunks, lane, cur);
+        }
+        for (int64_t g = g0; g < end; g += 16) {
+            uint32_t id2[4] = {0u, 0u, 0u, 0u};
+            if (GATHER && g + 32 < end) load_ids(g + 32, id2);
+            if (g + 16 < end) {
+                row_ptrs(g + 16, id1, p);
+                fetch4(p, nchunks, lane, nxt);
+            }
+            float sc[NB][4];
+            score4<DT, NB, NITER>(cur, qf, nq, lane, sc);
+            offer4(g, id0, sc);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+#pragma unroll
+                for (int it = 0; it < NITER; ++it) cur[r][it] = nxt[r][it];
+                id0[r] = id1[r];
+                id1[r] = id2[r];
+            }
+        }
+    }
+    __shared__ u64 lds[4 * NB * SLOTS * kWave];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) store_list(lds, wave, NB, b, lane, L[b]);
+    __syncthreads();
+    for (int b = wave; b < nq; b += 4) {
+        WaveTopK<SLOTS> M;
+        M.init();
+        merge_lists(M, lds, 0, 4, NB, b, k, lane);
+        write_keys(M, k, lane, dst_of(b));
+    }
+}
+
 // one work item per workgroup: item -> (list, its kIvfNB-pair group) by binary search in item_start
 template <int DT, int NITER, int SLOTS>
 __global__ __launch_bounds__(256) void ivf_scan_shared_kernel(const void* __restrict__ rows_, const uint32_t* __restrict__ ids, const int64_t* __restrict__ offsets,
@@ -1142,8 +1152,6 @@ __global__ __launch_bounds__(256) void ivf_scan_shared_kernel(const void* __rest
                                                               const unsigned* __restrict__ sorted_pairs, int nlist, int nprobe, int dpad,
                                                               const float* __restrict__ qn, int k, uint32_t row_base, u64* __restrict__ partial,
                                                               const uint32_t* __restrict__ dead) {
-    typedef RowTraits<DT> RT;
-    constexpr int E = RT::E;
     const unsigned item = blockIdx.x;
     if (item >= item_start[nlist]) return;   // (the grid is sized for the worst case: one item per pair)
     int lo_l = 0, hi_l = nlist;              // the last list whose item_start <= item
@@ -1155,133 +1163,16 @@ __global__ __launch_bounds__(256) void ivf_scan_shared_kernel(const void* __rest
     const unsigned g = item - item_start[list];
     const unsigned p0 = pair_start[list] + g * kIvfNB, p1e = pair_start[list + 1];
     const int nq = (int)((p1e - p0) < (unsigned)kIvfNB ? (p1e - p0) : (unsigned)kIvfNB);
-    const int lane = lane_id();
-    const int wave = (int)(threadIdx.x >> 6);
-    const int nchunks = dpad / E;
     unsigned pair[kIvfNB];
-    WaveTopK<SLOTS> L[kIvfNB];
-    const int64_t begin = offsets[list], end = offsets[list + 1];
-    const uint4* base = reinterpret_cast<const uint4*>(rows_);
-    if constexpr (NITER == kWideRows) {  // wide rows: the item's queries in LDS (64 KiB at most), the rows walked segment by segment
-        __shared__ __attribute__((aligned(16))) float lds_q[kIvfNB * kWideMaxFloats];
-        const int qstride = wide_qfloats(nchunks, E);
-#pragma unroll
-        for (int b = 0; b < kIvfNB; ++b) {
-            pair[b] = b < nq ? sorted_pairs[p0 + b] : 0u;
-            const float* src = b < nq ? qn + (int64_t)(pair[b] / (unsigned)nprobe) * dpad : nullptr;
-            wide_stage_query(lds_q + b * qstride, src, dpad, qstride, (int)threadIdx.x, 256);
-            L[b].init();
-        }
-        __syncthreads();
-        const int nseg = wide_nseg(nchunks);
-        for (int64_t g4 = begin + wave * 4; g4 < end; g4 += 16) {
-            const uint4* p[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) p[r] = base + (g4 + r < end ? g4 + r : end - 1) * (int64_t)nchunks + lane;
-            float a[kIvfNB][4];
-#pragma unroll
-            for (int b = 0; b < kIvfNB; ++b)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) a[b][r] = 0.0f;
-            for (int s = 0; s < nseg; ++s) wide_segment<DT, kIvfNB, 4>(p, s, nchunks, lane, lds_q, qstride, a);
-#pragma unroll
-            for (int b = 0; b < kIvfNB; ++b)
-                if (b < nq) {
-                    const float y = butterfly_sum4(a[b][0], a[b][1], a[b][2], a[b][3], lane);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const float sc = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(y), 16 * r));
-                        if (g4 + r < end && !(dead && row_dead(dead, ids[g4 + r]))) L[b].offer(make_key(sc, row_base + ids[g4 + r]), k, lane);
-                    }
-                }
-        }
-    } else {
-    float qf[kIvfNB][NITER > 0 ? NITER : 1][E];
+    const float* q[kIvfNB];
 #pragma unroll
     for (int b = 0; b < kIvfNB; ++b) {
         pair[b] = b < nq ? sorted_pairs[p0 + b] : 0u;
-        const int64_t qi = (int64_t)(pair[b] / (unsigned)nprobe);
-#pragma unroll
-        for (int it = 0; it < NITER; ++it) {
-            const int j = lane + kWave * it;
-#pragma unroll
-            for (int e = 0; e < E; ++e) qf[b][it][e] = (b < nq && j < nchunks) ? qn[qi * dpad + (int64_t)j * E + e] : 0.0f;
-        }
+        q[b] = b < nq ? qn + (int64_t)(pair[b] / (unsigned)nprobe) * dpad : nullptr;
     }
-#pragma unroll
-    for (int b = 0; b < kIvfNB; ++b) L[b].init();
-    // the rows of step g4 + 16 are on their way while step g4 is scored (raw 16-byte chunks: half the registers of widened rows)
-    uint4 cur[4][NITER > 0 ? NITER : 1], nxt[4][NITER > 0 ? NITER : 1];
-    auto fetch = [&](int64_t g4, uint4 (&dst)[4][NITER > 0 ? NITER : 1]) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            int64_t row = g4 + r < end ? g4 + r : end - 1;
-            row = row < begin ? begin : row;
-            const uint4* p = base + row * (int64_t)nchunks + lane;
-#pragma unroll
-            for (int it = 0; it < NITER; ++it) dst[r][it] = (lane + kWave * it < nchunks) ? p[kWave * it] : make_uint4(0u, 0u, 0u, 0u);
-        }
-    };
-    if (end > begin) fetch(begin + wave * 4, cur);
-    for (int64_t g4 = begin + wave * 4; g4 < end; g4 += 16) {
-        if (g4 + 16 < end) fetch(g4 + 16, nxt);
-        float a[kIvfNB][4];
-#pragma unroll
-        for (int b = 0; b < kIvfNB; ++b)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) a[b][r] = 0.0f;
-#pragma unroll
-        for (int it = 0; it < NITER; ++it)   // (it-major as in the per-pair kernel: the same fma order per (row, query), the same bits)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                float w[E];
-                RT::widen(cur[r][it], w);
-#pragma unroll
-                for (int b = 0; b < kIvfNB; ++b)
-                    if (b < nq) {
-#pragma unroll
-                        for (int e = 0; e < E; ++e) a[b][r] = __builtin_fmaf(qf[b][it][e], w[e], a[b][r]);
-                    }
-            }
-#pragma unroll
-        for (int b = 0; b < kIvfNB; ++b)
-            if (b < nq) {
-                const float y = butterfly_sum4(a[b][0], a[b][1], a[b][2], a[b][3], lane);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float sc = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(y), 16 * r));
-                    if (g4 + r < end && !(dead && row_dead(dead, ids[g4 + r]))) L[b].offer(make_key(sc, row_base + ids[g4 + r]), k, lane);
-                }
-            }
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int it = 0; it < NITER; ++it) cur[r][it] = nxt[r][it];
-    }
-    }  // (NITER)
-    __shared__ u64 lds[4 * kIvfNB * SLOTS * kWave];
-#pragma unroll
-    for (int b = 0; b < kIvfNB; ++b)
-#pragma unroll
-        for (int sl = 0; sl < SLOTS; ++sl) lds[((wave * kIvfNB + b) * SLOTS + sl) * kWave + lane] = L[b].v[sl];
-    __syncthreads();
-    for (int b = wave; b < nq; b += 4) {
-        WaveTopK<SLOTS> M;
-        M.init();
-        for (int wv = 0; wv < 4; ++wv)
-#pragma unroll
-            for (int sl = 0; sl < SLOTS; ++sl) {
-                u64 cand = lds[((wv * kIvfNB + b) * SLOTS + sl) * kWave + lane];
-                if (sl * kWave + lane >= k) cand = 0ull;
-                M.offer_lanes(cand, k, lane);
-            }
-        u64* dst = partial + (int64_t)pair[b] * k;   // the pair's own slot: [query][probe rank][k]
-#pragma unroll
-        for (int sl = 0; sl < SLOTS; ++sl) {
-            const int rank = sl * kWave + lane;
-            if (rank < k) dst[rank] = M.v[sl];
-        }
-    }
+    // the pair's own slot of the partial buffer: [query][probe rank][k]
+    list_scan_body<DT, kIvfNB, NITER, SLOTS, false>(rows_, ids, offsets[list], offsets[list + 1], dpad, q, nq, k, row_base, dead,
+                                                    [&](int b) { return partial + (int64_t)pair[b] * k; });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1394,165 +1285,25 @@ __global__ __launch_bounds__(256) void scope_scan_kernel(const void* __restrict_
                                                          int64_t count, uint32_t max_scope, const uint32_t* __restrict__ scopes,
                                                          const unsigned* __restrict__ sorted_q, const unsigned* __restrict__ rank, int B, int split, int dpad,
                                                          const float* __restrict__ qn, int k, uint32_t row_base, u64* __restrict__ partial) {
-    typedef RowTraits<DT> RT;
-    constexpr int E = RT::E;
     constexpr int NB = scope_nb(DT, NITER);
     const int p0 = (int)blockIdx.x, part = (int)blockIdx.y;
     const unsigned r0 = rank[p0];
     if (r0 % NB != 0u) return;
     int nq = 1;
     while (nq < NB && p0 + nq < B && rank[p0 + nq] == r0 + (unsigned)nq) ++nq;   // (ranks count up inside a scope and restart at 0)
-    unsigned qi[NB];
+    const float* q[NB];
 #pragma unroll
-    for (int b = 0; b < NB; ++b) qi[b] = b < nq ? sorted_q[p0 + b] : 0u;
-    const uint32_t scope = scopes[qi[0]];
+    for (int b = 0; b < NB; ++b) q[b] = b < nq ? qn + (int64_t)sorted_q[p0 + b] * dpad : nullptr;
+    const uint32_t scope = scopes[sorted_q[p0]];
     int64_t lo = 0, hi = 0;   // the scope's rows: scope_perm[lo, hi); scope 0 = every listed row (`count`: the live rows); a scope nobody carries = none
     if (scope == 0u) hi = count;
     else if (scope <= max_scope) { lo = offsets[scope]; hi = offsets[scope + 1]; }
     const int64_t per = scope_part_rows(hi - lo, split);
     const int64_t begin = lo + part * per < hi ? lo + part * per : hi;
     const int64_t end = begin + per < hi ? begin + per : hi;
-
-    const int lane = lane_id();
-    const int wave = (int)(threadIdx.x >> 6);
-    const int nchunks = dpad / E;
-    WaveTopK<SLOTS> L[NB];
-    const uint4* base = reinterpret_cast<const uint4*>(rows_);
-    auto load_ids = [&](int64_t g4, uint32_t (&dst)[4]) {   // (g4 < end)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) dst[r] = perm[g4 + r < end ? g4 + r : end - 1];
-    };
-    if constexpr (NITER == kWideRows) {  // wide rows: the item's queries in LDS, the rows walked segment by segment
-        __shared__ __attribute__((aligned(16))) float lds_q[NB * kWideMaxFloats];
-        const int qstride = wide_qfloats(nchunks, E);
-#pragma unroll
-        for (int b = 0; b < NB; ++b) {
-            const float* src = b < nq ? qn + (int64_t)qi[b] * dpad : nullptr;
-            wide_stage_query(lds_q + b * qstride, src, dpad, qstride, (int)threadIdx.x, 256);
-            L[b].init();
-        }
-        __syncthreads();
-        const int nseg = wide_nseg(nchunks);
-        uint32_t id0[4] = {0u, 0u, 0u, 0u}, id1[4] = {0u, 0u, 0u, 0u};
-        if (begin + wave * 4 < end) load_ids(begin + wave * 4, id0);
-        for (int64_t g4 = begin + wave * 4; g4 < end; g4 += 16) {
-            if (g4 + 16 < end) load_ids(g4 + 16, id1);   // the next step's row slots are on their way while this step is scored
-            const uint4* p[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) p[r] = base + (int64_t)id0[r] * nchunks + lane;
-            float a[NB][4];
-#pragma unroll
-            for (int b = 0; b < NB; ++b)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) a[b][r] = 0.0f;
-            for (int s = 0; s < nseg; ++s) wide_segment<DT, NB, 4>(p, s, nchunks, lane, lds_q, qstride, a);
-#pragma unroll
-            for (int b = 0; b < NB; ++b)
-                if (b < nq) {
-                    const float y = butterfly_sum4(a[b][0], a[b][1], a[b][2], a[b][3], lane);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const float sc = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(y), 16 * r));
-                        if (g4 + r < end) L[b].offer(make_key(sc, row_base + id0[r]), k, lane);
-                    }
-                }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) id0[r] = id1[r];
-        }
-    } else {
-    float qf[NB][NITER > 0 ? NITER : 1][E];
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-#pragma unroll
-        for (int it = 0; it < NITER; ++it) {
-            const int j = lane + kWave * it;
-#pragma unroll
-            for (int e = 0; e < E; ++e) qf[b][it][e] = (b < nq && j < nchunks) ? qn[(int64_t)qi[b] * dpad + (int64_t)j * E + e] : 0.0f;
-        }
-        L[b].init();
-    }
-    // Two steps of look-ahead: the row slots of step g4 + 32 and the rows of step g4 + 16 (whose slots arrived a step ago) are in
-    // flight while step g4 is scored (raw 16-byte chunks, as in ivf_scan_shared_kernel)
-    uint4 cur[4][NITER > 0 ? NITER : 1], nxt[4][NITER > 0 ? NITER : 1];
-    uint32_t id0[4] = {0u, 0u, 0u, 0u}, id1[4] = {0u, 0u, 0u, 0u};
-    auto fetch = [&](const uint32_t (&id)[4], uint4 (&dst)[4][NITER > 0 ? NITER : 1]) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const uint4* p = base + (int64_t)id[r] * nchunks + lane;
-#pragma unroll
-            for (int it = 0; it < NITER; ++it) dst[r][it] = (lane + kWave * it < nchunks) ? p[kWave * it] : make_uint4(0u, 0u, 0u, 0u);
-        }
-    };
-    const int64_t g0 = begin + wave * 4;
-    if (g0 < end) {
-        load_ids(g0, id0);
-        if (g0 + 16 < end) load_ids(g0 + 16, id1);
-        fetch(id0, cur);
-    }
-    for (int64_t g4 = g0; g4 < end; g4 += 16) {
-        uint32_t id2[4] = {0u, 0u, 0u, 0u};
-        if (g4 + 32 < end) load_ids(g4 + 32, id2);
-        if (g4 + 16 < end) fetch(id1, nxt);
-        float a[NB][4];
-#pragma unroll
-        for (int b = 0; b < NB; ++b)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) a[b][r] = 0.0f;
-#pragma unroll
-        for (int it = 0; it < NITER; ++it)   // (it-major: the canonical fma order per (row, query))
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                float w[E];
-                RT::widen(cur[r][it], w);
-#pragma unroll
-                for (int b = 0; b < NB; ++b)
-                    if (b < nq) {
-#pragma unroll
-                        for (int e = 0; e < E; ++e) a[b][r] = __builtin_fmaf(qf[b][it][e], w[e], a[b][r]);
-                    }
-            }
-#pragma unroll
-        for (int b = 0; b < NB; ++b)
-            if (b < nq) {
-                const float y = butterfly_sum4(a[b][0], a[b][1], a[b][2], a[b][3], lane);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float sc = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(y), 16 * r));
-                    if (g4 + r < end) L[b].offer(make_key(sc, row_base + id0[r]), k, lane);
-                }
-            }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-#pragma unroll
-            for (int it = 0; it < NITER; ++it) cur[r][it] = nxt[r][it];
-            id0[r] = id1[r];
-            id1[r] = id2[r];
-        }
-    }
-    }  // (NITER)
-    __shared__ u64 lds[4 * NB * SLOTS * kWave];
-#pragma unroll
-    for (int b = 0; b < NB; ++b)
-#pragma unroll
-        for (int sl = 0; sl < SLOTS; ++sl) lds[((wave * NB + b) * SLOTS + sl) * kWave + lane] = L[b].v[sl];
-    __syncthreads();
-    for (int b = wave; b < nq; b += 4) {
-        WaveTopK<SLOTS> M;
-        M.init();
-        for (int wv = 0; wv < 4; ++wv)
-#pragma unroll
-            for (int sl = 0; sl < SLOTS; ++sl) {
-                u64 cand = lds[((wv * NB + b) * SLOTS + sl) * kWave + lane];
-                if (sl * kWave + lane >= k) cand = 0ull;
-                M.offer_lanes(cand, k, lane);
-            }
-        u64* dst = partial + ((int64_t)sorted_q[p0 + b] * split + part) * k;   // [query][part][k]
-#pragma unroll
-        for (int sl = 0; sl < SLOTS; ++sl) {
-            const int rk = sl * kWave + lane;
-            if (rk < k) dst[rk] = M.v[sl];
-        }
-    }
+    // no mask: the lists hold live rows only.  Query b's part of the partial buffer: [query][part][k]
+    list_scan_body<DT, NB, NITER, SLOTS, true>(rows_, perm, begin, end, dpad, q, nq, k, row_base, nullptr,
+                                               [&](int b) { return partial + ((int64_t)sorted_q[p0 + b] * split + part) * k; });
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -30,6 +30,7 @@
 #pragma once
 #include <type_traits>
 
+#include "exact_score.h"
 #include "row_traits.h"
 #include "wave_topk.h"
 
@@ -776,112 +777,6 @@ constexpr int kSurvChunk = 2048;  // hits examined per round; their survivors al
 constexpr int kFinWaves = CODD_FIN_WAVES;      // waves of a finalize workgroup (one query, or one share of its hits): the kernel is a chain of
 constexpr int kFinThreads = kFinWaves * kWave; // round trips (hit list, k anchor rows, survivor rows), so a query gets as many waves as pay
 
-// ---- wide rows: more than 4 chunks per lane (f32 rows above 1,024 elements, 2-byte rows above 2,048) ----
-// NITER = kWideRows selects the wide form of an exact-score body.  The full-width query no longer fits the registers (8 queries x 16
-// chunks x 4 f32 = 512 VGPRs), so it is staged ONCE per workgroup in LDS, fp32 and chunk-major: qs[j * E + e] for chunk j, zeros past
-// the row up to a whole segment.  The row is walked in segments of kSegIt chunks per lane (what NITER 4 holds in registers), the
-// segment's row loads all in flight before its first fmaf, and each lane's accumulators are carried from one segment to the next:
-// chunk j is still lane j % 64's and is visited in increasing j, so the per-lane chains, the butterfly behind them and the scores are
-// exactly DESIGN.md §3's.
-constexpr int kWideRows = 0;
-constexpr int kSegIt = 4;
-constexpr int kWideMaxFloats = 4096;  // LDS floats of one staged query: dpad <= 4096 rounds up to at most 4,096 (f32: 1,024 chunks; 2-byte: 512)
-__host__ __device__ constexpr int wide_nseg(int nchunks) { return (nchunks + kSegIt * kWave - 1) / (kSegIt * kWave); }
-__host__ __device__ constexpr int wide_qfloats(int nchunks, int E) { return wide_nseg(nchunks) * kSegIt * kWave * E; }
-
-// dst[0, nfloats) <- the query row src[0, dpad) followed by zeros (src == nullptr: all zeros); the workgroup's threads share it out
-__device__ __forceinline__ void wide_stage_query(float* __restrict__ dst, const float* __restrict__ src, int dpad, int nfloats, int tid, int nthreads) {
-    float4* d4 = reinterpret_cast<float4*>(dst);
-    const float4* s4 = reinterpret_cast<const float4*>(src);
-    const int have = src ? dpad >> 2 : 0;
-    for (int i = tid; i < (nfloats >> 2); i += nthreads) d4[i] = i < have ? s4[i] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-}
-
-// segment s of NR rows (p[r]: the row's chunk `lane`) against NQ staged queries (query b at qs + b * qstride): acc[b][r] continues
-// each lane's canonical fmaf chain over chunks lane + 64 (kSegIt s + it), it = 0 .. kSegIt-1.  f32: the segment widened as it lands,
-// one query's LDS values at a time; 2-byte rows: the 16-byte chunks stay raw until their step (a widened bf16 / fp16 chunk is twice
-// the registers) and chunk it's query values are read once for all rows.  Either way the same fmaf sequence per (query, row).
-template <int DT, int NQ, int NR>
-__device__ __forceinline__ void wide_segment(const uint4* const (&p)[NR], int s, int nchunks, int lane, const float* qs, int qstride, float (&acc)[NQ][NR]) {
-    typedef RowTraits<DT> RT;
-    constexpr int E = RT::E;
-    if constexpr (E == 4) {
-        float w[NR][kSegIt][E];
-#pragma unroll
-        for (int r = 0; r < NR; ++r)
-#pragma unroll
-            for (int it = 0; it < kSegIt; ++it) {
-                const int o = kWave * (kSegIt * s + it);
-                uint4 c = make_uint4(0u, 0u, 0u, 0u);
-                if (lane + o < nchunks) c = p[r][o];
-                RT::widen(c, w[r][it]);
-            }
-#pragma unroll
-        for (int b = 0; b < NQ; ++b) {
-            float q[kSegIt][E];
-#pragma unroll
-            for (int it = 0; it < kSegIt; ++it) {
-                const float4 v = *reinterpret_cast<const float4*>(qs + (int64_t)b * qstride + (int64_t)(lane + kWave * (kSegIt * s + it)) * E);
-                q[it][0] = v.x; q[it][1] = v.y; q[it][2] = v.z; q[it][3] = v.w;
-            }
-#pragma unroll
-            for (int r = 0; r < NR; ++r)
-#pragma unroll
-                for (int it = 0; it < kSegIt; ++it)
-#pragma unroll
-                    for (int e = 0; e < E; ++e) acc[b][r] = __builtin_fmaf(q[it][e], w[r][it][e], acc[b][r]);
-        }
-        return;
-    }
-    uint4 c[NR][kSegIt];
-#pragma unroll
-    for (int r = 0; r < NR; ++r)
-#pragma unroll
-        for (int it = 0; it < kSegIt; ++it) {
-            const int o = kWave * (kSegIt * s + it);
-            c[r][it] = make_uint4(0u, 0u, 0u, 0u);
-            if (lane + o < nchunks) c[r][it] = p[r][o];
-        }
-#pragma unroll
-    for (int it = 0; it < kSegIt; ++it) {
-        float q[NQ][E];
-#pragma unroll
-        for (int b = 0; b < NQ; ++b) {
-            const float4* src = reinterpret_cast<const float4*>(qs + (int64_t)b * qstride + (int64_t)(lane + kWave * (kSegIt * s + it)) * E);
-#pragma unroll
-            for (int e4 = 0; e4 < E / 4; ++e4) {
-                const float4 v = src[e4];
-                q[b][4 * e4] = v.x; q[b][4 * e4 + 1] = v.y; q[b][4 * e4 + 2] = v.z; q[b][4 * e4 + 3] = v.w;
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < NR; ++r) {
-            float w[E];
-            RT::widen(c[r][it], w);
-#pragma unroll
-            for (int b = 0; b < NQ; ++b)
-#pragma unroll
-                for (int e = 0; e < E; ++e) acc[b][r] = __builtin_fmaf(q[b][e], w[e], acc[b][r]);
-        }
-    }
-}
-
-// exact scores of 4 G rows (groups of four) against ONE staged query: every group's loads of a segment in flight together
-template <int DT, int G>
-__device__ __forceinline__ void wide_scores(const uint4* const (&p)[4 * G], int nchunks, int lane, const float* qs, float (&sc)[G][4]) {
-    float acc[1][4 * G];
-#pragma unroll
-    for (int r = 0; r < 4 * G; ++r) acc[0][r] = 0.0f;
-    const int nseg = wide_nseg(nchunks);
-    for (int s = 0; s < nseg; ++s) wide_segment<DT, 1, 4 * G>(p, s, nchunks, lane, qs, 0, acc);
-#pragma unroll
-    for (int h = 0; h < G; ++h) {
-        const float y = butterfly_sum4(acc[0][4 * h], acc[0][4 * h + 1], acc[0][4 * h + 2], acc[0][4 * h + 3], lane);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) sc[h][r] = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(y), 16 * r));
-    }
-}
-
 // finalize_body: what one workgroup of kFinThreads threads does for ONE query (or one share of its candidates): `my[0, total)`
 // are the query's candidate keys (approximate score, local row; 0 = empty slot), qn_q its normalised fp32 vector.
 //   eps1 : the slack between an approximate and an exact score — the whole of it, or (bmeta != nullptr, the int8 filter) its
@@ -910,19 +805,14 @@ __device__ __forceinline__ void finalize_body(const void* __restrict__ rows_, in
 
     // the query's fragments for the exact re-scoring: requested first, so the round trip overlaps step 1
     const int nchunks = dpad / E;
-    float qf[NITER > 0 ? NITER : 1][E];
+    float qf[1][NITER > 0 ? NITER : 1][E];
     float* lds_q = nullptr;
     if constexpr (NITER == kWideRows) {  // wide rows: the query in LDS (the first barrier below publishes it)
         __shared__ __attribute__((aligned(16))) float lds_qw[kWideMaxFloats];
         lds_q = lds_qw;
         wide_stage_query(lds_q, qn_q, dpad, wide_qfloats(nchunks, E), tid, kFinThreads);
     } else {
-#pragma unroll
-    for (int it = 0; it < NITER; ++it) {
-        const int j = lane + kWave * it;
-#pragma unroll
-        for (int e = 0; e < E; ++e) qf[it][e] = j < nchunks ? qn_q[(int64_t)j * E + e] : 0.0f;
-    }
+        load_query_frags(qn_q, nchunks, lane, qf[0]);
     }
 
     // 1. k-th largest approximate key
@@ -934,17 +824,10 @@ __device__ __forceinline__ void finalize_body(const void* __restrict__ rows_, in
         if (dead && key && row_dead(dead, key_row(key))) key = 0ull;
         L.offer_lanes(key, k, lane);
     }
-#pragma unroll
-    for (int s = 0; s < SLOTS; ++s) lds_list[(wave * SLOTS + s) * kWave + lane] = L.v[s];
+    store_list(lds_list, wave, 1, 0, lane, L);
     __syncthreads();
     if (wave == 0) {
-        for (int wv = 1; wv < kFinWaves; ++wv)
-#pragma unroll
-            for (int s = 0; s < SLOTS; ++s) {
-                u64 cand = lds_list[(wv * SLOTS + s) * kWave + lane];
-                if (s * kWave + lane >= k) cand = 0ull;
-                L.offer_lanes(cand, k, lane);
-            }
+        merge_lists(L, lds_list, 1, kFinWaves, 1, 0, k, lane);
         // rows of the k best approximate hits (or none when the list is not full: then every hit survives)
         if (lane == 0) lds_n = L.thr ? (unsigned)k : 0u;
         if (L.thr) {
@@ -956,41 +839,17 @@ __device__ __forceinline__ void finalize_body(const void* __restrict__ rows_, in
     __syncthreads();
     const uint4* base = reinterpret_cast<const uint4*>(rows_);
     // canonical exact scores of up to four rows per wave step (the expression of the exact scan)
-    auto rescore4 = [&](const unsigned (&rowid)[4], float (&sc)[4]) __attribute__((always_inline)) {
+    auto rescore4 = [&](const unsigned (&rowid)[4], float (&sc)[1][4]) __attribute__((always_inline)) {
+        const uint4* p[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) p[r] = base + (int64_t)rowid[r] * nchunks + lane;
         if constexpr (NITER == kWideRows) {
-            const uint4* p[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) p[r] = base + (int64_t)rowid[r] * nchunks + lane;
-            float sc1[1][4];
-            wide_scores<DT, 1>(p, nchunks, lane, lds_q, sc1);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) sc[r] = sc1[0][r];
-            return;
+            wide_scores<DT, 1, 1>(p, nchunks, lane, lds_q, 0, 1, sc);
+        } else {
+            uint4 c[4][NITER];
+            fetch4(p, nchunks, lane, c);
+            score4<DT, 1, NITER>(c, qf, 1, lane, sc);
         }
-        float w[4][NITER > 0 ? NITER : 1][E];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const uint4* p = base + (int64_t)rowid[r] * nchunks + lane;
-#pragma unroll
-            for (int it = 0; it < NITER; ++it) {
-                uint4 cch = make_uint4(0u, 0u, 0u, 0u);
-                if (lane + kWave * it < nchunks) cch = p[kWave * it];
-                RT::widen(cch, w[r][it]);
-            }
-        }
-        float a[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            float acc = 0.0f;
-#pragma unroll
-            for (int it = 0; it < NITER; ++it)
-#pragma unroll
-                for (int e = 0; e < E; ++e) acc = __builtin_fmaf(qf[it][e], w[r][it][e], acc);
-            a[r] = acc;
-        }
-        const float y = butterfly_sum4(a[0], a[1], a[2], a[3], lane);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) sc[r] = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(y), 16 * r));
     };
     // 1b. anchor: those k rows are k distinct rows with EXACT scores >= L' := their smallest exact score, so the true
     // k-th best score is >= L' and every true top-k row has an approximate score >= L' - eps (one eps, not two: the
@@ -1000,13 +859,13 @@ __device__ __forceinline__ void finalize_body(const void* __restrict__ rows_, in
         float worst = INFINITY;
         for (unsigned j = wave * 4; j < nk; j += 4 * kFinWaves) {
             unsigned rowid[4];
-            float sc[4];
+            float sc[1][4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) rowid[r] = lds_surv[j + r < nk ? j + r : nk - 1];
             rescore4(rowid, sc);
 #pragma unroll
             for (int r = 0; r < 4; ++r)
-                if (j + r < nk) worst = fminf(worst, sc[r]);
+                if (j + r < nk) worst = fminf(worst, sc[0][r]);
         }
         if (lane == 0) lds_anchor[wave] = worst;
         __syncthreads();
@@ -1045,7 +904,7 @@ __device__ __forceinline__ void finalize_body(const void* __restrict__ rows_, in
         // before the first is consumed (the loop is a chain of HBM round trips otherwise)
         for (unsigned j0 = wave * 8; j0 < ns; j0 += 8 * kFinWaves) {
             unsigned rowid8[2][4];
-            float sc8[2][4];
+            float sc8[1][8];
 #pragma unroll
             for (int h = 0; h < 2; ++h)
 #pragma unroll
@@ -1054,19 +913,17 @@ __device__ __forceinline__ void finalize_body(const void* __restrict__ rows_, in
                 const uint4* p[8];
 #pragma unroll
                 for (int hr = 0; hr < 8; ++hr) p[hr] = base + (int64_t)rowid8[hr >> 2][hr & 3] * nchunks + lane;
-                wide_scores<DT, 2>(p, nchunks, lane, lds_q, sc8);
+                wide_scores<DT, 1, 2>(p, nchunks, lane, lds_q, 0, 1, sc8);
             } else {
-                rescore4(rowid8[0], sc8[0]);
-                rescore4(rowid8[1], sc8[1]);
+                float s0[1][4], s1[1][4];
+                rescore4(rowid8[0], s0);
+                rescore4(rowid8[1], s1);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) { sc8[0][r] = s0[0][r]; sc8[0][4 + r] = s1[0][r]; }
             }
 #pragma unroll
-            for (int hr = 0; hr < 8; ++hr) {
-                const int r = hr & 3;
-                const unsigned j = j0 + 4 * (hr >> 2);
-                const unsigned (&rowid)[4] = rowid8[hr >> 2];
-                const float sc = sc8[hr >> 2][r];
-                if (j + r < ns) X.offer(make_key(sc, row_base + rowid[r]), k, lane);
-            }
+            for (int hr = 0; hr < 8; ++hr)
+                if (j0 + hr < ns) X.offer(make_key(sc8[0][hr], row_base + rowid8[hr >> 2][hr & 3]), k, lane);
         }
         __syncthreads();  // lds_surv is refilled by the next round
     }
@@ -1076,32 +933,13 @@ __device__ __forceinline__ void finalize_body(const void* __restrict__ rows_, in
     }
 
     // 4. merge the waves' lists
-#pragma unroll
-    for (int s = 0; s < SLOTS; ++s) lds_list[(wave * SLOTS + s) * kWave + lane] = X.v[s];
+    store_list(lds_list, wave, 1, 0, lane, X);
     __syncthreads();
     if (wave == 0) {
-        for (int wv = 1; wv < kFinWaves; ++wv)
-#pragma unroll
-            for (int s = 0; s < SLOTS; ++s) {
-                u64 cand = lds_list[(wv * SLOTS + s) * kWave + lane];
-                if (s * kWave + lane >= k) cand = 0ull;
-                X.offer_lanes(cand, k, lane);
-            }
-#pragma unroll
-        for (int s = 0; s < SLOTS; ++s) {
-            const int rank = s * kWave + lane;
-            if (rank < k) {
-                const u64 key = X.v[s];
-                if (nparts > 1) {
-                    part_keys_q[rank] = key;
-                } else {
-                    // the caller's (distance, row) outputs straight from here: no unpack launch behind the pass
-                    if (out_keys_q) out_keys_q[rank] = key;
-                    if (out_dist_q) out_dist_q[rank] = key ? 1.0f - key_score(key) : INFINITY;
-                    if (out_rows_q) out_rows_q[rank] = key ? (int64_t)key_row(key) : (int64_t)-1;
-                }
-            }
-        }
+        merge_lists(X, lds_list, 1, kFinWaves, 1, 0, k, lane);
+        // one share of several: its keys for the merge launch; else the caller's (distance, row) outputs straight from here
+        if (nparts > 1) write_keys(X, k, lane, part_keys_q);
+        else write_ranks(X, k, lane, out_keys_q, out_dist_q, out_rows_q);
     }
     __syncthreads();  // (a caller that loops over queries reuses the shared lists)
 }
@@ -1172,19 +1010,14 @@ __global__ __launch_bounds__(kAnchorWaves * kWave) void anchor_thr_kernel(const 
         return;
     }
     const int nchunks = dpad / E;
-    float qf[NITER > 0 ? NITER : 1][E];
+    float qf[1][NITER > 0 ? NITER : 1][E];
     float* lds_q = nullptr;
     if constexpr (NITER == kWideRows) {  // wide rows: the query in LDS (the barrier behind the bucket scan publishes it)
         __shared__ __attribute__((aligned(16))) float lds_qw[kWideMaxFloats];
         lds_q = lds_qw;
         wide_stage_query(lds_q, qn + (int64_t)q * dpad, dpad, wide_qfloats(nchunks, E), tid, kAnchorWaves * kWave);
     } else {
-#pragma unroll
-    for (int it = 0; it < NITER; ++it) {
-        const int j = lane + kWave * it;
-#pragma unroll
-        for (int e = 0; e < E; ++e) qf[it][e] = j < nchunks ? qn[(int64_t)q * dpad + (int64_t)j * E + e] : 0.0f;
-    }
+        load_query_frags(qn + (int64_t)q * dpad, nchunks, lane, qf[0]);
     }
     WaveTopK<SLOTS> L;
     L.init();
@@ -1194,19 +1027,11 @@ __global__ __launch_bounds__(kAnchorWaves * kWave) void anchor_thr_kernel(const 
         if (dead && key && row_dead(dead, key_row(key))) key = 0ull;
         L.offer_lanes(key, k, lane);
     }
-#pragma unroll
-    for (int s = 0; s < SLOTS; ++s) lds_list[(wave * SLOTS + s) * kWave + lane] = L.v[s];
+    store_list(lds_list, wave, 1, 0, lane, L);
     __syncthreads();
     if (wave == 0) {
-        for (int wv = 1; wv < kAnchorWaves; ++wv)
-#pragma unroll
-            for (int s = 0; s < SLOTS; ++s) {
-                u64 cand = lds_list[(wv * SLOTS + s) * kWave + lane];
-                if (s * kWave + lane >= k) cand = 0ull;
-                L.offer_lanes(cand, k, lane);
-            }
-#pragma unroll
-        for (int s = 0; s < SLOTS; ++s) lds_list[s * kWave + lane] = L.v[s];  // rank s * 64 + lane
+        merge_lists(L, lds_list, 1, kAnchorWaves, 1, 0, k, lane);
+        store_list(lds_list, 0, 1, 0, lane, L);  // rank s * 64 + lane
         if (lane == 0) lds_full = L.thr ? 1 : 0;
     }
     __syncthreads();
@@ -1219,62 +1044,36 @@ __global__ __launch_bounds__(kAnchorWaves * kWave) void anchor_thr_kernel(const 
     }
     const uint4* base = reinterpret_cast<const uint4*>(rows_);
     // exact scores of the rows ranked [j, j+4) (ranks past k-1 repeat the last one)
-    auto group = [&](int j, float (&sc)[4]) __attribute__((always_inline)) {
+    auto group = [&](int j, float (&sc)[1][4]) __attribute__((always_inline)) {
+        const uint4* p[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) p[r] = base + (int64_t)key_row(lds_list[j + r < k ? j + r : k - 1]) * nchunks + lane;  // (the rank is uniform)
         if constexpr (NITER == kWideRows) {
-            const uint4* p[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) p[r] = base + (int64_t)key_row(lds_list[j + r < k ? j + r : k - 1]) * nchunks + lane;
-            float sc1[1][4];
-            wide_scores<DT, 1>(p, nchunks, lane, lds_q, sc1);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) sc[r] = sc1[0][r];
-            return;
+            wide_scores<DT, 1, 1>(p, nchunks, lane, lds_q, 0, 1, sc);
+        } else {
+            uint4 c[4][NITER];
+            fetch4(p, nchunks, lane, c);
+            score4<DT, 1, NITER>(c, qf, 1, lane, sc);
         }
-        float w[4][NITER > 0 ? NITER : 1][E];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int rank = j + r < k ? j + r : k - 1;  // uniform
-            const u64 key = lds_list[rank];
-            const uint4* p = base + (int64_t)key_row(key) * nchunks + lane;
-#pragma unroll
-            for (int it = 0; it < NITER; ++it) {
-                uint4 cch = make_uint4(0u, 0u, 0u, 0u);
-                if (lane + kWave * it < nchunks) cch = p[kWave * it];
-                RT::widen(cch, w[r][it]);
-            }
-        }
-        float a[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            float acc = 0.0f;
-#pragma unroll
-            for (int it = 0; it < NITER; ++it)
-#pragma unroll
-                for (int e = 0; e < E; ++e) acc = __builtin_fmaf(qf[it][e], w[r][it][e], acc);
-            a[r] = acc;
-        }
-        const float y = butterfly_sum4(a[0], a[1], a[2], a[3], lane);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) sc[r] = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(y), 16 * r));
     };
     float worst = INFINITY;
     if (k <= 4 * kAnchorWaves) {  // the usual case (k = 10): one group of four rows per wave, one round trip
         if (4 * wave < k) {
-            float s0[4];
+            float s0[1][4];
             group(4 * wave, s0);
 #pragma unroll
             for (int r = 0; r < 4; ++r)
-                if (4 * wave + r < k) worst = fminf(worst, s0[r]);
+                if (4 * wave + r < k) worst = fminf(worst, s0[0][r]);
         }
     } else {
         for (int j = 8 * wave; j < k; j += 8 * kAnchorWaves) {  // two independent groups per step: both groups' row reads fly together
-            float s0[4], s1[4];
+            float s0[1][4], s1[1][4];
             group(j, s0);
             group(j + 4, s1);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                if (j + r < k) worst = fminf(worst, s0[r]);
-                if (j + 4 + r < k) worst = fminf(worst, s1[r]);
+                if (j + r < k) worst = fminf(worst, s0[0][r]);
+                if (j + 4 + r < k) worst = fminf(worst, s1[0][r]);
             }
         }
     }

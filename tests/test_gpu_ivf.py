@@ -115,6 +115,8 @@ def test_two_ivf_shards_merge_to_the_whole_answer(env):
         (50_000, 768, 128, 128, 16, 100, "bf16"),  # k above 64: two top-k slots per lane
         (30_000, 1024, 32, 256, 4, 10, "f16"),    # config 5's row width
         (20_000, 100, 300, 70, 16, 10, "f32"),    # more lists than any query group touches; ragged row width
+        (20_000, 768, 32, 40, 32, 10, "f32"),     # f32 at 3 chunks per lane; exhaustive probe: the flat search is compared as well
+        (20_000, 1024, 32, 40, 32, 100, "f32"),   # f32 at 4 chunks per lane, two list slots (both: 1,280 pairs, the shared scan)
     ],
 )
 def test_list_sharing_scan_returns_the_per_pair_scan_s_bits(env, n, d, nlist, B, nprobe, k, dtype):

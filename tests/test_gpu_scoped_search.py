@@ -55,7 +55,7 @@ def check(ix, rows_ref, dtype, labels, q, scopes, k):
 
 
 @pytest.mark.parametrize("dtype,dim", [("f32", 384), ("f32", 768), ("bf16", 384), ("bf16", 768), ("f16", 384), ("f16", 768),
-                                       ("f32", 1536), ("f32", 100), ("bf16", 2048), ("f16", 3072)])
+                                       ("f32", 1536), ("f32", 100), ("bf16", 2048), ("f16", 3072), ("f32", 1024), ("f16", 2048)])
 def test_scoped_search_equals_the_oracle_on_the_sub_matrix(Index, dtype, dim):
     rng = np.random.default_rng(dim + len(dtype))
     raw = rng.standard_normal((N, dim)).astype(np.float32)

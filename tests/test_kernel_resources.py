@@ -8,19 +8,11 @@ import re
 import subprocess
 
 from codd_query_engine_amd import build as b
+from tests._kernel_report import report_text, resource_rows
 
 
 def test_hot_kernels_do_not_spill():
-    cmd = [b._hipcc(), *[f for f in b.HIPCC_FLAGS if f != "-shared"], "-c", "-I", b.os.path.join(b._ROOT, "include"), "-I", b.CSRC,
-           "-Rpass-analysis=kernel-resource-usage", "-o", "/dev/null", b.os.path.join(b.CSRC, b.SOURCES[0])]
-    proc = subprocess.run(cmd, capture_output=True, text=True)
-    assert proc.returncode == 0, proc.stderr[-2000:]
-    report = b.resource_report(proc.stderr)
-    rows = {}
-    for line in report.splitlines()[1:]:
-        m = re.match(r"(.+?)\s+(\d+)\s+(\S+)\s+(\d+)\s+(\d+)\s+(\d+)\s+(\d+)\s+(\d+)$", line)
-        if m:
-            rows[m.group(1).strip()] = {"vgpr": int(m.group(2)), "spill": int(m.group(4)), "scratch": int(m.group(5)), "occ": int(m.group(6)), "sspill": int(m.group(8))}
+    report, rows = report_text(), resource_rows()
     hot = [name for name in rows if "gemm_filter_kernel" in name or "scan_topk_kernel<0, 1, 3" in name or "scan_topk_kernel<0, 8, 3" in name
            or "finalize_kernel<0, 3" in name]
     assert len(hot) >= 12, report

@@ -3,27 +3,14 @@ instantiation the dispatch can reach — three storage dtypes, 1 .. 4 chunks per
 slots per lane — must be built, and none may spill: a spill inside the row loop would put a scratch round trip between the
 gathered loads and their fmaf chains.  Same recipe as tests/test_kernel_resources.py: hipcc's own resource report, no GPU."""
 
-import re
-import subprocess
-
 import pytest
 
-from codd_query_engine_amd import build as b
+from tests._kernel_report import resource_rows
 
 
 @pytest.fixture(scope="module")
 def rows():
-    cmd = [b._hipcc(), *[f for f in b.HIPCC_FLAGS if f != "-shared"], "-c", "-I", b.os.path.join(b._ROOT, "include"), "-I", b.CSRC,
-           "-Rpass-analysis=kernel-resource-usage", "-o", "/dev/null", b.os.path.join(b.CSRC, b.SOURCES[0])]
-    proc = subprocess.run(cmd, capture_output=True, text=True)
-    assert proc.returncode == 0, proc.stderr[-2000:]
-    out = {}
-    for line in b.resource_report(proc.stderr).splitlines()[1:]:
-        m = re.match(r"(.+?)\s+(\d+)\s+(\S+)\s+(\d+)\s+(\d+)\s+(\d+)\s+(\d+)\s+(\d+)$", line)
-        if m:
-            out[m.group(1).strip()] = {"vgpr": int(m.group(2)), "spill": int(m.group(4)), "scratch": int(m.group(5)), "occ": int(m.group(6)),
-                                       "sspill": int(m.group(8))}
-    return out
+    return resource_rows()
 
 
 NAMES = [f"scope_scan_kernel<{dt}, {niter}, {sl}>" for dt in (0, 1, 2) for niter in (1, 2, 3, 4, 0) for sl in (1, 2)]
@@ -40,6 +27,29 @@ def test_scope_scan_neither_spills_nor_uses_scratch(rows, name):
     assert hit, name
     r = hit[0]
     assert r["spill"] == 0 and r["scratch"] == 0 and r["sspill"] == 0, (name, r)
+
+
+# occupancy (waves per SIMD) of every instantiation in the build before the list-driven scan body was shared with the IVF scan, from
+# that build's own report
+PARENT_OCC = {
+    "scope_scan_kernel<0, 1, 1>": 4, "scope_scan_kernel<0, 1, 2>": 4, "scope_scan_kernel<0, 2, 1>": 3, "scope_scan_kernel<0, 2, 2>": 3, "scope_scan_kernel<0, 3, 1>": 2,
+    "scope_scan_kernel<0, 3, 2>": 2, "scope_scan_kernel<0, 4, 1>": 2, "scope_scan_kernel<0, 4, 2>": 2, "scope_scan_kernel<0, 0, 1>": 2, "scope_scan_kernel<0, 0, 2>": 2,
+    "scope_scan_kernel<1, 1, 1>": 3, "scope_scan_kernel<1, 1, 2>": 3, "scope_scan_kernel<1, 2, 1>": 2, "scope_scan_kernel<1, 2, 2>": 2, "scope_scan_kernel<1, 3, 1>": 1,
+    "scope_scan_kernel<1, 3, 2>": 1, "scope_scan_kernel<1, 4, 1>": 1, "scope_scan_kernel<1, 4, 2>": 1, "scope_scan_kernel<1, 0, 1>": 2, "scope_scan_kernel<1, 0, 2>": 2,
+    "scope_scan_kernel<2, 1, 1>": 3, "scope_scan_kernel<2, 1, 2>": 3, "scope_scan_kernel<2, 2, 1>": 2, "scope_scan_kernel<2, 2, 2>": 2, "scope_scan_kernel<2, 3, 1>": 1,
+    "scope_scan_kernel<2, 3, 2>": 1, "scope_scan_kernel<2, 4, 1>": 1, "scope_scan_kernel<2, 4, 2>": 1, "scope_scan_kernel<2, 0, 1>": 2, "scope_scan_kernel<2, 0, 2>": 2,
+}
+
+
+def test_scope_scan_keeps_its_occupancy(rows):
+    assert set(PARENT_OCC) == set(NAMES)
+    occ = {}
+    for name in NAMES:
+        hit = [r for key, r in rows.items() if key.endswith(name)]
+        assert hit, name
+        occ[name] = hit[0]["occ"]
+    worse = [(name, occ[name], PARENT_OCC[name]) for name in NAMES if occ[name] < PARENT_OCC[name]]
+    assert not worse, worse
 
 
 def test_scope_list_builders_are_built_and_tiny(rows):

@@ -3,27 +3,14 @@ elements, 2-byte above 2,048).  The query lives in LDS and the row is walked in 
 registers than NITER 4 does; a spill would still compute the right scores, only with a scratch round trip in the row loop.
 Same recipe as tests/test_kernel_resources.py: hipcc's own resource report, no GPU."""
 
-import re
-import subprocess
-
 import pytest
 
-from codd_query_engine_amd import build as b
+from tests._kernel_report import resource_rows
 
 
 @pytest.fixture(scope="module")
 def rows():
-    cmd = [b._hipcc(), *[f for f in b.HIPCC_FLAGS if f != "-shared"], "-c", "-I", b.os.path.join(b._ROOT, "include"), "-I", b.CSRC,
-           "-Rpass-analysis=kernel-resource-usage", "-o", "/dev/null", b.os.path.join(b.CSRC, b.SOURCES[0])]
-    proc = subprocess.run(cmd, capture_output=True, text=True)
-    assert proc.returncode == 0, proc.stderr[-2000:]
-    out = {}
-    for line in b.resource_report(proc.stderr).splitlines()[1:]:
-        m = re.match(r"(.+?)\s+(\d+)\s+(\S+)\s+(\d+)\s+(\d+)\s+(\d+)\s+(\d+)\s+(\d+)$", line)
-        if m:
-            out[m.group(1).strip()] = {"vgpr": int(m.group(2)), "spill": int(m.group(4)), "scratch": int(m.group(5)), "occ": int(m.group(6)),
-                                       "sspill": int(m.group(8))}
-    return out
+    return resource_rows()
 
 
 # kernel -> template arguments after the dtype (NITER = 0 is the wide form); the wide scan runs 1, 4 or 8 queries per pass over
