@@ -1359,6 +1359,73 @@ __global__ __launch_bounds__(256) void compact_gather_kernel(const uint4* __rest
     if (lane == 0 && scope_of) bounce_scope[to] = scope_of[r];
 }
 
+// ---------------------------------------------------------------------------------------------
+// Masked search: one bitmap of ALLOWED row slots per call, shared by the batch's queries.
+//   mask_deny_kernel     dense route: deny[w] = ~allow[w] | dead[w], all ones from the mask's last word on — the bitmap every
+//                        exact-score kernel takes where it takes the tombstone bits (§14 with "dead" read as "denied")
+//   mask_prefix_kernel   list route: per bitmap word the visible (allowed, live) slots of its 256-word block that lie below it, and
+//                        the block's total (live_prefix_kernel's shape); scope_offsets_kernel turns the totals into block bases
+//   mask_scatter_kernel  ... and each word writes its visible slots, ascending, from base[block] + prefix[word]: the list is the
+//                        visible row slots in slot order, the same for every run
+//   mask_scan_kernel     (group of up to NB of the batch's queries, one of `split` parts of the list): list_scan_body's gathering
+//                        form, as scope_scan_kernel runs it; one partial list per (query, part), merge_keys_kernel behind it
+// ---------------------------------------------------------------------------------------------
+// the slots of bitmap word w among rows [0, n) that a masked search may return (dead: the tombstone bits, null = none)
+__device__ __forceinline__ uint32_t visible_bits(const uint32_t* __restrict__ allow, const uint32_t* __restrict__ dead, int64_t w, int64_t n) {
+    const int64_t left = n - w * 32;
+    const uint32_t in_range = left >= 32 ? 0xffffffffu : (left > 0 ? (1u << (uint32_t)left) - 1u : 0u);
+    return allow[w] & in_range & ~(dead ? dead[w] : 0u);
+}
+__global__ __launch_bounds__(256) void mask_deny_kernel(const uint32_t* __restrict__ allow, const uint32_t* __restrict__ dead, int64_t n, int64_t nwords,
+                                                        int64_t total_words, uint32_t* __restrict__ deny) {
+    const int64_t w = (int64_t)blockIdx.x * 256 + (int64_t)threadIdx.x;
+    if (w < total_words) deny[w] = w < nwords ? ~visible_bits(allow, dead, w, n) : 0xffffffffu;
+}
+__global__ __launch_bounds__(256) void mask_prefix_kernel(const uint32_t* __restrict__ allow, const uint32_t* __restrict__ dead, int64_t n, int64_t nwords,
+                                                          unsigned* __restrict__ prefix, unsigned* __restrict__ block_total) {
+    __shared__ unsigned s_p[256];
+    const int tid = (int)threadIdx.x;
+    const int64_t w = (int64_t)blockIdx.x * 256 + tid;
+    const unsigned mine = w < nwords ? (unsigned)__popc(visible_bits(allow, dead, w, n)) : 0u;
+    s_p[tid] = mine;
+    __syncthreads();
+    for (int off = 1; off < 256; off <<= 1) {   // Hillis-Steele inclusive scan
+        const unsigned a = tid >= off ? s_p[tid - off] : 0u;
+        __syncthreads();
+        s_p[tid] += a;
+        __syncthreads();
+    }
+    if (w < nwords) prefix[w] = s_p[tid] - mine;
+    if (tid == 255) block_total[blockIdx.x] = s_p[255];
+}
+__global__ __launch_bounds__(256) void mask_scatter_kernel(const uint32_t* __restrict__ allow, const uint32_t* __restrict__ dead, int64_t n, int64_t nwords,
+                                                           const unsigned* __restrict__ prefix, const unsigned* __restrict__ block_base, int64_t m,
+                                                           uint32_t* __restrict__ list) {
+    const int64_t w = (int64_t)blockIdx.x * 256 + (int64_t)threadIdx.x;
+    if (w >= nwords) return;
+    uint32_t v = visible_bits(allow, dead, w, n);
+    int64_t at = (int64_t)block_base[w >> 8] + prefix[w];
+    for (; v != 0u; v &= v - 1u, ++at)
+        if (at < m) list[at] = (uint32_t)(w * 32) + (uint32_t)(__ffs((int)v) - 1);   // (at < m always: the host counted the same bits)
+}
+// grid (ceil(B / NB), split): workgroup (g, part) serves queries g * NB .. g * NB + NB-1 over part `part` of list[0, m)
+template <int DT, int NITER, int SLOTS>
+__global__ __launch_bounds__(256) void mask_scan_kernel(const void* __restrict__ rows_, const uint32_t* __restrict__ list, int64_t m, int B, int split,
+                                                        int dpad, const float* __restrict__ qn, int k, uint32_t row_base, u64* __restrict__ partial) {
+    constexpr int NB = scope_nb(DT, NITER);
+    const int q0 = (int)blockIdx.x * NB, part = (int)blockIdx.y;
+    const int nq = B - q0 < NB ? B - q0 : NB;
+    const float* q[NB];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) q[b] = b < nq ? qn + (int64_t)(q0 + b) * dpad : nullptr;
+    const int64_t per = scope_part_rows(m, split);
+    const int64_t begin = part * per < m ? part * per : m;
+    const int64_t end = begin + per < m ? begin + per : m;
+    // no mask: the list holds visible rows only.  Query b's part of the partial buffer: [query][part][k]
+    list_scan_body<DT, NB, NITER, SLOTS, true>(rows_, list, begin, end, dpad, q, nq, k, row_base, nullptr,
+                                               [&](int b) { return partial + ((int64_t)(q0 + b) * split + part) * k; });
+}
+
 }  // namespace
 
 // =============================================================================================
@@ -1401,6 +1468,13 @@ struct WorkBufs {
     u64* ivf_partial = nullptr; int64_t ivf_partial_cap = 0;
     unsigned* ivf_group = nullptr; int64_t ivf_group_cap = 0;  // IVF at batch: [nlist] counters, [nlist+1] pair starts, [nlist+1] item starts, [B*nprobe] pairs by list
     unsigned* scope_group = nullptr; int64_t scope_group_cap = 0;  // scoped search: [B] queries in (scope, query) order, [B] their ranks inside the scope
+    // masked search: the call's allow bits, and what the two routes derive from them
+    uint32_t* mask_host = nullptr;   int64_t mask_host_cap = 0;    // pinned staging of the allow words; mask_uploaded: its last copy to the device
+    hipEvent_t mask_uploaded = nullptr; bool mask_upload_pending = false;
+    uint32_t* mask_allow = nullptr;  int64_t mask_allow_cap = 0;   // [ceil(count / 32)] device copy of the allow words
+    uint32_t* mask_deny = nullptr;   int64_t mask_deny_cap = 0;    // dense route: [ceil(capacity / 32)] ~allow | dead, ones past the mask
+    unsigned* mask_prefix = nullptr; int64_t mask_prefix_cap = 0;  // list route: [words] prefixes, [blocks] totals, [blocks + 1] bases
+    uint32_t* mask_list = nullptr;   int64_t mask_list_cap = 0;    // list route: [m] visible row slots, ascending
 };
 constexpr int kMaxWork = 4;
 struct WorkSlot {
@@ -1538,6 +1612,12 @@ struct codd_knn_index : WorkBufs {
     hipStream_t scope_stream = nullptr;  // the stream the last build ran on, and its completion
     hipEvent_t scope_ready = nullptr;
     int64_t stat_scoped_searches = 0, stat_scope_builds = 0;
+
+    // masked search
+    int mask_route = 0;        // "mask_route": 0 = by the routing rule, 1 = always the list route, 2 = always the dense route
+    int mask_list_pct = 100;   // "mask_list_pct": the list route's side of the cost comparison, in percent (100 = the derived rule)
+    unsigned long long* mask_dstats = nullptr;  // the device counters of the dense masked passes: kept apart from dstats, which the filter watch reads
+    int64_t stat_masked_searches = 0, stat_mask_list = 0, stat_mask_dense = 0, stat_last_mask_rows = 0;
 
     // tombstones: one bit per row slot, set = deleted.  Null until the first codd_knn_delete_host — the kernels
     // take a null pointer as "nothing was ever deleted" and load nothing.  The host keeps a mirror: the write paths refuse dead
@@ -1973,8 +2053,9 @@ int scan_geometry(const codd_knn_index* ix, int64_t n, int* niter, int64_t* bloc
 }
 
 // exact scan of `nqueries` dense normalised queries -> keys_out[nqueries][k]
+// (deny: the bitmap of rows no answer may hold — the tombstone bits, or a masked search's ~allow | dead; null = none)
 int exact_scan(codd_knn_index* ix, const float* qn, int nqueries, int k, uint32_t row_base, u64* keys_out, float* dist_out,
-               int64_t* rows_out, hipStream_t st) {
+               int64_t* rows_out, hipStream_t st, const uint32_t* deny) {
     const int64_t n = ix->count;
     int niter;
     int64_t blocks;
@@ -1990,7 +2071,7 @@ int exact_scan(codd_knn_index* ix, const float* qn, int nqueries, int k, uint32_
         const int nb = nqueries == 1 ? 1 : (nqueries <= 4 ? 4 : 8);
         ix->stat_last_scan_group = niter > 4 ? wide_scan_nb(ix->dtype, nb) : nb;
         ScanArgs a{ix->rows, n, ix->dpad, qn, nqueries, k, row_base, ix->partial, stride_q};
-        a.dead = ix->dead_bits;
+        a.dead = deny;
         {
             EvScope ev(ix, EV_SCAN, st);
             rc = launch_scan(ix->dtype, nb, niter, dim3((unsigned)blocks), st, a);
@@ -2350,7 +2431,7 @@ int fallback_geometry(codd_knn_index* ix, int k, int64_t* blocks, int64_t* strid
 // the queue (an empty queue costs one empty launch), its last block merges the per-block partials and writes each answer into
 // its query's slot.  No host round trip: the whole search stays asynchronous on `st`.
 int listed_fallback(codd_knn_index* ix, const float* qn, int k, uint32_t row_base, u64* keys_out, float* dist_out, int64_t* rows_out,
-                    hipStream_t st) {
+                    hipStream_t st, const uint32_t* deny) {
     int64_t blocks, stride_q;
     int rc;
     if ((rc = fallback_geometry(ix, k, &blocks, &stride_q)) != 0) return rc;
@@ -2360,7 +2441,7 @@ int listed_fallback(codd_knn_index* ix, const float* qn, int k, uint32_t row_bas
     a.merged_dist = dist_out;
     a.merged_rows = rows_out;
     a.count_total = &ix->dstats[2];
-    a.dead = ix->dead_bits;
+    a.dead = deny;
     {
         EvScope ev(ix, EV_SCAN, st);
         rc = launch_scan(ix->dtype, 8, niter_of(ix), dim3((unsigned)blocks), st, a);
@@ -2373,7 +2454,7 @@ int listed_fallback(codd_knn_index* ix, const float* qn, int k, uint32_t row_bas
 // one pass of <= 256 queries through sample -> threshold -> filter -> finalize (+ exact fallback)
 // keys_out and / or (dist_out, rows_out): what the caller wants written per query (any may be null)
 int filter_pass(codd_knn_index* ix, const float* qn, int nq, int k, uint32_t row_base, u64* keys_out, float* dist_out, int64_t* rows_out,
-                hipStream_t st, bool prepared = false, bool use8 = false) {
+                hipStream_t st, const uint32_t* deny, bool prepared = false, bool use8 = false) {
     const int64_t n = ix->count;
     const int nsteps = use8 ? dpad8_of(ix) / 128 : ix->dpad / 64;
     const uint4* shadow = use8 ? ix->shadow8 : ix->shadow;
@@ -2410,7 +2491,7 @@ int filter_pass(codd_knn_index* ix, const float* qn, int nq, int k, uint32_t row
     // thresholds anchored on the exact scores of the k best sampled rows (anchor_thr_kernel)
     rc = with_row_form(ix, k, "row too wide for the threshold kernel%s", [&](auto dt, auto ni, auto sl) {
         return launch_kernel<anchor_thr_kernel<dt, ni, sl>>(dim3(kTileQ), dim3(kAnchorWaves * kWave), 0, st, ix->bucket_max, ts, nq, k, ix->rows,
-                                                            ix->dpad, qn, eps, slack_q, ix->thr, use8 ? ix->thr + kTileQ : nullptr, ix->dead_bits);
+                                                            ix->dpad, qn, eps, slack_q, ix->thr, use8 ? ix->thr + kTileQ : nullptr, deny);
     });
     if (rc != 0) return rc;
     HIP_TRY(hipGetLastError());
@@ -2456,7 +2537,7 @@ int filter_pass(codd_knn_index* ix, const float* qn, int nq, int k, uint32_t row
                 } else {
                     return launch_kernel<finalize_fb_kernel<decltype(dt)::value, ni>>(
                         grid, dim3(kFinThreads), lds, st, ix->rows, ix->dpad, qn, ix->hits, c->hit_cnt, ix->hit_cap_q, c->flags, k, 2.0f * eps, row_base,
-                        keys_out, ix->dstats, slack_q, (u64*)nullptr, dist_out, rows_out, bm, nq, n, ix->fb_partial, stride_q, &c->fb_done, ix->dead_bits);
+                        keys_out, ix->dstats, slack_q, (u64*)nullptr, dist_out, rows_out, bm, nq, n, ix->fb_partial, stride_q, &c->fb_done, deny);
                 }
             });
         });
@@ -2469,19 +2550,19 @@ int filter_pass(codd_knn_index* ix, const float* qn, int nq, int k, uint32_t row
         rc = with_row_form(ix, k, "row too wide for the finalize kernel%s", [&](auto dt, auto ni, auto sl) {
             return launch_kernel<finalize_kernel<dt, ni, sl>>(dim3(nq, nparts), dim3(kFinThreads), 0, st, ix->rows, ix->dpad, qn, ix->hits, c->hit_cnt,
                                                               ix->hit_cap_q, c->flags, k, 2.0f * eps, row_base, keys_out, &c->fb_count, c->fb_list,
-                                                              ix->dstats, slack_q, ix->partial, dist_out, rows_out, bm, ix->dead_bits);
+                                                              ix->dstats, slack_q, ix->partial, dist_out, rows_out, bm, deny);
         });
     }
     if (rc != 0) return rc;
     HIP_TRY(hipGetLastError());
     if (nparts > 1 && (rc = launch_merge(ix->partial, nq, (int64_t)nparts * k, (int64_t)nparts * k, k, keys_out, dist_out, rows_out, st)) != 0) return rc;
-    return listed_fallback(ix, qn, k, row_base, keys_out, dist_out, rows_out, st);
+    return listed_fallback(ix, qn, k, row_base, keys_out, dist_out, rows_out, st, deny);
 }
 
 // ---- one launch for a single query (small_batch_kernel) + the (normally empty) list-driven fallback scan ----
 template <int DT, int NS>
 int launch_small_batch(int64_t nunits, hipStream_t st, const codd_knn_index* ix, const float* dev_queries, int k, uint32_t row_base, u64* cand,
-                       u64* out_keys, float* out_dist, int64_t* out_rows) {
+                       u64* out_keys, float* out_dist, int64_t* out_rows, const uint32_t* deny) {
     constexpr int E = DT == DT_F32 ? 4 : 8;
     constexpr int NITER = (NS * 128 / E + kWave - 1) / kWave;  // chunks of the PADDED row per lane (dpad <= NS * 128)
     constexpr int kWavesPerWg = kSbThreads / kWave;
@@ -2501,14 +2582,14 @@ int launch_small_batch(int64_t nunits, hipStream_t st, const codd_knn_index* ix,
     FilterCtl* c = ix->ctl;
     return launch_kernel<small_batch_kernel<DT, NITER, NS>>(grid, dim3(kSbThreads), 0, st, ix->shadow8, ix->bmeta, ix->rows, ix->count, ix->dim, ix->dpad,
                                                             dev_queries, k, row_base, ix->eps_r_bits, ix->qn, cand, dropmax, &c->sb_ticket, &c->fb_count,
-                                                            c->fb_list, out_keys, out_dist, out_rows, ix->dstats, ix->dead_bits);
+                                                            c->fb_list, out_keys, out_dist, out_rows, ix->dstats, deny);
 }
 bool small_batch_applies(const codd_knn_index* ix, int B, int k) {
     const int ns = dpad8_of(ix) / 128;
     return ix->small_batch_max > 0 && B == 1 && k <= kWave && (ns == 3 || ns == 4 || ns == 6 || ns == 8) && ix->count >= 4096;
 }
 int small_batch_search(codd_knn_index* ix, const float* dev_queries, int B, int k, uint32_t row_base, u64* out_keys, float* out_dist, int64_t* out_rows,
-                       hipStream_t st) {
+                       hipStream_t st, const uint32_t* deny) {
     (void)B;
     const int ns = dpad8_of(ix) / 128;
     const int64_t n = ix->count;
@@ -2522,14 +2603,14 @@ int small_batch_search(codd_knn_index* ix, const float* dev_queries, int B, int 
         EvScope ev(ix, EV_FILTER, st);
         rc = with_dtype(ix->dtype, [&](auto dt) {
             return with_int<3, 4, 6, 8>(ns, "small batch: unsupported row width%s", [&](auto nsc) {
-                return launch_small_batch<decltype(dt)::value, nsc>(nunits, st, ix, dev_queries, k, row_base, cand, out_keys, out_dist, out_rows);
+                return launch_small_batch<decltype(dt)::value, nsc>(nunits, st, ix, dev_queries, k, row_base, cand, out_keys, out_dist, out_rows, deny);
             });
         });
     }
     if (rc != 0) return rc;
     HIP_TRY(hipGetLastError());
     // a query the margin test could not clear (normally none): the list-driven exact scan, its last block merges
-    return listed_fallback(ix, ix->qn, k, row_base, out_keys, out_dist, out_rows, st);
+    return listed_fallback(ix, ix->qn, k, row_base, out_keys, out_dist, out_rows, st, deny);
 }
 
 bool filter_applies(const codd_knn_index* ix, int B, int k) {
@@ -2562,8 +2643,10 @@ int after_filter_search(codd_knn_index* ix, int B, bool use8, hipStream_t st) {
 }
 
 // the whole shard-local search: normalise queries, then filter passes or exact scans, keys out.
+// deny: the rows no answer may hold — ix->dead_bits, or, `masked`, the ~allow | dead of a masked search's dense route (DESIGN.md
+// §15).  A masked search says nothing about the corpus: it neither feeds the filter watch nor uses up a cooldown.
 int search_impl(codd_knn_index* ix, const float* dev_queries, int B, int k, uint32_t row_base, u64* out_keys,
-                float* out_dist, int64_t* out_rows, hipStream_t st) {
+                float* out_dist, int64_t* out_rows, hipStream_t st, const uint32_t* deny, bool masked = false) {
     if (!ix) return fail(CODD_KNN_EINVAL, "null index%s");
     if (!dev_queries) return fail(CODD_KNN_EINVAL, "null queries%s");
     if (B < 1 || B > CODD_KNN_MAX_BATCH) return fail(CODD_KNN_EINVAL, "B out of range [1,1024]%s");
@@ -2615,7 +2698,7 @@ int search_impl(codd_knn_index* ix, const float* dev_queries, int B, int k, uint
         }
     }
     const bool cooling = ix->cooldown_left > 0;
-    if (cooling && use_filter) ix->cooldown_left--;
+    if (cooling && use_filter && !masked) ix->cooldown_left--;
     // the int8 filter: every pass of <= 256 queries prepares its own block (a batch above 256 queries is several passes)
     const bool can8 = use_filter && ix->shadow8_enabled && (B <= ix->shadow8_max_batch || (B > kTileQ && ix->shadow8_max_batch >= kTileQ)) && CODD_MFMA16;
     // A corpus whose WORST block quantises badly keeps the int8 filter for the batches i8_tile_kernel takes as long as such blocks are
@@ -2654,8 +2737,8 @@ int search_impl(codd_knn_index* ix, const float* dev_queries, int B, int k, uint
         // survivors exactly in its last workgroup (small_batch_kernel) instead of the six-launch filter chain
         if (small_batch_applies(ix, B, k)) {
             if ((rc = ensure_buf(&ix->qn, &ix->qn_cap, (int64_t)B * ix->dpad)) != 0) return rc;
-            if ((rc = small_batch_search(ix, dev_queries, B, k, row_base, out_keys, out_dist, out_rows, st)) != 0) return rc;
-            return after_filter_search(ix, B, true, st);
+            if ((rc = small_batch_search(ix, dev_queries, B, k, row_base, out_keys, out_dist, out_rows, st, deny)) != 0) return rc;
+            return masked ? CODD_KNN_OK : after_filter_search(ix, B, true, st);
         }
         if ((rc = ensure_buf(&ix->qfrag8, &ix->qfrag8_cap, (int64_t)kTileQ * (dpad8 / 16))) != 0) return rc;
         if (!ix->qmeta) HIP_TRY(hipMalloc((void**)&ix->qmeta, 1024 * sizeof(float)));
@@ -2677,17 +2760,17 @@ int search_impl(codd_knn_index* ix, const float* dev_queries, int B, int k, uint
         return launch_merge(keys_dst, B, k, k, k, nullptr, out_dist, out_rows, st);
     }
     if (!use_filter)  // small batches: the per-block partials merge straight into the caller's buffers
-        return exact_scan(ix, ix->qn, B, k, row_base, out_keys, out_dist, out_rows, st);
+        return exact_scan(ix, ix->qn, B, k, row_base, out_keys, out_dist, out_rows, st, deny);
     if ((rc = ensure_filter_workspace(ix)) != 0) return rc;
     for (int q0 = 0; q0 < B; q0 += kTileQ) {
         const int nq = B - q0 < kTileQ ? B - q0 : kTileQ;
         if (use8 && (rc = prep8(q0, nq)) != 0) return rc;
         if ((rc = filter_pass(ix, ix->qn + (int64_t)q0 * ix->dpad, nq, k, row_base, out_keys ? out_keys + (int64_t)q0 * k : nullptr,
-                              out_dist ? out_dist + (int64_t)q0 * k : nullptr, out_rows ? out_rows + (int64_t)q0 * k : nullptr, st,
+                              out_dist ? out_dist + (int64_t)q0 * k : nullptr, out_rows ? out_rows + (int64_t)q0 * k : nullptr, st, deny,
                               fused_prep || use8, use8)) != 0)
             return rc;
     }
-    return after_filter_search(ix, B, use8, st);
+    return masked ? CODD_KNN_OK : after_filter_search(ix, B, use8, st);
 }
 
 // ---- scopes ----------------------------------------------------------------------------------
@@ -2806,7 +2889,7 @@ int codd_knn_destroy(codd_knn_index* ix) {
     DeviceGuard guard(ix->device);
     (void)hipDeviceSynchronize();
     void* bufs[] = {ix->rows, ix->shadow, ix->dstats, ix->rows_ivf, ix->ivf_ids, ix->ivf_offsets, ix->shadow8, ix->rscale, ix->bmeta, ix->eps_r_bits,
-                    ix->scope_of, ix->scope_perm, ix->scope_offsets, ix->dead_bits};
+                    ix->scope_of, ix->scope_perm, ix->scope_offsets, ix->dead_bits, ix->mask_dstats};
     if (ix->scope_ready) (void)hipEventDestroy(ix->scope_ready);
     if (ix->shadow8_ready) (void)hipEventDestroy(ix->shadow8_ready);
     if (ix->shadow_ready) (void)hipEventDestroy(ix->shadow_ready);
@@ -2823,9 +2906,11 @@ int codd_knn_destroy(codd_knn_index* ix) {
     for (WorkSlot& w : ix->slots) {
         void* wb[] = {w.bufs.qn, w.bufs.partial, w.bufs.keys_tmp, w.bufs.qfrag, w.bufs.thr, w.bufs.bucket_max, w.bufs.hits, w.bufs.ctl,
                       w.bufs.fb_partial, w.bufs.probe_keys, w.bufs.ivf_partial, w.bufs.ivf_group, w.bufs.qfrag8, w.bufs.qmeta, w.bufs.sb_cand,
-                      w.bufs.scope_group};
+                      w.bufs.scope_group, w.bufs.mask_allow, w.bufs.mask_deny, w.bufs.mask_prefix, w.bufs.mask_list};
         for (void* b : wb)
             if (b) (void)hipFree(b);
+        if (w.bufs.mask_host) (void)hipHostFree(w.bufs.mask_host);
+        if (w.bufs.mask_uploaded) (void)hipEventDestroy(w.bufs.mask_uploaded);
         if (w.handover) (void)hipEventDestroy(w.handover);
     }
     if (ix->coarse) (void)codd_knn_destroy(ix->coarse);
@@ -3001,7 +3086,7 @@ int codd_knn_search(codd_knn_index* ix, const float* dev_queries, int B, int k, 
     if (!dev_dist || !dev_rows) return fail(CODD_KNN_EINVAL, "null output%s");
     if (!ix) return fail(CODD_KNN_EINVAL, "null index%s");
     WorkScope work(ix, (hipStream_t)stream);
-    return search_impl(ix, dev_queries, B, k, 0u, nullptr, dev_dist, dev_rows, (hipStream_t)stream);
+    return search_impl(ix, dev_queries, B, k, 0u, nullptr, dev_dist, dev_rows, (hipStream_t)stream, ix->dead_bits);
 }
 
 int codd_knn_search_keys(codd_knn_index* ix, const float* dev_queries, int B, int k, uint32_t row_base, uint64_t* dev_keys, void* stream) {
@@ -3009,7 +3094,7 @@ int codd_knn_search_keys(codd_knn_index* ix, const float* dev_queries, int B, in
     if (!ix) return fail(CODD_KNN_EINVAL, "null index%s");
     if ((int64_t)row_base + ix->count >= 0xffffffffll) return fail(CODD_KNN_EINVAL, "global row ids must fit 32 bits%s");
     WorkScope work(ix, (hipStream_t)stream);
-    return search_impl(ix, dev_queries, B, k, row_base, (u64*)dev_keys, nullptr, nullptr, (hipStream_t)stream);
+    return search_impl(ix, dev_queries, B, k, row_base, (u64*)dev_keys, nullptr, nullptr, (hipStream_t)stream, ix->dead_bits);
 }
 
 int codd_knn_merge_keys(int device, const uint64_t* dev_keys_in, int B, int m, int k, uint64_t* dev_keys_out, float* dev_dist,
@@ -3185,7 +3270,7 @@ int codd_knn_ivf_search(codd_knn_index* ix, const float* dev_queries, int B, int
     if ((rc = ensure_buf(&ix->probe_keys, &ix->probe_cap, (int64_t)B * nprobe)) != 0) return rc;
     if ((rc = launch_normalize(DT_F32, dev_queries, B, ix->dim, ix->dpad, 1, nullptr, 0, ix->qn, nullptr, st)) != 0) return rc;
     // 1. coarse: the nprobe best lists per query (exact scan of the centroids, tiny)
-    if ((rc = exact_scan(ix->coarse, ix->qn, B, nprobe, 0u, ix->probe_keys, nullptr, nullptr, st)) != 0) return rc;
+    if ((rc = exact_scan(ix->coarse, ix->qn, B, nprobe, 0u, ix->probe_keys, nullptr, nullptr, st, ix->coarse->dead_bits)) != 0) return rc;
     const int niter = niter_of(ix);
     // 2a. a batch with enough (query, list) pairs to fill the chip without splitting lists: group the pairs by list on the
     //     device and scan every probed list once per kIvfNB of its queries (ivf_scan_shared_kernel)
@@ -3341,6 +3426,137 @@ int codd_knn_search_scoped(codd_knn_index* ix, const float* dev_queries, const u
     if (rc != 0) return rc;
     HIP_TRY(hipGetLastError());
     return launch_merge(ix->partial, B, m, m, k, (u64*)dev_keys, dev_dist, dev_rows, st);
+}
+
+}  // extern "C"
+
+namespace {
+
+// Which way a masked search of m visible rows goes (time only, both routes give the same bits).  Dense — the
+// ordinary dispatch under ~allow | dead — when the sample's anchors can be expected to hold 4k visible rows and the pass over the
+// whole index costs less than ceil(B / NB) gathered walks of the list; "mask_list_pct" scales the dense side of that comparison.
+bool mask_takes_dense(const codd_knn_index* ix, int B, int k, int64_t m) {
+    if (ix->mask_route == 1) return false;
+    if (ix->mask_route == 2) return true;
+    const int64_t n = ix->count;
+    const int64_t row_bytes = (int64_t)ix->dpad * (int64_t)elem_size(ix->dtype);
+    const int nb = scope_nb(ix->dtype, niter_of(ix) > 4 ? kWideRows : niter_of(ix));
+    const double list_bytes = 2.0 * (double)((B + nb - 1) / nb) * (double)m * (double)row_bytes;
+    double dense_bytes;
+    if (filter_applies(ix, B, k)) {
+        const bool can8 = ix->shadow8_enabled && CODD_MFMA16 && (B <= ix->shadow8_max_batch || (B > kTileQ && ix->shadow8_max_batch >= kTileQ));
+        const int nq = B < kTileQ ? B : kTileQ;
+        const int nbq = nq <= 32 ? 1 : (nq <= 64 ? 2 : (nq <= 128 ? 4 : 8));
+        const int64_t ts = sample_tile_count(ix, (n + kTileRows - 1) / kTileRows, k, can8, nbq);
+        if ((double)m * (double)ts < 4.0 * (double)k * (double)n) return false;   // too few visible anchors: the pass would end in the fallback scan
+        dense_bytes = (double)((B + kTileQ - 1) / kTileQ) * (double)n * (double)(can8 ? dpad8_of(ix) : 2 * ix->dpad);
+    } else {
+        // the exact scan reads the rows once per group of 8 queries, streaming: twice the rate of the gathered walk, as above
+        dense_bytes = (double)((B + 7) / 8) * (double)n * (double)row_bytes;
+    }
+    return list_bytes * 100.0 > dense_bytes * (double)ix->mask_list_pct;
+}
+
+}  // namespace
+
+extern "C" {
+
+int codd_knn_search_masked(codd_knn_index* ix, const float* dev_queries, int B, int k, const uint32_t* host_allow_bits, int64_t nwords,
+                           uint32_t row_base, uint64_t* dev_keys, float* dev_dist, int64_t* dev_rows, void* stream) {
+    if (!ix || !dev_queries) return fail(CODD_KNN_EINVAL, "null index or queries%s");
+    if (B < 1 || B > CODD_KNN_MAX_BATCH) return fail(CODD_KNN_EINVAL, "B out of range [1,1024]%s");
+    if (k < 1 || k > CODD_KNN_MAX_K) return fail(CODD_KNN_EINVAL, "k out of range [1,128]%s");
+    if ((int64_t)row_base + ix->count >= 0xffffffffll) return fail(CODD_KNN_EINVAL, "global row ids must fit 32 bits%s");
+    DeviceGuard guard(ix->device);
+    hipStream_t st = (hipStream_t)stream;
+    WorkScope work(ix, st);
+    const int64_t n = ix->count;
+    if (nwords != (n + 31) / 32) return fail(CODD_KNN_EINVAL, "search_masked: nwords must be ceil(count / 32)%s");
+    if (nwords > 0 && !host_allow_bits) return fail(CODD_KNN_EINVAL, "null allow bits%s");
+    ix->stat_masked_searches++;
+    int rc;
+    if ((rc = wait_rows(ix, st)) != 0) return rc;
+    // The host words: clipped to [0, count) into the workspace's pinned staging buffer, counted against the tombstone mirror on
+    // the way (m: the rows this call may see, exact, nothing read back), then one asynchronous copy from the staging buffer.  The
+    // caller's words are not touched again; the staging buffer's previous copy (the stream's last masked search) is waited for first.
+    int64_t m = 0;
+    if (nwords > 0) {
+        if (ix->mask_upload_pending) HIP_TRY(hipEventSynchronize(ix->mask_uploaded));
+        ix->mask_upload_pending = false;
+        if (nwords > ix->mask_host_cap) {
+            if (ix->mask_host) (void)hipHostFree(ix->mask_host);
+            ix->mask_host = nullptr; ix->mask_host_cap = 0;
+            const int64_t cap = nwords + nwords / 2 + 64;
+            HIP_TRY(hipHostMalloc((void**)&ix->mask_host, (size_t)cap * sizeof(uint32_t), hipHostMallocDefault));
+            ix->mask_host_cap = cap;
+        }
+        if (!ix->mask_uploaded) HIP_TRY(hipEventCreateWithFlags(&ix->mask_uploaded, hipEventDisableTiming));
+        const bool any_dead = ix->dead_count > 0;
+        for (int64_t w = 0; w < nwords; ++w) {
+            const int64_t left = n - w * 32;
+            const uint32_t a = host_allow_bits[w] & (left >= 32 ? 0xffffffffu : (1u << (uint32_t)left) - 1u);
+            ix->mask_host[w] = a;
+            m += __builtin_popcount(any_dead && (size_t)w < ix->dead_host.size() ? a & ~ix->dead_host[(size_t)w] : a);
+        }
+    }
+    ix->stat_last_mask_rows = m;
+    if (m == 0) {  // nothing visible (or nothing stored): all-empty result, no scan
+        if ((rc = ensure_buf(&ix->keys_tmp, &ix->keys_tmp_cap, (int64_t)B * k)) != 0) return rc;
+        u64* keys_dst = dev_keys ? (u64*)dev_keys : ix->keys_tmp;
+        HIP_TRY(hipMemsetAsync(keys_dst, 0, (size_t)B * k * sizeof(u64), st));
+        if (!dev_dist && !dev_rows) return CODD_KNN_OK;
+        return launch_merge(keys_dst, B, k, k, k, nullptr, dev_dist, dev_rows, st);
+    }
+    if ((rc = ensure_buf(&ix->mask_allow, &ix->mask_allow_cap, nwords)) != 0) return rc;
+    HIP_TRY(hipMemcpyAsync(ix->mask_allow, ix->mask_host, (size_t)nwords * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(ix->mask_uploaded, st));
+    ix->mask_upload_pending = true;
+
+    if (mask_takes_dense(ix, B, k, m)) {
+        ix->stat_mask_dense++;
+        const int64_t total_words = (ix->capacity + 31) / 32;   // (as long as the tombstone bits: every kernel that reads those reads these)
+        if ((rc = ensure_buf(&ix->mask_deny, &ix->mask_deny_cap, total_words)) != 0) return rc;
+        hipLaunchKernelGGL(mask_deny_kernel, dim3((unsigned)((total_words + 255) / 256)), dim3(256), 0, st, ix->mask_allow, ix->dead_bits, n, nwords,
+                           total_words, ix->mask_deny);
+        HIP_TRY(hipGetLastError());
+        std::swap(ix->dstats, ix->mask_dstats);   // (the passes below count into the masked searches' own counters)
+        rc = search_impl(ix, dev_queries, B, k, row_base, (u64*)dev_keys, dev_dist, dev_rows, st, ix->mask_deny, true);
+        std::swap(ix->dstats, ix->mask_dstats);
+        return rc;
+    }
+
+    ix->stat_mask_list++;
+    const int64_t nblocks = (nwords + 255) / 256;
+    if ((rc = ensure_buf(&ix->mask_prefix, &ix->mask_prefix_cap, nwords + 2 * nblocks + 1)) != 0) return rc;
+    if ((rc = ensure_buf(&ix->mask_list, &ix->mask_list_cap, m)) != 0) return rc;
+    unsigned* prefix = ix->mask_prefix;
+    unsigned* block_total = prefix + nwords;
+    unsigned* block_base = block_total + nblocks;
+    hipLaunchKernelGGL(mask_prefix_kernel, dim3((unsigned)nblocks), dim3(256), 0, st, ix->mask_allow, ix->dead_bits, n, nwords, prefix, block_total);
+    hipLaunchKernelGGL(scope_offsets_kernel, dim3(1), dim3(1024), 0, st, block_total, (int)nblocks, block_base);
+    hipLaunchKernelGGL(mask_scatter_kernel, dim3((unsigned)nblocks), dim3(256), 0, st, ix->mask_allow, ix->dead_bits, n, nwords, prefix, block_base, m,
+                       ix->mask_list);
+    HIP_TRY(hipGetLastError());
+    // the split of codd_knn_search_scoped, and no more parts than the list has workgroup steps (16 rows)
+    const int64_t groups = (B + 3) / 4;
+    int split = (int)((4 * (int64_t)ix->num_cus + groups - 1) / groups);
+    split = split < 1 ? 1 : (split > 256 ? 256 : split);
+    if ((int64_t)split > (m + 15) / 16) split = (int)((m + 15) / 16);
+    const int64_t pm = (int64_t)split * k;
+    if ((rc = ensure_buf(&ix->qn, &ix->qn_cap, (int64_t)B * ix->dpad)) != 0) return rc;
+    if ((rc = ensure_buf(&ix->partial, &ix->partial_cap, (int64_t)B * pm)) != 0) return rc;
+    if ((rc = launch_normalize(DT_F32, dev_queries, B, ix->dim, ix->dpad, 1, nullptr, 0, ix->qn, nullptr, st)) != 0) return rc;
+    {
+        EvScope ev(ix, EV_SCAN, st);
+        rc = with_row_form(ix, k, "row too wide for the mask scan%s", [&](auto dt, auto ni, auto sl) {
+            constexpr int NB = scope_nb(decltype(dt)::value, decltype(ni)::value);
+            return launch_kernel<mask_scan_kernel<dt, ni, sl>>(dim3((unsigned)((B + NB - 1) / NB), (unsigned)split), dim3(256), 0, st, ix->rows, ix->mask_list, m,
+                                                               B, split, ix->dpad, ix->qn, k, row_base, ix->partial);
+        });
+    }
+    if (rc != 0) return rc;
+    HIP_TRY(hipGetLastError());
+    return launch_merge(ix->partial, B, pm, pm, k, (u64*)dev_keys, dev_dist, dev_rows, st);
 }
 
 int codd_knn_delete_host(codd_knn_index* ix, const int64_t* host_slots, int64_t n) {
@@ -3647,6 +3863,16 @@ int codd_knn_set_option(codd_knn_index* ix, const char* key, int64_t value) {
         ix->compact_chunk_rows = value;
         return CODD_KNN_OK;
     }
+    if (strcmp(key, "mask_route") == 0) {
+        if (value < 0 || value > 2) return fail(CODD_KNN_EINVAL, "mask_route must be 0 (auto), 1 (list) or 2 (dense)%s");
+        ix->mask_route = (int)value;
+        return CODD_KNN_OK;
+    }
+    if (strcmp(key, "mask_list_pct") == 0) {
+        if (value < 0 || value > 100000) return fail(CODD_KNN_EINVAL, "mask_list_pct must be in [0,100000]%s");
+        ix->mask_list_pct = (int)value;
+        return CODD_KNN_OK;
+    }
     if (strcmp(key, "hit_cap") == 0) {
         if (value < 16 || value > (1 << 20)) return fail(CODD_KNN_EINVAL, "hit_cap must be in [16,2^20]%s");
         ix->hit_cap_q = (int)value;
@@ -3704,6 +3930,10 @@ int codd_knn_get_stat(const codd_knn_index* ix, const char* key, int64_t* out) {
     else if (strcmp(key, "scoped_searches") == 0) *out = ix->stat_scoped_searches;
     else if (strcmp(key, "scope_builds") == 0) *out = ix->stat_scope_builds;
     else if (strcmp(key, "scopes") == 0) *out = (int64_t)ix->max_scope;
+    else if (strcmp(key, "masked_searches") == 0) *out = ix->stat_masked_searches;
+    else if (strcmp(key, "mask_list_searches") == 0) *out = ix->stat_mask_list;
+    else if (strcmp(key, "mask_dense_searches") == 0) *out = ix->stat_mask_dense;
+    else if (strcmp(key, "last_mask_rows") == 0) *out = ix->stat_last_mask_rows;
     else if (strcmp(key, "dead_rows") == 0) *out = ix->dead_count;
     else if (strcmp(key, "delete_calls") == 0) *out = ix->stat_delete_calls;
     else if (strcmp(key, "compactions") == 0) *out = ix->stat_compactions;
@@ -3740,6 +3970,16 @@ int codd_knn_get_stat(const codd_knn_index* ix, const char* key, int64_t* out) {
             HIP_TRY(hipMemcpy(h, ix->dstats, sizeof(h), hipMemcpyDeviceToHost));
         }
         *out = (int64_t)(key[0] == 'f' && key[1] == 'a' ? h[2] : (strcmp(key, "filter_hits") == 0 ? h[0] : h[1]));
+    }
+    else if (strcmp(key, "mask_filter_hits") == 0 || strcmp(key, "mask_filter_survivors") == 0 || strcmp(key, "mask_fallback_queries") == 0) {
+        // the same device counters, of the dense masked passes alone: synchronises
+        unsigned long long h[4] = {0, 0, 0, 0};
+        if (ix->mask_dstats) {
+            DeviceGuard guard(ix->device);
+            HIP_TRY(hipDeviceSynchronize());
+            HIP_TRY(hipMemcpy(h, ix->mask_dstats, sizeof(h), hipMemcpyDeviceToHost));
+        }
+        *out = (int64_t)(key[12] == 'h' ? h[0] : (key[12] == 's' ? h[1] : h[2]));
     }
     else if (strcmp(key, "capacity_rows") == 0) *out = ix->capacity;
     else if (strcmp(key, "num_cus") == 0) *out = ix->num_cus;

@@ -78,6 +78,10 @@ class Collection:
         self._dirty = False
         self._generation = 0
         self._scope_of_namespace: dict[str, int] = {}  # namespace string -> scope label of the engine (from 1, first seen first)
+        # general `where`: per metadata key, (value class, value) -> row slots, built on first use; compiled masks by canonical filter.
+        # Both are dropped by every upsert / delete / compact / load.
+        self._key_index: dict[str, dict[tuple, np.ndarray]] = {}
+        self._mask_cache: dict[str, np.ndarray] = {}
 
     # ------------------------------------------------------------------ helpers
     def _engine_for(self, dim: int):
@@ -125,6 +129,109 @@ class Collection:
             if isinstance(cond, dict) and list(cond) == ["$eq"] and isinstance(cond["$eq"], str):
                 return cond["$eq"]
         raise ValueError(f"unsupported where filter {where!r}; supported: {cls._WHERE_FORMS}")
+
+    # ------------------------------------------------------------------ general where -> row mask
+    _COMPARISONS = ("$eq", "$ne", "$gt", "$gte", "$lt", "$lte")
+    _MASK_CACHE_SIZE = 32
+    _WHERE_GRAMMAR = ('{"key": value}, {"key": {"$eq"|"$ne"|"$gt"|"$gte"|"$lt"|"$lte": value}}, {"key": {"$in"|"$nin": [values]}}, '
+                      '{"$and"|"$or": [filters]}; values are str / int / float / bool')
+
+    def _where_error(self, where, why: str) -> ValueError:
+        return ValueError(f"unsupported where filter {where!r}: {why}; supported: {self._WHERE_FORMS}, and on an engine with masked search "
+                          f"{self._WHERE_GRAMMAR}")
+
+    @staticmethod
+    def _value_class(v) -> Optional[str]:
+        """'b' bool, 'n' int / float, 's' str; None for anything else.  Values only ever meet values of their own class."""
+        if isinstance(v, bool):
+            return "b"
+        if isinstance(v, (int, float)):
+            return "n"
+        return "s" if isinstance(v, str) else None
+
+    def _check_where(self, where, top=None) -> None:
+        """ValueError unless `where` is a filter of ChromaDB's metadata grammar."""
+        top = where if top is None else top
+        if not isinstance(where, dict) or len(where) != 1:
+            raise self._where_error(top, "a filter is a dict with exactly one key")
+        (key, cond), = where.items()
+        if not isinstance(key, str):
+            raise self._where_error(top, "keys are strings")
+        if key in ("$and", "$or"):
+            if not isinstance(cond, (list, tuple)) or len(cond) == 0:
+                raise self._where_error(top, f"{key} takes a non-empty list of filters")
+            for sub in cond:
+                self._check_where(sub, top)
+            return
+        if key.startswith("$"):
+            raise self._where_error(top, f"unknown operator {key}")
+        if not isinstance(cond, dict):
+            cond = {"$eq": cond}
+        if len(cond) != 1:
+            raise self._where_error(top, "a condition is a value or a dict with exactly one operator")
+        (op, val), = cond.items()
+        if op in ("$in", "$nin"):
+            if not isinstance(val, (list, tuple)) or len(val) == 0 or any(self._value_class(v) is None for v in val):
+                raise self._where_error(top, f"{op} takes a non-empty list of str / int / float / bool")
+        elif op in self._COMPARISONS:
+            if self._value_class(val) is None:
+                raise self._where_error(top, f"{op} takes a str / int / float / bool")
+        else:
+            raise self._where_error(top, f"unknown operator {op!r}")
+
+    def _index_of_key(self, key: str) -> dict[tuple, np.ndarray]:
+        """(value class, value) -> ascending row slots of the live records that carry `key` with that value."""
+        index = self._key_index.get(key)
+        if index is None:
+            found: dict[tuple, list[int]] = {}
+            for slot, md in enumerate(self._metadatas):
+                if md and key in md and self._ids[slot] is not None:
+                    cls = self._value_class(md[key])
+                    if cls is not None:
+                        found.setdefault((cls, md[key]), []).append(slot)
+            index = {kv: np.asarray(slots, dtype=np.int64) for kv, slots in found.items()}
+            self._key_index[key] = index
+        return index
+
+    def _eval_where(self, where) -> np.ndarray:
+        (key, cond), = where.items()
+        n = len(self._ids)
+        if key in ("$and", "$or"):
+            masks = [self._eval_where(sub) for sub in cond]
+            return np.logical_and.reduce(masks) if key == "$and" else np.logical_or.reduce(masks)
+        (op, val), = (cond if isinstance(cond, dict) else {"$eq": cond}).items()
+        index = self._index_of_key(key)
+        mask = np.zeros(n, dtype=bool)
+        if op in ("$eq", "$ne", "$in", "$nin"):
+            for v in (val if op in ("$in", "$nin") else [val]):
+                slots = index.get((self._value_class(v), v))
+                if slots is not None:
+                    mask[slots] = True
+            if op in ("$ne", "$nin"):  # (a record without the key passes; a deleted slot never does)
+                live = np.fromiter((doc_id is not None for doc_id in self._ids), dtype=bool, count=n)
+                mask = live & ~mask
+            return mask
+        cls = self._value_class(val)
+        test = {"$gt": lambda a: a > val, "$gte": lambda a: a >= val, "$lt": lambda a: a < val, "$lte": lambda a: a <= val}[op]
+        for (c, stored), slots in index.items():  # (the key's distinct values, not its records)
+            if c == cls and test(stored):
+                mask[slots] = True
+        return mask
+
+    def _where_mask(self, where) -> np.ndarray:
+        """The checked filter as a bool array over the row slots (deleted slots False); cached by the filter's canonical JSON."""
+        canon = json.dumps(where, sort_keys=True, ensure_ascii=False)
+        mask = self._mask_cache.get(canon)
+        if mask is None:
+            mask = self._eval_where(where)
+            if len(self._mask_cache) >= self._MASK_CACHE_SIZE:
+                self._mask_cache.pop(next(iter(self._mask_cache)))
+            self._mask_cache[canon] = mask
+        return mask
+
+    def _forget_where_index(self) -> None:
+        self._key_index.clear()
+        self._mask_cache.clear()
 
     def _where_scopes(self, where, B: int) -> Optional[np.ndarray]:
         """Per-query scope labels of a `where` (None when no query is restricted); -1 marks a namespace nobody stored."""
@@ -185,6 +292,7 @@ class Collection:
             if metadatas is not None:
                 self._metadatas[slot] = dict(metadatas[i]) if metadatas[i] is not None else None
         self._dirty = True
+        self._forget_where_index()
         # the rows' namespaces as scope labels of the engine (an engine without scoped search is not asked)
         if metadatas is not None and hasattr(engine, "set_scopes"):
             scopes = np.array([self._scope_for(md) for md in metadatas], dtype=np.uint32)
@@ -221,6 +329,7 @@ class Collection:
             self._documents[s] = None
             self._metadatas[s] = None
         self._dirty = True
+        self._forget_where_index()
         if len(self._ids) - len(self._slot_of) > self.AUTO_COMPACT_SHARE * len(self._ids):
             self.compact()
 
@@ -237,6 +346,7 @@ class Collection:
         self._documents = [self._documents[s] for s in keep]
         self._metadatas = [self._metadatas[s] for s in keep]
         self._slot_of = {doc_id: i for i, doc_id in enumerate(self._ids)}
+        self._forget_where_index()
         return new_count
 
     def add(self, ids: Sequence[str], embeddings=None, metadatas=None, documents=None) -> None:
@@ -250,13 +360,17 @@ class Collection:
 
     # ------------------------------------------------------------------ reads
     def get(self, ids: Optional[Sequence[str]] = None, limit: Optional[int] = None, offset: int = 0,
-            include: Sequence[str] = ("metadatas", "documents")) -> dict:
-        """chromadb Collection.get: FLAT lists; unknown ids are skipped (store.py:260-261)."""
+            include: Sequence[str] = ("metadatas", "documents"), where=None) -> dict:
+        """chromadb Collection.get: FLAT lists; unknown ids are skipped (store.py:260-261).  `where`: a metadata filter in the
+        grammar `query` accepts (one dict); with `ids`, the records that satisfy both."""
+        if where is not None:
+            self._check_where(where)
+            allowed = self._where_mask(where)
         if ids is None:
-            live = [s for s, doc_id in enumerate(self._ids) if doc_id is not None]
+            live = [s for s, doc_id in enumerate(self._ids) if doc_id is not None and (where is None or allowed[s])]
             slots = live[offset : (None if limit is None else offset + limit)]
         else:
-            slots = [self._slot_of[i] for i in ids if i in self._slot_of]
+            slots = [self._slot_of[i] for i in ids if i in self._slot_of and (where is None or allowed[self._slot_of[i]])]
         return {
             "ids": [self._ids[s] for s in slots],
             "metadatas": [self._metadatas[s] for s in slots] if "metadatas" in include else None,
@@ -269,10 +383,13 @@ class Collection:
         """chromadb Collection.query: NESTED lists, one inner list per query, ascending
         distance, min(n_results, count) hits each (store.py:314-329).
 
-        `where` restricts the search to one namespace (the metadata key every record of the path carries):
-        {"namespace": "x"} or {"namespace": {"$eq": "x"}}; as an extension a list of such dicts / None, one per
-        query.  The answer is the exact top-k among that namespace's rows (fewer when it holds fewer); a namespace
-        nobody stored gives an empty inner list.  Any other filter raises ValueError."""
+        `where` restricts the search by metadata, in ChromaDB's grammar: {"key": value}, {"key": {"$eq" | "$ne" | "$gt" | "$gte" |
+        "$lt" | "$lte": value}}, {"key": {"$in" | "$nin": [values]}}, {"$and" | "$or": [filters]}; as an extension a list of
+        filters / None, one per query.  The answer is the exact top-k among the records that satisfy the filter (fewer when
+        fewer do; nobody: an empty inner list).  A record without the key fails $eq, $in and the comparisons and passes $ne and
+        $nin; a str never compares with a number.  {"namespace": "x"} and {"namespace": {"$eq": "x"}} go through the engine's scoped
+        search, every other filter through its masked search (search_masked) under a row mask compiled here; an engine without
+        it accepts the namespace forms only.  A malformed filter raises ValueError."""
         if (query_texts is None) == (query_embeddings is None):
             raise ValueError("give exactly one of query_texts / query_embeddings")
         if n_results < 1:
@@ -292,8 +409,11 @@ class Collection:
         if q.shape[1] != self._engine.dim:
             raise ValueError(f"query dimension {q.shape[1]} does not match collection dimension {self._engine.dim}")
         k = min(int(n_results), len(self._slot_of))  # (the live count: deleted records are never returned)
-        scopes = None if where is None else self._where_scopes(where, B)
-        if scopes is None:
+        general = self._general_wheres(where, B)  # (None: nothing but namespace forms, the scoped path below)
+        scopes = None if where is None or general is not None else self._where_scopes(where, B)
+        if general is not None:
+            dist, rows = self._search_by_filter(q, k, general)
+        elif scopes is None:
             dist, rows = self._engine.search(q, k)
         else:
             if not hasattr(self._engine, "search_scoped"):
@@ -315,6 +435,68 @@ class Collection:
                 out["documents"][b] = [self._documents[r] for r, _ in hit]
         return out
 
+
+    def _general_wheres(self, where, B: int) -> Optional[list]:
+        """None when every query's filter is None or a namespace form (the scoped path, as before).  Otherwise the per-query filters,
+        each checked against the grammar; needs an engine with search_masked, else the ValueError that names the namespace forms."""
+        if where is None:
+            return None
+        if isinstance(where, (list, tuple)):
+            if len(where) != B:
+                return None  # (_where_scopes raises the length error)
+            per_query = list(where)
+        else:
+            per_query = [where] * B
+        found = False
+        for w in per_query:
+            try:
+                self._where_namespace(w)
+            except ValueError:
+                found = True
+        if not found:
+            return None
+        if not hasattr(self._engine, "search_masked"):
+            bad = next(w for w in per_query if not self._is_namespace_form(w))
+            raise ValueError(f"unsupported where filter {bad!r}; supported: {self._WHERE_FORMS}")
+        for w in per_query:
+            if w is not None and not self._is_namespace_form(w):
+                self._check_where(w)
+        return per_query
+
+    @classmethod
+    def _is_namespace_form(cls, where) -> bool:
+        try:
+            cls._where_namespace(where)
+            return True
+        except ValueError:
+            return False
+
+    def _search_by_filter(self, q: np.ndarray, k: int, per_query: list):
+        """One engine call per group of queries with the same filter: None -> search, a namespace form -> search_scoped, each distinct
+        general filter -> search_masked under its compiled mask (no call when nobody matches: that query's hits stay empty)."""
+        B = q.shape[0]
+        dist = np.full((B, k), np.inf, dtype=np.float32)
+        rows = np.full((B, k), -1, dtype=np.int64)
+        plain = [b for b, w in enumerate(per_query) if w is None]
+        scoped = [b for b, w in enumerate(per_query) if w is not None and self._is_namespace_form(w)]
+        if plain:
+            dist[plain], rows[plain] = self._engine.search(q[plain], k)
+        if scoped:
+            if not hasattr(self._engine, "search_scoped"):
+                raise NotImplementedError(f"{type(self._engine).__name__} has no scoped search: `where` needs an engine with search_scoped")
+            labels = np.array([self._scope_of_namespace.get(self._where_namespace(per_query[b]), -1) for b in scoped], dtype=np.int64)
+            known = [b for b, s in zip(scoped, labels.tolist()) if s >= 0]
+            if known:
+                dist[known], rows[known] = self._engine.search_scoped(q[known], labels[labels >= 0].astype(np.uint32), k)
+        groups: dict[str, list[int]] = {}
+        for b, w in enumerate(per_query):
+            if w is not None and not self._is_namespace_form(w):
+                groups.setdefault(json.dumps(w, sort_keys=True, ensure_ascii=False), []).append(b)
+        for members in groups.values():
+            mask = self._where_mask(per_query[members[0]])
+            if mask.any():
+                dist[members], rows[members] = self._engine.search_masked(q[members], mask, k)
+        return dist, rows
 
     # ------------------------------------------------------------------ persistence
     def _write_generation(self, directory: str) -> None:
@@ -396,6 +578,7 @@ class Collection:
         self.metadata = dict(manifest.get("metadata") or {})
         self._ids, self._metadatas, self._documents = ids, metadatas, documents
         self._slot_of = {doc_id: i for i, doc_id in enumerate(ids)}
+        self._forget_where_index()
         # namespaces -> scope labels, from the stored metadata (the on-disk format knows nothing of scopes)
         self._scope_of_namespace = {}
         scopes = np.array([self._scope_for(md) for md in metadatas], dtype=np.uint32)

@@ -35,7 +35,8 @@ class DeviceKnnIndex:
 
     Engine protocol consumed by knn_client.Collection:
         count() / upsert(slots, vecs) / search(queries, k) -> (dist, rows) as numpy;
-        optionally set_scopes / search_scoped (`where=`) and delete / live_count / compact (`Collection.delete`).
+        optionally set_scopes / search_scoped (`where=` by namespace), search_masked (any other `where=`) and delete / live_count /
+        compact (`Collection.delete`).
     """
 
     def __init__(self, dim: int, dtype: str = "f32", device: str = "cuda:0"):
@@ -230,6 +231,55 @@ class DeviceKnnIndex:
             "codd_knn_search_scoped",
         )
         return keys
+
+    # ------------------------------------------------------------------ masks
+    def _allow_words(self, allow) -> np.ndarray:
+        """The allow mask as packed uint32 words: a bool array of length count() (bit r & 31 of word r >> 5 = row slot r), or the
+        words themselves (uint32, ceil(count() / 32) of them)."""
+        a = np.asarray(allow)
+        if a.ndim != 1:
+            raise ValueError(f"expected a 1-d allow mask, got shape {a.shape}")
+        if a.dtype == np.bool_:
+            n = self.count()
+            if a.shape[0] != n:
+                raise ValueError(f"expected a bool mask of length count() = {n}, got {a.shape[0]}")
+            packed = np.packbits(a, bitorder="little")
+            words = np.zeros((n + 31) // 32 * 4, dtype=np.uint8)
+            words[: packed.shape[0]] = packed
+            return words.view("<u4")
+        if a.dtype != np.uint32:
+            raise ValueError(f"allow must be a bool array or packed uint32 words, got dtype {a.dtype}")
+        return np.ascontiguousarray(a)
+
+    def _search_masked(self, queries, allow, k: int, row_base: int, want_keys: bool):
+        torch = _torch()
+        q = self._queries_tensor(queries)
+        B = q.shape[0]
+        words = self._allow_words(allow)
+        keys = torch.empty((B, k), dtype=torch.int64, device=self.device) if want_keys else None
+        dist = None if want_keys else torch.empty((B, k), dtype=torch.float32, device=self.device)
+        rows = None if want_keys else torch.empty((B, k), dtype=torch.int64, device=self.device)
+        native.check(
+            self._lib.codd_knn_search_masked(self._h, q.data_ptr(), B, int(k), words.ctypes.data, words.shape[0], int(row_base),
+                                             keys.data_ptr() if want_keys else None, None if want_keys else dist.data_ptr(),
+                                             None if want_keys else rows.data_ptr(), self._stream()),
+            "codd_knn_search_masked",
+        )
+        return keys, dist, rows
+
+    def search_masked_tensors(self, queries, allow, k: int):
+        """search_tensors among the rows `allow` names (one mask for the whole batch) that are not deleted."""
+        _, dist, rows = self._search_masked(queries, allow, k, 0, False)
+        return dist, rows
+
+    def search_masked(self, queries, allow, k: int):
+        """numpy in, numpy out (the façade's path for a general `where=`)."""
+        dist, rows = self.search_masked_tensors(queries, allow, k)
+        return dist.cpu().numpy(), rows.cpu().numpy()
+
+    def search_keys_masked(self, queries, allow, k: int, row_base: int = 0):
+        """search_keys among the rows `allow` names."""
+        return self._search_masked(queries, allow, k, row_base, True)[0]
 
     def merge_keys(self, keys, k: int):
         """Top-k of [B,m] packed keys -> (keys [B,k], dist [B,k], rows [B,k]) on device."""

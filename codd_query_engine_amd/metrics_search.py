@@ -41,14 +41,21 @@ class MetricsSearchClient:
     def __init__(self, semantic_metadata_store: MetricsSemanticMetadataStore):
         self.semantic_metadata_store = semantic_metadata_store
 
-    def search_relevant_metrics(self, query: str, limit: int = 5, namespace=None) -> list[SearchResult]:
-        """`namespace` (extension): only that namespace's metrics; None is the reference's call."""
-        if namespace is None:
+    def search_relevant_metrics(self, query: str, limit: int = 5, namespace=None, where=None) -> list[SearchResult]:
+        """`namespace` (extension): only that namespace's metrics; `where` (extension): a metadata filter such as
+        {"golden_signal_type": "latency"}; both None is the reference's call."""
+        if namespace is None and where is None:
             return project_search_results(self.semantic_metadata_store.search_metadata(query, n_results=limit))
-        return project_search_results(self.semantic_metadata_store.search_metadata(query, n_results=limit, namespace=namespace))
+        if where is None:
+            return project_search_results(self.semantic_metadata_store.search_metadata(query, n_results=limit, namespace=namespace))
+        return project_search_results(self.semantic_metadata_store.search_metadata(query, n_results=limit, namespace=namespace, where=where))
 
-    def search_relevant_metrics_batch(self, queries: list[str], limit: int = 5, namespace=None) -> list[list[SearchResult]]:
-        """Extension: one engine call for many queries (B up to 1024); `namespace`: one string, or a list with a string / None per query."""
-        if namespace is None:
+    def search_relevant_metrics_batch(self, queries: list[str], limit: int = 5, namespace=None, where=None) -> list[list[SearchResult]]:
+        """Extension: one engine call for many queries (B up to 1024); `namespace`: one string, or a list with a string / None per query;
+        `where`: one metadata filter for every query."""
+        if namespace is None and where is None:
             return [project_search_results(r) for r in self.semantic_metadata_store.search_metadata_batch(queries, n_results=limit)]
-        return [project_search_results(r) for r in self.semantic_metadata_store.search_metadata_batch(queries, n_results=limit, namespace=namespace)]
+        if where is None:
+            return [project_search_results(r) for r in self.semantic_metadata_store.search_metadata_batch(queries, n_results=limit, namespace=namespace)]
+        return [project_search_results(r)
+                for r in self.semantic_metadata_store.search_metadata_batch(queries, n_results=limit, namespace=namespace, where=where)]

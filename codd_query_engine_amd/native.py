@@ -47,6 +47,7 @@ ABI = [
     ("codd_knn_ivf_search", ctypes.c_int, [_c_idx, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     ("codd_knn_set_scopes_host", ctypes.c_int, [_c_idx, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]),
     ("codd_knn_search_scoped", ctypes.c_int, [_c_idx, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    ("codd_knn_search_masked", ctypes.c_int, [_c_idx, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     ("codd_knn_delete_host", ctypes.c_int, [_c_idx, ctypes.c_void_p, ctypes.c_int64]),
     ("codd_knn_live_count", ctypes.c_int, [_c_idx, _i64p]),
     ("codd_knn_compact", ctypes.c_int, [_c_idx, _i64p]),

@@ -251,33 +251,41 @@ class MetricsSemanticMetadataStore:
             shaped.append({"metric_name": name, "similarity_score": 1.0 - distance, **stored})
         return shaped
 
-    def search_metadata(self, query: str, n_results: int = 10, namespace: Optional[str] = None) -> list[dict]:
+    @staticmethod
+    def _where_of(namespace: Optional[str], where: Optional[dict]):
+        """The collection's `where` of one query: the namespace form, the caller's filter, or both under $and."""
+        if where is None:
+            return None if namespace is None else {"namespace": namespace}
+        return where if namespace is None else {"$and": [{"namespace": namespace}, where]}
+
+    def search_metadata(self, query: str, n_results: int = 10, namespace: Optional[str] = None, where: Optional[dict] = None) -> list[dict]:
         """Metrics most similar to `query`, best first (reference store.py:266-341).
 
         Empty query -> []; query longer than 1000 chars after sanitising or n_results < 1 ->
         ValidationError; n_results above 100 is capped with a warning.  `namespace` (extension) keeps the
-        search inside one namespace: the exact best matches among its metrics.
+        search inside one namespace: the exact best matches among its metrics.  `where` (extension): a metadata
+        filter in ChromaDB's grammar over the stored keys, e.g. {"golden_signal_type": "latency"}; with `namespace` both hold.
         """
         cleaned = self._clean_query(query)
         if cleaned is None:
             logger.debug("Empty query received, returning empty results")
             return []
         n_results = self._clamp_n_results(n_results)
-        if namespace is None:
+        if namespace is None and where is None:
             results = self.collection.query(query_texts=[cleaned], n_results=n_results)
         else:
-            results = self.collection.query(query_texts=[cleaned], n_results=n_results, where={"namespace": namespace})
+            results = self.collection.query(query_texts=[cleaned], n_results=n_results, where=self._where_of(namespace, where))
         if not results or not results.get("ids") or not results["ids"][0]:
             return []
         return self._shape_hits(
             results["ids"][0], results.get("metadatas", [[]])[0], results.get("distances", [[]])[0]
         )
 
-    def search_metadata_batch(self, queries: list[str], n_results: int = 10, namespace=None) -> list[list[dict]]:
+    def search_metadata_batch(self, queries: list[str], n_results: int = 10, namespace=None, where: Optional[dict] = None) -> list[list[dict]]:
         """Extension (the reference only ever sends one query): many queries, ONE engine call.
 
         Same per-query rules as search_metadata; an empty query yields [] at its position.  `namespace`: one
-        string for every query, or a list with a string / None per query.
+        string for every query, or a list with a string / None per query.  `where`: one metadata filter for every query.
         """
         if isinstance(namespace, (list, tuple)) and len(namespace) != len(queries):
             raise ValidationError(f"namespace has {len(namespace)} entries for {len(queries)} queries")
@@ -287,12 +295,12 @@ class MetricsSemanticMetadataStore:
         out: list[list[dict]] = [[] for _ in queries]
         if not live:
             return out
-        if namespace is None:
+        if namespace is None and where is None:
             results = self.collection.query(query_texts=[cleaned[i] for i in live], n_results=n_results)
         else:
             per_query = [namespace[i] for i in live] if isinstance(namespace, (list, tuple)) else [namespace] * len(live)
-            where = [None if ns is None else {"namespace": ns} for ns in per_query]
-            results = self.collection.query(query_texts=[cleaned[i] for i in live], n_results=n_results, where=where)
+            wheres = [self._where_of(ns, where) for ns in per_query]
+            results = self.collection.query(query_texts=[cleaned[i] for i in live], n_results=n_results, where=wheres)
         if not results or not results.get("ids"):
             return out
         all_md = results.get("metadatas") or []

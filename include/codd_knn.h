@@ -20,7 +20,7 @@
  *   - `stream` is a hipStream_t passed as void* (NULL = the null stream).  Calls
  *     are asynchronous with respect to the host unless stated otherwise.
  *   - thread-safety: the search entry points (codd_knn_search, _search_keys, _search_scoped,
- *     _ivf_search, _approx_scores) may be called from several host threads and on
+ *     _search_masked, _ivf_search, _approx_scores) may be called from several host threads and on
  *     several streams of one index: the index keeps one workspace per stream (up to
  *     4; a fifth stream takes over the least recently used one, ordered behind its
  *     previous owner on the device) and serialises only the enqueueing.  Searches on
@@ -205,6 +205,33 @@ int codd_knn_search_scoped(codd_knn_index* index, const float* dev_queries, cons
                            uint32_t row_base, uint64_t* dev_keys, float* dev_dist, int64_t* dev_rows, void* stream);
 
 /*
+ * Replaces: the general `where` of collection.query(query_texts=..., n_results=..., where=...) — ChromaDB's metadata grammar
+ *           ($eq, $ne, $gt, $gte, $lt, $lte, $in, $nin, $and, $or).  Metadata stays on the host: the façade evaluates the filter to
+ *           a set of row slots and hands it over as a bitmap, bit (r & 31) of word (r >> 5) set = row slot r may be returned.
+ *           One mask per call, shared by the B queries.
+ * search_masked: like codd_knn_search / _search_keys, restricted to the rows that are allowed AND live: per query the exact cosine
+ *           top-k among them — the same scores, tie rule and padding, min(k, m) hits where m is the number of such rows.  nwords
+ *           must equal ceil(count / 32), else EINVAL; bits at or above count in the last word are ignored.  m == 0 gives an
+ *           all-empty result (keys 0, rows -1, distances +inf) and launches no scan; an all-ones mask returns the bits of
+ *           codd_knn_search.  Any of dev_keys / dev_dist / dev_rows may be NULL.
+ *           host_allow_bits is host memory and is consumed before the call returns: the words are copied into a pinned staging
+ *           buffer of the stream's workspace (and counted there against the index's own mirror of the tombstones, which gives m
+ *           without reading anything back), from where one asynchronous copy on `stream` takes them to the device.  The caller
+ *           may reuse or free its words at once.  A second masked search on the same stream waits on the host until the first
+ *           one's copy has left the staging buffer — not for its kernels.  Those stay asynchronous on `stream`, ordered against
+ *           upserts like the other search entry points, and masked searches on different streams overlap.
+ *           Two routes, chosen from m, B and the index size; the choice affects time only, never the answer:
+ *           the LIST route expands the mask into the ascending list of visible row slots and walks it as a scoped search walks
+ *           a scope's list (m rows per group of up to four queries: small m); the DENSE route runs the ordinary dispatch of
+ *           codd_knn_search with ~allow | dead in the place of the tombstone bits (large m: the MFMA filters score every row,
+ *           the threshold anchors and the exact re-scoring drop the rows the mask denies).  A dense masked pass neither feeds
+ *           the survivor watch of "shadow8" nor starts or uses up a cooldown.  An index stored with normalize = 0 takes no
+ *           filter leg here either.
+ */
+int codd_knn_search_masked(codd_knn_index* index, const float* dev_queries, int B, int k, const uint32_t* host_allow_bits,
+                           int64_t nwords, uint32_t row_base, uint64_t* dev_keys, float* dev_dist, int64_t* dev_rows, void* stream);
+
+/*
  * Replaces: collection.delete(ids=..., where=...) — the row half (ChromaDB's own call; the reference never deletes).
  * delete_host: tombstones n row slots.  A slot outside [0, count) gives EINVAL and changes nothing; a slot that is dead already,
  *           or listed twice, is a no-op.  Exclusive like upsert, synchronous.  From then on NO search entry point returns the row:
@@ -265,6 +292,9 @@ int codd_knn_compact(codd_knn_index* index, int64_t* new_count);
  *            csrc/filter_i8.h's tile program on fp16 operands; 0: the first-generation kernel), "ivf_share" (1: codd_knn_ivf_search scans a probed list once for all queries of the
  *            batch that probe it, from 1,024 (query, list) pairs on; 0: once per pair),
  *            "compact_chunk_rows" (0: codd_knn_compact moves as many source rows per step as 64 MiB hold; N: N rows — tests),
+ *            "mask_route" (0: codd_knn_search_masked chooses its route by the rule of DESIGN.md §15; 1: always the list route; 2: always the
+ *            dense route), "mask_list_pct" (100: the weight of the dense side in that rule's cost comparison, in percent — above 100 more
+ *            searches take the list route, 0 none that the rule decides by cost),
  *            "debug_fail_shadow_alloc" (tests: the next N allocations of the 2-byte shadow fail);
  *            "profile" = N keeps N (start, stop) HIP-event pairs, one per heavy-kernel launch,
  *            recorded on the launch stream (0 = off; resets the log)
@@ -272,7 +302,10 @@ int codd_knn_compact(codd_knn_index* index, int64_t* new_count);
  *            last exact scan), "last_finalize_parts" (workgroups per query of the last filter pass's finalize),
  *            "ivf_shared_searches" (IVF searches that scanned each probed list once for all its queries), "scoped_searches",
  *            "scope_builds" (times the scope lists were rebuilt), "scopes" (highest scope label ever set), "dead_rows" (tombstones below count),
- *            "delete_calls", "compactions" (codd_knn_compact calls that moved rows), "filter_passes",
+ *            "delete_calls", "compactions" (codd_knn_compact calls that moved rows), "masked_searches", "mask_list_searches",
+ *            "mask_dense_searches" (masked searches by route), "last_mask_rows" (allowed live rows of the last masked search),
+ *            "mask_filter_hits", "mask_filter_survivors", "mask_fallback_queries" (the device counters of the dense masked passes, kept
+ *            apart from the three below), "filter_passes",
  *            "fallback_queries", "filter_hits", "filter_survivors", "capacity_rows",
  *            "device_bytes", "num_cus", "workspaces" (stream workspaces in use), "shadow8_builds", "shadow8_passes", "i8v2_passes",
  *            "shadow16_builds" (the bf16 shadow is built lazily, by the first search that needs it), "all_normalized",
