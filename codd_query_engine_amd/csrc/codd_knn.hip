@@ -32,6 +32,7 @@
 #ifndef CODD_EXPERIMENTS
 #define CODD_EXPERIMENTS 0  // 1 (build_variant only): the diagnostic switches that can return wrong results exist
 #endif
+#include "doc_match.h"
 #include "exact_score.h"
 #include "filter_gemm.h"
 #include "filter_i8.h"
@@ -1475,6 +1476,9 @@ struct WorkBufs {
     uint32_t* mask_deny = nullptr;   int64_t mask_deny_cap = 0;    // dense route: [ceil(capacity / 32)] ~allow | dead, ones past the mask
     unsigned* mask_prefix = nullptr; int64_t mask_prefix_cap = 0;  // list route: [words] prefixes, [blocks] totals, [blocks + 1] bases
     uint32_t* mask_list = nullptr;   int64_t mask_list_cap = 0;    // list route: [m] visible row slots, ascending
+    // codd_knn_search_masked_dev: the visible rows of a device mask, counted on the device and read back through pinned memory
+    unsigned long long* mask_m_dev = nullptr;
+    unsigned long long* mask_m_host = nullptr;
 };
 constexpr int kMaxWork = 4;
 struct WorkSlot {
@@ -1618,6 +1622,16 @@ struct codd_knn_index : WorkBufs {
     int mask_list_pct = 100;   // "mask_list_pct": the list route's side of the cost comparison, in percent (100 = the derived rule)
     unsigned long long* mask_dstats = nullptr;  // the device counters of the dense masked passes: kept apart from dstats, which the filter watch reads
     int64_t stat_masked_searches = 0, stat_mask_list = 0, stat_mask_dense = 0, stat_last_mask_rows = 0;
+    int64_t stat_masked_dev = 0;   // ... those of them whose mask was on the device already (codd_knn_search_masked_dev)
+
+    // document snapshot (optional, derived data like the shadows): every row slot's document in one byte arena, a 0x00
+    // behind each, zeros to the end of the allocation (csrc/doc_match.h), and the [count + 1] arena offsets.  Valid while the row
+    // epoch and the count are what they were when codd_knn_set_documents_host took it.
+    uint8_t* doc_arena = nullptr;
+    int64_t* doc_offsets = nullptr;
+    int64_t doc_bytes = 0;             // the arena: the documents' bytes plus one separator each
+    int64_t doc_count = -1, doc_epoch = -1;
+    int64_t stat_doc_matches = 0;
 
     // tombstones: one bit per row slot, set = deleted.  Null until the first codd_knn_delete_host — the kernels
     // take a null pointer as "nothing was ever deleted" and load nothing.  The host keeps a mirror: the write paths refuse dead
@@ -2889,7 +2903,7 @@ int codd_knn_destroy(codd_knn_index* ix) {
     DeviceGuard guard(ix->device);
     (void)hipDeviceSynchronize();
     void* bufs[] = {ix->rows, ix->shadow, ix->dstats, ix->rows_ivf, ix->ivf_ids, ix->ivf_offsets, ix->shadow8, ix->rscale, ix->bmeta, ix->eps_r_bits,
-                    ix->scope_of, ix->scope_perm, ix->scope_offsets, ix->dead_bits, ix->mask_dstats};
+                    ix->scope_of, ix->scope_perm, ix->scope_offsets, ix->dead_bits, ix->mask_dstats, ix->doc_arena, ix->doc_offsets};
     if (ix->scope_ready) (void)hipEventDestroy(ix->scope_ready);
     if (ix->shadow8_ready) (void)hipEventDestroy(ix->shadow8_ready);
     if (ix->shadow_ready) (void)hipEventDestroy(ix->shadow_ready);
@@ -2906,10 +2920,11 @@ int codd_knn_destroy(codd_knn_index* ix) {
     for (WorkSlot& w : ix->slots) {
         void* wb[] = {w.bufs.qn, w.bufs.partial, w.bufs.keys_tmp, w.bufs.qfrag, w.bufs.thr, w.bufs.bucket_max, w.bufs.hits, w.bufs.ctl,
                       w.bufs.fb_partial, w.bufs.probe_keys, w.bufs.ivf_partial, w.bufs.ivf_group, w.bufs.qfrag8, w.bufs.qmeta, w.bufs.sb_cand,
-                      w.bufs.scope_group, w.bufs.mask_allow, w.bufs.mask_deny, w.bufs.mask_prefix, w.bufs.mask_list};
+                      w.bufs.scope_group, w.bufs.mask_allow, w.bufs.mask_deny, w.bufs.mask_prefix, w.bufs.mask_list, w.bufs.mask_m_dev};
         for (void* b : wb)
             if (b) (void)hipFree(b);
         if (w.bufs.mask_host) (void)hipHostFree(w.bufs.mask_host);
+        if (w.bufs.mask_m_host) (void)hipHostFree(w.bufs.mask_m_host);
         if (w.bufs.mask_uploaded) (void)hipEventDestroy(w.bufs.mask_uploaded);
         if (w.handover) (void)hipEventDestroy(w.handover);
     }
@@ -3457,61 +3472,22 @@ bool mask_takes_dense(const codd_knn_index* ix, int B, int k, int64_t m) {
     return list_bytes * 100.0 > dense_bytes * (double)ix->mask_list_pct;
 }
 
-}  // namespace
-
-extern "C" {
-
-int codd_knn_search_masked(codd_knn_index* ix, const float* dev_queries, int B, int k, const uint32_t* host_allow_bits, int64_t nwords,
-                           uint32_t row_base, uint64_t* dev_keys, float* dev_dist, int64_t* dev_rows, void* stream) {
-    if (!ix || !dev_queries) return fail(CODD_KNN_EINVAL, "null index or queries%s");
-    if (B < 1 || B > CODD_KNN_MAX_BATCH) return fail(CODD_KNN_EINVAL, "B out of range [1,1024]%s");
-    if (k < 1 || k > CODD_KNN_MAX_K) return fail(CODD_KNN_EINVAL, "k out of range [1,128]%s");
-    if ((int64_t)row_base + ix->count >= 0xffffffffll) return fail(CODD_KNN_EINVAL, "global row ids must fit 32 bits%s");
-    DeviceGuard guard(ix->device);
-    hipStream_t st = (hipStream_t)stream;
-    WorkScope work(ix, st);
-    const int64_t n = ix->count;
-    if (nwords != (n + 31) / 32) return fail(CODD_KNN_EINVAL, "search_masked: nwords must be ceil(count / 32)%s");
-    if (nwords > 0 && !host_allow_bits) return fail(CODD_KNN_EINVAL, "null allow bits%s");
-    ix->stat_masked_searches++;
+// nothing visible (or nothing stored): all-empty result, no scan
+int masked_empty_result(codd_knn_index* ix, int B, int k, uint64_t* dev_keys, float* dev_dist, int64_t* dev_rows, hipStream_t st) {
     int rc;
-    if ((rc = wait_rows(ix, st)) != 0) return rc;
-    // The host words: clipped to [0, count) into the workspace's pinned staging buffer, counted against the tombstone mirror on
-    // the way (m: the rows this call may see, exact, nothing read back), then one asynchronous copy from the staging buffer.  The
-    // caller's words are not touched again; the staging buffer's previous copy (the stream's last masked search) is waited for first.
-    int64_t m = 0;
-    if (nwords > 0) {
-        if (ix->mask_upload_pending) HIP_TRY(hipEventSynchronize(ix->mask_uploaded));
-        ix->mask_upload_pending = false;
-        if (nwords > ix->mask_host_cap) {
-            if (ix->mask_host) (void)hipHostFree(ix->mask_host);
-            ix->mask_host = nullptr; ix->mask_host_cap = 0;
-            const int64_t cap = nwords + nwords / 2 + 64;
-            HIP_TRY(hipHostMalloc((void**)&ix->mask_host, (size_t)cap * sizeof(uint32_t), hipHostMallocDefault));
-            ix->mask_host_cap = cap;
-        }
-        if (!ix->mask_uploaded) HIP_TRY(hipEventCreateWithFlags(&ix->mask_uploaded, hipEventDisableTiming));
-        const bool any_dead = ix->dead_count > 0;
-        for (int64_t w = 0; w < nwords; ++w) {
-            const int64_t left = n - w * 32;
-            const uint32_t a = host_allow_bits[w] & (left >= 32 ? 0xffffffffu : (1u << (uint32_t)left) - 1u);
-            ix->mask_host[w] = a;
-            m += __builtin_popcount(any_dead && (size_t)w < ix->dead_host.size() ? a & ~ix->dead_host[(size_t)w] : a);
-        }
-    }
-    ix->stat_last_mask_rows = m;
-    if (m == 0) {  // nothing visible (or nothing stored): all-empty result, no scan
-        if ((rc = ensure_buf(&ix->keys_tmp, &ix->keys_tmp_cap, (int64_t)B * k)) != 0) return rc;
-        u64* keys_dst = dev_keys ? (u64*)dev_keys : ix->keys_tmp;
-        HIP_TRY(hipMemsetAsync(keys_dst, 0, (size_t)B * k * sizeof(u64), st));
-        if (!dev_dist && !dev_rows) return CODD_KNN_OK;
-        return launch_merge(keys_dst, B, k, k, k, nullptr, dev_dist, dev_rows, st);
-    }
-    if ((rc = ensure_buf(&ix->mask_allow, &ix->mask_allow_cap, nwords)) != 0) return rc;
-    HIP_TRY(hipMemcpyAsync(ix->mask_allow, ix->mask_host, (size_t)nwords * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipEventRecord(ix->mask_uploaded, st));
-    ix->mask_upload_pending = true;
+    if ((rc = ensure_buf(&ix->keys_tmp, &ix->keys_tmp_cap, (int64_t)B * k)) != 0) return rc;
+    u64* keys_dst = dev_keys ? (u64*)dev_keys : ix->keys_tmp;
+    HIP_TRY(hipMemsetAsync(keys_dst, 0, (size_t)B * k * sizeof(u64), st));
+    if (!dev_dist && !dev_rows) return CODD_KNN_OK;
+    return launch_merge(keys_dst, B, k, k, k, nullptr, dev_dist, dev_rows, st);
+}
 
+// The body both masked entry points run: the clipped allow words are in ix->mask_allow (written on `st`, or enqueued there) and m > 0,
+// the number of allowed live rows, is known on the host.  Chooses the route and enqueues it.
+int masked_search_body(codd_knn_index* ix, const float* dev_queries, int B, int k, int64_t nwords, int64_t m, uint32_t row_base,
+                       uint64_t* dev_keys, float* dev_dist, int64_t* dev_rows, hipStream_t st) {
+    const int64_t n = ix->count;
+    int rc;
     if (mask_takes_dense(ix, B, k, m)) {
         ix->stat_mask_dense++;
         const int64_t total_words = (ix->capacity + 31) / 32;   // (as long as the tombstone bits: every kernel that reads those reads these)
@@ -3557,6 +3533,171 @@ int codd_knn_search_masked(codd_knn_index* ix, const float* dev_queries, int B, 
     if (rc != 0) return rc;
     HIP_TRY(hipGetLastError());
     return launch_merge(ix->partial, B, pm, pm, k, (u64*)dev_keys, dev_dist, dev_rows, st);
+}
+
+bool docs_valid(const codd_knn_index* ix) { return ix->doc_arena && ix->doc_epoch == ix->epoch && ix->doc_count == ix->count; }
+
+}  // namespace
+
+extern "C" {
+
+int codd_knn_search_masked(codd_knn_index* ix, const float* dev_queries, int B, int k, const uint32_t* host_allow_bits, int64_t nwords,
+                           uint32_t row_base, uint64_t* dev_keys, float* dev_dist, int64_t* dev_rows, void* stream) {
+    if (!ix || !dev_queries) return fail(CODD_KNN_EINVAL, "null index or queries%s");
+    if (B < 1 || B > CODD_KNN_MAX_BATCH) return fail(CODD_KNN_EINVAL, "B out of range [1,1024]%s");
+    if (k < 1 || k > CODD_KNN_MAX_K) return fail(CODD_KNN_EINVAL, "k out of range [1,128]%s");
+    if ((int64_t)row_base + ix->count >= 0xffffffffll) return fail(CODD_KNN_EINVAL, "global row ids must fit 32 bits%s");
+    DeviceGuard guard(ix->device);
+    hipStream_t st = (hipStream_t)stream;
+    WorkScope work(ix, st);
+    const int64_t n = ix->count;
+    if (nwords != (n + 31) / 32) return fail(CODD_KNN_EINVAL, "search_masked: nwords must be ceil(count / 32)%s");
+    if (nwords > 0 && !host_allow_bits) return fail(CODD_KNN_EINVAL, "null allow bits%s");
+    ix->stat_masked_searches++;
+    int rc;
+    if ((rc = wait_rows(ix, st)) != 0) return rc;
+    // The host words: clipped to [0, count) into the workspace's pinned staging buffer, counted against the tombstone mirror on
+    // the way (m: the rows this call may see, exact, nothing read back), then one asynchronous copy from the staging buffer.  The
+    // caller's words are not touched again; the staging buffer's previous copy (the stream's last masked search) is waited for first.
+    int64_t m = 0;
+    if (nwords > 0) {
+        if (ix->mask_upload_pending) HIP_TRY(hipEventSynchronize(ix->mask_uploaded));
+        ix->mask_upload_pending = false;
+        if (nwords > ix->mask_host_cap) {
+            if (ix->mask_host) (void)hipHostFree(ix->mask_host);
+            ix->mask_host = nullptr; ix->mask_host_cap = 0;
+            const int64_t cap = nwords + nwords / 2 + 64;
+            HIP_TRY(hipHostMalloc((void**)&ix->mask_host, (size_t)cap * sizeof(uint32_t), hipHostMallocDefault));
+            ix->mask_host_cap = cap;
+        }
+        if (!ix->mask_uploaded) HIP_TRY(hipEventCreateWithFlags(&ix->mask_uploaded, hipEventDisableTiming));
+        const bool any_dead = ix->dead_count > 0;
+        for (int64_t w = 0; w < nwords; ++w) {
+            const int64_t left = n - w * 32;
+            const uint32_t a = host_allow_bits[w] & (left >= 32 ? 0xffffffffu : (1u << (uint32_t)left) - 1u);
+            ix->mask_host[w] = a;
+            m += __builtin_popcount(any_dead && (size_t)w < ix->dead_host.size() ? a & ~ix->dead_host[(size_t)w] : a);
+        }
+    }
+    ix->stat_last_mask_rows = m;
+    if (m == 0) return masked_empty_result(ix, B, k, dev_keys, dev_dist, dev_rows, st);
+    if ((rc = ensure_buf(&ix->mask_allow, &ix->mask_allow_cap, nwords)) != 0) return rc;
+    HIP_TRY(hipMemcpyAsync(ix->mask_allow, ix->mask_host, (size_t)nwords * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(ix->mask_uploaded, st));
+    ix->mask_upload_pending = true;
+    return masked_search_body(ix, dev_queries, B, k, nwords, m, row_base, dev_keys, dev_dist, dev_rows, st);
+}
+
+int codd_knn_search_masked_dev(codd_knn_index* ix, const float* dev_queries, int B, int k, const uint32_t* dev_allow_bits, int64_t nwords,
+                               uint32_t row_base, uint64_t* dev_keys, float* dev_dist, int64_t* dev_rows, void* stream) {
+    if (!ix || !dev_queries) return fail(CODD_KNN_EINVAL, "null index or queries%s");
+    if (B < 1 || B > CODD_KNN_MAX_BATCH) return fail(CODD_KNN_EINVAL, "B out of range [1,1024]%s");
+    if (k < 1 || k > CODD_KNN_MAX_K) return fail(CODD_KNN_EINVAL, "k out of range [1,128]%s");
+    if ((int64_t)row_base + ix->count >= 0xffffffffll) return fail(CODD_KNN_EINVAL, "global row ids must fit 32 bits%s");
+    DeviceGuard guard(ix->device);
+    hipStream_t st = (hipStream_t)stream;
+    WorkScope work(ix, st);
+    const int64_t n = ix->count;
+    if (nwords != (n + 31) / 32) return fail(CODD_KNN_EINVAL, "search_masked_dev: nwords must be ceil(count / 32)%s");
+    if (nwords > 0 && !dev_allow_bits) return fail(CODD_KNN_EINVAL, "null allow bits%s");
+    ix->stat_masked_searches++;
+    ix->stat_masked_dev++;
+    int rc;
+    if ((rc = wait_rows(ix, st)) != 0) return rc;
+    // The device words: clipped to [0, count) into the workspace's allow buffer and counted against the tombstone bits by one small
+    // kernel behind whatever wrote them on `st`; the count comes back through pinned memory — the one host synchronisation of the call
+    // (m chooses the route and sizes the list).
+    int64_t m = 0;
+    if (nwords > 0) {
+        if (!ix->mask_m_dev) HIP_TRY(hipMalloc((void**)&ix->mask_m_dev, sizeof(unsigned long long)));
+        if (!ix->mask_m_host) HIP_TRY(hipHostMalloc((void**)&ix->mask_m_host, sizeof(unsigned long long), hipHostMallocDefault));
+        if ((rc = ensure_buf(&ix->mask_allow, &ix->mask_allow_cap, nwords)) != 0) return rc;
+        HIP_TRY(hipMemsetAsync(ix->mask_m_dev, 0, sizeof(unsigned long long), st));
+        hipLaunchKernelGGL(mask_clip_count_kernel, dim3((unsigned)((nwords + 255) / 256)), dim3(256), 0, st, dev_allow_bits, ix->dead_bits, n, nwords,
+                           ix->mask_allow, ix->mask_m_dev);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(ix->mask_m_host, ix->mask_m_dev, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        m = (int64_t)*ix->mask_m_host;
+    }
+    ix->stat_last_mask_rows = m;
+    if (m == 0) return masked_empty_result(ix, B, k, dev_keys, dev_dist, dev_rows, st);
+    return masked_search_body(ix, dev_queries, B, k, nwords, m, row_base, dev_keys, dev_dist, dev_rows, st);
+}
+
+int codd_knn_set_documents_host(codd_knn_index* ix, const uint8_t* host_bytes, const int64_t* host_offsets, int64_t n) {
+    if (!ix || !host_offsets || n < 0) return fail(CODD_KNN_EINVAL, "set_documents: null index or offsets%s");
+    if (n != ix->count) return fail(CODD_KNN_EINVAL, "set_documents: n must equal the count (one document per row slot)%s");
+    if (host_offsets[0] != 0) return fail(CODD_KNN_EINVAL, "set_documents: offsets must start at 0%s");
+    for (int64_t r = 0; r < n; ++r)
+        if (host_offsets[r + 1] < host_offsets[r]) return fail(CODD_KNN_EINVAL, "set_documents: offsets must be non-decreasing%s");
+    const int64_t total = host_offsets[n];
+    if (total > 0 && !host_bytes) return fail(CODD_KNN_EINVAL, "set_documents: null bytes%s");
+    if (total > 0 && memchr(host_bytes, 0, (size_t)total)) return fail(CODD_KNN_EINVAL, "set_documents: a document holds a 0x00 byte%s");
+    DeviceGuard guard(ix->device);
+    HIP_TRY(hipDeviceSynchronize());
+    // the arena on the host first: document r at host_offsets[r] + r, its separator behind it, zeros to the end of the allocation
+    const int64_t bytes = total + n, alloc = doc_arena_alloc_bytes(bytes);
+    std::vector<uint8_t> arena;
+    std::vector<int64_t> offsets;
+    try {
+        arena.assign((size_t)alloc, (uint8_t)0);
+        offsets.resize((size_t)n + 1);
+    } catch (const std::bad_alloc&) {
+        return fail(CODD_KNN_ENOMEM, "host allocation failed%s");
+    }
+    for (int64_t r = 0; r < n; ++r) {
+        offsets[(size_t)r] = host_offsets[r] + r;
+        const int64_t len = host_offsets[r + 1] - host_offsets[r];
+        if (len > 0) memcpy(arena.data() + offsets[(size_t)r], host_bytes + host_offsets[r], (size_t)len);
+    }
+    offsets[(size_t)n] = bytes;
+    uint8_t* dev_arena = nullptr;
+    int64_t* dev_offsets = nullptr;
+    hipError_t e = hipMalloc((void**)&dev_arena, (size_t)alloc);
+    if (e == hipSuccess) e = hipMalloc((void**)&dev_offsets, ((size_t)n + 1) * sizeof(int64_t));
+    if (e == hipSuccess) e = hipMemcpy(dev_arena, arena.data(), (size_t)alloc, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dev_offsets, offsets.data(), ((size_t)n + 1) * sizeof(int64_t), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {   // (the previous snapshot stays as it was)
+        if (dev_arena) (void)hipFree(dev_arena);
+        if (dev_offsets) (void)hipFree(dev_offsets);
+        return fail(e == hipErrorOutOfMemory ? CODD_KNN_ENOMEM : CODD_KNN_EDEVICE, "set_documents: upload failed: %s", hipGetErrorString(e));
+    }
+    if (ix->doc_arena) (void)hipFree(ix->doc_arena);
+    if (ix->doc_offsets) (void)hipFree(ix->doc_offsets);
+    ix->doc_arena = dev_arena;
+    ix->doc_offsets = dev_offsets;
+    ix->doc_bytes = bytes;
+    ix->doc_count = n;
+    ix->doc_epoch = ix->epoch;
+    return CODD_KNN_OK;
+}
+
+int codd_knn_match_documents(codd_knn_index* ix, const uint8_t* host_needle, int needle_len, uint32_t* dev_bits, int64_t nwords, void* stream) {
+    if (!ix || !host_needle) return fail(CODD_KNN_EINVAL, "match_documents: null index or needle%s");
+    if (needle_len < 1 || needle_len > CODD_KNN_MAX_NEEDLE) return fail(CODD_KNN_EINVAL, "match_documents: needle_len out of range [1,256]%s");
+    if (memchr(host_needle, 0, (size_t)needle_len)) return fail(CODD_KNN_EINVAL, "match_documents: the needle holds a 0x00 byte%s");
+    static_assert(kDocMaxNeedle == CODD_KNN_MAX_NEEDLE, "doc_match.h and codd_knn.h disagree");
+    DeviceGuard guard(ix->device);
+    hipStream_t st = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lock(ix->mu);   // (no workspace: the kernel reads the snapshot and writes the caller's words)
+    if (!docs_valid(ix)) return fail(CODD_KNN_EINVAL, "match_documents: no document snapshot, or a stale one (rows changed since codd_knn_set_documents_host)%s");
+    if (nwords != (ix->count + 31) / 32) return fail(CODD_KNN_EINVAL, "match_documents: nwords must be ceil(count / 32)%s");
+    if (nwords == 0) return CODD_KNN_OK;
+    if (!dev_bits) return fail(CODD_KNN_EINVAL, "match_documents: null bits%s");
+    DocNeedle needle;
+    memset(&needle, 0, sizeof(needle));
+    memcpy(needle.w, host_needle, (size_t)needle_len);
+    HIP_TRY(hipMemsetAsync(dev_bits, 0, (size_t)nwords * sizeof(uint32_t), st));
+    const int64_t tiles = (ix->doc_bytes + kDocTile - 1) / kDocTile;
+    const int64_t most = (int64_t)ix->num_cus * 8;   // (grid-stride beyond eight workgroups per compute unit)
+    const int rc = launch_kernel<doc_match_kernel>(dim3((unsigned)(tiles < most ? tiles : most)), dim3(kDocThreads), 0, st,
+                                                   reinterpret_cast<const uint4*>(ix->doc_arena), ix->doc_bytes, tiles, ix->doc_offsets, ix->count, needle,
+                                                   needle_len, dev_bits);
+    if (rc != 0) return rc;
+    HIP_TRY(hipGetLastError());
+    ix->stat_doc_matches++;
+    return CODD_KNN_OK;
 }
 
 int codd_knn_delete_host(codd_knn_index* ix, const int64_t* host_slots, int64_t n) {
@@ -3934,6 +4075,11 @@ int codd_knn_get_stat(const codd_knn_index* ix, const char* key, int64_t* out) {
     else if (strcmp(key, "mask_list_searches") == 0) *out = ix->stat_mask_list;
     else if (strcmp(key, "mask_dense_searches") == 0) *out = ix->stat_mask_dense;
     else if (strcmp(key, "last_mask_rows") == 0) *out = ix->stat_last_mask_rows;
+    else if (strcmp(key, "masked_dev_searches") == 0) *out = ix->stat_masked_dev;
+    else if (strcmp(key, "docs_valid") == 0) *out = docs_valid(ix) ? 1 : 0;
+    else if (strcmp(key, "doc_bytes") == 0) *out = ix->doc_arena ? ix->doc_bytes : 0;
+    else if (strcmp(key, "doc_tile_bytes") == 0) *out = kDocTile;
+    else if (strcmp(key, "doc_matches") == 0) *out = ix->stat_doc_matches;
     else if (strcmp(key, "dead_rows") == 0) *out = ix->dead_count;
     else if (strcmp(key, "delete_calls") == 0) *out = ix->stat_delete_calls;
     else if (strcmp(key, "compactions") == 0) *out = ix->stat_compactions;
@@ -3985,7 +4131,8 @@ int codd_knn_get_stat(const codd_knn_index* ix, const char* key, int64_t* out) {
     else if (strcmp(key, "num_cus") == 0) *out = ix->num_cus;
     else if (strcmp(key, "device_bytes") == 0) {
         int64_t b = ix->capacity * (int64_t)ix->dpad * (int64_t)elem_size(ix->dtype) + ix->shadow_rows * (int64_t)ix->dpad * 2 +
-                    ix->shadow8_rows * ((int64_t)dpad8_of(ix) + 4) + (ix->scope_of_cap + ix->scope_perm_cap + ix->scope_lists_cap + ix->dead_words_cap) * 4;
+                    ix->shadow8_rows * ((int64_t)dpad8_of(ix) + 4) + (ix->scope_of_cap + ix->scope_perm_cap + ix->scope_lists_cap + ix->dead_words_cap) * 4 +
+                    (ix->doc_arena ? doc_arena_alloc_bytes(ix->doc_bytes) + (ix->doc_count + 1) * 8 : 0);
         for (const WorkSlot& w : ix->slots)
             b += w.bufs.qn_cap * 4 + w.bufs.partial_cap * 8 + w.bufs.keys_tmp_cap * 8 + w.bufs.hits_cap * 8 + w.bufs.bucket_cap * 8 +
                  w.bufs.qfrag_cap * 16 + w.bufs.fb_partial_cap * 8 + w.bufs.probe_cap * 8 + w.bufs.ivf_partial_cap * 8;

@@ -82,6 +82,12 @@ class Collection:
         # Both are dropped by every upsert / delete / compact / load.
         self._key_index: dict[str, dict[tuple, np.ndarray]] = {}
         self._mask_cache: dict[str, np.ndarray] = {}
+        # `where_document`: host masks by canonical filter; on a device engine the needles' bitmaps (packed words on the GPU) by needle
+        # bytes, and whether the engine holds the current documents.  Dropped with the two above.
+        self._doc_mask_cache: dict[str, np.ndarray] = {}
+        self._doc_bits_cache: dict[bytes, Any] = {}
+        self._docs_on_device = False
+        self._docs_fit_device: Optional[bool] = None   # no document holds NUL (None: not looked yet; one pass per change)
 
     # ------------------------------------------------------------------ helpers
     def _engine_for(self, dim: int):
@@ -232,6 +238,115 @@ class Collection:
     def _forget_where_index(self) -> None:
         self._key_index.clear()
         self._mask_cache.clear()
+        self._doc_mask_cache.clear()
+        self._doc_bits_cache.clear()
+        self._docs_on_device = False
+        self._docs_fit_device = None
+
+    # ------------------------------------------------------------------ where_document -> row mask
+    _WHERE_DOCUMENT_GRAMMAR = ('{"$contains": "text"}, {"$not_contains": "text"}, {"$and": [filters]}, {"$or": [filters]}; '
+                               'text is a non-empty str, matched case-sensitively as a substring of the stored document')
+    _DEVICE_NEEDLE_MAX = 256  # CODD_KNN_MAX_NEEDLE: longer needles, and needles holding NUL, are evaluated on the host
+
+    def _where_document_error(self, where_document, why: str) -> ValueError:
+        return ValueError(f"unsupported where_document filter {where_document!r}: {why}; supported: {self._WHERE_DOCUMENT_GRAMMAR}")
+
+    def _check_where_document(self, wd, top=None) -> None:
+        """ValueError unless `wd` is a filter of ChromaDB's document grammar."""
+        top = wd if top is None else top
+        if not isinstance(wd, dict) or len(wd) != 1:
+            raise self._where_document_error(top, "a filter is a dict with exactly one key")
+        (op, arg), = wd.items()
+        if op in ("$and", "$or"):
+            if not isinstance(arg, (list, tuple)) or len(arg) == 0:
+                raise self._where_document_error(top, f"{op} takes a non-empty list of filters")
+            for sub in arg:
+                self._check_where_document(sub, top)
+        elif op in ("$contains", "$not_contains"):
+            if not isinstance(arg, str) or arg == "":
+                raise self._where_document_error(top, f"{op} takes a non-empty str")
+        else:
+            raise self._where_document_error(top, f"unknown operator {op!r}")
+
+    @staticmethod
+    def _utf8(text: str) -> bytes:
+        return text.encode("utf-8", "surrogatepass")
+
+    def _live_mask(self) -> np.ndarray:
+        return np.fromiter((doc_id is not None for doc_id in self._ids), dtype=bool, count=len(self._ids))
+
+    def _contains_mask(self, needle: str) -> np.ndarray:
+        """bool over the row slots: the stored document contains `needle` (a record without a document contains nothing)."""
+        return np.fromiter((doc is not None and needle in doc for doc in self._documents), dtype=bool, count=len(self._documents))
+
+    def _eval_where_document(self, wd) -> np.ndarray:
+        (op, arg), = wd.items()
+        if op in ("$and", "$or"):
+            masks = [self._eval_where_document(sub) for sub in arg]
+            return np.logical_and.reduce(masks) if op == "$and" else np.logical_or.reduce(masks)
+        hit = self._contains_mask(arg)
+        return hit if op == "$contains" else self._live_mask() & ~hit   # (a deleted slot never passes)
+
+    def _where_document_mask(self, wd) -> np.ndarray:
+        """The checked filter as a bool array over the row slots, evaluated on the host (`needle in doc`); cached by canonical JSON."""
+        canon = json.dumps(wd, sort_keys=True, ensure_ascii=True)
+        mask = self._doc_mask_cache.get(canon)
+        if mask is None:
+            mask = self._eval_where_document(wd)
+            if len(self._doc_mask_cache) >= self._MASK_CACHE_SIZE:
+                self._doc_mask_cache.pop(next(iter(self._doc_mask_cache)))
+            self._doc_mask_cache[canon] = mask
+        return mask
+
+    # the device path: needles matched by the engine's kernel, bitmaps combined where they are
+    def _has_device_documents(self) -> bool:
+        return hasattr(self._engine, "match_documents") and hasattr(self._engine, "search_masked_dev")
+
+    def _words_on_device(self, mask: np.ndarray):
+        """A bool mask over the row slots as packed words on the engine's device (int32 tensor, match_documents' form)."""
+        import torch
+
+        n = mask.shape[0]
+        words = np.zeros((n + 31) // 32 * 4, dtype=np.uint8)
+        packed = np.packbits(mask, bitorder="little")
+        words[: packed.shape[0]] = packed
+        return torch.from_numpy(words.view("<i4")).to(self._engine.device)
+
+    def _needle_bits(self, needle: str):
+        """The bitmap of one $contains needle on the device, from the 32-entry cache or matched now (the first use after a change
+        uploads the document snapshot)."""
+        raw = self._utf8(needle)
+        bits = self._doc_bits_cache.get(raw)
+        if bits is None:
+            if len(raw) > self._DEVICE_NEEDLE_MAX or b"\x00" in raw:
+                bits = self._words_on_device(self._contains_mask(needle))
+            else:
+                if not self._docs_on_device:
+                    self._engine.set_documents([None if doc is None else self._utf8(doc) for doc in self._documents])
+                    self._docs_on_device = True
+                bits = self._engine.match_documents(raw)
+            if len(self._doc_bits_cache) >= self._MASK_CACHE_SIZE:
+                self._doc_bits_cache.pop(next(iter(self._doc_bits_cache)))
+            self._doc_bits_cache[raw] = bits
+        return bits
+
+    def _where_document_bits(self, wd):
+        (op, arg), = wd.items()
+        if op in ("$and", "$or"):
+            parts = [self._where_document_bits(sub) for sub in arg]
+            out = parts[0]
+            for part in parts[1:]:
+                out = out & part if op == "$and" else out | part
+            return out
+        bits = self._needle_bits(arg)
+        return bits if op == "$contains" else ~bits   # (the engine clips the words to the count and drops dead rows)
+
+    def _documents_fit_device(self) -> bool:
+        """The engine's arena separates documents by NUL: a collection whose documents hold one is filtered on the host.  One pass
+        over the documents per change of the collection (the flag is dropped with the snapshot's), not one per query."""
+        if self._docs_fit_device is None:
+            self._docs_fit_device = not any(doc is not None and "\x00" in doc for doc in self._documents)
+        return self._docs_fit_device
 
     def _where_scopes(self, where, B: int) -> Optional[np.ndarray]:
         """Per-query scope labels of a `where` (None when no query is restricted); -1 marks a namespace nobody stored."""
@@ -360,17 +475,23 @@ class Collection:
 
     # ------------------------------------------------------------------ reads
     def get(self, ids: Optional[Sequence[str]] = None, limit: Optional[int] = None, offset: int = 0,
-            include: Sequence[str] = ("metadatas", "documents"), where=None) -> dict:
+            include: Sequence[str] = ("metadatas", "documents"), where=None, where_document=None) -> dict:
         """chromadb Collection.get: FLAT lists; unknown ids are skipped (store.py:260-261).  `where`: a metadata filter in the
-        grammar `query` accepts (one dict); with `ids`, the records that satisfy both."""
+        grammar `query` accepts (one dict); `where_document`: a document filter in the grammar `query` accepts, evaluated on the
+        host; with `ids`, the records that satisfy all of them."""
+        allowed = None
         if where is not None:
             self._check_where(where)
             allowed = self._where_mask(where)
+        if where_document is not None:
+            self._check_where_document(where_document)
+            in_doc = self._where_document_mask(where_document)
+            allowed = in_doc if allowed is None else allowed & in_doc
         if ids is None:
-            live = [s for s, doc_id in enumerate(self._ids) if doc_id is not None and (where is None or allowed[s])]
+            live = [s for s, doc_id in enumerate(self._ids) if doc_id is not None and (allowed is None or allowed[s])]
             slots = live[offset : (None if limit is None else offset + limit)]
         else:
-            slots = [self._slot_of[i] for i in ids if i in self._slot_of and (where is None or allowed[self._slot_of[i]])]
+            slots = [self._slot_of[i] for i in ids if i in self._slot_of and (allowed is None or allowed[self._slot_of[i]])]
         return {
             "ids": [self._ids[s] for s in slots],
             "metadatas": [self._metadatas[s] for s in slots] if "metadatas" in include else None,
@@ -379,7 +500,7 @@ class Collection:
         }
 
     def query(self, query_texts: Optional[Sequence[str]] = None, query_embeddings=None, n_results: int = 10,
-              include: Sequence[str] = ("metadatas", "documents", "distances"), where=None) -> dict:
+              include: Sequence[str] = ("metadatas", "documents", "distances"), where=None, where_document=None) -> dict:
         """chromadb Collection.query: NESTED lists, one inner list per query, ascending
         distance, min(n_results, count) hits each (store.py:314-329).
 
@@ -389,9 +510,22 @@ class Collection:
         fewer do; nobody: an empty inner list).  A record without the key fails $eq, $in and the comparisons and passes $ne and
         $nin; a str never compares with a number.  {"namespace": "x"} and {"namespace": {"$eq": "x"}} go through the engine's scoped
         search, every other filter through its masked search (search_masked) under a row mask compiled here; an engine without
-        it accepts the namespace forms only.  A malformed filter raises ValueError."""
+        it accepts the namespace forms only.  A malformed filter raises ValueError.
+
+        `where_document` restricts the search by the stored documents, in ChromaDB's grammar: {"$contains": "text"}, {"$not_contains":
+        "text"}, {"$and" | "$or": [filters]}; one filter per call, shared by the queries.  Matching is case-sensitive, on the stored
+        document's UTF-8 bytes: a substring of code points is a substring of bytes.  A record whose document is None fails $contains
+        and passes $not_contains.  Combined with `where`, both must hold.  The answer is the exact top-k among the live records that
+        satisfy them (fewer when fewer do; nobody: an empty inner list).  On an engine with match_documents and search_masked_dev
+        the needles are matched on the device — the document snapshot is uploaded by the first such call after a change, each
+        needle's bitmap is cached (32 entries), $and / $or / $not_contains and a `where` mask are combined there, and one
+        search_masked_dev answers; a needle above 256 bytes or holding NUL is evaluated here and uploaded as a mask.  On an engine
+        with search_masked only, the filter is evaluated here (`needle in doc`) and goes through search_masked.  An engine with
+        neither raises ValueError, as does anything outside the grammar (an empty string, a non-string, an unknown operator)."""
         if (query_texts is None) == (query_embeddings is None):
             raise ValueError("give exactly one of query_texts / query_embeddings")
+        if where_document is not None:
+            self._check_where_document(where_document)
         if n_results < 1:
             raise ValueError("n_results must be >= 1")
         if query_embeddings is None:
@@ -409,9 +543,11 @@ class Collection:
         if q.shape[1] != self._engine.dim:
             raise ValueError(f"query dimension {q.shape[1]} does not match collection dimension {self._engine.dim}")
         k = min(int(n_results), len(self._slot_of))  # (the live count: deleted records are never returned)
-        general = self._general_wheres(where, B)  # (None: nothing but namespace forms, the scoped path below)
-        scopes = None if where is None or general is not None else self._where_scopes(where, B)
-        if general is not None:
+        general = None if where_document is not None else self._general_wheres(where, B)  # (None: nothing but namespace forms, the scoped path below)
+        scopes = None if where is None or general is not None or where_document is not None else self._where_scopes(where, B)
+        if where_document is not None:
+            dist, rows = self._search_by_document(q, k, where_document, where)
+        elif general is not None:
             dist, rows = self._search_by_filter(q, k, general)
         elif scopes is None:
             dist, rows = self._engine.search(q, k)
@@ -496,6 +632,45 @@ class Collection:
             mask = self._where_mask(per_query[members[0]])
             if mask.any():
                 dist[members], rows[members] = self._engine.search_masked(q[members], mask, k)
+        return dist, rows
+
+    def _search_by_document(self, q: np.ndarray, k: int, where_document, where):
+        """The exact top-k among the live records that satisfy `where_document` and, per query, `where` (None, a namespace form or a
+        general filter; one for all queries or a list): one masked engine call per distinct `where`."""
+        B = q.shape[0]
+        if not hasattr(self._engine, "search_masked"):
+            raise ValueError(f"unsupported where_document filter {where_document!r}: {type(self._engine).__name__} has no masked search; "
+                             f"supported on an engine with search_masked: {self._WHERE_DOCUMENT_GRAMMAR}")
+        if isinstance(where, (list, tuple)):
+            if len(where) != B:
+                raise ValueError(f"where has {len(where)} entries for {B} queries; supported: {self._WHERE_FORMS}")
+            per_query = list(where)
+        else:
+            per_query = [where] * B
+        groups: dict[str, list[int]] = {}
+        for b, w in enumerate(per_query):
+            if w is not None:
+                self._check_where(w)   # (the namespace forms are filters of the general grammar too)
+            groups.setdefault(json.dumps(w, sort_keys=True, ensure_ascii=False), []).append(b)
+        dist = np.full((B, k), np.inf, dtype=np.float32)
+        rows = np.full((B, k), -1, dtype=np.int64)
+        on_device = self._has_device_documents() and self._documents_fit_device()
+        for members in groups.values():
+            w = per_query[members[0]]
+            by_where = None if w is None else self._where_mask(w)
+            if by_where is not None and not by_where.any():
+                continue
+            if on_device:
+                bits = self._where_document_bits(where_document)
+                if by_where is not None:
+                    bits = bits & self._words_on_device(by_where)
+                dist[members], rows[members] = self._engine.search_masked_dev(q[members], bits, k)
+            else:
+                mask = self._where_document_mask(where_document)
+                if by_where is not None:
+                    mask = mask & by_where
+                if mask.any():
+                    dist[members], rows[members] = self._engine.search_masked(q[members], mask, k)
         return dist, rows
 
     # ------------------------------------------------------------------ persistence

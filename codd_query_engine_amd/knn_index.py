@@ -35,8 +35,8 @@ class DeviceKnnIndex:
 
     Engine protocol consumed by knn_client.Collection:
         count() / upsert(slots, vecs) / search(queries, k) -> (dist, rows) as numpy;
-        optionally set_scopes / search_scoped (`where=` by namespace), search_masked (any other `where=`) and delete / live_count /
-        compact (`Collection.delete`).
+        optionally set_scopes / search_scoped (`where=` by namespace), search_masked (any other `where=`), set_documents /
+        match_documents / search_masked_dev (`where_document=` on the device) and delete / live_count / compact (`Collection.delete`).
     """
 
     def __init__(self, dim: int, dtype: str = "f32", device: str = "cuda:0"):
@@ -280,6 +280,69 @@ class DeviceKnnIndex:
     def search_keys_masked(self, queries, allow, k: int, row_base: int = 0):
         """search_keys among the rows `allow` names."""
         return self._search_masked(queries, allow, k, row_base, True)[0]
+
+    # ------------------------------------------------------------------ documents (where_document)
+    def set_documents(self, documents) -> None:
+        """The document of every row slot, as bytes (None = no document, matched as empty): count() entries, none holding a 0x00
+        byte.  Replaces the engine's whole snapshot; it goes stale on the next upsert / load_rows / compact."""
+        docs = [b"" if d is None else bytes(d) for d in documents]
+        offsets = np.zeros(len(docs) + 1, dtype=np.int64)
+        if docs:
+            np.cumsum([len(d) for d in docs], out=offsets[1:])
+        blob = np.frombuffer(b"".join(docs), dtype=np.uint8)
+        native.check(
+            self._lib.codd_knn_set_documents_host(self._h, blob.ctypes.data if blob.size else None, offsets.ctypes.data, len(docs)),
+            "codd_knn_set_documents_host",
+        )
+
+    def match_documents(self, needle: bytes):
+        """The row slots whose document contains `needle` (1 .. native.MAX_NEEDLE bytes, no 0x00) as a byte substring: packed
+        words, bit r & 31 of word r >> 5 = row slot r, in an int32 CUDA tensor of ceil(count() / 32) words (uint32 bit patterns)."""
+        torch = _torch()
+        needle = bytes(needle)
+        nwords = (self.count() + 31) // 32
+        bits = torch.empty((nwords,), dtype=torch.int32, device=self.device)
+        native.check(
+            self._lib.codd_knn_match_documents(self._h, needle, len(needle), bits.data_ptr() if nwords else None, nwords, self._stream()),
+            "codd_knn_match_documents",
+        )
+        return bits
+
+    def _allow_words_tensor(self, allow_bits):
+        torch = _torch()
+        if not (isinstance(allow_bits, torch.Tensor) and allow_bits.is_cuda and allow_bits.dtype == torch.int32 and allow_bits.dim() == 1):
+            raise ValueError("expected the allow mask as a 1-d int32 CUDA tensor of packed words (match_documents' form)")
+        return allow_bits.to(self.device).contiguous()
+
+    def _search_masked_dev(self, queries, allow_bits, k: int, row_base: int, want_keys: bool):
+        torch = _torch()
+        q = self._queries_tensor(queries)
+        B = q.shape[0]
+        words = self._allow_words_tensor(allow_bits)
+        keys = torch.empty((B, k), dtype=torch.int64, device=self.device) if want_keys else None
+        dist = None if want_keys else torch.empty((B, k), dtype=torch.float32, device=self.device)
+        rows = None if want_keys else torch.empty((B, k), dtype=torch.int64, device=self.device)
+        native.check(
+            self._lib.codd_knn_search_masked_dev(self._h, q.data_ptr(), B, int(k), words.data_ptr() if words.shape[0] else None, words.shape[0],
+                                                 int(row_base), keys.data_ptr() if want_keys else None, None if want_keys else dist.data_ptr(),
+                                                 None if want_keys else rows.data_ptr(), self._stream()),
+            "codd_knn_search_masked_dev",
+        )
+        return keys, dist, rows
+
+    def search_masked_dev_tensors(self, queries, allow_bits, k: int):
+        """search_masked_tensors under a mask that is on the device already: packed words as match_documents returns them."""
+        _, dist, rows = self._search_masked_dev(queries, allow_bits, k, 0, False)
+        return dist, rows
+
+    def search_masked_dev(self, queries, allow_bits, k: int):
+        """numpy out (the façade's path for `where_document=`)."""
+        dist, rows = self.search_masked_dev_tensors(queries, allow_bits, k)
+        return dist.cpu().numpy(), rows.cpu().numpy()
+
+    def search_keys_masked_dev(self, queries, allow_bits, k: int, row_base: int = 0):
+        """search_keys among the rows the device mask names."""
+        return self._search_masked_dev(queries, allow_bits, k, row_base, True)[0]
 
     def merge_keys(self, keys, k: int):
         """Top-k of [B,m] packed keys -> (keys [B,k], dist [B,k], rows [B,k]) on device."""

@@ -41,18 +41,27 @@ class MetricsSearchClient:
     def __init__(self, semantic_metadata_store: MetricsSemanticMetadataStore):
         self.semantic_metadata_store = semantic_metadata_store
 
-    def search_relevant_metrics(self, query: str, limit: int = 5, namespace=None, where=None) -> list[SearchResult]:
+    def search_relevant_metrics(self, query: str, limit: int = 5, namespace=None, where=None, where_document=None) -> list[SearchResult]:
         """`namespace` (extension): only that namespace's metrics; `where` (extension): a metadata filter such as
-        {"golden_signal_type": "latency"}; both None is the reference's call."""
+        {"golden_signal_type": "latency"}; `where_document` (extension): a filter on the stored document text such as
+        {"$contains": "http"}; all None is the reference's call."""
+        if where_document is not None:
+            return project_search_results(self.semantic_metadata_store.search_metadata(query, n_results=limit, namespace=namespace, where=where,
+                                                                                       where_document=where_document))
         if namespace is None and where is None:
             return project_search_results(self.semantic_metadata_store.search_metadata(query, n_results=limit))
         if where is None:
             return project_search_results(self.semantic_metadata_store.search_metadata(query, n_results=limit, namespace=namespace))
         return project_search_results(self.semantic_metadata_store.search_metadata(query, n_results=limit, namespace=namespace, where=where))
 
-    def search_relevant_metrics_batch(self, queries: list[str], limit: int = 5, namespace=None, where=None) -> list[list[SearchResult]]:
+    def search_relevant_metrics_batch(self, queries: list[str], limit: int = 5, namespace=None, where=None,
+                                      where_document=None) -> list[list[SearchResult]]:
         """Extension: one engine call for many queries (B up to 1024); `namespace`: one string, or a list with a string / None per query;
-        `where`: one metadata filter for every query."""
+        `where`: one metadata filter for every query; `where_document`: one document filter for every query."""
+        if where_document is not None:
+            return [project_search_results(r)
+                    for r in self.semantic_metadata_store.search_metadata_batch(queries, n_results=limit, namespace=namespace, where=where,
+                                                                                where_document=where_document)]
         if namespace is None and where is None:
             return [project_search_results(r) for r in self.semantic_metadata_store.search_metadata_batch(queries, n_results=limit)]
         if where is None:

@@ -258,20 +258,26 @@ class MetricsSemanticMetadataStore:
             return None if namespace is None else {"namespace": namespace}
         return where if namespace is None else {"$and": [{"namespace": namespace}, where]}
 
-    def search_metadata(self, query: str, n_results: int = 10, namespace: Optional[str] = None, where: Optional[dict] = None) -> list[dict]:
+    def search_metadata(self, query: str, n_results: int = 10, namespace: Optional[str] = None, where: Optional[dict] = None,
+                        where_document: Optional[dict] = None) -> list[dict]:
         """Metrics most similar to `query`, best first (reference store.py:266-341).
 
         Empty query -> []; query longer than 1000 chars after sanitising or n_results < 1 ->
         ValidationError; n_results above 100 is capped with a warning.  `namespace` (extension) keeps the
         search inside one namespace: the exact best matches among its metrics.  `where` (extension): a metadata
         filter in ChromaDB's grammar over the stored keys, e.g. {"golden_signal_type": "latency"}; with `namespace` both hold.
+        `where_document` (extension): a filter on the stored document text in ChromaDB's grammar, e.g. {"$contains": "http"},
+        passed straight to the collection; every filter given must hold.
         """
         cleaned = self._clean_query(query)
         if cleaned is None:
             logger.debug("Empty query received, returning empty results")
             return []
         n_results = self._clamp_n_results(n_results)
-        if namespace is None and where is None:
+        if where_document is not None:
+            results = self.collection.query(query_texts=[cleaned], n_results=n_results, where=self._where_of(namespace, where),
+                                            where_document=where_document)
+        elif namespace is None and where is None:
             results = self.collection.query(query_texts=[cleaned], n_results=n_results)
         else:
             results = self.collection.query(query_texts=[cleaned], n_results=n_results, where=self._where_of(namespace, where))
@@ -281,11 +287,13 @@ class MetricsSemanticMetadataStore:
             results["ids"][0], results.get("metadatas", [[]])[0], results.get("distances", [[]])[0]
         )
 
-    def search_metadata_batch(self, queries: list[str], n_results: int = 10, namespace=None, where: Optional[dict] = None) -> list[list[dict]]:
+    def search_metadata_batch(self, queries: list[str], n_results: int = 10, namespace=None, where: Optional[dict] = None,
+                              where_document: Optional[dict] = None) -> list[list[dict]]:
         """Extension (the reference only ever sends one query): many queries, ONE engine call.
 
         Same per-query rules as search_metadata; an empty query yields [] at its position.  `namespace`: one
         string for every query, or a list with a string / None per query.  `where`: one metadata filter for every query.
+        `where_document`: one document filter for every query, passed straight to the collection.
         """
         if isinstance(namespace, (list, tuple)) and len(namespace) != len(queries):
             raise ValidationError(f"namespace has {len(namespace)} entries for {len(queries)} queries")
@@ -295,12 +303,16 @@ class MetricsSemanticMetadataStore:
         out: list[list[dict]] = [[] for _ in queries]
         if not live:
             return out
-        if namespace is None and where is None:
+        if namespace is None and where is None and where_document is None:
             results = self.collection.query(query_texts=[cleaned[i] for i in live], n_results=n_results)
         else:
             per_query = [namespace[i] for i in live] if isinstance(namespace, (list, tuple)) else [namespace] * len(live)
             wheres = [self._where_of(ns, where) for ns in per_query]
-            results = self.collection.query(query_texts=[cleaned[i] for i in live], n_results=n_results, where=wheres)
+            if where_document is None:
+                results = self.collection.query(query_texts=[cleaned[i] for i in live], n_results=n_results, where=wheres)
+            else:
+                results = self.collection.query(query_texts=[cleaned[i] for i in live], n_results=n_results,
+                                                where=None if all(w is None for w in wheres) else wheres, where_document=where_document)
         if not results or not results.get("ids"):
             return out
         all_md = results.get("metadatas") or []

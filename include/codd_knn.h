@@ -5,8 +5,9 @@
  * The reference has no FFI of its own: its seam is Python duck typing on the
  * chromadb client object injected into MetricsSemanticMetadataStore
  * (/root/reference/codd_dal/metrics/metrics_semantic_metadata_store.py:43-57).
- * Each entry point below names the chromadb call it takes over; string ids,
- * documents and metadata never cross this boundary (the Python façade
+ * Each entry point below names the chromadb call it takes over; string ids
+ * and metadata never cross this boundary, documents only as the bytes that
+ * codd_knn_match_documents searches (the Python façade
  * codd_query_engine_amd/knn_client.py keeps id <-> row slot and metadata on the
  * host, exactly the part of chromadb that is not arithmetic).
  *
@@ -20,12 +21,12 @@
  *   - `stream` is a hipStream_t passed as void* (NULL = the null stream).  Calls
  *     are asynchronous with respect to the host unless stated otherwise.
  *   - thread-safety: the search entry points (codd_knn_search, _search_keys, _search_scoped,
- *     _search_masked, _ivf_search, _approx_scores) may be called from several host threads and on
+ *     _search_masked, _search_masked_dev, _match_documents, _ivf_search, _approx_scores) may be called from several host threads and on
  *     several streams of one index: the index keeps one workspace per stream (up to
  *     4; a fifth stream takes over the least recently used one, ordered behind its
  *     previous owner on the device) and serialises only the enqueueing.  Searches on
  *     different streams then overlap on the GPU.  upsert/reserve/load/ivf_install/set_scopes/
- *     delete/compact are exclusive: no other call on the index may be in flight.
+ *     delete/compact/set_documents are exclusive: no other call on the index may be in flight.
  *   - rows are stored L2-normalised, zero padded to a multiple of 64 elements.
  *     score = <q/|q|, c/|c|> evaluated in fp32 in the canonical order of
  *     DESIGN.md §3; distance = 1 - score (fp32); ties -> lower row.
@@ -256,6 +257,44 @@ int codd_knn_live_count(const codd_knn_index* index, int64_t* out);
 int codd_knn_compact(codd_knn_index* index, int64_t* new_count);
 
 /*
+ * Replaces: the `where_document` of collection.query(query_texts=..., n_results=..., where_document={"$contains": "..."}) — ChromaDB's
+ *           substring filter on the stored documents (store.py:146-150 writes one per record).  The grammar ($contains, $not_contains,
+ *           $and, $or) stays with the façade; what crosses this boundary is bytes: the documents once, then one needle per call, and
+ *           the answer is a row bitmap on the device that codd_knn_search_masked_dev searches under.
+ * set_documents_host: the document of row slot r is host_bytes[host_offsets[r] .. host_offsets[r + 1]), possibly empty; host_offsets holds
+ *           n + 1 values.  n must equal the count, the offsets must be non-decreasing from 0, and no byte may be 0x00 — a violation of
+ *           any of these returns EINVAL and changes nothing.  Replaces the whole snapshot; exclusive and synchronous, like upsert_host.
+ *           The engine lays out its own ARENA: the documents back to back in slot order, one 0x00 behind every document (document r
+ *           starts at arena offset host_offsets[r] + r; the arena has host_offsets[n] + n bytes, the "doc_bytes" stat), zero bytes
+ *           behind the last separator up to the end of the allocation so that every load of the match kernel is unconditional, and the
+ *           n + 1 arena offsets as int64 on the device.  The snapshot is derived data, like the shadows and the scope lists: it is never
+ *           persisted, and it goes STALE on upsert_host, upsert_device, load_rows and a compact that moves rows, as an IVF layout does;
+ *           delete_host leaves it valid.
+ * match_documents: sets bit (r & 31) of dev_bits[r >> 5] iff document r contains the needle as a byte substring; every other bit of the
+ *           nwords words, the bits at or above the count among them, is zero.  Slot-addressed: a dead slot's document is matched as it
+ *           stands (the searches drop dead rows, as everywhere else).  needle_len in [1, CODD_KNN_MAX_NEEDLE], no 0x00 in the needle,
+ *           nwords == ceil(count / 32), else EINVAL; a stale or absent snapshot: EINVAL.  host_needle is consumed before the call
+ *           returns.  Asynchronous on `stream`: one hipMemsetAsync of dev_bits and one launch of doc_match_kernel (csrc/doc_match.h),
+ *           which streams the arena once, "doc_tile_bytes" start positions per workgroup step — its cost is the arena's bytes whatever
+ *           the documents' lengths are.  May be called from several host threads and streams, like a search.
+ * search_masked_dev: codd_knn_search_masked under a mask that is already on the device — the same answer contract, word for word: the
+ *           exact canonical top-k among the rows that are allowed AND live, min(k, m) hits, m == 0 an all-empty result with no scan, the
+ *           same two routes chosen by the same rule from m, B and the index size, the same "mask_route" / "mask_list_pct" options and
+ *           the same masked counters (plus "masked_dev_searches").  dev_allow_bits are nwords == ceil(count / 32) device words, read on
+ *           `stream` behind whatever wrote them there (codd_knn_match_documents, a torch bitwise op ...); a small kernel clips them to
+ *           [0, count) into the index's own allow buffer, so the caller's words are not needed once `stream` has run the call, and counts
+ *           m on the way against the tombstone bits.  m decides the route and sizes the list, so it is READ BACK: THE CALL SYNCHRONISES
+ *           `stream` ONCE, before it launches the scan (holding the index's enqueue lock meanwhile).  This entry point is therefore not
+ *           asynchronous with respect to the host; the scan, merge and outputs behind the read-back are enqueued as usual.
+ */
+#define CODD_KNN_MAX_NEEDLE 256
+int codd_knn_set_documents_host(codd_knn_index* index, const uint8_t* host_bytes, const int64_t* host_offsets, int64_t n);
+int codd_knn_match_documents(codd_knn_index* index, const uint8_t* host_needle, int needle_len,
+                             uint32_t* dev_bits, int64_t nwords, void* stream);
+int codd_knn_search_masked_dev(codd_knn_index* index, const float* dev_queries, int B, int k, const uint32_t* dev_allow_bits,
+                               int64_t nwords, uint32_t row_base, uint64_t* dev_keys, float* dev_dist, int64_t* dev_rows, void* stream);
+
+/*
  * Tuning / introspection (never needed for correctness).
  *   options: "scan_blocks_per_cu" (1..8); "filter" (0/1: MFMA filter path for large batches);
  *            "filter_min_batch" (9), "filter_min_rows" (1: batches >= filter_min_batch always
@@ -305,7 +344,10 @@ int codd_knn_compact(codd_knn_index* index, int64_t* new_count);
  *            "delete_calls", "compactions" (codd_knn_compact calls that moved rows), "masked_searches", "mask_list_searches",
  *            "mask_dense_searches" (masked searches by route), "last_mask_rows" (allowed live rows of the last masked search),
  *            "mask_filter_hits", "mask_filter_survivors", "mask_fallback_queries" (the device counters of the dense masked passes, kept
- *            apart from the three below), "filter_passes",
+ *            apart from the three below), "masked_dev_searches" (the masked searches among them that came through
+ *            codd_knn_search_masked_dev), "docs_valid" (1: a document snapshot exists and is not stale), "doc_bytes" (its arena: the
+ *            documents' bytes plus one separator each), "doc_tile_bytes" (arena bytes per workgroup step of doc_match_kernel),
+ *            "doc_matches" (codd_knn_match_documents calls that launched), "filter_passes",
  *            "fallback_queries", "filter_hits", "filter_survivors", "capacity_rows",
  *            "device_bytes", "num_cus", "workspaces" (stream workspaces in use), "shadow8_builds", "shadow8_passes", "i8v2_passes",
  *            "shadow16_builds" (the bf16 shadow is built lazily, by the first search that needs it), "all_normalized",
