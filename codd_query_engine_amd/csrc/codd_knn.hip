@@ -1647,6 +1647,7 @@ struct codd_knn_index : WorkBufs {
     int64_t stat_last_scan_group = 0;       // queries per pass over the rows of the last exact scan (1, 4 or 8; wide 2-byte rows: at most 4)
     int64_t stat_last_finalize_parts = 0;   // workgroups per query of the last filter pass's finalize
     int64_t stat_ivf_shared = 0;            // IVF searches that scanned each probed list once for all its queries (ivf_scan_shared_kernel)
+    int64_t stat_ivf_masked = 0;            // IVF searches under a row mask (codd_knn_ivf_search_masked, _masked_dev: DESIGN.md §17)
     int64_t stat_filter_passes = 0;
 
     // optional HIP-event timing of the heavy kernels (bench.py's roofline figure): one (start, stop)
@@ -3267,18 +3268,27 @@ int codd_knn_ivf_install(codd_knn_index* ix, const float* dev_centroids, int nli
     return CODD_KNN_OK;
 }
 
-int codd_knn_ivf_search(codd_knn_index* ix, const float* dev_queries, int B, int k, int nprobe, uint32_t row_base,
-                        uint64_t* dev_keys, float* dev_dist, int64_t* dev_rows, void* stream) {
+}  // extern "C"
+
+namespace {
+
+// what every IVF entry point checks before it takes a workspace; clamps nprobe to the number of lists
+int ivf_check_args(const codd_knn_index* ix, const float* dev_queries, int B, int k, int* nprobe) {
     if (!ix || !dev_queries) return fail(CODD_KNN_EINVAL, "null index or queries%s");
     if (B < 1 || B > CODD_KNN_MAX_BATCH) return fail(CODD_KNN_EINVAL, "B out of range [1,1024]%s");
     if (k < 1 || k > CODD_KNN_MAX_K) return fail(CODD_KNN_EINVAL, "k out of range [1,128]%s");
     if (!ix->coarse || ix->ivf_epoch != ix->epoch) return fail(CODD_KNN_EINVAL, "no IVF layout, or rows changed since codd_knn_ivf_install%s");
-    if (nprobe < 1) return fail(CODD_KNN_EINVAL, "nprobe must be >= 1%s");
-    if (nprobe > ix->ivf_nlist) nprobe = ix->ivf_nlist;
-    if (nprobe > CODD_KNN_MAX_K) return fail(CODD_KNN_ENOTSUP, "nprobe above 128 is not supported (probe the whole index with codd_knn_search)%s");
-    DeviceGuard guard(ix->device);
-    hipStream_t st = (hipStream_t)stream;
-    WorkScope work(ix, st), work_coarse(ix->coarse, st);
+    if (*nprobe < 1) return fail(CODD_KNN_EINVAL, "nprobe must be >= 1%s");
+    if (*nprobe > ix->ivf_nlist) *nprobe = ix->ivf_nlist;
+    if (*nprobe > CODD_KNN_MAX_K) return fail(CODD_KNN_ENOTSUP, "nprobe above 128 is not supported (probe the whole index with codd_knn_search)%s");
+    return CODD_KNN_OK;
+}
+
+// The body of every IVF search; the caller has checked the arguments, made the device current and holds the workspaces of the
+// index and of its coarse index for `st`.  deny: the ORIGINAL row slots no answer may hold — ix->dead_bits, or the ~allow | dead
+// of a masked search, which the list scans test where they test the tombstones.  Probe selection never sees it.
+int ivf_search_body(codd_knn_index* ix, const float* dev_queries, int B, int k, int nprobe, uint32_t row_base, uint64_t* dev_keys, float* dev_dist,
+                    int64_t* dev_rows, hipStream_t st, const uint32_t* deny) {
     int rc;
     if ((rc = wait_rows(ix, st)) != 0) return rc;
     if ((rc = ensure_buf(&ix->qn, &ix->qn_cap, (int64_t)B * ix->dpad)) != 0) return rc;
@@ -3314,7 +3324,7 @@ int codd_knn_ivf_search(codd_knn_index* ix, const float* dev_queries, int B, int
         rc = with_row_form(ix, k, "row too wide for the IVF scan%s", [&](auto dt, auto ni, auto sl) {
             return launch_kernel<ivf_scan_shared_kernel<dt, ni, sl>>(dim3((unsigned)bound), dim3(256), 0, st, ix->rows_ivf, ix->ivf_ids, ix->ivf_offsets,
                                                                      pair_start, item_start, sorted_pairs, nlist, nprobe, ix->dpad, ix->qn, k, row_base,
-                                                                     ix->ivf_partial, ix->dead_bits);
+                                                                     ix->ivf_partial, deny);
         });
         if (rc != 0) return rc;
         HIP_TRY(hipGetLastError());
@@ -3332,13 +3342,27 @@ int codd_knn_ivf_search(codd_knn_index* ix, const float* dev_queries, int B, int
         EvScope ev(ix, EV_SCAN, st);
         rc = with_row_form(ix, k, "row too wide for the IVF scan%s", [&](auto dt, auto ni, auto sl) {
             return launch_kernel<ivf_scan_kernel<dt, ni, sl>>(grid, block, 0, st, ix->rows_ivf, ix->ivf_ids, ix->ivf_offsets, ix->probe_keys, nprobe, split,
-                                                              ix->dpad, ix->qn, k, row_base, ix->ivf_partial, ix->dead_bits);
+                                                              ix->dpad, ix->qn, k, row_base, ix->ivf_partial, deny);
         });
     }
     if (rc != 0) return rc;
     HIP_TRY(hipGetLastError());
     // 3. top-k of the nprobe*split partial lists
     return launch_merge(ix->ivf_partial, B, m, m, k, (u64*)dev_keys, dev_dist, dev_rows, st);
+}
+
+}  // namespace
+
+extern "C" {
+
+int codd_knn_ivf_search(codd_knn_index* ix, const float* dev_queries, int B, int k, int nprobe, uint32_t row_base,
+                        uint64_t* dev_keys, float* dev_dist, int64_t* dev_rows, void* stream) {
+    int rc;
+    if ((rc = ivf_check_args(ix, dev_queries, B, k, &nprobe)) != 0) return rc;
+    DeviceGuard guard(ix->device);
+    hipStream_t st = (hipStream_t)stream;
+    WorkScope work(ix, st), work_coarse(ix->coarse, st);
+    return ivf_search_body(ix, dev_queries, B, k, nprobe, row_base, dev_keys, dev_dist, dev_rows, st, ix->dead_bits);
 }
 
 int codd_knn_set_scopes_host(codd_knn_index* ix, const int64_t* host_slots, const uint32_t* host_scopes, int64_t n) {
@@ -3535,6 +3559,55 @@ int masked_search_body(codd_knn_index* ix, const float* dev_queries, int B, int 
     return launch_merge(ix->partial, B, pm, pm, k, (u64*)dev_keys, dev_dist, dev_rows, st);
 }
 
+// The host words of a masked search (nwords > 0 of them): clipped to [0, n) into the workspace's pinned staging buffer and counted
+// against the tombstone mirror on the way (*m: the rows the call may see, exact, nothing read back).  The caller's words are not
+// touched again; the staging buffer's previous copy (the stream's last masked search) is waited for first.
+int stage_host_mask(codd_knn_index* ix, const uint32_t* host_allow_bits, int64_t nwords, int64_t n, int64_t* m) {
+    if (ix->mask_upload_pending) HIP_TRY(hipEventSynchronize(ix->mask_uploaded));
+    ix->mask_upload_pending = false;
+    if (nwords > ix->mask_host_cap) {
+        if (ix->mask_host) (void)hipHostFree(ix->mask_host);
+        ix->mask_host = nullptr; ix->mask_host_cap = 0;
+        const int64_t cap = nwords + nwords / 2 + 64;
+        HIP_TRY(hipHostMalloc((void**)&ix->mask_host, (size_t)cap * sizeof(uint32_t), hipHostMallocDefault));
+        ix->mask_host_cap = cap;
+    }
+    if (!ix->mask_uploaded) HIP_TRY(hipEventCreateWithFlags(&ix->mask_uploaded, hipEventDisableTiming));
+    const bool any_dead = ix->dead_count > 0;
+    int64_t seen = 0;
+    for (int64_t w = 0; w < nwords; ++w) {
+        const int64_t left = n - w * 32;
+        const uint32_t a = host_allow_bits[w] & (left >= 32 ? 0xffffffffu : (1u << (uint32_t)left) - 1u);
+        ix->mask_host[w] = a;
+        seen += __builtin_popcount(any_dead && (size_t)w < ix->dead_host.size() ? a & ~ix->dead_host[(size_t)w] : a);
+    }
+    *m = seen;
+    return CODD_KNN_OK;
+}
+
+// ... and one asynchronous copy on `st` takes the staged words to the workspace's allow buffer
+int upload_staged_mask(codd_knn_index* ix, int64_t nwords, hipStream_t st) {
+    int rc;
+    if ((rc = ensure_buf(&ix->mask_allow, &ix->mask_allow_cap, nwords)) != 0) return rc;
+    HIP_TRY(hipMemcpyAsync(ix->mask_allow, ix->mask_host, (size_t)nwords * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(ix->mask_uploaded, st));
+    ix->mask_upload_pending = true;
+    return CODD_KNN_OK;
+}
+
+// A masked IVF search behind its mask: `allow` are nwords device words, valid on `st` (the workspace's copy of the
+// host words, or the caller's own); deny = ~allow | dead over the nwords words that cover every row slot of the layout goes into the
+// workspace's deny buffer and takes the tombstones' place in the list scans.  Nothing depends on how many rows the mask leaves.
+int ivf_masked_body(codd_knn_index* ix, const float* dev_queries, int B, int k, int nprobe, const uint32_t* allow, int64_t nwords, uint32_t row_base,
+                    uint64_t* dev_keys, float* dev_dist, int64_t* dev_rows, hipStream_t st) {
+    int rc;
+    if ((rc = ensure_buf(&ix->mask_deny, &ix->mask_deny_cap, nwords)) != 0) return rc;
+    hipLaunchKernelGGL(mask_deny_kernel, dim3((unsigned)((nwords + 255) / 256)), dim3(256), 0, st, allow, ix->dead_bits, ix->count, nwords, nwords,
+                       ix->mask_deny);
+    HIP_TRY(hipGetLastError());
+    return ivf_search_body(ix, dev_queries, B, k, nprobe, row_base, dev_keys, dev_dist, dev_rows, st, ix->mask_deny);
+}
+
 bool docs_valid(const codd_knn_index* ix) { return ix->doc_arena && ix->doc_epoch == ix->epoch && ix->doc_count == ix->count; }
 
 }  // namespace
@@ -3560,31 +3633,10 @@ int codd_knn_search_masked(codd_knn_index* ix, const float* dev_queries, int B, 
     // the way (m: the rows this call may see, exact, nothing read back), then one asynchronous copy from the staging buffer.  The
     // caller's words are not touched again; the staging buffer's previous copy (the stream's last masked search) is waited for first.
     int64_t m = 0;
-    if (nwords > 0) {
-        if (ix->mask_upload_pending) HIP_TRY(hipEventSynchronize(ix->mask_uploaded));
-        ix->mask_upload_pending = false;
-        if (nwords > ix->mask_host_cap) {
-            if (ix->mask_host) (void)hipHostFree(ix->mask_host);
-            ix->mask_host = nullptr; ix->mask_host_cap = 0;
-            const int64_t cap = nwords + nwords / 2 + 64;
-            HIP_TRY(hipHostMalloc((void**)&ix->mask_host, (size_t)cap * sizeof(uint32_t), hipHostMallocDefault));
-            ix->mask_host_cap = cap;
-        }
-        if (!ix->mask_uploaded) HIP_TRY(hipEventCreateWithFlags(&ix->mask_uploaded, hipEventDisableTiming));
-        const bool any_dead = ix->dead_count > 0;
-        for (int64_t w = 0; w < nwords; ++w) {
-            const int64_t left = n - w * 32;
-            const uint32_t a = host_allow_bits[w] & (left >= 32 ? 0xffffffffu : (1u << (uint32_t)left) - 1u);
-            ix->mask_host[w] = a;
-            m += __builtin_popcount(any_dead && (size_t)w < ix->dead_host.size() ? a & ~ix->dead_host[(size_t)w] : a);
-        }
-    }
+    if (nwords > 0 && (rc = stage_host_mask(ix, host_allow_bits, nwords, n, &m)) != 0) return rc;
     ix->stat_last_mask_rows = m;
     if (m == 0) return masked_empty_result(ix, B, k, dev_keys, dev_dist, dev_rows, st);
-    if ((rc = ensure_buf(&ix->mask_allow, &ix->mask_allow_cap, nwords)) != 0) return rc;
-    HIP_TRY(hipMemcpyAsync(ix->mask_allow, ix->mask_host, (size_t)nwords * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipEventRecord(ix->mask_uploaded, st));
-    ix->mask_upload_pending = true;
+    if ((rc = upload_staged_mask(ix, nwords, st)) != 0) return rc;
     return masked_search_body(ix, dev_queries, B, k, nwords, m, row_base, dev_keys, dev_dist, dev_rows, st);
 }
 
@@ -3623,6 +3675,51 @@ int codd_knn_search_masked_dev(codd_knn_index* ix, const float* dev_queries, int
     ix->stat_last_mask_rows = m;
     if (m == 0) return masked_empty_result(ix, B, k, dev_keys, dev_dist, dev_rows, st);
     return masked_search_body(ix, dev_queries, B, k, nwords, m, row_base, dev_keys, dev_dist, dev_rows, st);
+}
+
+int codd_knn_ivf_search_masked(codd_knn_index* ix, const float* dev_queries, int B, int k, int nprobe, const uint32_t* host_allow_bits, int64_t nwords,
+                               uint32_t row_base, uint64_t* dev_keys, float* dev_dist, int64_t* dev_rows, void* stream) {
+    int rc;
+    if ((rc = ivf_check_args(ix, dev_queries, B, k, &nprobe)) != 0) return rc;
+    DeviceGuard guard(ix->device);
+    hipStream_t st = (hipStream_t)stream;
+    WorkScope work(ix, st), work_coarse(ix->coarse, st);
+    const int64_t n = ix->count;   // (>= 1: a layout exists)
+    if (nwords != (n + 31) / 32) return fail(CODD_KNN_EINVAL, "ivf_search_masked: nwords must be ceil(count / 32)%s");
+    if (!host_allow_bits) return fail(CODD_KNN_EINVAL, "null allow bits%s");
+    ix->stat_ivf_masked++;
+    int64_t m = 0;   // (counted by the staging pass, not needed: nothing here depends on it)
+    if ((rc = stage_host_mask(ix, host_allow_bits, nwords, n, &m)) != 0) return rc;
+    if ((rc = upload_staged_mask(ix, nwords, st)) != 0) return rc;
+    return ivf_masked_body(ix, dev_queries, B, k, nprobe, ix->mask_allow, nwords, row_base, dev_keys, dev_dist, dev_rows, st);
+}
+
+int codd_knn_ivf_search_masked_dev(codd_knn_index* ix, const float* dev_queries, int B, int k, int nprobe, const uint32_t* dev_allow_bits, int64_t nwords,
+                                   uint32_t row_base, uint64_t* dev_keys, float* dev_dist, int64_t* dev_rows, void* stream) {
+    int rc;
+    if ((rc = ivf_check_args(ix, dev_queries, B, k, &nprobe)) != 0) return rc;
+    DeviceGuard guard(ix->device);
+    hipStream_t st = (hipStream_t)stream;
+    WorkScope work(ix, st), work_coarse(ix->coarse, st);
+    if (nwords != (ix->count + 31) / 32) return fail(CODD_KNN_EINVAL, "ivf_search_masked_dev: nwords must be ceil(count / 32)%s");
+    if (!dev_allow_bits) return fail(CODD_KNN_EINVAL, "null allow bits%s");
+    ix->stat_ivf_masked++;
+    // the caller's words are read once, by mask_deny_kernel on `st` (which clips them to [0, count) itself): no count, no read-back
+    return ivf_masked_body(ix, dev_queries, B, k, nprobe, dev_allow_bits, nwords, row_base, dev_keys, dev_dist, dev_rows, st);
+}
+
+int codd_knn_slice_mask(int device, const uint32_t* dev_global_bits, int64_t global_rows, int64_t row_base, int64_t count, uint32_t* dev_out,
+                        int64_t nwords, void* stream) {
+    if (global_rows < 0 || row_base < 0 || count < 0) return fail(CODD_KNN_EINVAL, "slice_mask: negative global_rows, row_base or count%s");
+    if (nwords != (count + 31) / 32) return fail(CODD_KNN_EINVAL, "slice_mask: nwords must be ceil(count / 32)%s");
+    if (nwords == 0) return CODD_KNN_OK;
+    if (!dev_out || (global_rows > 0 && !dev_global_bits)) return fail(CODD_KNN_EINVAL, "slice_mask: null words%s");
+    DeviceGuard guard(device);
+    const int rc = launch_kernel<mask_slice_kernel>(dim3((unsigned)((nwords + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dev_global_bits, global_rows,
+                                                    row_base, count, dev_out, nwords);
+    if (rc != 0) return rc;
+    HIP_TRY(hipGetLastError());
+    return CODD_KNN_OK;
 }
 
 int codd_knn_set_documents_host(codd_knn_index* ix, const uint8_t* host_bytes, const int64_t* host_offsets, int64_t n) {
@@ -4068,6 +4165,7 @@ int codd_knn_get_stat(const codd_knn_index* ix, const char* key, int64_t* out) {
     else if (strcmp(key, "last_scan_group") == 0) *out = ix->stat_last_scan_group;
     else if (strcmp(key, "last_finalize_parts") == 0) *out = ix->stat_last_finalize_parts;
     else if (strcmp(key, "ivf_shared_searches") == 0) *out = ix->stat_ivf_shared;
+    else if (strcmp(key, "ivf_masked_searches") == 0) *out = ix->stat_ivf_masked;
     else if (strcmp(key, "scoped_searches") == 0) *out = ix->stat_scoped_searches;
     else if (strcmp(key, "scope_builds") == 0) *out = ix->stat_scope_builds;
     else if (strcmp(key, "scopes") == 0) *out = (int64_t)ix->max_scope;

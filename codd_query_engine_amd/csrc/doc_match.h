@@ -118,4 +118,25 @@ __global__ __launch_bounds__(256) void mask_clip_count_kernel(const uint32_t* __
     if (tid == 0 && s_sum[0] != 0u) atomicAdd(visible, (unsigned long long)s_sum[0]);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// A shard's words out of a mask over GLOBAL rows (codd_knn_slice_mask): out word w holds the global bits
+// [row_base + 32 w, row_base + 32 w + 32) — a funnel shift of the two global words they lie in, row_base being arbitrary — with
+// the bits past global_rows or past the shard's count zero.  One thread per output word; no load past the last global word.
+// ---------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void mask_slice_kernel(const uint32_t* __restrict__ global_bits, int64_t global_rows, int64_t row_base, int64_t count,
+                                                         uint32_t* __restrict__ out, int64_t nwords) {
+    const int64_t w = (int64_t)blockIdx.x * 256 + (int64_t)threadIdx.x;
+    if (w >= nwords) return;
+    const int64_t gwords = (global_rows + 31) >> 5;
+    const int64_t first = row_base + w * 32;   // the global row of this word's bit 0
+    const int64_t gw = first >> 5;
+    const uint32_t sh = (uint32_t)(first & 31);
+    const uint32_t lo = gw < gwords ? global_bits[gw] : 0u;
+    const uint32_t hi = sh != 0u && gw + 1 < gwords ? global_bits[gw + 1] : 0u;
+    const uint32_t v = sh != 0u ? (lo >> sh) | (hi << (32u - sh)) : lo;
+    const int64_t left_g = global_rows - first, left_c = count - w * 32;
+    const int64_t left = left_g < left_c ? left_g : left_c;
+    out[w] = v & (left >= 32 ? 0xffffffffu : (left > 0 ? (1u << (uint32_t)left) - 1u : 0u));
+}
+
 }  // namespace codd

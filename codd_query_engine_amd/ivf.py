@@ -94,10 +94,25 @@ def build_ivf(index: DeviceKnnIndex, nlist: int, iters: int = 8, sample: Optiona
             "train_rows": int(train.shape[0]), "iters": iters}
 
 
-def search_ivf(index: DeviceKnnIndex, queries, k: int, nprobe: int, row_base: int = 0):
-    """(dist [B,k] fp32 ascending, rows [B,k] int64 original slots, -1 padded) on the device."""
+def _is_device_mask(allow) -> bool:
     import torch
 
+    return isinstance(allow, torch.Tensor) and allow.is_cuda
+
+
+def search_ivf(index: DeviceKnnIndex, queries, k: int, nprobe: int, row_base: int = 0, allow=None):
+    """(dist [B,k] fp32 ascending, rows [B,k] int64 original slots, -1 padded) on the device.
+
+    allow: one row mask for the whole batch (a `where=` / `where_document=` filter).  A numpy bool array of length count() or
+    packed uint32 words go through codd_knn_ivf_search_masked; a 1-d int32 CUDA tensor of packed words (match_documents' form)
+    through codd_knn_ivf_search_masked_dev, with no host synchronisation.  The probed lists are the ones the unmasked search
+    probes; the mask only removes rows from them, so a small mask may leave fewer than k hits."""
+    import torch
+
+    if allow is not None:
+        if _is_device_mask(allow):
+            return index.ivf_search_masked_dev_tensors(queries, allow, k, nprobe, row_base)
+        return index.ivf_search_masked_tensors(queries, allow, k, nprobe, row_base)
     lib = native.load()
     q = index._queries_tensor(queries)
     B = q.shape[0]
@@ -111,10 +126,15 @@ def search_ivf(index: DeviceKnnIndex, queries, k: int, nprobe: int, row_base: in
     return dist, rows
 
 
-def search_ivf_keys(index: DeviceKnnIndex, queries, k: int, nprobe: int, row_base: int = 0):
-    """Shard-local half of a row-sharded IVF search: [B,k] packed keys carrying GLOBAL rows (as codd_knn_search_keys)."""
+def search_ivf_keys(index: DeviceKnnIndex, queries, k: int, nprobe: int, row_base: int = 0, allow=None):
+    """Shard-local half of a row-sharded IVF search: [B,k] packed keys carrying GLOBAL rows (as codd_knn_search_keys).
+    allow: as in search_ivf (the mask is over the shard's LOCAL row slots)."""
     import torch
 
+    if allow is not None:
+        if _is_device_mask(allow):
+            return index.ivf_search_keys_masked_dev(queries, allow, k, nprobe, row_base)
+        return index.ivf_search_keys_masked(queries, allow, k, nprobe, row_base)
     lib = native.load()
     q = index._queries_tensor(queries)
     B = q.shape[0]
@@ -128,10 +148,26 @@ def search_ivf_keys(index: DeviceKnnIndex, queries, k: int, nprobe: int, row_bas
 
 class IvfShardEngine:
     """What ShardedSearcher needs from an engine, answered by the shard's IVF lists (BASELINE configs[4]: every rank
-    builds an IVF over its own rows; the exchange is the same all_gather of B*k keys as for the flat search)."""
+    builds an IVF over its own rows; the exchange is the same all_gather of B*k keys as for the flat search).  The masked
+    forms answer a shard-local `allow` under the same `nprobe` lists (search_ivf_keys(..., allow=))."""
 
     def __init__(self, index: DeviceKnnIndex, nprobe: int):
         self.index, self.nprobe = index, int(nprobe)
 
+    def count(self) -> int:
+        return self.index.count()
+
     def search_keys(self, queries, k: int, row_base: int = 0):
         return search_ivf_keys(self.index, queries, k, self.nprobe, row_base)
+
+    def search_keys_masked(self, queries, allow, k: int, row_base: int = 0):
+        return self.index.ivf_search_keys_masked(queries, allow, k, self.nprobe, row_base)
+
+    def search_keys_masked_dev(self, queries, allow_bits, k: int, row_base: int = 0):
+        return self.index.ivf_search_keys_masked_dev(queries, allow_bits, k, self.nprobe, row_base)
+
+    def match_documents(self, needle: bytes):
+        return self.index.match_documents(needle)
+
+    def slice_mask(self, global_bits, global_rows: int, row_base: int):
+        return self.index.slice_mask(global_bits, global_rows, row_base)

@@ -37,6 +37,8 @@ class DeviceKnnIndex:
         count() / upsert(slots, vecs) / search(queries, k) -> (dist, rows) as numpy;
         optionally set_scopes / search_scoped (`where=` by namespace), search_masked (any other `where=`), set_documents /
         match_documents / search_masked_dev (`where_document=` on the device) and delete / live_count / compact (`Collection.delete`).
+    The ivf_search_*masked* methods are the same masks under an installed IVF layout (ivf.py), slice_mask cuts a shard's words
+    out of a mask over global rows (sharded.py).
     """
 
     def __init__(self, dim: int, dtype: str = "f32", device: str = "cuda:0"):
@@ -344,6 +346,51 @@ class DeviceKnnIndex:
         """search_keys among the rows the device mask names."""
         return self._search_masked_dev(queries, allow_bits, k, row_base, True)[0]
 
+    # ------------------------------------------------------------------ masks under an IVF layout
+    def _ivf_search_masked(self, queries, allow, k: int, nprobe: int, row_base: int, want_keys: bool, on_device: bool):
+        torch = _torch()
+        q = self._queries_tensor(queries)
+        B = q.shape[0]
+        if on_device:
+            words = self._allow_words_tensor(allow)
+            ptr, fn, name = words.data_ptr() if words.shape[0] else None, self._lib.codd_knn_ivf_search_masked_dev, "codd_knn_ivf_search_masked_dev"
+        else:
+            words = self._allow_words(allow)
+            ptr, fn, name = words.ctypes.data, self._lib.codd_knn_ivf_search_masked, "codd_knn_ivf_search_masked"
+        keys = torch.empty((B, k), dtype=torch.int64, device=self.device) if want_keys else None
+        dist = None if want_keys else torch.empty((B, k), dtype=torch.float32, device=self.device)
+        rows = None if want_keys else torch.empty((B, k), dtype=torch.int64, device=self.device)
+        native.check(
+            fn(self._h, q.data_ptr(), B, int(k), int(nprobe), ptr, words.shape[0], int(row_base), keys.data_ptr() if want_keys else None,
+               None if want_keys else dist.data_ptr(), None if want_keys else rows.data_ptr(), self._stream()),
+            name,
+        )
+        return keys, dist, rows
+
+    def ivf_search_masked_tensors(self, queries, allow, k: int, nprobe: int, row_base: int = 0):
+        """ivf.search_ivf among the rows `allow` names (host mask: bool array or packed uint32 words) that are not deleted: the
+        `nprobe` lists are chosen as without a mask, the top-k is exact among the allowed live rows of those lists."""
+        _, dist, rows = self._ivf_search_masked(queries, allow, k, nprobe, row_base, False, False)
+        return dist, rows
+
+    def ivf_search_keys_masked(self, queries, allow, k: int, nprobe: int, row_base: int = 0):
+        """ivf.search_ivf_keys among the rows the host mask names."""
+        return self._ivf_search_masked(queries, allow, k, nprobe, row_base, True, False)[0]
+
+    def ivf_search_masked_dev_tensors(self, queries, allow_bits, k: int, nprobe: int, row_base: int = 0):
+        """ivf_search_masked_tensors under a mask that is on the device already (match_documents' form).  Nothing is read back:
+        the call is asynchronous on the current stream."""
+        _, dist, rows = self._ivf_search_masked(queries, allow_bits, k, nprobe, row_base, False, True)
+        return dist, rows
+
+    def ivf_search_keys_masked_dev(self, queries, allow_bits, k: int, nprobe: int, row_base: int = 0):
+        """ivf.search_ivf_keys among the rows the device mask names."""
+        return self._ivf_search_masked(queries, allow_bits, k, nprobe, row_base, True, True)[0]
+
+    def slice_mask(self, global_bits, global_rows: int, row_base: int):
+        """This shard's words of a mask over GLOBAL rows: bit r of the result = global bit row_base + r, for r < count()."""
+        return slice_mask(global_bits, global_rows, row_base, self.count(), self.device)
+
     def merge_keys(self, keys, k: int):
         """Top-k of [B,m] packed keys -> (keys [B,k], dist [B,k], rows [B,k]) on device."""
         return merge_keys(keys, k, self.device)
@@ -387,6 +434,30 @@ def merge_keys(keys, k: int, device=None):
         "codd_knn_merge_keys",
     )
     return out_keys, dist, rows
+
+
+def slice_mask(global_bits, global_rows: int, row_base: int, count: int, device=None):
+    """codd_knn_slice_mask: rows [row_base, row_base + count) of a mask over `global_rows` global rows (1-d int32 CUDA tensor of
+    ceil(global_rows / 32) packed words) as the ceil(count / 32) words a shard's masked search takes; row_base need not be a
+    multiple of 32, bits past either end are zero.  Asynchronous on the current stream."""
+    torch = _torch()
+    lib = native.load()
+    if not (isinstance(global_bits, torch.Tensor) and global_bits.is_cuda and global_bits.dtype == torch.int32 and global_bits.dim() == 1):
+        raise ValueError("slice_mask wants the global mask as a 1-d int32 CUDA tensor of packed words")
+    global_rows, row_base, count = int(global_rows), int(row_base), int(count)
+    if global_rows < 0 or row_base < 0 or count < 0 or global_bits.shape[0] != (global_rows + 31) // 32:
+        raise ValueError(f"expected ceil({global_rows} / 32) global words and non-negative row_base / count, got {global_bits.shape[0]} words")
+    global_bits = global_bits.contiguous()
+    dev = global_bits.device if device is None else torch.device(device)
+    nwords = (count + 31) // 32
+    out = torch.empty((nwords,), dtype=torch.int32, device=dev)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    native.check(
+        lib.codd_knn_slice_mask(dev.index or 0, global_bits.data_ptr() if global_bits.shape[0] else None, global_rows, row_base, count,
+                                out.data_ptr() if nwords else None, nwords, stream),
+        "codd_knn_slice_mask",
+    )
+    return out
 
 
 def merge_shards(gathered, world_size: int, k: int, device=None):

@@ -30,6 +30,12 @@ def shard_bounds(n_total: int, world_size: int, rank: int) -> tuple[int, int]:
     return begin, min(n_total, begin + per)
 
 
+def _is_device_words(allow) -> bool:
+    import torch
+
+    return isinstance(allow, torch.Tensor) and allow.is_cuda
+
+
 class PendingSearch:
     """Handle of ShardedSearcher.search_async: the results live on a side stream until `.result()`."""
 
@@ -60,6 +66,10 @@ class ShardedSearcher:
     global rows.  Compacting ONE shard (engine.compact) changes its local slots, so the
     caller's row_base bookkeeping must follow: a global row is row_base + local slot, and
     whatever maps global rows to records has to be renumbered for that shard.
+
+    Masks are shard-local too: `allow=` names row slots of this rank's engine (a document filter over the shard's own
+    documents is engine.match_documents' words as they are); a mask compiled once over global rows is passed with
+    allow_global=True and every rank slices out rows [row_base, row_base + engine.count()) itself.
     """
 
     def __init__(self, engine: Any, row_base: int, group: Optional[Any] = None,
@@ -83,23 +93,50 @@ class ShardedSearcher:
         self._streams: list = []
         self._turn = 0
 
-    def search_keys_local(self, queries, k: int, scopes=None):
+    def _local_allow(self, allow):
+        """The shard's own mask out of one over GLOBAL rows: rows [row_base, row_base + engine.count()).  A device mask (int32
+        CUDA words) is cut by the slicing kernel on its device; a host mask (bool array over the global rows, or packed uint32
+        words) with numpy.  Global rows past the mask's end are not allowed."""
+        import numpy as np
+
+        count = int(self.engine.count())
+        if _is_device_words(allow):
+            return self.engine.slice_mask(allow, 32 * int(allow.shape[0]), self.row_base)
+        a = np.asarray(allow)
+        if a.ndim != 1 or a.dtype not in (np.bool_, np.uint32):
+            raise ValueError(f"allow must be a bool array, packed uint32 words or int32 CUDA words, got {a.dtype} {a.shape}")
+        bits = a if a.dtype == np.bool_ else np.unpackbits(np.ascontiguousarray(a).view(np.uint8), bitorder="little").astype(bool)
+        local = np.zeros(count, dtype=bool)
+        have = bits[self.row_base : self.row_base + count]
+        local[: have.shape[0]] = have
+        return local
+
+    def search_keys_local(self, queries, k: int, scopes=None, allow=None, allow_global: bool = False):
+        if allow is not None:
+            if scopes is not None:
+                raise ValueError("scopes and allow cannot be combined: fold the scope into the mask")
+            if allow_global:
+                allow = self._local_allow(allow)
+            if _is_device_words(allow):
+                return self.engine.search_keys_masked_dev(queries, allow, k, self.row_base)
+            return self.engine.search_keys_masked(queries, allow, k, self.row_base)
         if scopes is None:
             return self.engine.search_keys(queries, k, self.row_base)
         return self.engine.search_keys_scoped(queries, scopes, k, self.row_base)
 
-    def search_async(self, queries, k: int, depth: int = 2, scopes=None) -> "PendingSearch":
+    def search_async(self, queries, k: int, depth: int = 2, scopes=None, allow=None, allow_global: bool = False) -> "PendingSearch":
         """Issue one batch on a side stream and return at once; `.result()` makes the caller's stream wait for it.
 
         Consecutive batches go to `depth` alternating HIP streams, so the small kernels, the all_gather and the merge
         of batch i overlap the filter kernel of batch i+1 (the engine keeps one workspace per stream).  Every rank must
         issue its batches in the same order, as with `search`.  With a host engine (gloo tests) it runs synchronously.
+        A device `allow` must have been written on the caller's current stream (the side stream waits for that one).
         """
         import torch
 
         dev = getattr(queries, "device", None)
         if not (isinstance(queries, torch.Tensor) and dev is not None and dev.type == "cuda"):
-            return PendingSearch(None, self.search(queries, k, scopes))
+            return PendingSearch(None, self.search(queries, k, scopes, allow, allow_global))
         if len(self._streams) != depth:
             self._streams = [torch.cuda.Stream(device=dev) for _ in range(depth)]
             self._turn = 0
@@ -107,18 +144,27 @@ class ShardedSearcher:
         self._turn = (self._turn + 1) % depth
         side.wait_stream(torch.cuda.current_stream(dev))  # the queries are ready
         with torch.cuda.stream(side):
-            out = self.search(queries, k, scopes)
+            out = self.search(queries, k, scopes, allow, allow_global)
         queries.record_stream(side)
+        if _is_device_words(allow):
+            allow.record_stream(side)
         return PendingSearch(side, out)
 
-    def search(self, queries, k: int, scopes=None):
+    def search(self, queries, k: int, scopes=None, allow=None, allow_global: bool = False):
         """(dist [B,k], global rows [B,k]) — identical on every rank.  `scopes` ([B] scope labels, the same on every
         rank and the same labelling on every shard) restricts each query to its scope: the shards answer with
-        search_keys_scoped, the merge is the same."""
+        search_keys_scoped, the merge is the same.
+
+        `allow` restricts the whole batch to the rows a mask names (`where=` / `where_document=`): the shard-LOCAL mask, as
+        a host bool array of engine.count() entries or packed uint32 words (engine.search_keys_masked), or as int32 CUDA
+        words, e.g. what engine.match_documents returned (engine.search_keys_masked_dev).  With allow_global=True it is one
+        mask over the GLOBAL rows, the same on every rank, and each rank cuts its own rows out first (on the device for
+        device words).  `scopes` and `allow` together raise ValueError.  A rank whose mask allows nothing still joins the
+        collective, with the all-empty keys its engine returns."""
         import torch
         import torch.distributed as dist
 
-        local = self.search_keys_local(queries, k, scopes)  # [B,k] int64
+        local = self.search_keys_local(queries, k, scopes, allow, allow_global)  # [B,k] int64
         if self.world_size == 1 and not self.always_gather:
             _, d, r = self._merge(local, k)
             return d, r

@@ -21,7 +21,7 @@
  *   - `stream` is a hipStream_t passed as void* (NULL = the null stream).  Calls
  *     are asynchronous with respect to the host unless stated otherwise.
  *   - thread-safety: the search entry points (codd_knn_search, _search_keys, _search_scoped,
- *     _search_masked, _search_masked_dev, _match_documents, _ivf_search, _approx_scores) may be called from several host threads and on
+ *     _search_masked, _search_masked_dev, _match_documents, _ivf_search, _ivf_search_masked, _ivf_search_masked_dev, _approx_scores) may be called from several host threads and on
  *     several streams of one index: the index keeps one workspace per stream (up to
  *     4; a fifth stream takes over the least recently used one, ordered behind its
  *     previous owner on the device) and serialises only the enqueueing.  Searches on
@@ -295,6 +295,48 @@ int codd_knn_search_masked_dev(codd_knn_index* index, const float* dev_queries, 
                                int64_t nwords, uint32_t row_base, uint64_t* dev_keys, float* dev_dist, int64_t* dev_rows, void* stream);
 
 /*
+ * Replaces: the `where` / `where_document` of collection.query on the two routes that scale the engine: the coarse-IVF search and
+ *           the row-sharded search.  The masks are those of codd_knn_search_masked: bit (r & 31) of word (r >> 5)
+ *           set = ORIGINAL row slot r may be returned; one mask per call, shared by the B queries.
+ * ivf_search_masked: codd_knn_ivf_search restricted to the rows that are allowed AND live.  Probe selection is unchanged: the nprobe
+ *           best lists per query come from the exact centroid score, whatever the mask says — the mask removes rows from the probed
+ *           lists, it never sends the search to other lists.  The answer is the exact canonical top-k among the rows that are
+ *           allowed, live and in the probed lists: the same scores, tie rule and padding, min(k, such rows) hits — under a mask that
+ *           leaves few rows in the probed lists that is fewer than k, and fewer than codd_knn_search_masked finds.  With
+ *           nprobe == nlist the result is the bits of codd_knn_search_masked; an all-ones mask returns the bits of
+ *           codd_knn_ivf_search; a mask that allows no row (or only dead ones) gives an all-empty result (keys 0, rows -1, distances
+ *           +inf).  nwords must equal ceil(count / 32), else EINVAL; bits at or above count are ignored.  No IVF layout, or a stale one
+ *           (rows changed since codd_knn_ivf_install): EINVAL, as for codd_knn_ivf_search; B, k, nprobe and the three outputs as there.
+ *           host_allow_bits is host memory and is consumed before the call returns, by the staging and copy rules of
+ *           codd_knn_search_masked: the words are clipped into the pinned staging buffer of the stream's workspace, from where one
+ *           asynchronous copy on `stream` takes them to the device; the caller may reuse or free its words at once; a second
+ *           host-mask search on the same stream waits on the host until the first one's copy has left the staging buffer — not for
+ *           its kernels.  One small kernel then writes ~allow | dead into the workspace, and the list scans test that bitmap, by
+ *           original row slot, where they test the tombstone bits otherwise: the same kernels and launches as codd_knn_ivf_search
+ *           (the per-pair scan, or the list-sharing scan from 1,024 pairs on), one launch more.
+ * ivf_search_masked_dev: the same under a mask that is already on the device: nwords device words, read on `stream` behind whatever
+ *           wrote them there (codd_knn_match_documents, codd_knn_slice_mask, a torch bitwise op ...), once, by that small kernel;
+ *           the caller's words are not needed once `stream` has run the call.  THE ROUTE DOES NOT DEPEND ON THE NUMBER OF VISIBLE
+ *           ROWS, so nothing is counted and nothing is read back: unlike codd_knn_search_masked_dev this entry point does not
+ *           synchronise `stream` and is asynchronous with respect to the host, like codd_knn_ivf_search.
+ * slice_mask: a shard's words out of a mask over GLOBAL rows — a `where` mask is compiled once over global row numbers and
+ *           replicated; every rank of a row-sharded index cuts its own rows out on its device and searches under the result
+ *           (_search_masked_dev, _ivf_search_masked_dev).  Static like codd_knn_merge_keys, `device` as in codd_knn_create.
+ *           dev_global_bits: ceil(global_rows / 32) device words, bit g of the mask = global row g.  dev_out: nwords ==
+ *           ceil(count / 32) device words (else EINVAL); bit r of the result = global bit row_base + r for r < count and
+ *           row_base + r < global_rows, every other bit zero.  row_base is arbitrary — not a multiple of 32 in general: an output word
+ *           is a funnel shift of two neighbouring global words — and may lie at or past global_rows (all zero); negative
+ *           global_rows, row_base or count: EINVAL.  No word past the last global word is loaded; bits of that word at or above
+ *           global_rows are ignored.  Asynchronous on `stream`; one launch of mask_slice_kernel (csrc/doc_match.h).
+ */
+int codd_knn_ivf_search_masked(codd_knn_index* index, const float* dev_queries, int B, int k, int nprobe, const uint32_t* host_allow_bits,
+                               int64_t nwords, uint32_t row_base, uint64_t* dev_keys, float* dev_dist, int64_t* dev_rows, void* stream);
+int codd_knn_ivf_search_masked_dev(codd_knn_index* index, const float* dev_queries, int B, int k, int nprobe, const uint32_t* dev_allow_bits,
+                                   int64_t nwords, uint32_t row_base, uint64_t* dev_keys, float* dev_dist, int64_t* dev_rows, void* stream);
+int codd_knn_slice_mask(int device, const uint32_t* dev_global_bits, int64_t global_rows, int64_t row_base, int64_t count, uint32_t* dev_out,
+                        int64_t nwords, void* stream);
+
+/*
  * Tuning / introspection (never needed for correctness).
  *   options: "scan_blocks_per_cu" (1..8); "filter" (0/1: MFMA filter path for large batches);
  *            "filter_min_batch" (9), "filter_min_rows" (1: batches >= filter_min_batch always
@@ -339,7 +381,8 @@ int codd_knn_search_masked_dev(codd_knn_index* index, const float* dev_queries, 
  *            recorded on the launch stream (0 = off; resets the log)
  *   stats  : "searches", "scan_launches", "last_scan_blocks", "last_scan_group" (queries per pass over the rows of the
  *            last exact scan), "last_finalize_parts" (workgroups per query of the last filter pass's finalize),
- *            "ivf_shared_searches" (IVF searches that scanned each probed list once for all its queries), "scoped_searches",
+ *            "ivf_shared_searches" (IVF searches that scanned each probed list once for all its queries), "ivf_masked_searches" (IVF searches
+ *            under a row mask, host or device words), "scoped_searches",
  *            "scope_builds" (times the scope lists were rebuilt), "scopes" (highest scope label ever set), "dead_rows" (tombstones below count),
  *            "delete_calls", "compactions" (codd_knn_compact calls that moved rows), "masked_searches", "mask_list_searches",
  *            "mask_dense_searches" (masked searches by route), "last_mask_rows" (allowed live rows of the last masked search),
