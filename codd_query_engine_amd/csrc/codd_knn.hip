@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "codd_knn.h"
+#include "device_mem.h"
 
 #ifndef CODD_EXPERIMENTS
 #define CODD_EXPERIMENTS 0  // 1 (build_variant only): the diagnostic switches that can return wrong results exist
@@ -1450,41 +1451,42 @@ struct FilterCtl {
 // Search workspace.  An index keeps up to kMaxWork of them, one per HIP stream that searches it, so that searches
 // issued on different streams (the next batch while this batch's small kernels and its collective are still in
 // flight) never share scratch memory.  The index inherits one set of these fields: WorkScope loads the calling
-// stream's set into them for the duration of one call and stores it back.
+// stream's set into them for the duration of one call and stores it back (a swap each way: one owner at any time).
 struct WorkBufs {
     // (grown on demand, never inside a captured region after warm-up)
-    float* qn = nullptr;       int64_t qn_cap = 0;        // [B][dpad] normalised queries
-    u64* partial = nullptr;    int64_t partial_cap = 0;   // [B][blocks][k]
-    u64* keys_tmp = nullptr;   int64_t keys_tmp_cap = 0;  // [B][k]
-    uint4* qfrag = nullptr;    int64_t qfrag_cap = 0;     // pieces
-    float* thr = nullptr;                                  // [512]: thr[256], thr0[256]
-    u64* bucket_max = nullptr; int64_t bucket_cap = 0;     // [256][sample tiles] best (score, row) key per sampled tile
-    u64* hits = nullptr;       int64_t hits_cap = 0;      // [256][hit_cap_q]
-    FilterCtl* ctl = nullptr;                              // device
-    u64* fb_partial = nullptr; int64_t fb_partial_cap = 0; // [256][blocks][k] partials of the fallback scan
-    uint4* qfrag8 = nullptr;   int64_t qfrag8_cap = 0;    // int8 query fragments (pieces)
-    float* qmeta = nullptr;                                // [1024]: per query: scale, 2*eps (device-wide bound), A, B (eps per block = A + B e_block)
-    u64* sb_cand = nullptr;    int64_t sb_cand_cap = 0;    // small_batch_kernel: [waves][kSbKeep] published keys, then [waves] dropmax
-    u64* probe_keys = nullptr; int64_t probe_cap = 0;      // IVF: [B][nprobe] coarse keys
-    u64* ivf_partial = nullptr; int64_t ivf_partial_cap = 0;
-    unsigned* ivf_group = nullptr; int64_t ivf_group_cap = 0;  // IVF at batch: [nlist] counters, [nlist+1] pair starts, [nlist+1] item starts, [B*nprobe] pairs by list
-    unsigned* scope_group = nullptr; int64_t scope_group_cap = 0;  // scoped search: [B] queries in (scope, query) order, [B] their ranks inside the scope
+    DevBuf<float> qn;             // [B][dpad] normalised queries
+    DevBuf<u64> partial;          // [B][blocks][k]
+    DevBuf<u64> keys_tmp;         // [B][k]
+    DevBuf<uint4> qfrag;          // pieces
+    DevBuf<float> thr;            // [512]: thr[256], thr0[256]
+    DevBuf<u64> bucket_max;       // [256][sample tiles] best (score, row) key per sampled tile
+    DevBuf<u64> hits;             // [256][hit_cap_q]
+    DevBuf<FilterCtl> ctl;        // device
+    DevBuf<u64> fb_partial;       // [256][blocks][k] partials of the fallback scan
+    DevBuf<uint4> qfrag8;         // int8 query fragments (pieces)
+    DevBuf<float> qmeta;          // [1024]: per query: scale, 2*eps (device-wide bound), A, B (eps per block = A + B e_block)
+    DevBuf<u64> sb_cand;          // small_batch_kernel: [waves][kSbKeep] published keys, then [waves] dropmax
+    DevBuf<u64> probe_keys;       // IVF: [B][nprobe] coarse keys
+    DevBuf<u64> ivf_partial;
+    DevBuf<unsigned> ivf_group;   // IVF at batch: [nlist] counters, [nlist+1] pair starts, [nlist+1] item starts, [B*nprobe] pairs by list
+    DevBuf<unsigned> scope_group; // scoped search: [B] queries in (scope, query) order, [B] their ranks inside the scope
     // masked search: the call's allow bits, and what the two routes derive from them
-    uint32_t* mask_host = nullptr;   int64_t mask_host_cap = 0;    // pinned staging of the allow words; mask_uploaded: its last copy to the device
-    hipEvent_t mask_uploaded = nullptr; bool mask_upload_pending = false;
-    uint32_t* mask_allow = nullptr;  int64_t mask_allow_cap = 0;   // [ceil(count / 32)] device copy of the allow words
-    uint32_t* mask_deny = nullptr;   int64_t mask_deny_cap = 0;    // dense route: [ceil(capacity / 32)] ~allow | dead, ones past the mask
-    unsigned* mask_prefix = nullptr; int64_t mask_prefix_cap = 0;  // list route: [words] prefixes, [blocks] totals, [blocks + 1] bases
-    uint32_t* mask_list = nullptr;   int64_t mask_list_cap = 0;    // list route: [m] visible row slots, ascending
+    PinnedBuf<uint32_t> mask_host;  // pinned staging of the allow words; mask_uploaded: its last copy to the device
+    Event mask_uploaded; bool mask_upload_pending = false;
+    DevBuf<uint32_t> mask_allow;    // [ceil(count / 32)] device copy of the allow words
+    DevBuf<uint32_t> mask_deny;     // dense route: [ceil(capacity / 32)] ~allow | dead, ones past the mask
+    DevBuf<unsigned> mask_prefix;   // list route: [words] prefixes, [blocks] totals, [blocks + 1] bases
+    DevBuf<uint32_t> mask_list;     // list route: [m] visible row slots, ascending
     // codd_knn_search_masked_dev: the visible rows of a device mask, counted on the device and read back through pinned memory
-    unsigned long long* mask_m_dev = nullptr;
-    unsigned long long* mask_m_host = nullptr;
+    DevBuf<unsigned long long> mask_m_dev;
+    PinnedBuf<unsigned long long> mask_m_host;
 };
+static_assert(!std::is_copy_constructible<WorkBufs>::value, "a workspace has one owner (WorkScope swaps, never copies)");
 constexpr int kMaxWork = 4;
 struct WorkSlot {
     WorkBufs bufs;
     hipStream_t stream = nullptr;
-    hipEvent_t handover = nullptr;  // recorded on the old stream when the slot changes hands
+    Event handover;                 // recorded on the old stream when the slot changes hands
     bool used = false;
     uint64_t tick = 0;              // last use (LRU)
 };
@@ -1499,31 +1501,31 @@ struct codd_knn_index : WorkBufs {
     int scan_blocks_per_cu = 4;
     int64_t capacity = 0;  // row slots allocated
     int64_t count = 0;     // highest written slot + 1
-    void* rows = nullptr;  // [capacity][dpad] storage dtype
+    DevBuf<unsigned char> rows;  // [capacity][dpad] storage dtype, as bytes
     // bf16 fragment-order copy, whole 256-row tiles.  Derived data like the int8 shadow: built lazily from the stored rows by the
     // first search that needs it (batches above 256 queries, an index with the int8 filter off or cooling down, the IVF
     // build), brought up to date incrementally over the rows written since
-    uint4* shadow = nullptr;
+    DevBuf<uint4> shadow;
     int64_t shadow_rows = 0;       // rows the shadow allocation covers (multiple of 256)
     int64_t shadow_epoch = -1;
     int64_t dirty16_lo = 0, dirty16_hi = 0;
     hipStream_t shadow_stream = nullptr;
-    hipEvent_t shadow_ready = nullptr;
+    Event shadow_ready;
     int64_t stat_shadow_builds = 0;
     int64_t shadow_nomem_epoch = -1;   // row epoch at which allocating the bf16 shadow failed: not retried until rows change
     int64_t stat_shadow_nomem = 0;
     int debug_fail_shadow_alloc = 0;   // test hook ("debug_fail_shadow_alloc"): the next bf16-shadow allocation reports out of memory
     // stored rows written on a caller's stream (upsert_device): searches on other streams wait for this on the device
-    hipEvent_t rows_ready = nullptr;
+    Event rows_ready;
     hipStream_t rows_stream = nullptr;
     bool rows_event_set = false;
     // ... and rows read on a caller's stream outside a search (copy_rows_f32): the next writer on another stream waits for it
-    hipEvent_t reader_done = nullptr;
+    Event reader_done;
     hipStream_t reader_stream = nullptr;
     bool reader_event_set = false;
     // staging of codd_knn_upsert_host (kept between calls: the indexer job upserts in small batches)
-    float* stage_vec = nullptr;   int64_t stage_vec_cap = 0;
-    int64_t* stage_slot = nullptr; int64_t stage_slot_cap = 0;
+    DevBuf<float> stage_vec;
+    DevBuf<int64_t> stage_slot;
     bool all_normalized = true;    // false once a caller stored rows with normalize = 0
 
     // filter path knobs
@@ -1536,7 +1538,7 @@ struct codd_knn_index : WorkBufs {
     int hit_cap_q = 131072;  // candidates kept per query before it falls back to the exact scan (256 MiB per searching stream at 256 queries:
                              // a cluster of 60,000 near-identical rows — closer to each other than either filter's slack — stays on the filter path)
 
-    unsigned long long* dstats = nullptr;                  // device counters: hits, survivors, fallback queries
+    DevBuf<unsigned long long> dstats;                     // device counters: hits, survivors, fallback queries
 
     // int8 shadow for small batches (optional; rebuilt lazily from the stored rows when they have changed)
     int shadow8_enabled = 1;
@@ -1557,23 +1559,23 @@ struct codd_knn_index : WorkBufs {
     int sample_div8 = 28;         // its thresholds come from a larger sample (the int8 slack is ~5x the bf16 one)
     int sample_rounds8 = 2;       // ... of at least this many rounds of workgroups (one tile each) when the batch has more than 32 queries (3 until the round-3 epilogue:
                                   // at 1.25M rows two rounds trade 13 us of sample for 7 us of filter, gpurun_out/r3n/ab_sample_1p25m.txt)
-    uint4* shadow8 = nullptr;
+    DevBuf<uint4> shadow8;
     int64_t shadow8_rows = 0;     // rows the allocation covers (multiple of 256)
-    float* rscale = nullptr;      // [shadow8_rows]
-    float2* bmeta = nullptr;      // [shadow8_rows / 32]: per 32-row block {scale, largest error norm |c - c~| of its rows}; NaN scale: no row of the block exists
-    unsigned* eps_r_bits = nullptr;  // device scalar: max row error norm (float bits)
+    DevBuf<float> rscale;         // [shadow8_rows]
+    DevBuf<float2> bmeta;         // [shadow8_rows / 32]: per 32-row block {scale, largest error norm |c - c~| of its rows}; NaN scale: no row of the block exists
+    DevBuf<unsigned> eps_r_bits;     // device scalar: max row error norm (float bits)
     int64_t shadow8_epoch = -1;
     int64_t dirty_lo = 0, dirty_hi = 0;  // rows written since the int8 shadow was last brought up to date: [lo, hi)
     hipStream_t shadow8_stream = nullptr;  // the stream the last rebuild ran on, and its completion
-    hipEvent_t shadow8_ready = nullptr;
+    Event shadow8_ready;
     int64_t stat_shadow8_builds = 0, stat_shadow8_passes = 0, stat_i8v2_passes = 0, stat_f16_tile_passes = 0;
     int f16_tile = 1;             // the 2-byte filter of 129..256 queries over rows of 6, 12, ... 64-element K-steps (768 elements: 12) runs the tile program of
                                   // filter_i8.h on fp16 operands ("f16_tile" option; 0 = gemm_filter_kernel)
     // the worst row's quantisation error, copied back asynchronously after every build: a corpus with badly
     // quantisable rows (one large element, many small ones) would make the int8 bound useless and send every small batch
     // to the exact-scan fallback, so such an index keeps the bf16 filter.  Performance only: never needed for exactness.
-    float* eps_r_host = nullptr;        // pinned
-    hipEvent_t eps_r_copied = nullptr;
+    PinnedBuf<float> eps_r_host;
+    Event eps_r_copied;
     float eps_r_known = 0.0f;
     int64_t wide_blocks_known = 0;      // blocks whose error norm exceeds shadow8_max_eps, as last read back
     float shadow8_max_eps = 0.04f;
@@ -1583,8 +1585,8 @@ struct codd_knn_index : WorkBufs {
     // asynchronously; when the int8 passes since the last look left more than shadow8_max_surv survivors per query, or
     // sent queries to the fallback, the next shadow8_cooldown searches take the bf16 filter, then the int8 one is
     // tried again.  Performance only: either filter returns the same bits.
-    unsigned long long* watch_host = nullptr;  // pinned copy of dstats[0..3]
-    hipEvent_t watch_copied = nullptr;
+    PinnedBuf<unsigned long long> watch_host;  // copy of dstats[0..3]
+    Event watch_copied;
     bool watch_pending = false;
     unsigned long long watch_surv = 0, watch_fb = 0;  // counter values at the last look
     int64_t watch_q8 = 0, watch_q16 = 0;              // queries filtered since then, by path
@@ -1598,37 +1600,37 @@ struct codd_knn_index : WorkBufs {
     float exp_slack_scale = 1.0f;  // always 1 in the shipped library; "exp_slack_pct" exists only in -DCODD_EXPERIMENTS=1 builds
 
     // IVF (optional): rows regrouped by coarse list, original slots, list offsets, the coarse index
-    codd_knn_index* coarse = nullptr;  // nlist centroids, f32
-    void* rows_ivf = nullptr;
-    uint32_t* ivf_ids = nullptr;
-    int64_t* ivf_offsets = nullptr;    // [nlist + 1]
+    codd_knn_index* coarse = nullptr;  // nlist centroids, f32 (owned: destroyed through codd_knn_destroy)
+    DevBuf<unsigned char> rows_ivf;
+    DevBuf<uint32_t> ivf_ids;
+    DevBuf<int64_t> ivf_offsets;       // [nlist + 1]
     int64_t ivf_count = 0;             // rows covered by the IVF layout (must equal count to be fresh)
     int ivf_nlist = 0;
     int64_t ivf_epoch = -1, epoch = 0;  // epoch bumps on every row write; search requires ivf_epoch == epoch
 
     // scopes (optional): a label per row slot and, derived from it like the shadows, the row slots grouped by label
-    uint32_t* scope_of = nullptr;      int64_t scope_of_cap = 0;   // [capacity], 0 = no label; allocated by the first call that needs it
-    uint32_t* scope_perm = nullptr;    int64_t scope_perm_cap = 0; // [count] row slots grouped by scope
-    unsigned* scope_offsets = nullptr; int64_t scope_lists_cap = 0; // [nlist + 1] group starts, then [nlist] counters of the build
+    DevBuf<uint32_t> scope_of;         // [capacity], 0 = no label; allocated by the first call that needs it
+    DevBuf<uint32_t> scope_perm;       // [count] row slots grouped by scope
+    DevBuf<unsigned> scope_offsets;    // [nlist + 1] group starts, then [nlist] counters of the build
     uint32_t max_scope = 0;            // highest label ever set
     int64_t scope_gen = 0;             // bumps on every codd_knn_set_scopes_host
     int64_t scope_built_gen = -1, scope_built_count = -1;  // what scope_perm / scope_offsets were built from
     hipStream_t scope_stream = nullptr;  // the stream the last build ran on, and its completion
-    hipEvent_t scope_ready = nullptr;
+    Event scope_ready;
     int64_t stat_scoped_searches = 0, stat_scope_builds = 0;
 
     // masked search
     int mask_route = 0;        // "mask_route": 0 = by the routing rule, 1 = always the list route, 2 = always the dense route
     int mask_list_pct = 100;   // "mask_list_pct": the list route's side of the cost comparison, in percent (100 = the derived rule)
-    unsigned long long* mask_dstats = nullptr;  // the device counters of the dense masked passes: kept apart from dstats, which the filter watch reads
+    DevBuf<unsigned long long> mask_dstats;     // the device counters of the dense masked passes: kept apart from dstats, which the filter watch reads
     int64_t stat_masked_searches = 0, stat_mask_list = 0, stat_mask_dense = 0, stat_last_mask_rows = 0;
     int64_t stat_masked_dev = 0;   // ... those of them whose mask was on the device already (codd_knn_search_masked_dev)
 
     // document snapshot (optional, derived data like the shadows): every row slot's document in one byte arena, a 0x00
     // behind each, zeros to the end of the allocation (csrc/doc_match.h), and the [count + 1] arena offsets.  Valid while the row
     // epoch and the count are what they were when codd_knn_set_documents_host took it.
-    uint8_t* doc_arena = nullptr;
-    int64_t* doc_offsets = nullptr;
+    DevBuf<uint8_t> doc_arena;
+    DevBuf<int64_t> doc_offsets;
     int64_t doc_bytes = 0;             // the arena: the documents' bytes plus one separator each
     int64_t doc_count = -1, doc_epoch = -1;
     int64_t stat_doc_matches = 0;
@@ -1636,7 +1638,7 @@ struct codd_knn_index : WorkBufs {
     // tombstones: one bit per row slot, set = deleted.  Null until the first codd_knn_delete_host — the kernels
     // take a null pointer as "nothing was ever deleted" and load nothing.  The host keeps a mirror: the write paths refuse dead
     // slots from it and compaction derives the row mapping from it, so nothing is ever read back.
-    uint32_t* dead_bits = nullptr;     int64_t dead_words_cap = 0;  // [ceil(capacity / 32)] device words
+    DevBuf<uint32_t> dead_bits;                                     // [ceil(capacity / 32)] device words
     std::vector<uint32_t> dead_host;                                // the same bits
     int64_t dead_count = 0;                                         // dead slots below `count`
     int64_t first_dead = INT64_MAX;                                 // lowest dead slot
@@ -1653,14 +1655,18 @@ struct codd_knn_index : WorkBufs {
     // optional HIP-event timing of the heavy kernels (bench.py's roofline figure): one (start, stop)
     // pair per launch, recorded on the launch stream, read after a sync
     bool profile = false;
-    std::vector<hipEvent_t> ev;  // 2 * pairs
+    std::vector<Event> ev;  // 2 * pairs
     std::vector<int> ev_kind;
     int ev_used = 0;
 
     WorkSlot slots[kMaxWork];
     uint64_t tick = 0;
     std::mutex mu;  // one host thread at a time enqueues a search (the launches themselves are asynchronous)
+
+    // (the members free themselves: the caller has made `device` current and idle, see codd_knn_destroy)
+    ~codd_knn_index() { (void)codd_knn_destroy(coarse); }
 };
+static_assert(!std::is_copy_constructible<codd_knn_index>::value, "an index owns its device memory");
 
 namespace {
 
@@ -1743,7 +1749,7 @@ struct WorkScope {
             slot = lru;
             WorkSlot& w = ix->slots[slot];
             bool ordered = false;
-            if (!w.handover) (void)hipEventCreateWithFlags(&w.handover, hipEventDisableTiming);
+            (void)w.handover.ensure();
             if (w.handover && hipEventRecord(w.handover, w.stream) == hipSuccess) ordered = hipStreamWaitEvent(st, w.handover, 0) == hipSuccess;
             if (!ordered) {
                 (void)hipGetLastError();
@@ -1754,11 +1760,10 @@ struct WorkScope {
         w.used = true;
         w.stream = st;
         w.tick = ++ix->tick;
-        static_cast<WorkBufs&>(*ix) = w.bufs;
+        std::swap(static_cast<WorkBufs&>(*ix), w.bufs);
     }
     ~WorkScope() {
-        ix->slots[slot].bufs = static_cast<WorkBufs&>(*ix);
-        static_cast<WorkBufs&>(*ix) = WorkBufs();
+        std::swap(static_cast<WorkBufs&>(*ix), ix->slots[slot].bufs);
         ix->mu.unlock();
     }
     WorkScope(const WorkScope&) = delete;
@@ -1780,37 +1785,24 @@ int grow_rows(codd_knn_index* ix, int64_t need, bool exact) {
         while (cap < need) cap += cap / 2 + 1024;
     }
     const size_t row_bytes = (size_t)ix->dpad * elem_size(ix->dtype);
-    void* fresh = nullptr;
-    HIP_TRY(hipMalloc(&fresh, (size_t)cap * row_bytes));
+    DevBuf<unsigned char> fresh;
+    HIP_TRY(fresh.reset(cap * (int64_t)row_bytes));
     hipError_t e = hipMemset(fresh, 0, (size_t)cap * row_bytes);
     if (e == hipSuccess && ix->rows && ix->count > 0) e = hipMemcpy(fresh, ix->rows, (size_t)ix->count * row_bytes, hipMemcpyDeviceToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(fresh);
-        return fail(CODD_KNN_EDEVICE, "row copy on growth failed: %s", hipGetErrorString(e));
-    }
-    if (ix->scope_of && ix->scope_of_cap < cap) {  // the labels grow with the row store: new slots start with scope 0
-        uint32_t* labels = nullptr;
-        e = hipMalloc((void**)&labels, (size_t)cap * sizeof(uint32_t));
+    if (e != hipSuccess) return fail(CODD_KNN_EDEVICE, "row copy on growth failed: %s", hipGetErrorString(e));
+    if (ix->scope_of && ix->scope_of.cap() < cap) {  // the labels grow with the row store: new slots start with scope 0
+        DevBuf<uint32_t> labels;
+        e = labels.reset(cap);
         if (e == hipSuccess) e = hipMemset(labels, 0, (size_t)cap * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMemcpy(labels, ix->scope_of, (size_t)ix->scope_of_cap * sizeof(uint32_t), hipMemcpyDeviceToDevice);
-        if (e != hipSuccess) {
-            if (labels) (void)hipFree(labels);
-            (void)hipFree(fresh);
-            return fail(e == hipErrorOutOfMemory ? CODD_KNN_ENOMEM : CODD_KNN_EDEVICE, "growing the scope labels failed: %s", hipGetErrorString(e));
-        }
-        (void)hipFree(ix->scope_of);
-        ix->scope_of = labels;
-        ix->scope_of_cap = cap;
+        if (e == hipSuccess) e = hipMemcpy(labels, ix->scope_of, (size_t)ix->scope_of.bytes(), hipMemcpyDeviceToDevice);
+        if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? CODD_KNN_ENOMEM : CODD_KNN_EDEVICE, "growing the scope labels failed: %s", hipGetErrorString(e));
+        ix->scope_of = std::move(labels);
     }
     if (ix->dead_bits) {  // ... and so do the tombstone bits, once they exist
         const int rc = grow_dead_bits(ix, cap);
-        if (rc != 0) {
-            (void)hipFree(fresh);
-            return rc;
-        }
+        if (rc != 0) return rc;
     }
-    if (ix->rows) (void)hipFree(ix->rows);
-    ix->rows = fresh;
+    ix->rows = std::move(fresh);
     ix->capacity = cap;
     return CODD_KNN_OK;
 }
@@ -1818,23 +1810,18 @@ int grow_rows(codd_knn_index* ix, int64_t need, bool exact) {
 // the tombstone bits cover `slots` row slots (device words and host mirror; contents kept, new words zero).  Exclusive callers only.
 int grow_dead_bits(codd_knn_index* ix, int64_t slots) {
     const int64_t words = (slots + 31) / 32;
-    if (words <= ix->dead_words_cap) return CODD_KNN_OK;
+    if (words <= ix->dead_bits.cap()) return CODD_KNN_OK;
     try {
         ix->dead_host.resize((size_t)words, 0u);
     } catch (const std::bad_alloc&) {
         return fail(CODD_KNN_ENOMEM, "host allocation failed%s");
     }
-    uint32_t* fresh = nullptr;
-    hipError_t e = hipMalloc((void**)&fresh, (size_t)words * sizeof(uint32_t));
+    DevBuf<uint32_t> fresh;
+    hipError_t e = fresh.reset(words);
     if (e == hipSuccess) e = hipMemset(fresh, 0, (size_t)words * sizeof(uint32_t));
-    if (e == hipSuccess && ix->dead_bits) e = hipMemcpy(fresh, ix->dead_bits, (size_t)ix->dead_words_cap * sizeof(uint32_t), hipMemcpyDeviceToDevice);
-    if (e != hipSuccess) {
-        if (fresh) (void)hipFree(fresh);
-        return fail(e == hipErrorOutOfMemory ? CODD_KNN_ENOMEM : CODD_KNN_EDEVICE, "growing the tombstone bits failed: %s", hipGetErrorString(e));
-    }
-    if (ix->dead_bits) (void)hipFree(ix->dead_bits);
-    ix->dead_bits = fresh;
-    ix->dead_words_cap = words;
+    if (e == hipSuccess && ix->dead_bits) e = hipMemcpy(fresh, ix->dead_bits, (size_t)ix->dead_bits.bytes(), hipMemcpyDeviceToDevice);
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? CODD_KNN_ENOMEM : CODD_KNN_EDEVICE, "growing the tombstone bits failed: %s", hipGetErrorString(e));
+    ix->dead_bits = std::move(fresh);
     return CODD_KNN_OK;
 }
 
@@ -1856,20 +1843,6 @@ int64_t live_in_range(const codd_knn_index* ix, int64_t lo, int64_t hi) {
         else { dead += (ix->dead_host[(size_t)(r >> 5)] >> (r & 31)) & 1u; ++r; }
     }
     return (hi - lo) - dead;
-}
-
-template <typename T>
-int ensure_buf(T** buf, int64_t* cap, int64_t need) {
-    if (need <= *cap) return CODD_KNN_OK;
-    if (*buf) {
-        HIP_TRY(hipDeviceSynchronize());  // a previous search may still read it
-        (void)hipFree(*buf);
-        *buf = nullptr;
-        *cap = 0;
-    }
-    HIP_TRY(hipMalloc((void**)buf, (size_t)need * sizeof(T)));
-    *cap = need;
-    return CODD_KNN_OK;
 }
 
 // ---- kernel dispatch -------------------------------------------------------------------------
@@ -1961,7 +1934,7 @@ constexpr size_t kLdsNoOptIn = 64 * 1024;
 
 // every launch of a template kernel, and every launch with dynamic LDS; the caller checks hipGetLastError
 template <auto Kernel, typename... Args>
-int launch_kernel(dim3 grid, dim3 block, Lds lds, hipStream_t st, Args... args) {
+int launch_kernel(dim3 grid, dim3 block, Lds lds, hipStream_t st, Args&&... args) {  // (by reference: an owning buffer converts to its pointer at the launch itself)
     int rc;
     if (lds.bytes > kLdsNoOptIn && (rc = opt_in_lds<Kernel>(lds.opt_in)) != 0) return rc;
     hipLaunchKernelGGL(Kernel, grid, block, lds.bytes, st, args...);
@@ -2078,7 +2051,7 @@ int exact_scan(codd_knn_index* ix, const float* qn, int nqueries, int k, uint32_
     if (rc != 0) return rc;
     ix->stat_last_scan_blocks = blocks;
     const int64_t stride_q = blocks * k;
-    if ((rc = ensure_buf(&ix->partial, &ix->partial_cap, (int64_t)nqueries * stride_q)) != 0) return rc;
+    HIP_TRY(ix->partial.ensure((int64_t)nqueries * stride_q));
     {
         // ONE launch: up to 8 queries ride along per pass over the rows; a larger batch loops over groups
         // of 8 inside the kernel (small corpora stay L2-resident across the groups, and a batch costs one
@@ -2130,17 +2103,16 @@ size_t filter_lds_bytes(int mode) {
 }
 
 int ensure_filter_workspace(codd_knn_index* ix) {
-    int rc;
-    if ((rc = ensure_buf(&ix->qfrag, &ix->qfrag_cap, (int64_t)kTileQ * (ix->dpad / 8))) != 0) return rc;
-    if ((rc = ensure_buf(&ix->bucket_max, &ix->bucket_cap, (int64_t)ix->sample_tiles * kTileQ)) != 0) return rc;
-    if ((rc = ensure_buf(&ix->hits, &ix->hits_cap, (int64_t)kTileQ * ix->hit_cap_q)) != 0) return rc;
-    if (!ix->thr) HIP_TRY(hipMalloc((void**)&ix->thr, 2 * kTileQ * sizeof(float)));  // thr[q], then thr0[q] (per-block form, int8 tile kernel)
+    HIP_TRY(ix->qfrag.ensure((int64_t)kTileQ * (ix->dpad / 8)));
+    HIP_TRY(ix->bucket_max.ensure((int64_t)ix->sample_tiles * kTileQ));
+    HIP_TRY(ix->hits.ensure((int64_t)kTileQ * ix->hit_cap_q));
+    if (!ix->thr) HIP_TRY(ix->thr.reset(2 * kTileQ));  // thr[q], then thr0[q] (per-block form, int8 tile kernel)
     if (!ix->ctl) {
-        HIP_TRY(hipMalloc((void**)&ix->ctl, sizeof(FilterCtl)));
+        HIP_TRY(ix->ctl.reset(1));
         HIP_TRY(hipMemset(ix->ctl, 0, sizeof(FilterCtl)));  // (the filter passes clear it per pass; small_batch_kernel relies on zeros left behind)
     }
     if (!ix->dstats) {
-        HIP_TRY(hipMalloc((void**)&ix->dstats, 4 * sizeof(unsigned long long)));
+        HIP_TRY(ix->dstats.reset(4));
         HIP_TRY(hipMemset(ix->dstats, 0, 4 * sizeof(unsigned long long)));
     }
     return CODD_KNN_OK;
@@ -2186,7 +2158,7 @@ int wait_rows(codd_knn_index* ix, hipStream_t st) {
 int wait_searching_streams(codd_knn_index* ix) {
     for (WorkSlot& w : ix->slots) {
         if (!w.used) continue;
-        if (!w.handover) HIP_TRY(hipEventCreateWithFlags(&w.handover, hipEventDisableTiming));
+        HIP_TRY(w.handover.ensure());
         if (hipEventRecord(w.handover, w.stream) == hipSuccess) HIP_TRY(hipEventSynchronize(w.handover));
         else (void)hipGetLastError();  // (a stream that no longer exists has nothing in flight)
     }
@@ -2211,14 +2183,13 @@ int ensure_shadow(codd_knn_index* ix, hipStream_t st) {
         if (ix->shadow_nomem_epoch == ix->epoch) return CODD_KNN_ENOMEM;
         int rc;
         if ((rc = wait_searching_streams(ix)) != 0) return rc;
-        if (ix->shadow) (void)hipFree(ix->shadow);
-        ix->shadow = nullptr; ix->shadow_rows = 0;
+        (void)ix->shadow.reset();
+        ix->shadow_rows = 0;
         const int64_t rows = need + need / 8;
         const int64_t rows_al = (rows + kTileRows - 1) / kTileRows * kTileRows;
-        hipError_t me = ix->debug_fail_shadow_alloc ? hipErrorOutOfMemory : hipMalloc((void**)&ix->shadow, (size_t)rows_al * ix->dpad * 2);
+        hipError_t me = ix->debug_fail_shadow_alloc ? hipErrorOutOfMemory : ix->shadow.reset(rows_al * ix->dpad * 2 / (int64_t)sizeof(uint4));
         if (me != hipSuccess) {
             (void)hipGetLastError();
-            ix->shadow = nullptr;
             ix->shadow_nomem_epoch = ix->epoch;
             ix->stat_shadow_nomem++;
             return fail(CODD_KNN_ENOMEM, "bf16 shadow: %s", hipGetErrorString(me));
@@ -2227,10 +2198,10 @@ int ensure_shadow(codd_knn_index* ix, hipStream_t st) {
         HIP_TRY(hipMemsetAsync(ix->shadow, 0, (size_t)rows_al * ix->dpad * 2, st));  // rows beyond the count are masked, their bytes only have to be defined
         first = 0; m = n;
     }
-    if (!ix->shadow_ready) HIP_TRY(hipEventCreateWithFlags(&ix->shadow_ready, hipEventDisableTiming));
+    HIP_TRY(ix->shadow_ready.ensure());
     if (m > 0) {
         const dim3 grid((unsigned)((m + 3) / 4)), block(256);
-        uint2* sh = reinterpret_cast<uint2*>(ix->shadow);
+        uint2* sh = reinterpret_cast<uint2*>(ix->shadow.get());
         const int rc = with_dtype(ix->dtype, [&](auto dt) {
             return launch_kernel<shadow_from_rows_kernel<dt>>(grid, block, 0, st, ix->rows, first, m, ix->dpad, sh);
         });
@@ -2258,30 +2229,37 @@ int ensure_shadow8(codd_knn_index* ix, hipStream_t st) {
     int64_t first = ix->dirty_lo, m = ix->dirty_hi - ix->dirty_lo;  // rows to (re)quantise
     if (first + m > n) m = n > first ? n - first : 0;  // (never past the count: the allocation below is only checked against it)
     if (!ix->eps_r_bits) {
-        HIP_TRY(hipMalloc((void**)&ix->eps_r_bits, 2 * sizeof(unsigned)));
+        HIP_TRY(ix->eps_r_bits.reset(2));
         HIP_TRY(hipMemsetAsync(ix->eps_r_bits, 0, 2 * sizeof(unsigned), st));
     }
     if (need > ix->shadow8_rows) {
         // (every stream that may still read the old allocation has to be done with it)
         int rcw;
         if ((rcw = wait_searching_streams(ix)) != 0) return rcw;
-        if (ix->shadow8) (void)hipFree(ix->shadow8);
-        if (ix->rscale) (void)hipFree(ix->rscale);
-        if (ix->bmeta) (void)hipFree(ix->bmeta);
-        ix->shadow8 = nullptr; ix->rscale = nullptr; ix->bmeta = nullptr; ix->shadow8_rows = 0;
+        (void)ix->shadow8.reset();
+        (void)ix->rscale.reset();
+        (void)ix->bmeta.reset();
+        ix->shadow8_rows = 0;
         const int64_t rows = need + need / 8;  // head room: appends do not reallocate every time
         const int64_t rows_al = (rows + kTileRows - 1) / kTileRows * kTileRows;
-        HIP_TRY(hipMalloc((void**)&ix->shadow8, (size_t)rows_al * dpad8));
-        HIP_TRY(hipMalloc((void**)&ix->rscale, (size_t)rows_al * sizeof(float)));
-        HIP_TRY(hipMalloc((void**)&ix->bmeta, (size_t)(rows_al / 32 + 64) * sizeof(float2)));  // (+64: a wave's DMA reads 32 blocks from a tile's first one)
-        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)ix->bmeta, (int)0x7fc00000, (size_t)(rows_al / 32 + 64) * 2, st));  // NaN: no such block yet
+        // the three belong together: built in locals, handed over together (a failure leaves the index without an int8 shadow, not with a third of one)
+        DevBuf<uint4> s8;
+        DevBuf<float> rs;
+        DevBuf<float2> bm;
+        HIP_TRY(s8.reset(rows_al * dpad8 / (int64_t)sizeof(uint4)));
+        HIP_TRY(rs.reset(rows_al));
+        HIP_TRY(bm.reset(rows_al / 32 + 64));  // (+64: a wave's DMA reads 32 blocks from a tile's first one)
+        ix->shadow8 = std::move(s8);
+        ix->rscale = std::move(rs);
+        ix->bmeta = std::move(bm);
+        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)ix->bmeta.get(), (int)0x7fc00000, (size_t)(rows_al / 32 + 64) * 2, st));  // NaN: no such block yet
         ix->shadow8_rows = rows_al;
         // rows beyond the count are masked (row < n), their bytes only have to be defined
         HIP_TRY(hipMemsetAsync(ix->shadow8, 0, (size_t)rows_al * dpad8, st));
         HIP_TRY(hipMemsetAsync(ix->eps_r_bits, 0, 2 * sizeof(unsigned), st));
         first = 0; m = n;  // a fresh allocation holds nothing yet
     }
-    if (!ix->shadow8_ready) HIP_TRY(hipEventCreateWithFlags(&ix->shadow8_ready, hipEventDisableTiming));
+    HIP_TRY(ix->shadow8_ready.ensure());
     if (m > 0) {
         // Whole 32-row blocks (one scale per block): the rows that share a block with the dirty range are quantised again,
         // with the block's new scale, and the block's error norm is measured again.
@@ -2307,10 +2285,10 @@ int ensure_shadow8(codd_knn_index* ix, hipStream_t st) {
     }
     HIP_TRY(hipEventRecord(ix->shadow8_ready, st));
     if (!ix->eps_r_host) {
-        HIP_TRY(hipHostMalloc((void**)&ix->eps_r_host, 2 * sizeof(float), hipHostMallocDefault));
+        HIP_TRY(ix->eps_r_host.reset(2));
         ix->eps_r_host[0] = 0.0f;
         ix->eps_r_host[1] = 0.0f;
-        HIP_TRY(hipEventCreateWithFlags(&ix->eps_r_copied, hipEventDisableTiming));
+        HIP_TRY(ix->eps_r_copied.ensure());
     }
     HIP_TRY(hipMemcpyAsync(ix->eps_r_host, ix->eps_r_bits, 2 * sizeof(float), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipEventRecord(ix->eps_r_copied, st));
@@ -2439,7 +2417,8 @@ int fallback_geometry(codd_knn_index* ix, int k, int64_t* blocks, int64_t* strid
     if ((rc = scan_geometry(ix, ix->count, &niter, blocks)) != 0) return rc;
     if (*blocks > ix->num_cus) *blocks = ix->num_cus;
     *stride_q = *blocks * k;
-    return ensure_buf(&ix->fb_partial, &ix->fb_partial_cap, (int64_t)kTileQ * *stride_q);
+    HIP_TRY(ix->fb_partial.ensure((int64_t)kTileQ * *stride_q));
+    return CODD_KNN_OK;
 }
 
 // exact-scan fallback for the queries a pass queued (normally none), entirely on the device and in ONE launch: the scan walks
@@ -2486,7 +2465,7 @@ int filter_pass(codd_knn_index* ix, const float* qn, int nq, int k, uint32_t row
 
     if (!prepared) {  // (a batch of <= 256 queries arrives with its fragments and a cleared control block: prep_queries_kernel)
         hipLaunchKernelGGL(qfrag_kernel, dim3((kTileQ * (ix->dpad / 8) + 255) / 256), dim3(256), 0, st, qn, nq, ix->dpad, ix->qfrag,
-                           reinterpret_cast<unsigned*>(ix->ctl), (int)(sizeof(FilterCtl) / 4));
+                           reinterpret_cast<unsigned*>(ix->ctl.get()), (int)(sizeof(FilterCtl) / 4));
         HIP_TRY(hipGetLastError());
     }
 
@@ -2524,7 +2503,7 @@ int filter_pass(codd_knn_index* ix, const float* qn, int nq, int k, uint32_t row
 #endif
         } else if (prog.family == FilterProgram::TILE_F16) {
             // (thr doubles as the 256 readable bytes the kernel's per-tile metadata request needs; fp16 operands carry no scales)
-            fa.bmeta = reinterpret_cast<const float2*>(ix->thr);
+            fa.bmeta = reinterpret_cast<const float2*>(ix->thr.get());
         }
         if ((rc = launch_filter_program<MODE_FILTER>(prog, g, st, fa)) != 0) return rc;
     }
@@ -2534,7 +2513,7 @@ int filter_pass(codd_knn_index* ix, const float* qn, int nq, int k, uint32_t row
     // query's re-scoring out between several workgroups, then merge their lists
     const int nparts = use8 ? (nq <= 8 ? 16 : (nq <= 32 ? 8 : (nq <= 64 ? 4 : 1))) : 1;
     ix->stat_last_finalize_parts = nparts;
-    if (nparts > 1 && (rc = ensure_buf(&ix->partial, &ix->partial_cap, (int64_t)nq * nparts * k)) != 0) return rc;
+    if (nparts > 1) HIP_TRY(ix->partial.ensure((int64_t)nq * nparts * k));
     const float2* bm = slack_q && (ix->per_block & 2) ? ix->bmeta : nullptr;  // (the int8 passes: slack per 32-row block)
     FilterCtl* c = ix->ctl;
     // one list slot per lane and one workgroup per query (the large batches): finalize and the exact-scan fallback share ONE
@@ -2611,7 +2590,7 @@ int small_batch_search(codd_knn_index* ix, const float* dev_queries, int B, int 
     constexpr int kWavesPerWg = kSbThreads / kWave;
     const int64_t nunits = (n + 15) / 16;
     int rc;
-    if ((rc = ensure_buf(&ix->sb_cand, &ix->sb_cand_cap, (int64_t)(2 * ix->num_cus) * kWavesPerWg * (kSbKeep + 1))) != 0) return rc;
+    HIP_TRY(ix->sb_cand.ensure((int64_t)(2 * ix->num_cus) * kWavesPerWg * (kSbKeep + 1)));
     u64* cand = ix->sb_cand;
     ix->stat_small_batch++;
     {
@@ -2645,8 +2624,8 @@ int after_filter_search(codd_knn_index* ix, int B, bool use8, hipStream_t st) {
     (use8 ? ix->watch_q8 : ix->watch_q16) += B;
     if (ix->shadow8_enabled && !ix->watch_pending && ix->dstats && (ix->stat_searches <= 32 || (ix->stat_searches & 7) == 0)) {
         if (!ix->watch_host) {
-            HIP_TRY(hipHostMalloc((void**)&ix->watch_host, 4 * sizeof(unsigned long long), hipHostMallocDefault));
-            HIP_TRY(hipEventCreateWithFlags(&ix->watch_copied, hipEventDisableTiming));
+            HIP_TRY(ix->watch_host.reset(4));
+            HIP_TRY(ix->watch_copied.ensure());
         }
         HIP_TRY(hipMemcpyAsync(ix->watch_host, ix->dstats, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipEventRecord(ix->watch_copied, st));
@@ -2670,14 +2649,14 @@ int search_impl(codd_knn_index* ix, const float* dev_queries, int B, int k, uint
     ix->stat_searches++;
     const int64_t n = ix->count;
     int rc;
-    if ((rc = ensure_buf(&ix->qn, &ix->qn_cap, (int64_t)B * ix->dpad)) != 0) return rc;
-    if ((rc = ensure_buf(&ix->keys_tmp, &ix->keys_tmp_cap, (int64_t)B * k)) != 0) return rc;
+    HIP_TRY(ix->qn.ensure((int64_t)B * ix->dpad));
+    HIP_TRY(ix->keys_tmp.ensure((int64_t)B * k));
     if ((rc = wait_rows(ix, st)) != 0) return rc;
     bool use_filter = n > 0 && filter_applies(ix, B, k);
     if (ix->eps_r_copied) {
         if (hipEventQuery(ix->eps_r_copied) == hipSuccess) {
             ix->eps_r_known = ix->eps_r_host[0];
-            ix->wide_blocks_known = (int64_t)reinterpret_cast<const unsigned*>(ix->eps_r_host)[1];
+            ix->wide_blocks_known = (int64_t)reinterpret_cast<const unsigned*>(ix->eps_r_host.get())[1];
         }
         else (void)hipGetLastError();  // "not ready" must not surface in a later error check
     }
@@ -2740,8 +2719,8 @@ int search_impl(codd_knn_index* ix, const float* dev_queries, int B, int k, uint
     const int dpad8 = dpad8_of(ix);
     auto prep8 = [&](int q0, int nq) -> int {
         hipLaunchKernelGGL(prep_queries8_kernel, dim3(kTileQ / 4), dim3(256), 0, st, dev_queries + (int64_t)q0 * ix->dim, nq, ix->dim, ix->dpad, dpad8,
-                           ix->qn + (int64_t)q0 * ix->dpad, reinterpret_cast<uint32_t*>(ix->qfrag8), ix->qmeta, ix->eps_r_bits,
-                           reinterpret_cast<unsigned*>(ix->ctl), (int)(sizeof(FilterCtl) / 4), ix->exp_slack_scale);
+                           ix->qn + (int64_t)q0 * ix->dpad, reinterpret_cast<uint32_t*>(ix->qfrag8.get()), ix->qmeta, ix->eps_r_bits,
+                           reinterpret_cast<unsigned*>(ix->ctl.get()), (int)(sizeof(FilterCtl) / 4), ix->exp_slack_scale);
         HIP_TRY(hipGetLastError());
         return CODD_KNN_OK;
     };
@@ -2751,15 +2730,15 @@ int search_impl(codd_knn_index* ix, const float* dev_queries, int B, int k, uint
         // a handful of queries: ONE launch streams the int8 shadow, keeps the best approximate scores per wave and re-scores the
         // survivors exactly in its last workgroup (small_batch_kernel) instead of the six-launch filter chain
         if (small_batch_applies(ix, B, k)) {
-            if ((rc = ensure_buf(&ix->qn, &ix->qn_cap, (int64_t)B * ix->dpad)) != 0) return rc;
+            HIP_TRY(ix->qn.ensure((int64_t)B * ix->dpad));
             if ((rc = small_batch_search(ix, dev_queries, B, k, row_base, out_keys, out_dist, out_rows, st, deny)) != 0) return rc;
             return masked ? CODD_KNN_OK : after_filter_search(ix, B, true, st);
         }
-        if ((rc = ensure_buf(&ix->qfrag8, &ix->qfrag8_cap, (int64_t)kTileQ * (dpad8 / 16))) != 0) return rc;
-        if (!ix->qmeta) HIP_TRY(hipMalloc((void**)&ix->qmeta, 1024 * sizeof(float)));
+        HIP_TRY(ix->qfrag8.ensure((int64_t)kTileQ * (dpad8 / 16)));
+        if (!ix->qmeta) HIP_TRY(ix->qmeta.reset(1024));
     } else if (fused_prep) {
         hipLaunchKernelGGL(prep_queries_kernel, dim3(kTileQ / 4), dim3(256), 0, st, dev_queries, B, ix->dim, ix->dpad, ix->qn,
-                           reinterpret_cast<uint2*>(ix->qfrag), reinterpret_cast<unsigned*>(ix->ctl), (int)(sizeof(FilterCtl) / 4));
+                           reinterpret_cast<uint2*>(ix->qfrag.get()), reinterpret_cast<unsigned*>(ix->ctl.get()), (int)(sizeof(FilterCtl) / 4));
         HIP_TRY(hipGetLastError());
     } else if ((rc = launch_normalize(DT_F32, dev_queries, B, ix->dim, ix->dpad, 1, nullptr, 0, ix->qn, nullptr, st)) != 0) {
         return rc;
@@ -2793,12 +2772,11 @@ int search_impl(codd_knn_index* ix, const float* dev_queries, int B, int k, uint
 // the label array, as long as the row store, zero (= no label) until codd_knn_set_scopes_host writes it.  Only ever called with
 // scope_of == nullptr or from an exclusive call: a live array is regrown by grow_rows alone.
 int ensure_scope_labels(codd_knn_index* ix, hipStream_t st) {
-    if (ix->scope_of && ix->scope_of_cap >= ix->count) return CODD_KNN_OK;
+    if (ix->scope_of && ix->scope_of.cap() >= ix->count) return CODD_KNN_OK;
     if (ix->scope_of) return fail(CODD_KNN_EDEVICE, "scope labels shorter than the row store%s");
     const int64_t cap = ix->capacity > ix->count ? ix->capacity : ix->count;
     if (cap < 1) return CODD_KNN_OK;
-    HIP_TRY(hipMalloc((void**)&ix->scope_of, (size_t)cap * sizeof(uint32_t)));
-    ix->scope_of_cap = cap;
+    HIP_TRY(ix->scope_of.reset(cap));
     HIP_TRY(hipMemsetAsync(ix->scope_of, 0, (size_t)cap * sizeof(uint32_t), st));
     return CODD_KNN_OK;
 }
@@ -2815,27 +2793,18 @@ int ensure_scope_lists(codd_knn_index* ix, hipStream_t st) {
     int rc;
     if ((rc = ensure_scope_labels(ix, st)) != 0) return rc;
     const int64_t nlist = (int64_t)ix->max_scope + 1;
-    if (n > ix->scope_perm_cap || 2 * nlist + 1 > ix->scope_lists_cap) {
+    if (n > ix->scope_perm.cap() || 2 * nlist + 1 > ix->scope_offsets.cap()) {
         if ((rc = wait_searching_streams(ix)) != 0) return rc;   // (growth is the one place where a search call blocks)
-        if (n > ix->scope_perm_cap) {
-            if (ix->scope_perm) (void)hipFree(ix->scope_perm);
-            ix->scope_perm = nullptr; ix->scope_perm_cap = 0;
-            const int64_t cap = ix->capacity > n ? ix->capacity : n;
-            HIP_TRY(hipMalloc((void**)&ix->scope_perm, (size_t)cap * sizeof(uint32_t)));
-            ix->scope_perm_cap = cap;
-        }
-        if (2 * nlist + 1 > ix->scope_lists_cap) {
-            if (ix->scope_offsets) (void)hipFree(ix->scope_offsets);
-            ix->scope_offsets = nullptr; ix->scope_lists_cap = 0;
+        if (n > ix->scope_perm.cap()) HIP_TRY(ix->scope_perm.reset(ix->capacity > n ? ix->capacity : n));
+        if (2 * nlist + 1 > ix->scope_offsets.cap()) {
             int64_t cap = 2049;
             while (cap < 2 * nlist + 1) cap = 2 * cap - 1;
-            HIP_TRY(hipMalloc((void**)&ix->scope_offsets, (size_t)cap * sizeof(unsigned)));
-            ix->scope_lists_cap = cap;
+            HIP_TRY(ix->scope_offsets.reset(cap));
         }
     }
     for (WorkSlot& w : ix->slots) {
         if (!w.used || w.stream == st) continue;
-        if (!w.handover) HIP_TRY(hipEventCreateWithFlags(&w.handover, hipEventDisableTiming));
+        HIP_TRY(w.handover.ensure());
         if (hipEventRecord(w.handover, w.stream) == hipSuccess) HIP_TRY(hipStreamWaitEvent(st, w.handover, 0));
         else (void)hipGetLastError();  // (a stream that no longer exists has nothing in flight)
     }
@@ -2848,13 +2817,23 @@ int ensure_scope_lists(codd_knn_index* ix, hipStream_t st) {
     hipLaunchKernelGGL(scope_offsets_kernel, dim3(1), dim3(1024), 0, st, fill, (int)nlist, start);
     hipLaunchKernelGGL(scope_scatter_kernel, dim3(rb), dim3(256), 0, st, ix->scope_of, n, (int)nlist, start, fill, ix->scope_perm, ix->dead_bits);
     HIP_TRY(hipGetLastError());
-    if (!ix->scope_ready) HIP_TRY(hipEventCreateWithFlags(&ix->scope_ready, hipEventDisableTiming));
+    HIP_TRY(ix->scope_ready.ensure());
     HIP_TRY(hipEventRecord(ix->scope_ready, st));
     ix->scope_stream = st;
     ix->scope_built_gen = ix->scope_gen;
     ix->scope_built_count = n;
     ix->stat_scope_builds++;
     return CODD_KNN_OK;
+}
+
+// the IVF layout and its coarse index go (a new install, a failed one)
+void drop_ivf(codd_knn_index* ix) {
+    (void)ix->rows_ivf.reset();
+    (void)ix->ivf_ids.reset();
+    (void)ix->ivf_offsets.reset();
+    (void)codd_knn_destroy(ix->coarse);
+    ix->coarse = nullptr;
+    ix->ivf_epoch = -1;
 }
 
 }  // namespace
@@ -2903,34 +2882,7 @@ int codd_knn_destroy(codd_knn_index* ix) {
     if (!ix) return CODD_KNN_OK;
     DeviceGuard guard(ix->device);
     (void)hipDeviceSynchronize();
-    void* bufs[] = {ix->rows, ix->shadow, ix->dstats, ix->rows_ivf, ix->ivf_ids, ix->ivf_offsets, ix->shadow8, ix->rscale, ix->bmeta, ix->eps_r_bits,
-                    ix->scope_of, ix->scope_perm, ix->scope_offsets, ix->dead_bits, ix->mask_dstats, ix->doc_arena, ix->doc_offsets};
-    if (ix->scope_ready) (void)hipEventDestroy(ix->scope_ready);
-    if (ix->shadow8_ready) (void)hipEventDestroy(ix->shadow8_ready);
-    if (ix->shadow_ready) (void)hipEventDestroy(ix->shadow_ready);
-    if (ix->rows_ready) (void)hipEventDestroy(ix->rows_ready);
-    if (ix->reader_done) (void)hipEventDestroy(ix->reader_done);
-    if (ix->stage_vec) (void)hipFree(ix->stage_vec);
-    if (ix->stage_slot) (void)hipFree(ix->stage_slot);
-    if (ix->watch_copied) (void)hipEventDestroy(ix->watch_copied);
-    if (ix->watch_host) (void)hipHostFree(ix->watch_host);
-    if (ix->eps_r_copied) (void)hipEventDestroy(ix->eps_r_copied);
-    if (ix->eps_r_host) (void)hipHostFree(ix->eps_r_host);
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
-    for (WorkSlot& w : ix->slots) {
-        void* wb[] = {w.bufs.qn, w.bufs.partial, w.bufs.keys_tmp, w.bufs.qfrag, w.bufs.thr, w.bufs.bucket_max, w.bufs.hits, w.bufs.ctl,
-                      w.bufs.fb_partial, w.bufs.probe_keys, w.bufs.ivf_partial, w.bufs.ivf_group, w.bufs.qfrag8, w.bufs.qmeta, w.bufs.sb_cand,
-                      w.bufs.scope_group, w.bufs.mask_allow, w.bufs.mask_deny, w.bufs.mask_prefix, w.bufs.mask_list, w.bufs.mask_m_dev};
-        for (void* b : wb)
-            if (b) (void)hipFree(b);
-        if (w.bufs.mask_host) (void)hipHostFree(w.bufs.mask_host);
-        if (w.bufs.mask_m_host) (void)hipHostFree(w.bufs.mask_m_host);
-        if (w.bufs.mask_uploaded) (void)hipEventDestroy(w.bufs.mask_uploaded);
-        if (w.handover) (void)hipEventDestroy(w.handover);
-    }
-    if (ix->coarse) (void)codd_knn_destroy(ix->coarse);
-    for (hipEvent_t e : ix->ev) (void)hipEventDestroy(e);
+    // (every buffer and event is a member that frees itself; the device is current and idle, as their destructors need)
     delete ix;
     return CODD_KNN_OK;
 }
@@ -2959,23 +2911,11 @@ int codd_knn_upsert_host(codd_knn_index* ix, const int64_t* host_slots, const fl
     int rc = grow_rows(ix, max_slot + 1, /*exact=*/false);
     if (rc != 0) return rc;
     // stage in bounded pieces (<= 64 MiB of vectors per piece) through buffers the index keeps between calls (the indexer job
-    // upserts one small batch at a time: a hipMalloc / hipFree pair per call used to dominate them)
+    // upserts one small batch at a time: an allocation and a release per call used to dominate them)
     const int64_t piece = (int64_t)(64ll << 20) / ((int64_t)ix->dim * 4) + 1;
     const int64_t pn = n < piece ? n : piece;
-    if (pn * ix->dim > ix->stage_vec_cap) {
-        if (ix->stage_vec) (void)hipFree(ix->stage_vec);
-        ix->stage_vec = nullptr; ix->stage_vec_cap = 0;
-        const int64_t want = pn * ix->dim < 65536 ? 65536 : pn * ix->dim;
-        HIP_TRY(hipMalloc((void**)&ix->stage_vec, (size_t)want * sizeof(float)));
-        ix->stage_vec_cap = want;
-    }
-    if (pn > ix->stage_slot_cap) {
-        if (ix->stage_slot) (void)hipFree(ix->stage_slot);
-        ix->stage_slot = nullptr; ix->stage_slot_cap = 0;
-        const int64_t want = pn < 4096 ? 4096 : pn;
-        HIP_TRY(hipMalloc((void**)&ix->stage_slot, (size_t)want * sizeof(int64_t)));
-        ix->stage_slot_cap = want;
-    }
+    if (pn * ix->dim > ix->stage_vec.cap()) HIP_TRY(ix->stage_vec.reset(pn * ix->dim < 65536 ? 65536 : pn * ix->dim));
+    if (pn > ix->stage_slot.cap()) HIP_TRY(ix->stage_slot.reset(pn < 4096 ? 4096 : pn));
     float* dvec = ix->stage_vec;
     int64_t* dslot = ix->stage_slot;
     rc = CODD_KNN_OK;
@@ -3017,7 +2957,7 @@ int codd_knn_upsert_device(codd_knn_index* ix, int64_t first_slot, const float* 
     // kernels may still be reading the rows this launch overwrites): the writing stream waits for every searching stream
     for (WorkSlot& w : ix->slots) {
         if (!w.used || w.stream == wst) continue;
-        if (!w.handover) HIP_TRY(hipEventCreateWithFlags(&w.handover, hipEventDisableTiming));
+        HIP_TRY(w.handover.ensure());
         if (hipEventRecord(w.handover, w.stream) == hipSuccess) HIP_TRY(hipStreamWaitEvent(wst, w.handover, 0));
         else (void)hipGetLastError();  // (a stream that no longer exists has nothing in flight)
     }
@@ -3029,7 +2969,7 @@ int codd_knn_upsert_device(codd_knn_index* ix, int64_t first_slot, const float* 
     int rc = launch_normalize(ix->dtype, dev_vecs, n, ix->dim, ix->dpad, normalize, nullptr, first_slot, ix->rows, nullptr, wst);
     if (rc != 0) return rc;
     // ... and searches on other streams wait for this write (wait_rows)
-    if (!ix->rows_ready) HIP_TRY(hipEventCreateWithFlags(&ix->rows_ready, hipEventDisableTiming));
+    HIP_TRY(ix->rows_ready.ensure());
     HIP_TRY(hipEventRecord(ix->rows_ready, wst));
     ix->rows_stream = wst;
     ix->rows_event_set = true;
@@ -3049,11 +2989,11 @@ int codd_knn_load_rows(codd_knn_index* ix, int64_t first_slot, const void* host_
     int rc = grow_rows(ix, first_slot + n, /*exact=*/false);
     if (rc != 0) return rc;
     const size_t row_bytes = (size_t)ix->dpad * elem_size(ix->dtype);
-    HIP_TRY(hipMemcpy((char*)ix->rows + (size_t)first_slot * row_bytes, host_rows, (size_t)n * row_bytes, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(ix->rows + (size_t)first_slot * row_bytes, host_rows, (size_t)n * row_bytes, hipMemcpyHostToDevice));
     // the loaded rows are taken as they are, so their norms are checked: the filters stay on only for unit rows
     // (tolerance = the storage type's rounding of a unit vector)
-    unsigned* dev_bits = nullptr;
-    HIP_TRY(hipMalloc((void**)&dev_bits, sizeof(unsigned)));
+    DevBuf<unsigned> dev_bits;
+    HIP_TRY(dev_bits.reset(1));
     hipError_t e = hipMemset(dev_bits, 0, sizeof(unsigned));
     const dim3 grid((unsigned)((n + 3) / 4)), block(256);
     if (e == hipSuccess) {
@@ -3064,7 +3004,6 @@ int codd_knn_load_rows(codd_knn_index* ix, int64_t first_slot, const void* host_
     }
     float worst = 0.0f;
     if (e == hipSuccess) e = hipMemcpy(&worst, dev_bits, sizeof(float), hipMemcpyDeviceToHost);
-    (void)hipFree(dev_bits);
     if (e != hipSuccess) return fail(CODD_KNN_EDEVICE, "norm check of the loaded rows failed: %s", hipGetErrorString(e));
     const float tol = ix->dtype == DT_F32 ? 1e-4f : (ix->dtype == DT_BF16 ? 4e-3f : 6e-4f);
     if (!(worst <= tol)) ix->all_normalized = false;
@@ -3094,7 +3033,7 @@ int codd_knn_read_rows(const codd_knn_index* ix, int64_t first, int64_t n, void*
     DeviceGuard guard(ix->device);
     const size_t row_bytes = (size_t)ix->dpad * elem_size(ix->dtype);
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(host_out, (const char*)ix->rows + (size_t)first * row_bytes, (size_t)n * row_bytes, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(host_out, ix->rows + (size_t)first * row_bytes, (size_t)n * row_bytes, hipMemcpyDeviceToHost));
     return CODD_KNN_OK;
 }
 
@@ -3136,16 +3075,16 @@ int codd_knn_approx_scores(codd_knn_index* ix, const float* dev_queries, int B, 
     WorkScope work(ix, st);
     int rc;
     if ((rc = wait_rows(ix, st)) != 0) return rc;
-    if ((rc = ensure_buf(&ix->qn, &ix->qn_cap, (int64_t)B * ix->dpad)) != 0) return rc;
+    HIP_TRY(ix->qn.ensure((int64_t)B * ix->dpad));
     if ((rc = ensure_filter_workspace(ix)) != 0) return rc;
     if (ix->shadow8_enabled && B <= 32 && CODD_MFMA16) {
         // the int8 filter's scores (what a batch of <= 32 queries is filtered with when "shadow8" is on)
         if ((rc = ensure_shadow8(ix, st)) != 0) return rc;
         const int dpad8 = dpad8_of(ix);
-        if ((rc = ensure_buf(&ix->qfrag8, &ix->qfrag8_cap, (int64_t)kTileQ * (dpad8 / 16))) != 0) return rc;
-        if (!ix->qmeta) HIP_TRY(hipMalloc((void**)&ix->qmeta, 1024 * sizeof(float)));
+        HIP_TRY(ix->qfrag8.ensure((int64_t)kTileQ * (dpad8 / 16)));
+        if (!ix->qmeta) HIP_TRY(ix->qmeta.reset(1024));
         hipLaunchKernelGGL(prep_queries8_kernel, dim3(kTileQ / 4), dim3(256), 0, st, dev_queries, B, ix->dim, ix->dpad, dpad8, ix->qn,
-                           reinterpret_cast<uint32_t*>(ix->qfrag8), ix->qmeta, ix->eps_r_bits, reinterpret_cast<unsigned*>(ix->ctl),
+                           reinterpret_cast<uint32_t*>(ix->qfrag8.get()), ix->qmeta, ix->eps_r_bits, reinterpret_cast<unsigned*>(ix->ctl.get()),
                            (int)(sizeof(FilterCtl) / 4), 1.0f);
         const int64_t ntiles8 = (ix->count + kTileRows - 1) / kTileRows;
         const int64_t g8 = ntiles8 < ix->num_cus ? ntiles8 : ix->num_cus;
@@ -3186,7 +3125,7 @@ int codd_knn_copy_rows_f32(codd_knn_index* ix, int64_t first, int64_t n, float* 
     });
     if (rc != 0) return rc;
     HIP_TRY(hipGetLastError());
-    if (!ix->reader_done) HIP_TRY(hipEventCreateWithFlags(&ix->reader_done, hipEventDisableTiming));
+    HIP_TRY(ix->reader_done.ensure());
     if (ix->reader_event_set && ix->reader_stream != st) HIP_TRY(hipStreamWaitEvent(st, ix->reader_done, 0));  // (one event: chain the readers too)
     HIP_TRY(hipEventRecord(ix->reader_done, st));
     ix->reader_stream = st;
@@ -3201,13 +3140,7 @@ int codd_knn_ivf_install(codd_knn_index* ix, const float* dev_centroids, int nli
     DeviceGuard guard(ix->device);
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(hipDeviceSynchronize());
-    // drop a previous layout
-    void* old[] = {ix->rows_ivf, ix->ivf_ids, ix->ivf_offsets};
-    for (void* b : old)
-        if (b) (void)hipFree(b);
-    ix->rows_ivf = nullptr; ix->ivf_ids = nullptr; ix->ivf_offsets = nullptr;
-    if (ix->coarse) { (void)codd_knn_destroy(ix->coarse); ix->coarse = nullptr; }
-    ix->ivf_epoch = -1;
+    drop_ivf(ix);  // a previous layout
 
     const size_t row_bytes = (size_t)ix->dpad * elem_size(ix->dtype);
     const int64_t n = ix->count;
@@ -3220,8 +3153,8 @@ int codd_knn_ivf_install(codd_knn_index* ix, const float* dev_centroids, int nli
         bool ok = off[0] == 0 && off[(size_t)nlist] == n;
         for (int l = 0; ok && l < nlist; ++l) ok = off[(size_t)l] <= off[(size_t)l + 1];
         if (!ok) return fail(CODD_KNN_EINVAL, "ivf_install: offsets must start at 0, never decrease and end at the row count%s");
-        unsigned* bad = nullptr;
-        HIP_TRY(hipMalloc((void**)&bad, sizeof(unsigned)));
+        DevBuf<unsigned> bad;
+        HIP_TRY(bad.reset(1));
         hipError_t e = hipMemsetAsync(bad, 0, sizeof(unsigned), st);
         unsigned host_bad = 1;
         if (e == hipSuccess) {
@@ -3230,36 +3163,29 @@ int codd_knn_ivf_install(codd_knn_index* ix, const float* dev_centroids, int nli
         }
         if (e == hipSuccess) e = hipMemcpyAsync(&host_bad, bad, sizeof(unsigned), hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
-        (void)hipFree(bad);
         if (e != hipSuccess) return fail(CODD_KNN_EDEVICE, "ivf_install: permutation check failed: %s", hipGetErrorString(e));
         if (host_bad) return fail(CODD_KNN_EINVAL, "ivf_install: permutation entries must lie in [0, count)%s");
     }
-    auto drop_partial = [&]() {  // a failed install leaves no half-built layout (and no leak) behind
-        void* part[] = {ix->rows_ivf, ix->ivf_ids, ix->ivf_offsets};
-        for (void* b_ : part)
-            if (b_) (void)hipFree(b_);
-        ix->rows_ivf = nullptr; ix->ivf_ids = nullptr; ix->ivf_offsets = nullptr;
-        if (ix->coarse) { (void)codd_knn_destroy(ix->coarse); ix->coarse = nullptr; }
-    };
+    // (a failed install leaves no half-built layout behind: drop_ivf)
     int rc = CODD_KNN_OK;
-    hipError_t he = hipMalloc(&ix->rows_ivf, (size_t)n * row_bytes);
-    if (he == hipSuccess) he = hipMalloc((void**)&ix->ivf_ids, (size_t)n * sizeof(uint32_t));
-    if (he == hipSuccess) he = hipMalloc((void**)&ix->ivf_offsets, (size_t)(nlist + 1) * sizeof(int64_t));
+    hipError_t he = ix->rows_ivf.reset(n * (int64_t)row_bytes);
+    if (he == hipSuccess) he = ix->ivf_ids.reset(n);
+    if (he == hipSuccess) he = ix->ivf_offsets.reset((int64_t)nlist + 1);
     if (he == hipSuccess) he = hipMemcpyAsync(ix->ivf_offsets, dev_offsets, (size_t)(nlist + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, st);
     if (he == hipSuccess) {
-        hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, reinterpret_cast<const uint4*>(ix->rows), dev_perm, n,
-                           (int)(row_bytes / 16), reinterpret_cast<uint4*>(ix->rows_ivf), ix->ivf_ids);
+        hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, reinterpret_cast<const uint4*>(ix->rows.get()), dev_perm, n,
+                           (int)(row_bytes / 16), reinterpret_cast<uint4*>(ix->rows_ivf.get()), ix->ivf_ids);
         he = hipGetLastError();
     }
     if (he != hipSuccess) {
-        drop_partial();
+        drop_ivf(ix);
         return fail(he == hipErrorOutOfMemory ? CODD_KNN_ENOMEM : CODD_KNN_EDEVICE, "ivf_install: building the list layout failed: %s", hipGetErrorString(he));
     }
     rc = codd_knn_create(&ix->coarse, ix->device, ix->dim, DT_F32, CODD_KNN_METRIC_COSINE);
     if (rc == 0) rc = codd_knn_upsert_device(ix->coarse, 0, dev_centroids, nlist, 1, stream);
     if (rc == 0 && hipStreamSynchronize(st) != hipSuccess) rc = fail(CODD_KNN_EDEVICE, "ivf_install: device work failed%s");
     if (rc != 0) {
-        drop_partial();
+        drop_ivf(ix);
         return rc;
     }
     ix->ivf_nlist = nlist;
@@ -3271,6 +3197,24 @@ int codd_knn_ivf_install(codd_knn_index* ix, const float* dev_centroids, int nli
 }  // extern "C"
 
 namespace {
+
+// what the scoped and the masked entry points check before they take a workspace
+int search_check_args(const codd_knn_index* ix, const float* dev_queries, int B, int k, uint32_t row_base) {
+    if (!ix || !dev_queries) return fail(CODD_KNN_EINVAL, "null index or queries%s");
+    if (B < 1 || B > CODD_KNN_MAX_BATCH) return fail(CODD_KNN_EINVAL, "B out of range [1,1024]%s");
+    if (k < 1 || k > CODD_KNN_MAX_K) return fail(CODD_KNN_EINVAL, "k out of range [1,128]%s");
+    if ((int64_t)row_base + ix->count >= 0xffffffffll) return fail(CODD_KNN_EINVAL, "global row ids must fit 32 bits%s");
+    return CODD_KNN_OK;
+}
+
+// nothing visible (or nothing stored): all-empty result, no scan
+int empty_result(codd_knn_index* ix, int B, int k, uint64_t* dev_keys, float* dev_dist, int64_t* dev_rows, hipStream_t st) {
+    HIP_TRY(ix->keys_tmp.ensure((int64_t)B * k));
+    u64* keys_dst = dev_keys ? (u64*)dev_keys : ix->keys_tmp.get();
+    HIP_TRY(hipMemsetAsync(keys_dst, 0, (size_t)B * k * sizeof(u64), st));
+    if (!dev_dist && !dev_rows) return CODD_KNN_OK;
+    return launch_merge(keys_dst, B, k, k, k, nullptr, dev_dist, dev_rows, st);
+}
 
 // what every IVF entry point checks before it takes a workspace; clamps nprobe to the number of lists
 int ivf_check_args(const codd_knn_index* ix, const float* dev_queries, int B, int k, int* nprobe) {
@@ -3291,8 +3235,8 @@ int ivf_search_body(codd_knn_index* ix, const float* dev_queries, int B, int k, 
                     int64_t* dev_rows, hipStream_t st, const uint32_t* deny) {
     int rc;
     if ((rc = wait_rows(ix, st)) != 0) return rc;
-    if ((rc = ensure_buf(&ix->qn, &ix->qn_cap, (int64_t)B * ix->dpad)) != 0) return rc;
-    if ((rc = ensure_buf(&ix->probe_keys, &ix->probe_cap, (int64_t)B * nprobe)) != 0) return rc;
+    HIP_TRY(ix->qn.ensure((int64_t)B * ix->dpad));
+    HIP_TRY(ix->probe_keys.ensure((int64_t)B * nprobe));
     if ((rc = launch_normalize(DT_F32, dev_queries, B, ix->dim, ix->dpad, 1, nullptr, 0, ix->qn, nullptr, st)) != 0) return rc;
     // 1. coarse: the nprobe best lists per query (exact scan of the centroids, tiny)
     if ((rc = exact_scan(ix->coarse, ix->qn, B, nprobe, 0u, ix->probe_keys, nullptr, nullptr, st, ix->coarse->dead_bits)) != 0) return rc;
@@ -3305,8 +3249,8 @@ int ivf_search_body(codd_knn_index* ix, const float* dev_queries, int B, int k, 
     if (ix->ivf_share && npairs >= 1024 && npairs >= 2 * (int64_t)ix->ivf_nlist && !(ix->dtype != DT_F32 && niter == 4)) {
         const int nlist = ix->ivf_nlist;
         ix->stat_ivf_shared++;
-        if ((rc = ensure_buf(&ix->ivf_group, &ix->ivf_group_cap, 3 * (int64_t)nlist + 2 + npairs)) != 0) return rc;
-        if ((rc = ensure_buf(&ix->ivf_partial, &ix->ivf_partial_cap, npairs * k)) != 0) return rc;
+        HIP_TRY(ix->ivf_group.ensure(3 * (int64_t)nlist + 2 + npairs));
+        HIP_TRY(ix->ivf_partial.ensure(npairs * k));
         unsigned* cnt = ix->ivf_group;
         unsigned* pair_start = cnt + nlist;
         unsigned* item_start = pair_start + nlist + 1;
@@ -3336,7 +3280,7 @@ int ivf_search_body(codd_knn_index* ix, const float* dev_queries, int B, int k, 
     int split = (int)((4 * (int64_t)ix->num_cus + (int64_t)B * nprobe - 1) / ((int64_t)B * nprobe));
     split = split < 1 ? 1 : (split > 16 ? 16 : split);
     const int64_t m = (int64_t)nprobe * split * k;
-    if ((rc = ensure_buf(&ix->ivf_partial, &ix->ivf_partial_cap, (int64_t)B * m)) != 0) return rc;
+    HIP_TRY(ix->ivf_partial.ensure((int64_t)B * m));
     const dim3 grid((unsigned)(nprobe * split), (unsigned)B), block(256);
     {
         EvScope ev(ix, EV_SCAN, st);
@@ -3399,13 +3343,8 @@ int codd_knn_set_scopes_host(codd_knn_index* ix, const int64_t* host_slots, cons
     HIP_TRY(hipDeviceSynchronize());
     int rc;
     if ((rc = ensure_scope_labels(ix, nullptr)) != 0) return rc;
-    if (ix->stage_slot_cap < 4096) {  // (the staging buffer codd_knn_upsert_host keeps between calls)
-        if (ix->stage_slot) (void)hipFree(ix->stage_slot);
-        ix->stage_slot = nullptr; ix->stage_slot_cap = 0;
-        HIP_TRY(hipMalloc((void**)&ix->stage_slot, (size_t)4096 * sizeof(int64_t)));
-        ix->stage_slot_cap = 4096;
-    }
-    const int64_t total = (int64_t)packed.size(), pn = ix->stage_slot_cap;
+    if (ix->stage_slot.cap() < 4096) HIP_TRY(ix->stage_slot.reset(4096));  // (the staging buffer codd_knn_upsert_host keeps between calls)
+    const int64_t total = (int64_t)packed.size(), pn = ix->stage_slot.cap();
     for (int64_t i0 = 0; i0 < total; i0 += pn) {
         const int64_t m = total - i0 < pn ? total - i0 : pn;
         HIP_TRY(hipMemcpy(ix->stage_slot, packed.data() + i0, (size_t)m * sizeof(int64_t), hipMemcpyHostToDevice));
@@ -3422,32 +3361,24 @@ int codd_knn_search_scoped(codd_knn_index* ix, const float* dev_queries, const u
                            uint64_t* dev_keys, float* dev_dist, int64_t* dev_rows, void* stream) {
     if (!ix || !dev_queries) return fail(CODD_KNN_EINVAL, "null index or queries%s");
     if (!dev_scopes) return fail(CODD_KNN_EINVAL, "null scopes%s");
-    if (B < 1 || B > CODD_KNN_MAX_BATCH) return fail(CODD_KNN_EINVAL, "B out of range [1,1024]%s");
-    if (k < 1 || k > CODD_KNN_MAX_K) return fail(CODD_KNN_EINVAL, "k out of range [1,128]%s");
-    if ((int64_t)row_base + ix->count >= 0xffffffffll) return fail(CODD_KNN_EINVAL, "global row ids must fit 32 bits%s");
+    int rc;
+    if ((rc = search_check_args(ix, dev_queries, B, k, row_base)) != 0) return rc;
     DeviceGuard guard(ix->device);
     hipStream_t st = (hipStream_t)stream;
     WorkScope work(ix, st);
     ix->stat_scoped_searches++;
     const int64_t n = ix->count;
-    int rc;
     if ((rc = wait_rows(ix, st)) != 0) return rc;
-    if (n == 0) {  // nothing stored: all-empty result, as codd_knn_search gives
-        if ((rc = ensure_buf(&ix->keys_tmp, &ix->keys_tmp_cap, (int64_t)B * k)) != 0) return rc;
-        u64* keys_dst = dev_keys ? (u64*)dev_keys : ix->keys_tmp;
-        HIP_TRY(hipMemsetAsync(keys_dst, 0, (size_t)B * k * sizeof(u64), st));
-        if (!dev_dist && !dev_rows) return CODD_KNN_OK;
-        return launch_merge(keys_dst, B, k, k, k, nullptr, dev_dist, dev_rows, st);
-    }
+    if (n == 0) return empty_result(ix, B, k, dev_keys, dev_dist, dev_rows, st);  // nothing stored: all-empty result, as codd_knn_search gives
     // enough work items to fill the chip whatever the batch: a scope's list is cut into `split` parts.  The batch has between
     // ceil(B / 4) (one scope) and B (all different) groups of queries; the lower bound sizes the split, surplus workgroups are cheap.
     const int64_t groups = (B + 3) / 4;
     int split = (int)((4 * (int64_t)ix->num_cus + groups - 1) / groups);
     split = split < 1 ? 1 : (split > 256 ? 256 : split);
     const int64_t m = (int64_t)split * k;
-    if ((rc = ensure_buf(&ix->qn, &ix->qn_cap, (int64_t)B * ix->dpad)) != 0) return rc;
-    if ((rc = ensure_buf(&ix->partial, &ix->partial_cap, (int64_t)B * m)) != 0) return rc;
-    if ((rc = ensure_buf(&ix->scope_group, &ix->scope_group_cap, (int64_t)2 * CODD_KNN_MAX_BATCH)) != 0) return rc;
+    HIP_TRY(ix->qn.ensure((int64_t)B * ix->dpad));
+    HIP_TRY(ix->partial.ensure((int64_t)B * m));
+    HIP_TRY(ix->scope_group.ensure((int64_t)2 * CODD_KNN_MAX_BATCH));
     if ((rc = ensure_scope_lists(ix, st)) != 0) return rc;
     if ((rc = launch_normalize(DT_F32, dev_queries, B, ix->dim, ix->dpad, 1, nullptr, 0, ix->qn, nullptr, st)) != 0) return rc;
     unsigned* sorted_q = ix->scope_group;
@@ -3496,16 +3427,6 @@ bool mask_takes_dense(const codd_knn_index* ix, int B, int k, int64_t m) {
     return list_bytes * 100.0 > dense_bytes * (double)ix->mask_list_pct;
 }
 
-// nothing visible (or nothing stored): all-empty result, no scan
-int masked_empty_result(codd_knn_index* ix, int B, int k, uint64_t* dev_keys, float* dev_dist, int64_t* dev_rows, hipStream_t st) {
-    int rc;
-    if ((rc = ensure_buf(&ix->keys_tmp, &ix->keys_tmp_cap, (int64_t)B * k)) != 0) return rc;
-    u64* keys_dst = dev_keys ? (u64*)dev_keys : ix->keys_tmp;
-    HIP_TRY(hipMemsetAsync(keys_dst, 0, (size_t)B * k * sizeof(u64), st));
-    if (!dev_dist && !dev_rows) return CODD_KNN_OK;
-    return launch_merge(keys_dst, B, k, k, k, nullptr, dev_dist, dev_rows, st);
-}
-
 // The body both masked entry points run: the clipped allow words are in ix->mask_allow (written on `st`, or enqueued there) and m > 0,
 // the number of allowed live rows, is known on the host.  Chooses the route and enqueues it.
 int masked_search_body(codd_knn_index* ix, const float* dev_queries, int B, int k, int64_t nwords, int64_t m, uint32_t row_base,
@@ -3515,7 +3436,7 @@ int masked_search_body(codd_knn_index* ix, const float* dev_queries, int B, int 
     if (mask_takes_dense(ix, B, k, m)) {
         ix->stat_mask_dense++;
         const int64_t total_words = (ix->capacity + 31) / 32;   // (as long as the tombstone bits: every kernel that reads those reads these)
-        if ((rc = ensure_buf(&ix->mask_deny, &ix->mask_deny_cap, total_words)) != 0) return rc;
+        HIP_TRY(ix->mask_deny.ensure(total_words));
         hipLaunchKernelGGL(mask_deny_kernel, dim3((unsigned)((total_words + 255) / 256)), dim3(256), 0, st, ix->mask_allow, ix->dead_bits, n, nwords,
                            total_words, ix->mask_deny);
         HIP_TRY(hipGetLastError());
@@ -3527,8 +3448,8 @@ int masked_search_body(codd_knn_index* ix, const float* dev_queries, int B, int 
 
     ix->stat_mask_list++;
     const int64_t nblocks = (nwords + 255) / 256;
-    if ((rc = ensure_buf(&ix->mask_prefix, &ix->mask_prefix_cap, nwords + 2 * nblocks + 1)) != 0) return rc;
-    if ((rc = ensure_buf(&ix->mask_list, &ix->mask_list_cap, m)) != 0) return rc;
+    HIP_TRY(ix->mask_prefix.ensure(nwords + 2 * nblocks + 1));
+    HIP_TRY(ix->mask_list.ensure(m));
     unsigned* prefix = ix->mask_prefix;
     unsigned* block_total = prefix + nwords;
     unsigned* block_base = block_total + nblocks;
@@ -3543,8 +3464,8 @@ int masked_search_body(codd_knn_index* ix, const float* dev_queries, int B, int 
     split = split < 1 ? 1 : (split > 256 ? 256 : split);
     if ((int64_t)split > (m + 15) / 16) split = (int)((m + 15) / 16);
     const int64_t pm = (int64_t)split * k;
-    if ((rc = ensure_buf(&ix->qn, &ix->qn_cap, (int64_t)B * ix->dpad)) != 0) return rc;
-    if ((rc = ensure_buf(&ix->partial, &ix->partial_cap, (int64_t)B * pm)) != 0) return rc;
+    HIP_TRY(ix->qn.ensure((int64_t)B * ix->dpad));
+    HIP_TRY(ix->partial.ensure((int64_t)B * pm));
     if ((rc = launch_normalize(DT_F32, dev_queries, B, ix->dim, ix->dpad, 1, nullptr, 0, ix->qn, nullptr, st)) != 0) return rc;
     {
         EvScope ev(ix, EV_SCAN, st);
@@ -3565,14 +3486,8 @@ int masked_search_body(codd_knn_index* ix, const float* dev_queries, int B, int 
 int stage_host_mask(codd_knn_index* ix, const uint32_t* host_allow_bits, int64_t nwords, int64_t n, int64_t* m) {
     if (ix->mask_upload_pending) HIP_TRY(hipEventSynchronize(ix->mask_uploaded));
     ix->mask_upload_pending = false;
-    if (nwords > ix->mask_host_cap) {
-        if (ix->mask_host) (void)hipHostFree(ix->mask_host);
-        ix->mask_host = nullptr; ix->mask_host_cap = 0;
-        const int64_t cap = nwords + nwords / 2 + 64;
-        HIP_TRY(hipHostMalloc((void**)&ix->mask_host, (size_t)cap * sizeof(uint32_t), hipHostMallocDefault));
-        ix->mask_host_cap = cap;
-    }
-    if (!ix->mask_uploaded) HIP_TRY(hipEventCreateWithFlags(&ix->mask_uploaded, hipEventDisableTiming));
+    if (nwords > ix->mask_host.cap()) HIP_TRY(ix->mask_host.reset(nwords + nwords / 2 + 64));
+    HIP_TRY(ix->mask_uploaded.ensure());
     const bool any_dead = ix->dead_count > 0;
     int64_t seen = 0;
     for (int64_t w = 0; w < nwords; ++w) {
@@ -3587,8 +3502,7 @@ int stage_host_mask(codd_knn_index* ix, const uint32_t* host_allow_bits, int64_t
 
 // ... and one asynchronous copy on `st` takes the staged words to the workspace's allow buffer
 int upload_staged_mask(codd_knn_index* ix, int64_t nwords, hipStream_t st) {
-    int rc;
-    if ((rc = ensure_buf(&ix->mask_allow, &ix->mask_allow_cap, nwords)) != 0) return rc;
+    HIP_TRY(ix->mask_allow.ensure(nwords));
     HIP_TRY(hipMemcpyAsync(ix->mask_allow, ix->mask_host, (size_t)nwords * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     HIP_TRY(hipEventRecord(ix->mask_uploaded, st));
     ix->mask_upload_pending = true;
@@ -3600,8 +3514,7 @@ int upload_staged_mask(codd_knn_index* ix, int64_t nwords, hipStream_t st) {
 // workspace's deny buffer and takes the tombstones' place in the list scans.  Nothing depends on how many rows the mask leaves.
 int ivf_masked_body(codd_knn_index* ix, const float* dev_queries, int B, int k, int nprobe, const uint32_t* allow, int64_t nwords, uint32_t row_base,
                     uint64_t* dev_keys, float* dev_dist, int64_t* dev_rows, hipStream_t st) {
-    int rc;
-    if ((rc = ensure_buf(&ix->mask_deny, &ix->mask_deny_cap, nwords)) != 0) return rc;
+    HIP_TRY(ix->mask_deny.ensure(nwords));
     hipLaunchKernelGGL(mask_deny_kernel, dim3((unsigned)((nwords + 255) / 256)), dim3(256), 0, st, allow, ix->dead_bits, ix->count, nwords, nwords,
                        ix->mask_deny);
     HIP_TRY(hipGetLastError());
@@ -3616,10 +3529,8 @@ extern "C" {
 
 int codd_knn_search_masked(codd_knn_index* ix, const float* dev_queries, int B, int k, const uint32_t* host_allow_bits, int64_t nwords,
                            uint32_t row_base, uint64_t* dev_keys, float* dev_dist, int64_t* dev_rows, void* stream) {
-    if (!ix || !dev_queries) return fail(CODD_KNN_EINVAL, "null index or queries%s");
-    if (B < 1 || B > CODD_KNN_MAX_BATCH) return fail(CODD_KNN_EINVAL, "B out of range [1,1024]%s");
-    if (k < 1 || k > CODD_KNN_MAX_K) return fail(CODD_KNN_EINVAL, "k out of range [1,128]%s");
-    if ((int64_t)row_base + ix->count >= 0xffffffffll) return fail(CODD_KNN_EINVAL, "global row ids must fit 32 bits%s");
+    int rc;
+    if ((rc = search_check_args(ix, dev_queries, B, k, row_base)) != 0) return rc;
     DeviceGuard guard(ix->device);
     hipStream_t st = (hipStream_t)stream;
     WorkScope work(ix, st);
@@ -3627,7 +3538,6 @@ int codd_knn_search_masked(codd_knn_index* ix, const float* dev_queries, int B, 
     if (nwords != (n + 31) / 32) return fail(CODD_KNN_EINVAL, "search_masked: nwords must be ceil(count / 32)%s");
     if (nwords > 0 && !host_allow_bits) return fail(CODD_KNN_EINVAL, "null allow bits%s");
     ix->stat_masked_searches++;
-    int rc;
     if ((rc = wait_rows(ix, st)) != 0) return rc;
     // The host words: clipped to [0, count) into the workspace's pinned staging buffer, counted against the tombstone mirror on
     // the way (m: the rows this call may see, exact, nothing read back), then one asynchronous copy from the staging buffer.  The
@@ -3635,17 +3545,15 @@ int codd_knn_search_masked(codd_knn_index* ix, const float* dev_queries, int B, 
     int64_t m = 0;
     if (nwords > 0 && (rc = stage_host_mask(ix, host_allow_bits, nwords, n, &m)) != 0) return rc;
     ix->stat_last_mask_rows = m;
-    if (m == 0) return masked_empty_result(ix, B, k, dev_keys, dev_dist, dev_rows, st);
+    if (m == 0) return empty_result(ix, B, k, dev_keys, dev_dist, dev_rows, st);
     if ((rc = upload_staged_mask(ix, nwords, st)) != 0) return rc;
     return masked_search_body(ix, dev_queries, B, k, nwords, m, row_base, dev_keys, dev_dist, dev_rows, st);
 }
 
 int codd_knn_search_masked_dev(codd_knn_index* ix, const float* dev_queries, int B, int k, const uint32_t* dev_allow_bits, int64_t nwords,
                                uint32_t row_base, uint64_t* dev_keys, float* dev_dist, int64_t* dev_rows, void* stream) {
-    if (!ix || !dev_queries) return fail(CODD_KNN_EINVAL, "null index or queries%s");
-    if (B < 1 || B > CODD_KNN_MAX_BATCH) return fail(CODD_KNN_EINVAL, "B out of range [1,1024]%s");
-    if (k < 1 || k > CODD_KNN_MAX_K) return fail(CODD_KNN_EINVAL, "k out of range [1,128]%s");
-    if ((int64_t)row_base + ix->count >= 0xffffffffll) return fail(CODD_KNN_EINVAL, "global row ids must fit 32 bits%s");
+    int rc;
+    if ((rc = search_check_args(ix, dev_queries, B, k, row_base)) != 0) return rc;
     DeviceGuard guard(ix->device);
     hipStream_t st = (hipStream_t)stream;
     WorkScope work(ix, st);
@@ -3654,16 +3562,15 @@ int codd_knn_search_masked_dev(codd_knn_index* ix, const float* dev_queries, int
     if (nwords > 0 && !dev_allow_bits) return fail(CODD_KNN_EINVAL, "null allow bits%s");
     ix->stat_masked_searches++;
     ix->stat_masked_dev++;
-    int rc;
     if ((rc = wait_rows(ix, st)) != 0) return rc;
     // The device words: clipped to [0, count) into the workspace's allow buffer and counted against the tombstone bits by one small
     // kernel behind whatever wrote them on `st`; the count comes back through pinned memory — the one host synchronisation of the call
     // (m chooses the route and sizes the list).
     int64_t m = 0;
     if (nwords > 0) {
-        if (!ix->mask_m_dev) HIP_TRY(hipMalloc((void**)&ix->mask_m_dev, sizeof(unsigned long long)));
-        if (!ix->mask_m_host) HIP_TRY(hipHostMalloc((void**)&ix->mask_m_host, sizeof(unsigned long long), hipHostMallocDefault));
-        if ((rc = ensure_buf(&ix->mask_allow, &ix->mask_allow_cap, nwords)) != 0) return rc;
+        if (!ix->mask_m_dev) HIP_TRY(ix->mask_m_dev.reset(1));
+        if (!ix->mask_m_host) HIP_TRY(ix->mask_m_host.reset(1));
+        HIP_TRY(ix->mask_allow.ensure(nwords));
         HIP_TRY(hipMemsetAsync(ix->mask_m_dev, 0, sizeof(unsigned long long), st));
         hipLaunchKernelGGL(mask_clip_count_kernel, dim3((unsigned)((nwords + 255) / 256)), dim3(256), 0, st, dev_allow_bits, ix->dead_bits, n, nwords,
                            ix->mask_allow, ix->mask_m_dev);
@@ -3673,7 +3580,7 @@ int codd_knn_search_masked_dev(codd_knn_index* ix, const float* dev_queries, int
         m = (int64_t)*ix->mask_m_host;
     }
     ix->stat_last_mask_rows = m;
-    if (m == 0) return masked_empty_result(ix, B, k, dev_keys, dev_dist, dev_rows, st);
+    if (m == 0) return empty_result(ix, B, k, dev_keys, dev_dist, dev_rows, st);
     return masked_search_body(ix, dev_queries, B, k, nwords, m, row_base, dev_keys, dev_dist, dev_rows, st);
 }
 
@@ -3749,21 +3656,16 @@ int codd_knn_set_documents_host(codd_knn_index* ix, const uint8_t* host_bytes, c
         if (len > 0) memcpy(arena.data() + offsets[(size_t)r], host_bytes + host_offsets[r], (size_t)len);
     }
     offsets[(size_t)n] = bytes;
-    uint8_t* dev_arena = nullptr;
-    int64_t* dev_offsets = nullptr;
-    hipError_t e = hipMalloc((void**)&dev_arena, (size_t)alloc);
-    if (e == hipSuccess) e = hipMalloc((void**)&dev_offsets, ((size_t)n + 1) * sizeof(int64_t));
+    DevBuf<uint8_t> dev_arena;
+    DevBuf<int64_t> dev_offsets;
+    hipError_t e = dev_arena.reset(alloc);
+    if (e == hipSuccess) e = dev_offsets.reset(n + 1);
     if (e == hipSuccess) e = hipMemcpy(dev_arena, arena.data(), (size_t)alloc, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(dev_offsets, offsets.data(), ((size_t)n + 1) * sizeof(int64_t), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {   // (the previous snapshot stays as it was)
-        if (dev_arena) (void)hipFree(dev_arena);
-        if (dev_offsets) (void)hipFree(dev_offsets);
-        return fail(e == hipErrorOutOfMemory ? CODD_KNN_ENOMEM : CODD_KNN_EDEVICE, "set_documents: upload failed: %s", hipGetErrorString(e));
-    }
-    if (ix->doc_arena) (void)hipFree(ix->doc_arena);
-    if (ix->doc_offsets) (void)hipFree(ix->doc_offsets);
-    ix->doc_arena = dev_arena;
-    ix->doc_offsets = dev_offsets;
+    // (on failure the previous snapshot stays as it was)
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? CODD_KNN_ENOMEM : CODD_KNN_EDEVICE, "set_documents: upload failed: %s", hipGetErrorString(e));
+    ix->doc_arena = std::move(dev_arena);
+    ix->doc_offsets = std::move(dev_offsets);
     ix->doc_bytes = bytes;
     ix->doc_count = n;
     ix->doc_epoch = ix->epoch;
@@ -3789,7 +3691,7 @@ int codd_knn_match_documents(codd_knn_index* ix, const uint8_t* host_needle, int
     const int64_t tiles = (ix->doc_bytes + kDocTile - 1) / kDocTile;
     const int64_t most = (int64_t)ix->num_cus * 8;   // (grid-stride beyond eight workgroups per compute unit)
     const int rc = launch_kernel<doc_match_kernel>(dim3((unsigned)(tiles < most ? tiles : most)), dim3(kDocThreads), 0, st,
-                                                   reinterpret_cast<const uint4*>(ix->doc_arena), ix->doc_bytes, tiles, ix->doc_offsets, ix->count, needle,
+                                                   reinterpret_cast<const uint4*>(ix->doc_arena.get()), ix->doc_bytes, tiles, ix->doc_offsets, ix->count, needle,
                                                    needle_len, dev_bits);
     if (rc != 0) return rc;
     HIP_TRY(hipGetLastError());
@@ -3823,23 +3725,18 @@ int codd_knn_delete_host(codd_knn_index* ix, const int64_t* host_slots, int64_t 
     }
     auto undo = [&]() {
         for (int64_t slot : fresh) ix->dead_host[(size_t)(slot >> 5)] &= ~(1u << (uint32_t)(slot & 31));
-        if (ix->dead_bits) (void)hipMemcpy(ix->dead_bits, ix->dead_host.data(), (size_t)ix->dead_words_cap * sizeof(uint32_t), hipMemcpyHostToDevice);
+        if (ix->dead_bits) (void)hipMemcpy(ix->dead_bits, ix->dead_host.data(), (size_t)ix->dead_bits.bytes(), hipMemcpyHostToDevice);
     };
     // the staging buffer codd_knn_upsert_host keeps between calls, grown once to hold the call's slots (at most 1M of them, 8 MiB:
     // a piece costs a copy, a launch and a synchronisation — 5M slots through 4,096-slot pieces were 1,221 such round trips)
     const int64_t total = (int64_t)fresh.size();
     const int64_t want = total < 4096 ? 4096 : (total < (1ll << 20) ? total : (1ll << 20));
-    if (ix->stage_slot_cap < want) {
-        if (ix->stage_slot) (void)hipFree(ix->stage_slot);
-        ix->stage_slot = nullptr; ix->stage_slot_cap = 0;
-        if (hipMalloc((void**)&ix->stage_slot, (size_t)want * sizeof(int64_t)) != hipSuccess) {
-            (void)hipGetLastError();
-            undo();
-            return fail(CODD_KNN_ENOMEM, "delete: staging buffer%s");
-        }
-        ix->stage_slot_cap = want;
+    if (ix->stage_slot.cap() < want && ix->stage_slot.reset(want) != hipSuccess) {
+        (void)hipGetLastError();
+        undo();
+        return fail(CODD_KNN_ENOMEM, "delete: staging buffer%s");
     }
-    const int64_t pn = ix->stage_slot_cap;
+    const int64_t pn = ix->stage_slot.cap();
     for (int64_t i0 = 0; i0 < total; i0 += pn) {
         const int64_t m = total - i0 < pn ? total - i0 : pn;
         hipError_t e = hipMemcpy(ix->stage_slot, fresh.data() + i0, (size_t)m * sizeof(int64_t), hipMemcpyHostToDevice);
@@ -3886,24 +3783,13 @@ int codd_knn_compact(codd_knn_index* ix, int64_t* new_count) {
     if (chunk > n - first) chunk = n - first;
     if (chunk < 1) chunk = 1;
     const int64_t bounce_floats = (chunk * (int64_t)row_bytes + 3) / 4;
-    if (bounce_floats > ix->stage_vec_cap) {
-        if (ix->stage_vec) (void)hipFree(ix->stage_vec);
-        ix->stage_vec = nullptr; ix->stage_vec_cap = 0;
-        const int64_t want = bounce_floats < 65536 ? 65536 : bounce_floats;
-        HIP_TRY(hipMalloc((void**)&ix->stage_vec, (size_t)want * sizeof(float)));
-        ix->stage_vec_cap = want;
-    }
-    if ((chunk + 1) / 2 > ix->stage_slot_cap) {  // the chunk's scope labels, 4 bytes each
-        if (ix->stage_slot) (void)hipFree(ix->stage_slot);
-        ix->stage_slot = nullptr; ix->stage_slot_cap = 0;
-        const int64_t want = (chunk + 1) / 2 < 4096 ? 4096 : (chunk + 1) / 2;
-        HIP_TRY(hipMalloc((void**)&ix->stage_slot, (size_t)want * sizeof(int64_t)));
-        ix->stage_slot_cap = want;
-    }
+    if (bounce_floats > ix->stage_vec.cap()) HIP_TRY(ix->stage_vec.reset(bounce_floats < 65536 ? 65536 : bounce_floats));
+    if ((chunk + 1) / 2 > ix->stage_slot.cap())  // the chunk's scope labels, 4 bytes each
+        HIP_TRY(ix->stage_slot.reset((chunk + 1) / 2 < 4096 ? 4096 : (chunk + 1) / 2));
     // new slot of a live row = its rank among the live rows: prefix sums over the bitmap, on the device
     const int64_t nwords = (n + 31) / 32, nblocks = (nwords + 255) / 256;
-    unsigned* sums = nullptr;   // [nwords] per-word prefix, [nblocks] block totals, [nblocks + 1] block bases
-    HIP_TRY(hipMalloc((void**)&sums, (size_t)(nwords + 2 * nblocks + 1) * sizeof(unsigned)));
+    DevBuf<unsigned> sums;   // [nwords] per-word prefix, [nblocks] block totals, [nblocks + 1] block bases
+    HIP_TRY(sums.reset(nwords + 2 * nblocks + 1));
     unsigned* prefix = sums;
     unsigned* block_total = prefix + nwords;
     unsigned* block_base = block_total + nblocks;
@@ -3911,9 +3797,9 @@ int codd_knn_compact(codd_knn_index* ix, int64_t* new_count) {
     hipLaunchKernelGGL(scope_offsets_kernel, dim3(1), dim3(1024), 0, nullptr, block_total, (int)nblocks, block_base);
     hipError_t e = hipGetLastError();
     // ascending chunks of source rows from the first dead slot on (the rows below it stay where they are), ordered on one stream
-    uint4* rows4 = reinterpret_cast<uint4*>(ix->rows);
-    uint4* bounce = reinterpret_cast<uint4*>(ix->stage_vec);
-    uint32_t* bounce_scope = reinterpret_cast<uint32_t*>(ix->stage_slot);
+    uint4* rows4 = reinterpret_cast<uint4*>(ix->rows.get());
+    uint4* bounce = reinterpret_cast<uint4*>(ix->stage_vec.get());
+    uint32_t* bounce_scope = reinterpret_cast<uint32_t*>(ix->stage_slot.get());
     int64_t dbase = first;  // every slot below the first dead one is live
     for (int64_t s0 = first; s0 < n && e == hipSuccess; s0 += chunk) {
         const int64_t s1 = s0 + chunk < n ? s0 + chunk : n;
@@ -3922,14 +3808,14 @@ int codd_knn_compact(codd_knn_index* ix, int64_t* new_count) {
         hipLaunchKernelGGL(compact_gather_kernel, dim3((unsigned)((s1 - s0 + 3) / 4)), dim3(256), 0, nullptr, rows4, ix->dead_bits, n, prefix, block_base,
                            ix->scope_of, s0, s1, dbase, chunk, cpr, bounce, bounce_scope);
         e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync((char*)ix->rows + (size_t)dbase * row_bytes, bounce, (size_t)moved * row_bytes, hipMemcpyDeviceToDevice, nullptr);
+        if (e == hipSuccess) e = hipMemcpyAsync(ix->rows + (size_t)dbase * row_bytes, bounce, (size_t)moved * row_bytes, hipMemcpyDeviceToDevice, nullptr);
         if (e == hipSuccess && ix->scope_of)
             e = hipMemcpyAsync(ix->scope_of + dbase, bounce_scope, (size_t)moved * sizeof(uint32_t), hipMemcpyDeviceToDevice, nullptr);
         dbase += moved;
     }
     // the slots past the live rows are new slots again: no label, no tombstone; the int8 shadow's scales there read "no such row"
     if (e == hipSuccess && ix->scope_of) e = hipMemsetAsync(ix->scope_of + live, 0, (size_t)(n - live) * sizeof(uint32_t), nullptr);
-    if (e == hipSuccess) e = hipMemsetAsync(ix->dead_bits, 0, (size_t)ix->dead_words_cap * sizeof(uint32_t), nullptr);
+    if (e == hipSuccess) e = hipMemsetAsync(ix->dead_bits, 0, (size_t)ix->dead_bits.bytes(), nullptr);
     if (e == hipSuccess && ix->rscale) {
         const int64_t hi = n < ix->shadow8_rows ? n : ix->shadow8_rows;
         if (hi > live) e = hipMemsetD32Async((hipDeviceptr_t)(ix->rscale + live), (int)0x7fc00000, (size_t)(hi - live), nullptr);
@@ -3937,7 +3823,6 @@ int codd_knn_compact(codd_knn_index* ix, int64_t* new_count) {
         if (e == hipSuccess && b1 > b0) e = hipMemsetD32Async((hipDeviceptr_t)(ix->bmeta + b0), (int)0x7fc00000, (size_t)(b1 - b0) * 2, nullptr);
     }
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    (void)hipFree(sums);
     // A device failure in the middle leaves rows partly moved under an unchanged bitmap and count: the index is unusable from
     // then on (destroy it and rebuild the collection), as the header says.  Nothing short of a device error gets here.
     if (e != hipSuccess) return fail(CODD_KNN_EDEVICE, "compaction failed, the index is unusable: %s", hipGetErrorString(e));
@@ -3973,7 +3858,7 @@ int codd_knn_compact(codd_knn_index* ix, int64_t* new_count) {
 int codd_knn_exp_read_stamps(codd_knn_index* ix, unsigned long long* host_out, int n_u64, void* stream) {
     if (!ix || !host_out) return CODD_KNN_EINVAL;
     WorkScope work(ix, (hipStream_t)stream);
-    if (!ix->bucket_max || (int64_t)n_u64 > ix->bucket_cap) return CODD_KNN_EINVAL;
+    if (!ix->bucket_max || (int64_t)n_u64 > ix->bucket_max.cap()) return CODD_KNN_EINVAL;
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(host_out, ix->bucket_max, (size_t)n_u64 * 8, hipMemcpyDeviceToHost));
     return CODD_KNN_OK;
@@ -4121,9 +4006,9 @@ int codd_knn_set_option(codd_knn_index* ix, const char* key, int64_t value) {
         if (value < 0 || value > 65536) return fail(CODD_KNN_EINVAL, "profile pairs must be in [0,65536]%s");
         DeviceGuard guard(ix->device);
         while ((int64_t)ix->ev.size() < 2 * value) {
-            hipEvent_t e;
-            HIP_TRY(hipEventCreate(&e));
-            ix->ev.push_back(e);
+            Event e;
+            HIP_TRY(e.ensure(hipEventDefault));
+            ix->ev.push_back(std::move(e));
         }
         ix->ev_kind.assign(ix->ev.size() / 2, 0);
         ix->profile = value > 0;
@@ -4131,6 +4016,14 @@ int codd_knn_set_option(codd_knn_index* ix, const char* key, int64_t value) {
         return CODD_KNN_OK;
     }
     return fail(CODD_KNN_EINVAL, "unknown option: %s", key);
+}
+
+int codd_knn_debug_live_allocations(int64_t* buffers, int64_t* bytes, int64_t* events) {
+    if (!buffers || !bytes || !events) return fail(CODD_KNN_EINVAL, "debug_live_allocations: null output%s");
+    *buffers = g_live_buffers.load();
+    *bytes = g_live_bytes.load();
+    *events = g_live_events.load();
+    return CODD_KNN_OK;
 }
 
 int codd_knn_get_stat(const codd_knn_index* ix, const char* key, int64_t* out) {
@@ -4192,7 +4085,7 @@ int codd_knn_get_stat(const codd_knn_index* ix, const char* key, int64_t* out) {
     else if (strcmp(key, "small_batch_passes") == 0) *out = ix->stat_small_batch;
     else if (strcmp(key, "shadow8_cooldowns") == 0) *out = ix->stat_cooldowns;
     else if (strcmp(key, "shadow8_wide_blocks") == 0) {  // blocks whose error norm exceeds shadow8_max_eps, as last read back
-        if (ix->eps_r_copied && hipEventQuery(ix->eps_r_copied) == hipSuccess) *out = (int64_t)reinterpret_cast<const unsigned*>(ix->eps_r_host)[1];
+        if (ix->eps_r_copied && hipEventQuery(ix->eps_r_copied) == hipSuccess) *out = (int64_t)reinterpret_cast<const unsigned*>(ix->eps_r_host.get())[1];
         else {
             (void)hipGetLastError();
             *out = ix->wide_blocks_known;
@@ -4229,12 +4122,12 @@ int codd_knn_get_stat(const codd_knn_index* ix, const char* key, int64_t* out) {
     else if (strcmp(key, "num_cus") == 0) *out = ix->num_cus;
     else if (strcmp(key, "device_bytes") == 0) {
         int64_t b = ix->capacity * (int64_t)ix->dpad * (int64_t)elem_size(ix->dtype) + ix->shadow_rows * (int64_t)ix->dpad * 2 +
-                    ix->shadow8_rows * ((int64_t)dpad8_of(ix) + 4) + (ix->scope_of_cap + ix->scope_perm_cap + ix->scope_lists_cap + ix->dead_words_cap) * 4 +
-                    (ix->doc_arena ? doc_arena_alloc_bytes(ix->doc_bytes) + (ix->doc_count + 1) * 8 : 0);
+                    ix->shadow8_rows * ((int64_t)dpad8_of(ix) + 4) + ix->scope_of.bytes() + ix->scope_perm.bytes() + ix->scope_offsets.bytes() + ix->dead_bits.bytes() +
+                    ix->doc_arena.bytes() + ix->doc_offsets.bytes();
         for (const WorkSlot& w : ix->slots)
-            b += w.bufs.qn_cap * 4 + w.bufs.partial_cap * 8 + w.bufs.keys_tmp_cap * 8 + w.bufs.hits_cap * 8 + w.bufs.bucket_cap * 8 +
-                 w.bufs.qfrag_cap * 16 + w.bufs.fb_partial_cap * 8 + w.bufs.probe_cap * 8 + w.bufs.ivf_partial_cap * 8;
-        *out = b;
+            b += w.bufs.qn.bytes() + w.bufs.partial.bytes() + w.bufs.keys_tmp.bytes() + w.bufs.hits.bytes() + w.bufs.bucket_max.bytes() +
+                 w.bufs.qfrag.bytes() + w.bufs.fb_partial.bytes() + w.bufs.probe_keys.bytes() + w.bufs.ivf_partial.bytes();
+        *out = b;  // (the terms it has always had: DESIGN.md §18 lists what it leaves out)
     } else if (strcmp(key, "workspaces") == 0) {
         int64_t c = 0;
         for (const WorkSlot& w : ix->slots) c += w.used ? 1 : 0;

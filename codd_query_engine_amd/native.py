@@ -60,6 +60,7 @@ ABI = [
     ("codd_knn_compact", ctypes.c_int, [_c_idx, _i64p]),
     ("codd_knn_set_option", ctypes.c_int, [_c_idx, ctypes.c_char_p, ctypes.c_int64]),
     ("codd_knn_get_stat", ctypes.c_int, [_c_idx, ctypes.c_char_p, _i64p]),
+    ("codd_knn_debug_live_allocations", ctypes.c_int, [_i64p, _i64p, _i64p]),
 ]
 
 
@@ -113,3 +114,10 @@ def last_error() -> str:
 def check(rc: int, what: str) -> None:
     if rc != 0:
         raise NativeLibraryError(f"{what} failed with code {rc}: {last_error()}")
+
+
+def live_allocations() -> tuple:
+    """(buffers, bytes, events) the library holds in this process right now (codd_knn_debug_live_allocations)."""
+    out = [ctypes.c_int64() for _ in range(3)]
+    check(load().codd_knn_debug_live_allocations(*[ctypes.byref(o) for o in out]), "debug_live_allocations")
+    return tuple(o.value for o in out)

@@ -401,6 +401,11 @@ int codd_knn_slice_mask(int device, const uint32_t* dev_global_bits, int64_t glo
 int codd_knn_set_option(codd_knn_index* index, const char* key, int64_t value);
 int codd_knn_get_stat(const codd_knn_index* index, const char* key, int64_t* out);
 
+/* What the library holds at this moment, in the whole process: device and pinned host buffers, their bytes, and HIP events.
+ * Every index takes what it allocates back in codd_knn_destroy, so the three figures return to what they were before
+ * codd_knn_create (tests compare against such a baseline: other indexes may be alive).  No device call; EINVAL for a null pointer. */
+int codd_knn_debug_live_allocations(int64_t* buffers, int64_t* bytes, int64_t* events);
+
 #ifdef __cplusplus
 }
 #endif

@@ -49,6 +49,26 @@ def test_error_codes_without_a_device():
         native.check(-22, "demo")
 
 
+def test_live_allocations_of_a_process_that_never_created_an_index():
+    # (a fresh interpreter: in this one, GPU tests that ran earlier may hold indexes)
+    import subprocess
+    import sys
+
+    code = "from codd_query_engine_amd import native; print(native.live_allocations())"
+    out = subprocess.run([sys.executable, "-c", code], cwd=ROOT, capture_output=True, text=True, check=True).stdout
+    assert out.strip() == "(0, 0, 0)"
+
+
+def test_live_allocations_rejects_null_pointers():
+    lib = native.load()
+    v = ctypes.c_int64()
+    ok = ctypes.byref(v)
+    for args in ((None, ok, ok), (ok, None, ok), (ok, ok, None)):
+        assert lib.codd_knn_debug_live_allocations(*args) == -22
+    assert "null" in native.last_error()
+    assert all(x >= 0 for x in native.live_allocations())
+
+
 def test_product_path_fails_loudly_without_gpu():
     import torch
 
