@@ -3198,7 +3198,7 @@ int codd_knn_ivf_install(codd_knn_index* ix, const float* dev_centroids, int nli
 
 namespace {
 
-// what the scoped and the masked entry points check before they take a workspace
+// what the scoped, the masked and the IVF entry points check before they take a workspace
 int search_check_args(const codd_knn_index* ix, const float* dev_queries, int B, int k, uint32_t row_base) {
     if (!ix || !dev_queries) return fail(CODD_KNN_EINVAL, "null index or queries%s");
     if (B < 1 || B > CODD_KNN_MAX_BATCH) return fail(CODD_KNN_EINVAL, "B out of range [1,1024]%s");
@@ -3217,10 +3217,9 @@ int empty_result(codd_knn_index* ix, int B, int k, uint64_t* dev_keys, float* de
 }
 
 // what every IVF entry point checks before it takes a workspace; clamps nprobe to the number of lists
-int ivf_check_args(const codd_knn_index* ix, const float* dev_queries, int B, int k, int* nprobe) {
-    if (!ix || !dev_queries) return fail(CODD_KNN_EINVAL, "null index or queries%s");
-    if (B < 1 || B > CODD_KNN_MAX_BATCH) return fail(CODD_KNN_EINVAL, "B out of range [1,1024]%s");
-    if (k < 1 || k > CODD_KNN_MAX_K) return fail(CODD_KNN_EINVAL, "k out of range [1,128]%s");
+int ivf_check_args(const codd_knn_index* ix, const float* dev_queries, int B, int k, uint32_t row_base, int* nprobe) {
+    int rc;
+    if ((rc = search_check_args(ix, dev_queries, B, k, row_base)) != 0) return rc;
     if (!ix->coarse || ix->ivf_epoch != ix->epoch) return fail(CODD_KNN_EINVAL, "no IVF layout, or rows changed since codd_knn_ivf_install%s");
     if (*nprobe < 1) return fail(CODD_KNN_EINVAL, "nprobe must be >= 1%s");
     if (*nprobe > ix->ivf_nlist) *nprobe = ix->ivf_nlist;
@@ -3302,7 +3301,7 @@ extern "C" {
 int codd_knn_ivf_search(codd_knn_index* ix, const float* dev_queries, int B, int k, int nprobe, uint32_t row_base,
                         uint64_t* dev_keys, float* dev_dist, int64_t* dev_rows, void* stream) {
     int rc;
-    if ((rc = ivf_check_args(ix, dev_queries, B, k, &nprobe)) != 0) return rc;
+    if ((rc = ivf_check_args(ix, dev_queries, B, k, row_base, &nprobe)) != 0) return rc;
     DeviceGuard guard(ix->device);
     hipStream_t st = (hipStream_t)stream;
     WorkScope work(ix, st), work_coarse(ix->coarse, st);
@@ -3587,7 +3586,7 @@ int codd_knn_search_masked_dev(codd_knn_index* ix, const float* dev_queries, int
 int codd_knn_ivf_search_masked(codd_knn_index* ix, const float* dev_queries, int B, int k, int nprobe, const uint32_t* host_allow_bits, int64_t nwords,
                                uint32_t row_base, uint64_t* dev_keys, float* dev_dist, int64_t* dev_rows, void* stream) {
     int rc;
-    if ((rc = ivf_check_args(ix, dev_queries, B, k, &nprobe)) != 0) return rc;
+    if ((rc = ivf_check_args(ix, dev_queries, B, k, row_base, &nprobe)) != 0) return rc;
     DeviceGuard guard(ix->device);
     hipStream_t st = (hipStream_t)stream;
     WorkScope work(ix, st), work_coarse(ix->coarse, st);
@@ -3604,7 +3603,7 @@ int codd_knn_ivf_search_masked(codd_knn_index* ix, const float* dev_queries, int
 int codd_knn_ivf_search_masked_dev(codd_knn_index* ix, const float* dev_queries, int B, int k, int nprobe, const uint32_t* dev_allow_bits, int64_t nwords,
                                    uint32_t row_base, uint64_t* dev_keys, float* dev_dist, int64_t* dev_rows, void* stream) {
     int rc;
-    if ((rc = ivf_check_args(ix, dev_queries, B, k, &nprobe)) != 0) return rc;
+    if ((rc = ivf_check_args(ix, dev_queries, B, k, row_base, &nprobe)) != 0) return rc;
     DeviceGuard guard(ix->device);
     hipStream_t st = (hipStream_t)stream;
     WorkScope work(ix, st), work_coarse(ix->coarse, st);

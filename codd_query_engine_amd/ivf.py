@@ -109,6 +109,7 @@ def search_ivf(index: DeviceKnnIndex, queries, k: int, nprobe: int, row_base: in
     probes; the mask only removes rows from them, so a small mask may leave fewer than k hits."""
     import torch
 
+    row_base = native.check_row_base(row_base, index.count())
     if allow is not None:
         if _is_device_mask(allow):
             return index.ivf_search_masked_dev_tensors(queries, allow, k, nprobe, row_base)
@@ -119,7 +120,7 @@ def search_ivf(index: DeviceKnnIndex, queries, k: int, nprobe: int, row_base: in
     dist = torch.empty((B, k), dtype=torch.float32, device=index.device)
     rows = torch.empty((B, k), dtype=torch.int64, device=index.device)
     native.check(
-        lib.codd_knn_ivf_search(index._h, q.data_ptr(), B, int(k), int(nprobe), int(row_base), None, dist.data_ptr(), rows.data_ptr(),
+        lib.codd_knn_ivf_search(index._h, q.data_ptr(), B, int(k), int(nprobe), row_base, None, dist.data_ptr(), rows.data_ptr(),
                                 index._stream()),
         "codd_knn_ivf_search",
     )
@@ -131,6 +132,7 @@ def search_ivf_keys(index: DeviceKnnIndex, queries, k: int, nprobe: int, row_bas
     allow: as in search_ivf (the mask is over the shard's LOCAL row slots)."""
     import torch
 
+    row_base = native.check_row_base(row_base, index.count())
     if allow is not None:
         if _is_device_mask(allow):
             return index.ivf_search_keys_masked_dev(queries, allow, k, nprobe, row_base)
@@ -140,7 +142,7 @@ def search_ivf_keys(index: DeviceKnnIndex, queries, k: int, nprobe: int, row_bas
     B = q.shape[0]
     keys = torch.empty((B, k), dtype=torch.int64, device=index.device)
     native.check(
-        lib.codd_knn_ivf_search(index._h, q.data_ptr(), B, int(k), int(nprobe), int(row_base), keys.data_ptr(), None, None, index._stream()),
+        lib.codd_knn_ivf_search(index._h, q.data_ptr(), B, int(k), int(nprobe), row_base, keys.data_ptr(), None, None, index._stream()),
         "codd_knn_ivf_search",
     )
     return keys

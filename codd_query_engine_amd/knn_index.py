@@ -152,12 +152,13 @@ class DeviceKnnIndex:
 
     def search_keys(self, queries, k: int, row_base: int = 0):
         """Shard-local packed keys [B,k] (u64 bit patterns in an int64 tensor), descending."""
+        row_base = native.check_row_base(row_base, self.count())
         torch = _torch()
         q = self._queries_tensor(queries)
         B = q.shape[0]
         keys = torch.empty((B, k), dtype=torch.int64, device=self.device)
         native.check(
-            self._lib.codd_knn_search_keys(self._h, q.data_ptr(), B, int(k), int(row_base), keys.data_ptr(), self._stream()),
+            self._lib.codd_knn_search_keys(self._h, q.data_ptr(), B, int(k), row_base, keys.data_ptr(), self._stream()),
             "codd_knn_search_keys",
         )
         return keys
@@ -223,13 +224,14 @@ class DeviceKnnIndex:
 
     def search_keys_scoped(self, queries, scopes, k: int, row_base: int = 0):
         """search_keys among the rows whose scope equals the query's."""
+        row_base = native.check_row_base(row_base, self.count())
         torch = _torch()
         q = self._queries_tensor(queries)
         B = q.shape[0]
         s = self._scopes_tensor(scopes, B)
         keys = torch.empty((B, k), dtype=torch.int64, device=self.device)
         native.check(
-            self._lib.codd_knn_search_scoped(self._h, q.data_ptr(), s.data_ptr(), B, int(k), int(row_base), keys.data_ptr(), None, None, self._stream()),
+            self._lib.codd_knn_search_scoped(self._h, q.data_ptr(), s.data_ptr(), B, int(k), row_base, keys.data_ptr(), None, None, self._stream()),
             "codd_knn_search_scoped",
         )
         return keys
@@ -254,6 +256,7 @@ class DeviceKnnIndex:
         return np.ascontiguousarray(a)
 
     def _search_masked(self, queries, allow, k: int, row_base: int, want_keys: bool):
+        row_base = native.check_row_base(row_base, self.count())
         torch = _torch()
         q = self._queries_tensor(queries)
         B = q.shape[0]
@@ -262,7 +265,7 @@ class DeviceKnnIndex:
         dist = None if want_keys else torch.empty((B, k), dtype=torch.float32, device=self.device)
         rows = None if want_keys else torch.empty((B, k), dtype=torch.int64, device=self.device)
         native.check(
-            self._lib.codd_knn_search_masked(self._h, q.data_ptr(), B, int(k), words.ctypes.data, words.shape[0], int(row_base),
+            self._lib.codd_knn_search_masked(self._h, q.data_ptr(), B, int(k), words.ctypes.data, words.shape[0], row_base,
                                              keys.data_ptr() if want_keys else None, None if want_keys else dist.data_ptr(),
                                              None if want_keys else rows.data_ptr(), self._stream()),
             "codd_knn_search_masked",
@@ -317,6 +320,7 @@ class DeviceKnnIndex:
         return allow_bits.to(self.device).contiguous()
 
     def _search_masked_dev(self, queries, allow_bits, k: int, row_base: int, want_keys: bool):
+        row_base = native.check_row_base(row_base, self.count())
         torch = _torch()
         q = self._queries_tensor(queries)
         B = q.shape[0]
@@ -326,7 +330,7 @@ class DeviceKnnIndex:
         rows = None if want_keys else torch.empty((B, k), dtype=torch.int64, device=self.device)
         native.check(
             self._lib.codd_knn_search_masked_dev(self._h, q.data_ptr(), B, int(k), words.data_ptr() if words.shape[0] else None, words.shape[0],
-                                                 int(row_base), keys.data_ptr() if want_keys else None, None if want_keys else dist.data_ptr(),
+                                                 row_base, keys.data_ptr() if want_keys else None, None if want_keys else dist.data_ptr(),
                                                  None if want_keys else rows.data_ptr(), self._stream()),
             "codd_knn_search_masked_dev",
         )
@@ -348,6 +352,7 @@ class DeviceKnnIndex:
 
     # ------------------------------------------------------------------ masks under an IVF layout
     def _ivf_search_masked(self, queries, allow, k: int, nprobe: int, row_base: int, want_keys: bool, on_device: bool):
+        row_base = native.check_row_base(row_base, self.count())
         torch = _torch()
         q = self._queries_tensor(queries)
         B = q.shape[0]
@@ -361,7 +366,7 @@ class DeviceKnnIndex:
         dist = None if want_keys else torch.empty((B, k), dtype=torch.float32, device=self.device)
         rows = None if want_keys else torch.empty((B, k), dtype=torch.int64, device=self.device)
         native.check(
-            fn(self._h, q.data_ptr(), B, int(k), int(nprobe), ptr, words.shape[0], int(row_base), keys.data_ptr() if want_keys else None,
+            fn(self._h, q.data_ptr(), B, int(k), int(nprobe), ptr, words.shape[0], row_base, keys.data_ptr() if want_keys else None,
                None if want_keys else dist.data_ptr(), None if want_keys else rows.data_ptr(), self._stream()),
             name,
         )

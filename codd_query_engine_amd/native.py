@@ -21,6 +21,7 @@ MAX_K = 128
 MAX_BATCH = 1024
 MAX_SCOPE = 1048575
 MAX_NEEDLE = 256
+MAX_GLOBAL_ROW = 0xFFFFFFFD  # the low word of a packed key is 0xFFFFFFFF - global row, and 0 = empty: row_base + count < 0xFFFFFFFF
 
 # every symbol include/codd_knn.h declares: (name, restype, argtypes)
 _c_idx = ctypes.c_void_p
@@ -114,6 +115,16 @@ def last_error() -> str:
 def check(rc: int, what: str) -> None:
     if rc != 0:
         raise NativeLibraryError(f"{what} failed with code {rc}: {last_error()}")
+
+
+def check_row_base(row_base: int, count: int) -> int:
+    """The `row_base` of a shard of `count` rows as the C ABI takes it.  ctypes converts to uint32 without a range check
+    (2**32 + 5 would arrive as 5, -1 as 0xFFFFFFFF), so every wrapper that forwards a row_base passes it through here first:
+    ValueError unless 0 <= row_base and row_base + count < 0xFFFFFFFF (include/codd_knn.h, conventions)."""
+    row_base, count = int(row_base), int(count)
+    if row_base < 0 or count < 0 or row_base + count > MAX_GLOBAL_ROW + 1:
+        raise ValueError(f"global row ids must fit 32 bits: row_base {row_base} + count {count} must stay below 0xFFFFFFFF, row_base >= 0")
+    return row_base
 
 
 def live_allocations() -> tuple:

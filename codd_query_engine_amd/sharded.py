@@ -76,9 +76,11 @@ class ShardedSearcher:
                  merge: Optional[Callable[[Any, int], tuple]] = None, always_gather: bool = False):
         import torch.distributed as dist
 
+        from .native import check_row_base
+
         self.engine = engine
         self.always_gather = always_gather  # exercise the collective even with one rank (rehearsals)
-        self.row_base = int(row_base)
+        self.row_base = check_row_base(row_base, 0)  # (the sign and >= 2^32 here; row_base + count by the engine, per search)
         self.group = group
         self.world_size = dist.get_world_size(group) if dist.is_initialized() else 1
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0

@@ -30,6 +30,10 @@
  *   - rows are stored L2-normalised, zero padded to a multiple of 64 elements.
  *     score = <q/|q|, c/|c|> evaluated in fp32 in the canonical order of
  *     DESIGN.md §3; distance = 1 - score (fp32); ties -> lower row.
+ *   - every entry point with a `row_base` (codd_knn_search_keys, _search_scoped, _search_masked,
+ *     _search_masked_dev, _ivf_search, _ivf_search_masked, _ivf_search_masked_dev) writes global rows
+ *     row_base + row, which must fit the low word of a packed key: the highest global row is
+ *     0xFFFFFFFD, i.e. row_base + count < 0xFFFFFFFF, else EINVAL and nothing is enqueued or written.
  *   - a row slot can be deleted (codd_knn_delete_host): it becomes a tombstone that no search entry
  *     point returns and no write accepts, until codd_knn_compact moves the live rows down over it
  *     (stable: slot order kept).  An index nobody deleted from behaves, and runs, exactly as before

@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import numpy as np
 
+from codd_query_engine_amd import native
 from oracle import knn_oracle as o
 
 
@@ -59,6 +60,7 @@ class OracleEngine:
         return o.search(self._rows, self.dtype, self._prep(queries), k)
 
     def search_keys(self, queries, k: int, row_base: int = 0) -> np.ndarray:
+        row_base = native.check_row_base(row_base, self.count())   # (as DeviceKnnIndex.search_keys: the oracle's uint32 would truncate too)
         return o.search_keys(self._rows, self.dtype, self._prep(queries), k, row_base)
 
     @staticmethod

@@ -6,6 +6,7 @@ from __future__ import annotations
 
 import numpy as np
 
+from codd_query_engine_amd import native
 from oracle import knn_oracle as o
 from tests._oracle_engine import OracleEngine
 
@@ -53,6 +54,7 @@ class ScopedOracleEngine(OracleEngine):
         return super().search(queries, k)
 
     def search_keys_scoped(self, queries, scopes, k: int, row_base: int = 0) -> np.ndarray:
+        row_base = native.check_row_base(row_base, self.count())
         qn = self._prep(queries)
         keys = np.zeros((qn.shape[0], k), dtype=np.uint64)
         labels = self._labels()
