@@ -55,8 +55,30 @@ namespace {
 // IEEE division per element; a zero / non-finite norm stores an all-zero row.
 // shadow (optional): the bf16 rounding of the STORED value, in fragment order (filter_gemm.h).
 // ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ float butterfly_max(float v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, kWave));
+    return v;
+}
 // |x| of one vector by the canonical sum of squares: chunk j of 4 elements belongs to lane j % 64
-__device__ __forceinline__ float canonical_norm(const float* __restrict__ x, int d, int nch, int lane) {
+//
+// The squares are taken in fp32, so a vector of finite elements can have a sum of squares that underflows (elements near 1e-23
+// and below: the few bits left of a subnormal sum put the stored norm at 0.8 .. 1.2, or at 0) or overflows (elements near 1e18
+// and above).  Cosine does not depend on scale: where the sum leaves [2^-100, 2^100] the vector is scaled by the exact power of
+// two `sh` that brings its largest magnitude into [1, 2) and the same chain runs on the scaled values; the caller divides
+// scaled(x[i], sh) by the returned norm.  Inside the band (every ordinary vector) sh = 0 and nothing changes.  The branch is
+// wave-uniform: butterfly_sum and butterfly_max leave the same value in every lane.
+// Returns 0 for a vector with a non-finite element or without a non-zero one (the callers' zero row).
+constexpr float kNormBandLo = 0x1p-100f, kNormBandHi = 0x1p+100f;
+__device__ __forceinline__ float scaled(float t, int sh) { return sh ? __builtin_ldexpf(t, sh) : t; }
+// floor(log2 m) of a finite m > 0 from its bits, subnormals included
+__device__ __forceinline__ int floor_log2_f32(float m) {
+    const uint32_t u = __float_as_uint(m) & 0x7fffffffu;
+    const int e = (int)(u >> 23);
+    return e ? e - 127 : (31 - __builtin_clz(u)) - 149;
+}
+__device__ __forceinline__ float canonical_norm(const float* __restrict__ x, int d, int nch, int lane, int& sh) {
+    sh = 0;
     float acc = 0.0f;
     for (int j = lane; j < nch; j += kWave) {
 #pragma unroll
@@ -66,7 +88,32 @@ __device__ __forceinline__ float canonical_norm(const float* __restrict__ x, int
             acc = __builtin_fmaf(v, v, acc);
         }
     }
-    return __builtin_sqrtf(butterfly_sum(acc));
+    float n2 = butterfly_sum(acc);
+    if (!(n2 >= kNormBandLo && n2 <= kNormBandHi)) {
+        float m = 0.0f;
+        for (int j = lane; j < nch; j += kWave) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int i = j * 4 + e;
+                m = fmaxf(m, fabsf(i < d ? x[i] : 0.0f));
+            }
+        }
+        m = butterfly_max(m);
+        // a NaN element makes n2 NaN (fmaxf would skip it); an infinite one makes m infinite
+        if (n2 != n2 || !(m > 0.0f) || !(m < INFINITY)) return 0.0f;
+        sh = -floor_log2_f32(m);
+        acc = 0.0f;
+        for (int j = lane; j < nch; j += kWave) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int i = j * 4 + e;
+                const float v = i < d ? __builtin_ldexpf(x[i], sh) : 0.0f;
+                acc = __builtin_fmaf(v, v, acc);
+            }
+        }
+        n2 = butterfly_sum(acc);
+    }
+    return __builtin_sqrtf(n2);
 }
 
 // Query preparation of one filter pass in ONE launch (B <= 256): q <- q/|q| exactly as normalize_rows_kernel<f32> does
@@ -83,7 +130,8 @@ __global__ __launch_bounds__(256) void prep_queries_kernel(const float* __restri
         return;
     }
     const float* x = in + (int64_t)q * d;
-    const float nrm = canonical_norm(x, d, nch, lane);
+    int sh;
+    const float nrm = canonical_norm(x, d, nch, lane, sh);
     const bool zero_row = !(nrm > 0.0f) || !(nrm < INFINITY);
     for (int j = lane; j < nch; j += kWave) {
         float v[4];
@@ -91,7 +139,7 @@ __global__ __launch_bounds__(256) void prep_queries_kernel(const float* __restri
         for (int e = 0; e < 4; ++e) {
             const int i = j * 4 + e;
             const float t = i < d ? x[i] : 0.0f;
-            v[e] = zero_row ? 0.0f : t / nrm;
+            v[e] = zero_row ? 0.0f : scaled(t, sh) / nrm;
         }
         reinterpret_cast<float4*>(qn)[(int64_t)q * nch + j] = make_float4(v[0], v[1], v[2], v[3]);
         qfrag[codd::qfrag_piece_index(q, j >> 1) * 2 + (j & 1)] = make_uint2(codd::pack_bf16x2(v[0], v[1]), codd::pack_bf16x2(v[2], v[3]));
@@ -110,9 +158,10 @@ __global__ __launch_bounds__(256) void normalize_rows_kernel(const float* __rest
     const int nch = dpad >> 2;
     const int nsteps = dpad >> 6;
     float scale_div = 1.0f;
+    int sh = 0;
     bool zero_row = false;
     if (normalize) {
-        const float nrm = canonical_norm(x, d, nch, lane);
+        const float nrm = canonical_norm(x, d, nch, lane, sh);
         zero_row = !(nrm > 0.0f) || !(nrm < INFINITY);
         scale_div = nrm;
     }
@@ -123,7 +172,7 @@ __global__ __launch_bounds__(256) void normalize_rows_kernel(const float* __rest
         for (int e = 0; e < 4; ++e) {
             const int i = j * 4 + e;
             float t = i < d ? x[i] : 0.0f;
-            if (normalize) t = zero_row ? 0.0f : t / scale_div;
+            if (normalize) t = zero_row ? 0.0f : scaled(t, sh) / scale_div;
             v[e] = t;
         }
         if (DT == DT_F32) {
@@ -491,11 +540,6 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const uint4* __restric
 // its 32-row block / 127 (rscale[] holds it once per row), in the same fragment order as the bf16 shadow with 16-element pieces and 128-element K-steps.  The
 // filter's error bound needs |c - c~| for the worst row: every wave folds its row's error norm into *eps_r (ordered bits).
 // ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float butterfly_max(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, kWave));
-    return v;
-}
 __device__ __forceinline__ uint32_t quantize4(const float (&v)[4], float inv_scale, float scale, float& err2) {
     uint32_t packed = 0;
 #pragma unroll
@@ -651,7 +695,8 @@ __global__ __launch_bounds__(256) void prep_queries8_kernel(const float* __restr
         return;
     }
     const float* x = in + (int64_t)q * d;
-    const float nrm = canonical_norm(x, d, nch, lane);
+    int sh;
+    const float nrm = canonical_norm(x, d, nch, lane, sh);
     const bool zero_row = !(nrm > 0.0f) || !(nrm < INFINITY);
     float vmax = 0.0f;
     for (int j = lane; j < nch; j += kWave) {
@@ -660,7 +705,7 @@ __global__ __launch_bounds__(256) void prep_queries8_kernel(const float* __restr
         for (int e = 0; e < 4; ++e) {
             const int i = j * 4 + e;
             const float t = i < d ? x[i] : 0.0f;
-            v[e] = zero_row ? 0.0f : t / nrm;
+            v[e] = zero_row ? 0.0f : scaled(t, sh) / nrm;
             vmax = fmaxf(vmax, fabsf(v[e]));
         }
         reinterpret_cast<float4*>(qn)[(int64_t)q * nch + j] = make_float4(v[0], v[1], v[2], v[3]);
@@ -675,7 +720,7 @@ __global__ __launch_bounds__(256) void prep_queries8_kernel(const float* __restr
             for (int e = 0; e < 4; ++e) {
                 const int i = j * 4 + e;
                 const float t = i < d ? x[i] : 0.0f;
-                v[e] = zero_row ? 0.0f : t / nrm;
+                v[e] = zero_row ? 0.0f : scaled(t, sh) / nrm;
             }
         }
         qfrag8[codd::qfrag_piece_index(q, j >> 2) * 4 + (j & 3)] = quantize4(v, inv_scale, scale, err2);
@@ -753,7 +798,8 @@ __global__ __launch_bounds__(kSbThreads) void small_batch_kernel(const uint4* __
 
     // ---- the query: normalise (block 0 also stores qn: the last workgroup and the fallback scan read it) and quantise ----
     if (wave == 0) {
-        const float nrm = canonical_norm(in, d, nch, lane);
+        int sh;
+        const float nrm = canonical_norm(in, d, nch, lane, sh);
         const bool zero_row = !(nrm > 0.0f) || !(nrm < INFINITY);
         float vmax = 0.0f;
         for (int j = lane; j < nch; j += kWave) {
@@ -762,7 +808,7 @@ __global__ __launch_bounds__(kSbThreads) void small_batch_kernel(const uint4* __
             for (int e = 0; e < 4; ++e) {
                 const int i = j * 4 + e;
                 const float t = i < d ? in[i] : 0.0f;
-                v[e] = zero_row ? 0.0f : t / nrm;
+                v[e] = zero_row ? 0.0f : scaled(t, sh) / nrm;
                 vmax = fmaxf(vmax, fabsf(v[e]));
             }
             if (blockIdx.x == 0) reinterpret_cast<float4*>(qn)[j] = make_float4(v[0], v[1], v[2], v[3]);
@@ -777,7 +823,7 @@ __global__ __launch_bounds__(kSbThreads) void small_batch_kernel(const uint4* __
                 for (int e = 0; e < 4; ++e) {
                     const int i = j * 4 + e;
                     const float t = i < d ? in[i] : 0.0f;
-                    v[e] = zero_row ? 0.0f : t / nrm;
+                    v[e] = zero_row ? 0.0f : scaled(t, sh) / nrm;
                 }
             }
             reinterpret_cast<uint32_t*>(s_q8)[j] = quantize4(v, inv_scale, scale, err2);

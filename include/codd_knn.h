@@ -27,7 +27,11 @@
  *     previous owner on the device) and serialises only the enqueueing.  Searches on
  *     different streams then overlap on the GPU.  upsert/reserve/load/ivf_install/set_scopes/
  *     delete/compact/set_documents are exclusive: no other call on the index may be in flight.
- *   - rows are stored L2-normalised, zero padded to a multiple of 64 elements.
+ *   - rows are stored L2-normalised, zero padded to a multiple of 64 elements.  Normalisation
+ *     (rows and queries alike) holds for every finite non-zero fp32 vector, whatever its scale:
+ *     where the fp32 sum of squares leaves [2^-100, 2^100] the vector is first scaled by an exact
+ *     power of two.  A vector with a NaN or infinite element, or all zeros, is the
+ *     zero vector: score 0, distance 1 against everything.
  *     score = <q/|q|, c/|c|> evaluated in fp32 in the canonical order of
  *     DESIGN.md §3; distance = 1 - score (fp32); ties -> lower row.
  *   - every entry point with a `row_base` (codd_knn_search_keys, _search_scoped, _search_masked,

@@ -159,18 +159,43 @@ static float canon_dot(const float* q, const float* c, int dpad, int E) {
 
 float oracle_canon_dot(const float* q, const float* c, int dpad, int E) { return canon_dot(q, c, dpad, E); }
 
-/* Row normalisation as the ingest kernel does it: n2 = canon_dot(x,x) with E=4
- * (the ingest input is always fp32), inv-free IEEE division by sqrtf(n2);
- * a zero (or non-finite-norm) row is stored as zeros -> score 0 -> distance 1. */
+/* floor(log2 m) of a finite m > 0 from its bits (subnormals included): the same integer arithmetic as the kernels' */
+static inline int floor_log2_f32(float m) {
+    const uint32_t u = f32_as_u32(m) & 0x7fffffffu;
+    const int e = (int)(u >> 23);
+    return e ? e - 127 : (31 - __builtin_clz(u)) - 149;
+}
+
+#define NORM_BAND_LO 0x1p-100f
+#define NORM_BAND_HI 0x1p+100f
+
+/* Row normalisation as the ingest kernel does it (canonical_norm in codd_knn.hip): n2 = canon_dot(x,x) with E=4
+ * (the ingest input is always fp32), inv-free IEEE division by sqrtf(n2).  Where n2 leaves [2^-100, 2^100] (the
+ * squares underflow or overflow although the elements are finite) the row is first scaled by the exact power of two
+ * that brings its largest magnitude into [1, 2) (ldexpf), and the same chain, root and division run on the scaled
+ * values: cosine does not depend on scale.  A row with a non-finite element, or all zeros, is stored as zeros ->
+ * score 0 -> distance 1. */
 void oracle_normalize_rows(const float* in, float* out, int64_t n, int d, int dpad) {
 #pragma omp parallel for schedule(static)
     for (int64_t r = 0; r < n; ++r) {
         float* o = out + r * (int64_t)dpad;
         const float* x = in + r * (int64_t)d;
         for (int i = 0; i < dpad; ++i) o[i] = i < d ? x[i] : 0.0f;
-        const float n2 = canon_dot(o, o, dpad, 4);
+        float n2 = canon_dot(o, o, dpad, 4);
+        int zero_row = 0;
+        if (!(n2 >= NORM_BAND_LO && n2 <= NORM_BAND_HI)) {
+            float m = 0.0f;
+            for (int i = 0; i < dpad; ++i) m = fmaxf(m, fabsf(o[i]));
+            /* a NaN element makes n2 NaN (fmaxf would skip it); an infinite one makes m infinite */
+            zero_row = n2 != n2 || !(m > 0.0f) || !(m < INFINITY);
+            if (!zero_row) {
+                const int sh = -floor_log2_f32(m);
+                for (int i = 0; i < dpad; ++i) o[i] = ldexpf(o[i], sh);
+                n2 = canon_dot(o, o, dpad, 4);
+            }
+        }
         const float nrm = sqrtf(n2);
-        if (!(nrm > 0.0f) || !(nrm < INFINITY)) {
+        if (zero_row) {
             for (int i = 0; i < dpad; ++i) o[i] = 0.0f;
         } else {
             for (int i = 0; i < dpad; ++i) o[i] = o[i] / nrm;

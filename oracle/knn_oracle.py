@@ -82,7 +82,9 @@ def pad_dim(d: int) -> int:
 
 def normalize_rows(x: np.ndarray, dpad: int | None = None) -> np.ndarray:
     """fp32 [n,d] -> fp32 [n,dpad], rows scaled to unit L2 norm exactly as the ingest
-    kernel does (canonical sum of squares, IEEE sqrt and divide); zero rows stay zero."""
+    kernel does (canonical sum of squares, IEEE sqrt and divide; a power-of-two rescale first where
+    the fp32 sum of squares leaves [2^-100, 2^100]); zero rows and rows with a non-finite element
+    come back as zeros."""
     x = np.ascontiguousarray(x, dtype=np.float32)
     n, d = x.shape
     dpad = pad_dim(d) if dpad is None else dpad
