@@ -38,6 +38,7 @@
 #include "filter_gemm.h"
 #include "filter_i8.h"
 #include "row_traits.h"
+#include "text_embed.h"
 #include "wave_topk.h"
 
 using namespace codd;
@@ -1713,6 +1714,22 @@ struct codd_knn_index : WorkBufs {
     ~codd_knn_index() { (void)codd_knn_destroy(coarse); }
 };
 static_assert(!std::is_copy_constructible<codd_knn_index>::value, "an index owns its device memory");
+
+// The device embedder: no index behind it — an index does not exist before the first upsert fixes the width.
+// One pinned staging buffer and its device copy, both laid out [n + 1 offsets][bytes]; `uploaded` frees the staging buffer for
+// the next call, `embedded` orders a call on another stream behind the kernel that still reads the device copy.
+struct codd_knn_embedder {
+    int device = 0;
+    int dim = 0;
+    float trigram_weight = 0.0f;
+    bool device_seen = false;          // the first call that embeds checks that `device` exists; create and destroy touch no device before
+    PinnedBuf<unsigned char> stage_host;
+    DevBuf<unsigned char> stage_dev;
+    Event uploaded, embedded;
+    bool upload_pending = false, embedded_set = false;
+    hipStream_t last_stream = nullptr;
+    std::mutex mu;                     // one host thread at a time stages and enqueues
+};
 
 namespace {
 
@@ -3741,6 +3758,84 @@ int codd_knn_match_documents(codd_knn_index* ix, const uint8_t* host_needle, int
     if (rc != 0) return rc;
     HIP_TRY(hipGetLastError());
     ix->stat_doc_matches++;
+    return CODD_KNN_OK;
+}
+
+int codd_knn_embedder_create(codd_knn_embedder** out, int device, int dim, float trigram_weight) {
+    if (!out) return fail(CODD_KNN_EINVAL, "embedder_create: null out pointer%s");
+    *out = nullptr;
+    static_assert(kEmbedMaxDim == 4096 && kEmbedMinDim == 8, "text_embed.h and codd_knn.h disagree");
+    if (dim < kEmbedMinDim || dim > kEmbedMaxDim) return fail(CODD_KNN_EINVAL, "embedder_create: dim out of range [8,4096]%s");
+    if (!(trigram_weight - trigram_weight == 0.0f)) return fail(CODD_KNN_EINVAL, "embedder_create: trigram_weight must be finite%s");
+    if (device < 0) return fail(CODD_KNN_EINVAL, "embedder_create: no such device%s");
+    codd_knn_embedder* e = new (std::nothrow) codd_knn_embedder();
+    if (!e) return fail(CODD_KNN_ENOMEM, "host allocation failed%s");
+    e->device = device;
+    e->dim = dim;
+    e->trigram_weight = trigram_weight;
+    *out = e;
+    return CODD_KNN_OK;
+}
+
+int codd_knn_embedder_destroy(codd_knn_embedder* e) {
+    if (!e) return CODD_KNN_OK;
+    if (e->device_seen) {   // (its buffers and events free themselves: the device is current and idle, as their destructors need)
+        DeviceGuard guard(e->device);
+        (void)hipDeviceSynchronize();
+        delete e;
+    } else {
+        delete e;
+    }
+    return CODD_KNN_OK;
+}
+
+int codd_knn_embed_texts_host(codd_knn_embedder* e, const uint8_t* host_bytes, const int64_t* host_offsets, int64_t n, float* dev_out, void* stream) {
+    if (!e || !host_offsets || n < 0) return fail(CODD_KNN_EINVAL, "embed_texts: null embedder or offsets, or negative n%s");
+    if (n > CODD_KNN_MAX_EMBED_TEXTS) return fail(CODD_KNN_EINVAL, "embed_texts: more than CODD_KNN_MAX_EMBED_TEXTS texts%s");
+    if (host_offsets[0] != 0) return fail(CODD_KNN_EINVAL, "embed_texts: offsets must start at 0%s");
+    for (int64_t r = 0; r < n; ++r)
+        if (host_offsets[r + 1] < host_offsets[r]) return fail(CODD_KNN_EINVAL, "embed_texts: offsets must be non-decreasing%s");
+    const int64_t total = host_offsets[n];
+    if (total > CODD_KNN_MAX_EMBED_BYTES) return fail(CODD_KNN_EINVAL, "embed_texts: more than CODD_KNN_MAX_EMBED_BYTES bytes of text%s");
+    if (total > 0 && !host_bytes) return fail(CODD_KNN_EINVAL, "embed_texts: null bytes%s");
+    unsigned char seen = 0;
+    for (int64_t i = 0; i < total; ++i) seen |= host_bytes[i];
+    if (seen & 0x80) return fail(CODD_KNN_EINVAL, "embed_texts: a byte at or above 0x80 (ASCII only: other texts are embedded on the host)%s");
+    if (n == 0) return CODD_KNN_OK;
+    if (!dev_out) return fail(CODD_KNN_EINVAL, "embed_texts: null output%s");
+    std::lock_guard<std::mutex> lock(e->mu);
+    if (!e->device_seen) {
+        int ndev = 0;
+        HIP_TRY(hipGetDeviceCount(&ndev));
+        if (e->device >= ndev) return fail(CODD_KNN_EINVAL, "embed_texts: no such device%s");
+        e->device_seen = true;
+    }
+    DeviceGuard guard(e->device);
+    hipStream_t st = (hipStream_t)stream;
+    // the staging buffer: the previous call's copy has to have left it — the only wait on the host; its kernel is not waited for
+    if (e->upload_pending) HIP_TRY(hipEventSynchronize(e->uploaded));
+    e->upload_pending = false;
+    const int64_t off_bytes = (n + 1) * (int64_t)sizeof(int64_t), need = off_bytes + total;
+    if (need > e->stage_host.cap()) HIP_TRY(e->stage_host.reset(need + need / 2 + 4096));
+    HIP_TRY(e->stage_dev.ensure(e->stage_host.cap()));
+    HIP_TRY(e->uploaded.ensure());
+    HIP_TRY(e->embedded.ensure());
+    memcpy(e->stage_host.get(), host_offsets, (size_t)off_bytes);
+    if (total > 0) memcpy(e->stage_host.get() + off_bytes, host_bytes, (size_t)total);
+    // the device copy may still be read by the previous call's kernel on another stream: this stream waits for it on the device
+    if (e->embedded_set && e->last_stream != st) HIP_TRY(hipStreamWaitEvent(st, e->embedded, 0));
+    HIP_TRY(hipMemcpyAsync(e->stage_dev, e->stage_host, (size_t)need, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(e->uploaded, st));
+    e->upload_pending = true;
+    const int64_t most = (int64_t)1 << 20;   // (grid-stride beyond that many texts)
+    const int rc = launch_kernel<text_embed_kernel>(dim3((unsigned)(n < most ? n : most)), dim3(kEmbedThreads), (size_t)e->dim * sizeof(float), st,
+                                                    (const uint8_t*)(e->stage_dev.get() + off_bytes), reinterpret_cast<const int64_t*>(e->stage_dev.get()), n,
+                                                    e->dim, e->trigram_weight, dev_out);
+    if (rc != 0) return rc;
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(e->embedded, st));
+    e->embedded_set = true;
+    e->last_stream = st;
     return CODD_KNN_OK;
 }
 

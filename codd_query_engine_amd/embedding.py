@@ -13,7 +13,9 @@ reference's own store tests assert (tests/test_reference_scenarios.py).  Any cal
 
 from __future__ import annotations
 
+import ctypes
 import re
+import threading
 import zlib
 from typing import Protocol, Sequence
 
@@ -36,6 +38,8 @@ class HashingEmbeddingFunction:
         self.trigram_weight = float(trigram_weight)
         self._cache: dict = {}
         self._cache_max = 1 << 18   # tokens remembered (a few tens of MB at most)
+        self._native: dict = {}     # embed_on_device: device index -> codd_knn_embedder handle, created on first use
+        self._native_lock = threading.Lock()
 
     def _bucket(self, feature: str) -> int:
         return zlib.crc32(feature.encode("utf-8")) % self.dim
@@ -73,6 +77,78 @@ class HashingEmbeddingFunction:
             flat = np.concatenate(idx) + np.repeat(np.asarray([r for r, _ in rows], dtype=np.intp) * self.dim, [m for _, m in rows])
             np.add.at(out.reshape(-1), flat, np.concatenate(wts))
         return out
+
+    # ------------------------------------------------------------------ the same vectors, computed on the GPU
+    def _native_embedder(self, dev_index: int):
+        from . import native
+
+        with self._native_lock:
+            h = self._native.get(dev_index)
+            if h is None:
+                h = ctypes.c_void_p()
+                native.check(native.load().codd_knn_embedder_create(ctypes.byref(h), dev_index, self.dim, self.trigram_weight),
+                             "codd_knn_embedder_create")
+                self._native[dev_index] = h
+            return h
+
+    def embed_on_device(self, texts: Sequence[str], device):
+        """`self(texts)` as a float32 [n, dim] tensor on `device`, bit for bit, computed there (csrc/text_embed.h through
+        codd_knn_embed_texts_host): the ASCII texts (`str.isascii()`) packed into one byte arena and embedded by one kernel call on
+        the current stream; the rows of the other texts — Unicode's `\\w` and `lower()` are not restated on the device — come from
+        the host path and are copied into their places.  One native embedder per device, created on first use and destroyed by
+        close().  dim above 4096 (the kernel's accumulator is a text's `dim` floats in LDS): ValueError."""
+        import torch
+
+        from . import native
+
+        if self.dim > native.MAX_EMBED_DIM:
+            raise ValueError(f"embed_on_device covers dim <= {native.MAX_EMBED_DIM}, this embedder has dim {self.dim}")
+        texts = list(texts)
+        n = len(texts)
+        dev = torch.device(device)
+        dev_index = dev.index if dev.index is not None else torch.cuda.current_device()
+        out = torch.empty((n, self.dim), dtype=torch.float32, device=dev)
+        on_device = [i for i, t in enumerate(texts) if t.isascii()]
+        if on_device:
+            lib, h = native.load(), self._native_embedder(dev_index)
+            stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            whole = len(on_device) == n
+            mine = texts if whole else [texts[i] for i in on_device]
+            vecs = out if whole else torch.empty((len(mine), self.dim), dtype=torch.float32, device=dev)
+            first = 0
+            while first < len(mine):   # (one call unless the batch exceeds what one call takes)
+                last, size = first, 0
+                while last < len(mine) and last - first < native.MAX_EMBED_TEXTS and (last == first or size + len(mine[last]) <= native.MAX_EMBED_BYTES):
+                    size += len(mine[last])
+                    last += 1
+                blob = "".join(mine[first:last]).encode("ascii")
+                offsets = np.zeros(last - first + 1, dtype=np.int64)
+                np.cumsum([len(t) for t in mine[first:last]], out=offsets[1:])   # (ASCII: characters are bytes)
+                native.check(lib.codd_knn_embed_texts_host(h, blob, offsets.ctypes.data, last - first, vecs[first:last].data_ptr(), stream),
+                             "codd_knn_embed_texts_host")
+                first = last
+            if not whole:
+                out[torch.as_tensor(on_device, dtype=torch.int64, device=dev)] = vecs
+        if len(on_device) < n:
+            rest = [i for i, t in enumerate(texts) if not t.isascii()]
+            out[torch.as_tensor(rest, dtype=torch.int64, device=dev)] = torch.from_numpy(self([texts[i] for i in rest])).to(dev)
+        return out
+
+    def close(self) -> None:
+        """Destroy the native embedders embed_on_device created (none: nothing happens; the next call creates them again)."""
+        with self._native_lock:
+            handles, self._native = list(self._native.values()), {}
+        if handles:
+            from . import native
+
+            for h in handles:
+                native.load().codd_knn_embedder_destroy(h)
+
+    def __del__(self):  # best effort
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class LocalTransformerEmbeddingFunction:

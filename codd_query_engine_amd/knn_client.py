@@ -63,6 +63,9 @@ class Collection:
     """
 
     AUTO_COMPACT_SHARE = 0.5  # compact() runs by itself once dead slots exceed this share of all slots
+    # Texts per call from which query_texts / documents are embedded on the engine's device (embed_on_device) instead of on the host.
+    # Measured (profiles/embed/README.md): one text costs the same on both routes, from two on the device route wins.
+    DEVICE_EMBED_MIN_TEXTS = 2
 
     def __init__(self, name: str, metadata: Optional[dict], embedding_function: EmbeddingFunction,
                  engine_factory: Callable[[int], Any]):
@@ -109,6 +112,22 @@ class Collection:
     def count(self) -> int:
         """Live records (deleted ones do not count)."""
         return len(self._slot_of)
+
+    # ------------------------------------------------------------------ text -> vector on the engine's device
+    def _embeds_on_device(self, engine, engine_method: str, n_texts: int) -> bool:
+        """The routing rule of DESIGN.md §19: the embedder can embed on a device, the engine lives on one and takes device tensors
+        through `engine_method`, and the batch is large enough for the device route to be the faster one."""
+        return (hasattr(self._embed, "embed_on_device") and engine is not None and hasattr(engine, engine_method)
+                and getattr(engine, "device", None) is not None and n_texts >= self.DEVICE_EMBED_MIN_TEXTS)
+
+    @staticmethod
+    def _rows_of(q, members):
+        """q[members] for the host matrix or the device tensor the queries are (members: row numbers or a bool mask)."""
+        if isinstance(q, np.ndarray):
+            return q[members]
+        import torch
+
+        return q[torch.as_tensor(np.asarray(members), device=q.device)]
 
     # ------------------------------------------------------------------ namespaces -> scopes
     def _scope_for(self, metadata: Optional[dict]) -> int:
@@ -363,7 +382,10 @@ class Collection:
     # ------------------------------------------------------------------ writes
     def upsert(self, ids: Sequence[str], embeddings=None, metadatas: Optional[Sequence[Optional[dict]]] = None,
                documents: Optional[Sequence[Optional[str]]] = None) -> None:
-        """Insert-or-replace by id (chromadb Collection.upsert; store.py:236-238)."""
+        """Insert-or-replace by id (chromadb Collection.upsert; store.py:236-238).  Without `embeddings` the documents are embedded:
+        on the engine's device when the embedder has embed_on_device, the engine upsert_device and a device, the call holds at
+        least DEVICE_EMBED_MIN_TEXTS documents and every id is new; on the host otherwise.  The same vectors
+        either way."""
         ids = list(ids)
         n = len(ids)
         if n == 0:
@@ -378,7 +400,13 @@ class Collection:
         if embeddings is None:
             if documents is None or any(d is None for d in documents):
                 raise ValueError("upsert needs embeddings or documents to embed")
-            vecs = self._as_matrix(self._embed(list(documents)))
+            # the device route: every id is new, so the rows are the contiguous run of slots from len(self._ids) that upsert_device
+            # writes; the width is the embedder's.  Anything else is embedded here and goes through engine.upsert, as before.
+            if (hasattr(self._embed, "embed_on_device") and n >= self.DEVICE_EMBED_MIN_TEXTS and not any(i in self._slot_of for i in ids)
+                    and self._embeds_on_device(self._engine_for(int(self._embed.dim)), "upsert_device", n)):
+                vecs = self._embed.embed_on_device(list(documents), self._engine.device)
+            else:
+                vecs = self._as_matrix(self._embed(list(documents)))
         else:
             vecs = self._as_matrix(embeddings)
         if vecs.shape[0] != n:
@@ -395,7 +423,11 @@ class Collection:
                 next_slot += 1
                 fresh.append(doc_id)
             slots[i] = slot
-        engine.upsert(slots, vecs)  # device first: host bookkeeping only changes if it succeeded
+        # device first: host bookkeeping only changes if it succeeded
+        if isinstance(vecs, np.ndarray):
+            engine.upsert(slots, vecs)
+        else:
+            engine.upsert_device(int(slots[0]), vecs)
         for doc_id in fresh:
             self._slot_of[doc_id] = len(self._ids)
             self._ids.append(doc_id)
@@ -502,7 +534,9 @@ class Collection:
     def query(self, query_texts: Optional[Sequence[str]] = None, query_embeddings=None, n_results: int = 10,
               include: Sequence[str] = ("metadatas", "documents", "distances"), where=None, where_document=None) -> dict:
         """chromadb Collection.query: NESTED lists, one inner list per query, ascending
-        distance, min(n_results, count) hits each (store.py:314-329).
+        distance, min(n_results, count) hits each (store.py:314-329).  `query_texts` are embedded on the engine's device, and stay
+        there, when the embedder has embed_on_device, the engine search_tensors and a device, and there are at least
+        DEVICE_EMBED_MIN_TEXTS of them; on the host otherwise.  The same vectors either way.
 
         `where` restricts the search by metadata, in ChromaDB's grammar: {"key": value}, {"key": {"$eq" | "$ne" | "$gt" | "$gte" |
         "$lt" | "$lte": value}}, {"key": {"$in" | "$nin": [values]}}, {"$and" | "$or": [filters]}; as an extension a list of
@@ -531,7 +565,11 @@ class Collection:
         if query_embeddings is None:
             if isinstance(query_texts, str):
                 query_texts = [query_texts]
-            q = self._as_matrix(self._embed(list(query_texts)))
+            query_texts = list(query_texts)
+            if self._embeds_on_device(self._engine, "search_tensors", len(query_texts)):
+                q = self._embed.embed_on_device(query_texts, self._engine.device)   # (stays a device tensor: the engine takes it as it is)
+            else:
+                q = self._as_matrix(self._embed(query_texts))
         else:
             q = self._as_matrix(query_embeddings)
         B = q.shape[0]
@@ -558,7 +596,7 @@ class Collection:
             dist = np.full((B, k), np.inf, dtype=np.float32)
             rows = np.full((B, k), -1, dtype=np.int64)
             if known.any():
-                dist[known], rows[known] = self._engine.search_scoped(q[known], scopes[known].astype(np.uint32), k)
+                dist[known], rows[known] = self._engine.search_scoped(self._rows_of(q, known), scopes[known].astype(np.uint32), k)
         out = empty
         for b in range(B):
             hit = [(int(r), float(d)) for r, d in zip(rows[b].tolist(), dist[b].tolist()) if r >= 0]
@@ -607,7 +645,7 @@ class Collection:
         except ValueError:
             return False
 
-    def _search_by_filter(self, q: np.ndarray, k: int, per_query: list):
+    def _search_by_filter(self, q, k: int, per_query: list):
         """One engine call per group of queries with the same filter: None -> search, a namespace form -> search_scoped, each distinct
         general filter -> search_masked under its compiled mask (no call when nobody matches: that query's hits stay empty)."""
         B = q.shape[0]
@@ -616,14 +654,14 @@ class Collection:
         plain = [b for b, w in enumerate(per_query) if w is None]
         scoped = [b for b, w in enumerate(per_query) if w is not None and self._is_namespace_form(w)]
         if plain:
-            dist[plain], rows[plain] = self._engine.search(q[plain], k)
+            dist[plain], rows[plain] = self._engine.search(self._rows_of(q, plain), k)
         if scoped:
             if not hasattr(self._engine, "search_scoped"):
                 raise NotImplementedError(f"{type(self._engine).__name__} has no scoped search: `where` needs an engine with search_scoped")
             labels = np.array([self._scope_of_namespace.get(self._where_namespace(per_query[b]), -1) for b in scoped], dtype=np.int64)
             known = [b for b, s in zip(scoped, labels.tolist()) if s >= 0]
             if known:
-                dist[known], rows[known] = self._engine.search_scoped(q[known], labels[labels >= 0].astype(np.uint32), k)
+                dist[known], rows[known] = self._engine.search_scoped(self._rows_of(q, known), labels[labels >= 0].astype(np.uint32), k)
         groups: dict[str, list[int]] = {}
         for b, w in enumerate(per_query):
             if w is not None and not self._is_namespace_form(w):
@@ -631,10 +669,10 @@ class Collection:
         for members in groups.values():
             mask = self._where_mask(per_query[members[0]])
             if mask.any():
-                dist[members], rows[members] = self._engine.search_masked(q[members], mask, k)
+                dist[members], rows[members] = self._engine.search_masked(self._rows_of(q, members), mask, k)
         return dist, rows
 
-    def _search_by_document(self, q: np.ndarray, k: int, where_document, where):
+    def _search_by_document(self, q, k: int, where_document, where):
         """The exact top-k among the live records that satisfy `where_document` and, per query, `where` (None, a namespace form or a
         general filter; one for all queries or a list): one masked engine call per distinct `where`."""
         B = q.shape[0]
@@ -664,13 +702,13 @@ class Collection:
                 bits = self._where_document_bits(where_document)
                 if by_where is not None:
                     bits = bits & self._words_on_device(by_where)
-                dist[members], rows[members] = self._engine.search_masked_dev(q[members], bits, k)
+                dist[members], rows[members] = self._engine.search_masked_dev(self._rows_of(q, members), bits, k)
             else:
                 mask = self._where_document_mask(where_document)
                 if by_where is not None:
                     mask = mask & by_where
                 if mask.any():
-                    dist[members], rows[members] = self._engine.search_masked(q[members], mask, k)
+                    dist[members], rows[members] = self._engine.search_masked(self._rows_of(q, members), mask, k)
         return dist, rows
 
     # ------------------------------------------------------------------ persistence

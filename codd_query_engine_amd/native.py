@@ -21,6 +21,9 @@ MAX_K = 128
 MAX_BATCH = 1024
 MAX_SCOPE = 1048575
 MAX_NEEDLE = 256
+MAX_EMBED_DIM = 4096       # codd_knn_embedder_create: dim in [8, 4096]
+MAX_EMBED_BYTES = 1 << 28  # CODD_KNN_MAX_EMBED_BYTES: text bytes per codd_knn_embed_texts_host call
+MAX_EMBED_TEXTS = 1 << 24  # CODD_KNN_MAX_EMBED_TEXTS
 MAX_GLOBAL_ROW = 0xFFFFFFFD  # the low word of a packed key is 0xFFFFFFFF - global row, and 0 = empty: row_base + count < 0xFFFFFFFF
 
 # every symbol include/codd_knn.h declares: (name, restype, argtypes)
@@ -56,6 +59,9 @@ ABI = [
     ("codd_knn_ivf_search_masked", ctypes.c_int, [_c_idx, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     ("codd_knn_ivf_search_masked_dev", ctypes.c_int, [_c_idx, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     ("codd_knn_slice_mask", ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
+    ("codd_knn_embedder_create", ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int, ctypes.c_float]),
+    ("codd_knn_embedder_destroy", ctypes.c_int, [ctypes.c_void_p]),
+    ("codd_knn_embed_texts_host", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
     ("codd_knn_delete_host", ctypes.c_int, [_c_idx, ctypes.c_void_p, ctypes.c_int64]),
     ("codd_knn_live_count", ctypes.c_int, [_c_idx, _i64p]),
     ("codd_knn_compact", ctypes.c_int, [_c_idx, _i64p]),

@@ -345,6 +345,42 @@ int codd_knn_slice_mask(int device, const uint32_t* dev_global_bits, int64_t glo
                         int64_t nwords, void* stream);
 
 /*
+ * Replaces: the embedding step inside collection.query(query_texts=[...]) (store.py:314-316) and collection.upsert(documents=[...])
+ *           (store.py:236-238) — what chromadb's client does to the texts before the search — for the façade's default embedder,
+ *           HashingEmbeddingFunction (codd_query_engine_amd/embedding.py): ASCII text in, its vectors out, on the device, BIT-EQUAL to
+ *           the host embedder.  An index does not exist before the first upsert fixes the width, so the embedder is an
+ *           object of its own.
+ * embedder_create: dim in [8, 4096] and a finite trigram_weight (the fp32 rounding of the host's), else EINVAL; device >= 0.  Touches no
+ *           device: that `device` exists is checked by the first call that embeds (EINVAL there).
+ * embedder_destroy: frees the embedder's staging buffers and events (codd_knn_debug_live_allocations returns to its earlier values);
+ *           NULL: OK.  No call on the embedder may be in flight on the host.
+ * embed_texts_host: text r is host_bytes[host_offsets[r] .. host_offsets[r + 1]), possibly empty; host_offsets holds n + 1 values.  The
+ *           offsets alone separate the texts — no separator bytes, 0x00 is an ordinary non-word byte.  dev_out: n x dim fp32 on the
+ *           embedder's device, EVERY element written (a bucket without a feature is +0.0; the caller clears nothing).  Per text: a word
+ *           byte is [0-9A-Za-z_], low() maps A-Z to a-z, a token is a maximal run of word bytes inside the text; for each word byte at
+ *           position p, in increasing p: if p starts a token, out[crc32("w:" + low(token)) % dim] += 1.0f; then always
+ *           out[crc32("t:" + a + low(b[p]) + c) % dim] += trigram_weight, a = low(b[p - 1]) or '^' at the token's start, c = low(b[p + 1])
+ *           or '$' at its end; crc32 is zlib's.  The fp32 additions into one bucket happen in exactly this order, whatever the lanes'
+ *           timing: the order is part of the bits.
+ *           EINVAL, with nothing enqueued: a null embedder, offsets or output; n < 0 or n > CODD_KNN_MAX_EMBED_TEXTS; offsets that do not
+ *           start at 0 or decrease; more than CODD_KNN_MAX_EMBED_BYTES bytes; null host_bytes unless the total is 0; a byte at or above
+ *           0x80 (such texts are the host embedder's: Unicode's \w and lower() are not restated here).  n == 0: OK, no launch.
+ *           host_bytes and host_offsets are consumed before the call returns: copied into the embedder's pinned staging buffer, from
+ *           where one asynchronous copy on `stream` takes them to the device, and one launch of text_embed_kernel (csrc/text_embed.h)
+ *           follows.  By the staging rule of codd_knn_search_masked, a second call waits on the host until the first one's copy has left
+ *           the staging buffer — not for its kernel; a call on another stream is ordered on the device behind the previous call's
+ *           kernel, which reads the same device copy of the texts.  Everything else is asynchronous on `stream`.  Calls from several
+ *           host threads are serialised by the embedder's own lock.
+ */
+#define CODD_KNN_MAX_EMBED_BYTES (1ll << 28)   /* text bytes per codd_knn_embed_texts_host call */
+#define CODD_KNN_MAX_EMBED_TEXTS (1ll << 24)   /* texts per call */
+typedef struct codd_knn_embedder codd_knn_embedder;
+int codd_knn_embedder_create(codd_knn_embedder** out, int device, int dim, float trigram_weight);
+int codd_knn_embedder_destroy(codd_knn_embedder* e);
+int codd_knn_embed_texts_host(codd_knn_embedder* e, const uint8_t* host_bytes, const int64_t* host_offsets, int64_t n, float* dev_out,
+                              void* stream);
+
+/*
  * Tuning / introspection (never needed for correctness).
  *   options: "scan_blocks_per_cu" (1..8); "filter" (0/1: MFMA filter path for large batches);
  *            "filter_min_batch" (9), "filter_min_rows" (1: batches >= filter_min_batch always
