@@ -12,6 +12,9 @@
 //                           step, 16-B/lane coalesced loads, fmaf chains in canonical order,
 //                           wave-distributed top-k lists
 //   merge_keys_kernel       integer top-k of packed keys (per-block partials, shard partials)
+//   raw_rows_kernel         ingest + query prep of an ip or l2 index: vectors as given, non-finite ones as zeros
+//   scan_topk_l2, scan_topk_wide_l2, scope_scan_l2, mask_scan_l2, merge_keys_l2
+//                           the squared-L2 forms of the exact-score kernels; ip runs the dot-product ones
 //   filter_gemm.h           large batches: bf16 MFMA filter + exact fp32 re-score (finalize)
 //
 // HBM-bound byte streaming throughout: the corpus is read once per pass, each row by exactly one
@@ -198,6 +201,43 @@ __global__ __launch_bounds__(256) void normalize_rows_kernel(const float* __rest
     }
 }
 
+// raw_rows_kernel: ingest and query prep of an ip or l2 index, one wave per input vector: the vector is used as
+// given — padded with zeros to dpad, rounded to the storage dtype DT, not normalised — except that a vector with a NaN or infinite
+// element, or without a non-zero one, is stored as zeros.  out row = slots ? slots[r] : first_slot + r, as normalize_rows_kernel.
+template <int DT>
+__global__ __launch_bounds__(256) void raw_rows_kernel(const float* __restrict__ in, int64_t n, int d, int dpad, const int64_t* __restrict__ slots,
+                                                       int64_t first_slot, void* __restrict__ out_) {
+    const int lane = lane_id();
+    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= n) return;
+    const float* x = in + r * (int64_t)d;
+    const int nch = dpad >> 2;
+    bool bad = false, any = false;
+    for (int i = lane; i < d; i += kWave) {
+        const float v = x[i];
+        bad = bad || !(fabsf(v) < INFINITY);   // (NaN compares false too)
+        any = any || v != 0.0f;
+    }
+    const bool zero_row = __ballot(bad) != 0ull || __ballot(any) == 0ull;
+    const int64_t orow = slots ? slots[r] : first_slot + r;
+    for (int j = lane; j < nch; j += kWave) {
+        float v[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int i = j * 4 + e;
+            v[e] = (i < d && !zero_row) ? x[i] : 0.0f;
+        }
+        if (DT == DT_F32) {
+            reinterpret_cast<float4*>(out_)[orow * (int64_t)nch + j] = make_float4(v[0], v[1], v[2], v[3]);
+        } else {
+            uint16_t hb[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) hb[e] = DT == DT_BF16 ? f32_to_bf16_rne(v[e]) : f32_to_f16_rne(v[e]);
+            reinterpret_cast<uint2*>(out_)[orow * (int64_t)nch + j] = make_uint2((uint32_t)hb[0] | ((uint32_t)hb[1] << 16), (uint32_t)hb[2] | ((uint32_t)hb[3] << 16));
+        }
+    }
+}
+
 // shadow_from_rows_kernel: rebuild the bf16 fragment-order shadow of rows [first, first+n) from the
 // stored rows themselves (index load from disk: the rows arrive already normalised and rounded).
 template <int DT>
@@ -247,7 +287,7 @@ __device__ __forceinline__ uint32_t group_dead_bits(const uint32_t* __restrict__
     return dead[gu >> 3] >> ((gu & 7u) * 4u);
 }
 
-template <int DT, int NB, int NITER, int SLOTS, int NW>
+template <int DT, int NB, int NITER, int SLOTS, int NW, int METRIC = kMetricDot>
 __device__ __forceinline__ void scan_topk_body(const void* __restrict__ rows_, int64_t n, int dpad, const float* __restrict__ qn, int total, int k,
                                                uint32_t row_base, u64* __restrict__ partial, int64_t partial_stride_q,
                                                const unsigned* __restrict__ qlist, bool listed, unsigned* __restrict__ merge_done,
@@ -296,11 +336,11 @@ __device__ __forceinline__ void scan_topk_body(const void* __restrict__ rows_, i
             for (int b = 0; b < NB; ++b)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) acc[b][r] = 0.0f;
-            for (int s = 0; s < nseg; ++s) wide_segment<DT, NB, 4>(p, s, nchunks, lane, qs, qstride, acc);
+            for (int s = 0; s < nseg; ++s) wide_segment<DT, NB, 4, METRIC>(p, s, nchunks, lane, qs, qstride, acc);
             const uint32_t dm = group_dead_bits(dead, g);
 #pragma unroll
             for (int b = 0; b < NB; ++b) {   // (one query's tail and offers at a time: NB x 4 scores at once spill scalar registers)
-                const float y = packed4(acc[b], lane);
+                const float y = packed4<METRIC>(acc[b], lane);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int64_t row = g * 4 + r;
@@ -329,7 +369,7 @@ __device__ __forceinline__ void scan_topk_body(const void* __restrict__ rows_, i
         const uint32_t dm = group_dead_bits(dead, g);
 #pragma unroll
         for (int b = 0; b < NB; ++b) {   // (an absent query's fragments are zeros: its list is never read)
-            const float y = score4_one(w, qf[b], lane);
+            const float y = score4_one<NITER, E, METRIC>(w, qf[b], lane);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int64_t row = g * 4 + r;
@@ -376,7 +416,7 @@ __device__ __forceinline__ void scan_topk_body(const void* __restrict__ rows_, i
                 M.offer_lanes(i < m ? src[i] : 0ull, k, lane);
             }
             const int64_t o = (int64_t)qlist[qi] * k;
-            write_ranks(M, k, lane, merged_keys ? merged_keys + o : nullptr, merged_dist ? merged_dist + o : nullptr, merged_rows ? merged_rows + o : nullptr);
+            write_ranks<SLOTS, METRIC>(M, k, lane, merged_keys ? merged_keys + o : nullptr, merged_dist ? merged_dist + o : nullptr, merged_rows ? merged_rows + o : nullptr);
         }
     }
 }
@@ -414,6 +454,26 @@ __global__ __launch_bounds__(kWideScanWaves * kWave) void scan_topk_wide_kernel(
     scan_topk_body<DT, NB, kWideRows, SLOTS, kWideScanWaves>(rows_, n, dpad, qn, total, k, row_base, partial, partial_stride_q, qlist, qcount_ptr != nullptr,
                                                              merge_done, merged_keys, merged_dist, merged_rows, count_total, (int)blockIdx.x, (int)gridDim.x,
                                                              reinterpret_cast<u64*>(smem_raw), dead);
+}
+
+// The squared-L2 scans: scan_topk_body under kMetricL2, dense queries only (an l2 index takes no filter leg, so
+// the list-driven fallback forms are not built).  Kernels of their own, so that every dot-product kernel stays the code it was.
+template <int DT, int NB, int NITER, int SLOTS>
+__global__ __launch_bounds__(256) void scan_topk_l2(const void* __restrict__ rows_, int64_t n, int dpad, const float* __restrict__ qn, int nq, int k,
+                                                    uint32_t row_base, u64* __restrict__ partial, int64_t partial_stride_q,
+                                                    const uint32_t* __restrict__ dead) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    scan_topk_body<DT, NB, NITER, SLOTS, 4, kMetricL2>(rows_, n, dpad, qn, nq, k, row_base, partial, partial_stride_q, nullptr, false, nullptr, nullptr, nullptr,
+                                                       nullptr, nullptr, (int)blockIdx.x, (int)gridDim.x, reinterpret_cast<u64*>(smem_raw), dead);
+}
+template <int DT, int NB, int SLOTS>
+__global__ __launch_bounds__(kWideScanWaves * kWave) void scan_topk_wide_l2(const void* __restrict__ rows_, int64_t n, int dpad, const float* __restrict__ qn,
+                                                                            int nq, int k, uint32_t row_base, u64* __restrict__ partial,
+                                                                            int64_t partial_stride_q, const uint32_t* __restrict__ dead) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    scan_topk_body<DT, NB, kWideRows, SLOTS, kWideScanWaves, kMetricL2>(rows_, n, dpad, qn, nq, k, row_base, partial, partial_stride_q, nullptr, false, nullptr,
+                                                                        nullptr, nullptr, nullptr, nullptr, (int)blockIdx.x, (int)gridDim.x,
+                                                                        reinterpret_cast<u64*>(smem_raw), dead);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -478,12 +538,12 @@ __global__ __launch_bounds__(kFinThreads) void finalize_fb_kernel(const void* __
 // keys and/or (distance, row).  Used for the per-block partials of a scan, for the all-gathered
 // shard partials, and (m == k) to unpack final keys.
 // ---------------------------------------------------------------------------------------------
-template <int SLOTS>
-__global__ __launch_bounds__(256) void merge_keys_kernel(const u64* __restrict__ in, int64_t m, int64_t in_stride, int64_t seg_len,
-                                                         int64_t seg_stride, int k, u64* __restrict__ out_keys, float* __restrict__ out_dist,
-                                                         int64_t* __restrict__ out_rows, const unsigned* __restrict__ out_list,
-                                                         const unsigned* __restrict__ count_ptr,
-                                                         unsigned long long* __restrict__ count_total) {
+template <int SLOTS, int METRIC>
+__device__ __forceinline__ void merge_keys_body(const u64* __restrict__ in, int64_t m, int64_t in_stride, int64_t seg_len,
+                                                int64_t seg_stride, int k, u64* __restrict__ out_keys, float* __restrict__ out_dist,
+                                                int64_t* __restrict__ out_rows, const unsigned* __restrict__ out_list,
+                                                const unsigned* __restrict__ count_ptr,
+                                                unsigned long long* __restrict__ count_total) {
     const int lane = lane_id();
     const int wave = (int)(threadIdx.x >> 6);
     // LISTED (fallback queue): only the first *count_ptr blocks work, block i answers query out_list[i]
@@ -509,7 +569,21 @@ __global__ __launch_bounds__(256) void merge_keys_kernel(const u64* __restrict__
     if (wave != 0) return;
     merge_lists(L, lds, 1, 4, 1, 0, k, lane);
     const int64_t o = oblock * k;
-    write_ranks(L, k, lane, out_keys ? out_keys + o : nullptr, out_dist ? out_dist + o : nullptr, out_rows ? out_rows + o : nullptr);
+    write_ranks<SLOTS, METRIC>(L, k, lane, out_keys ? out_keys + o : nullptr, out_dist ? out_dist + o : nullptr, out_rows ? out_rows + o : nullptr);
+}
+template <int SLOTS>
+__global__ __launch_bounds__(256) void merge_keys_kernel(const u64* __restrict__ in, int64_t m, int64_t in_stride, int64_t seg_len,
+                                                         int64_t seg_stride, int k, u64* __restrict__ out_keys, float* __restrict__ out_dist,
+                                                         int64_t* __restrict__ out_rows, const unsigned* __restrict__ out_list,
+                                                         const unsigned* __restrict__ count_ptr,
+                                                         unsigned long long* __restrict__ count_total) {
+    merge_keys_body<SLOTS, kMetricDot>(in, m, in_stride, seg_len, seg_stride, k, out_keys, out_dist, out_rows, out_list, count_ptr, count_total);
+}
+// the same merge for keys of squared-L2 scores: the distance written is 0 - score
+template <int SLOTS>
+__global__ __launch_bounds__(256) void merge_keys_l2(const u64* __restrict__ in, int64_t m, int64_t in_stride, int64_t seg_len, int64_t seg_stride, int k,
+                                                     u64* __restrict__ out_keys, float* __restrict__ out_dist, int64_t* __restrict__ out_rows) {
+    merge_keys_body<SLOTS, kMetricL2>(in, m, in_stride, seg_len, seg_stride, k, out_keys, out_dist, out_rows, nullptr, nullptr, nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1087,7 +1161,7 @@ __global__ __launch_bounds__(256) void ivf_pair_scatter_kernel(const u64* __rest
 //   GATHER = true (scopes): position i names row ids[i] of the original store and reports it.  Two steps of look-ahead: the row
 //                  slots of step g + 32 and the rows of step g + 16 (whose slots arrived a step ago) are in flight
 //   dead: the tombstone bits of the reported ids, null = no mask
-template <int DT, int NB, int NITER, int SLOTS, bool GATHER, class DstOf>
+template <int DT, int NB, int NITER, int SLOTS, bool GATHER, int METRIC = kMetricDot, class DstOf>
 __device__ __forceinline__ void list_scan_body(const void* __restrict__ rows_, const uint32_t* __restrict__ ids, int64_t begin, int64_t end, int dpad,
                                                const float* const (&q)[NB], int nq, int k, uint32_t row_base, const uint32_t* __restrict__ dead,
                                                DstOf dst_of) {
@@ -1144,7 +1218,7 @@ __device__ __forceinline__ void list_scan_body(const void* __restrict__ rows_, c
             const uint4* p[4];
             row_ptrs(g, id0, p);
             float sc[NB][4];
-            wide_scores<DT, NB, 1>(p, nchunks, lane, lds_q, qstride, nq, sc);
+            wide_scores<DT, NB, 1, METRIC>(p, nchunks, lane, lds_q, qstride, nq, sc);
             offer4(g, id0, sc);
 #pragma unroll
             for (int r = 0; r < 4; ++r) id0[r] = id1[r];
@@ -1171,7 +1245,7 @@ __device__ __forceinline__ void list_scan_body(const void* __restrict__ rows_, c
                 fetch4(p, nchunks, lane, nxt);
             }
             float sc[NB][4];
-            score4<DT, NB, NITER>(cur, qf, nq, lane, sc);
+            score4<DT, NB, NITER, METRIC>(cur, qf, nq, lane, sc);
             offer4(g, id0, sc);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -1329,11 +1403,11 @@ __host__ __device__ constexpr int64_t scope_part_rows(int64_t len, int split) { 
 
 // grid (B, split): workgroup (p, part) serves the queries at positions p .. p + NB-1 of the grouped order when p opens a group of NB
 // (rank[p] % NB == 0) and leaves at once otherwise.
-template <int DT, int NITER, int SLOTS>
-__global__ __launch_bounds__(256) void scope_scan_kernel(const void* __restrict__ rows_, const uint32_t* __restrict__ perm, const unsigned* __restrict__ offsets,
-                                                         int64_t count, uint32_t max_scope, const uint32_t* __restrict__ scopes,
-                                                         const unsigned* __restrict__ sorted_q, const unsigned* __restrict__ rank, int B, int split, int dpad,
-                                                         const float* __restrict__ qn, int k, uint32_t row_base, u64* __restrict__ partial) {
+template <int DT, int NITER, int SLOTS, int METRIC>
+__device__ __forceinline__ void scope_scan_body(const void* __restrict__ rows_, const uint32_t* __restrict__ perm, const unsigned* __restrict__ offsets,
+                                                int64_t count, uint32_t max_scope, const uint32_t* __restrict__ scopes,
+                                                const unsigned* __restrict__ sorted_q, const unsigned* __restrict__ rank, int B, int split, int dpad,
+                                                const float* __restrict__ qn, int k, uint32_t row_base, u64* __restrict__ partial) {
     constexpr int NB = scope_nb(DT, NITER);
     const int p0 = (int)blockIdx.x, part = (int)blockIdx.y;
     const unsigned r0 = rank[p0];
@@ -1351,8 +1425,22 @@ __global__ __launch_bounds__(256) void scope_scan_kernel(const void* __restrict_
     const int64_t begin = lo + part * per < hi ? lo + part * per : hi;
     const int64_t end = begin + per < hi ? begin + per : hi;
     // no mask: the lists hold live rows only.  Query b's part of the partial buffer: [query][part][k]
-    list_scan_body<DT, NB, NITER, SLOTS, true>(rows_, perm, begin, end, dpad, q, nq, k, row_base, nullptr,
-                                               [&](int b) { return partial + ((int64_t)sorted_q[p0 + b] * split + part) * k; });
+    list_scan_body<DT, NB, NITER, SLOTS, true, METRIC>(rows_, perm, begin, end, dpad, q, nq, k, row_base, nullptr,
+                                                       [&](int b) { return partial + ((int64_t)sorted_q[p0 + b] * split + part) * k; });
+}
+template <int DT, int NITER, int SLOTS>
+__global__ __launch_bounds__(256) void scope_scan_kernel(const void* __restrict__ rows_, const uint32_t* __restrict__ perm, const unsigned* __restrict__ offsets,
+                                                         int64_t count, uint32_t max_scope, const uint32_t* __restrict__ scopes,
+                                                         const unsigned* __restrict__ sorted_q, const unsigned* __restrict__ rank, int B, int split, int dpad,
+                                                         const float* __restrict__ qn, int k, uint32_t row_base, u64* __restrict__ partial) {
+    scope_scan_body<DT, NITER, SLOTS, kMetricDot>(rows_, perm, offsets, count, max_scope, scopes, sorted_q, rank, B, split, dpad, qn, k, row_base, partial);
+}
+template <int DT, int NITER, int SLOTS>
+__global__ __launch_bounds__(256) void scope_scan_l2(const void* __restrict__ rows_, const uint32_t* __restrict__ perm, const unsigned* __restrict__ offsets,
+                                                     int64_t count, uint32_t max_scope, const uint32_t* __restrict__ scopes,
+                                                     const unsigned* __restrict__ sorted_q, const unsigned* __restrict__ rank, int B, int split, int dpad,
+                                                     const float* __restrict__ qn, int k, uint32_t row_base, u64* __restrict__ partial) {
+    scope_scan_body<DT, NITER, SLOTS, kMetricL2>(rows_, perm, offsets, count, max_scope, scopes, sorted_q, rank, B, split, dpad, qn, k, row_base, partial);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1458,9 +1546,9 @@ __global__ __launch_bounds__(256) void mask_scatter_kernel(const uint32_t* __res
         if (at < m) list[at] = (uint32_t)(w * 32) + (uint32_t)(__ffs((int)v) - 1);   // (at < m always: the host counted the same bits)
 }
 // grid (ceil(B / NB), split): workgroup (g, part) serves queries g * NB .. g * NB + NB-1 over part `part` of list[0, m)
-template <int DT, int NITER, int SLOTS>
-__global__ __launch_bounds__(256) void mask_scan_kernel(const void* __restrict__ rows_, const uint32_t* __restrict__ list, int64_t m, int B, int split,
-                                                        int dpad, const float* __restrict__ qn, int k, uint32_t row_base, u64* __restrict__ partial) {
+template <int DT, int NITER, int SLOTS, int METRIC>
+__device__ __forceinline__ void mask_scan_body(const void* __restrict__ rows_, const uint32_t* __restrict__ list, int64_t m, int B, int split,
+                                               int dpad, const float* __restrict__ qn, int k, uint32_t row_base, u64* __restrict__ partial) {
     constexpr int NB = scope_nb(DT, NITER);
     const int q0 = (int)blockIdx.x * NB, part = (int)blockIdx.y;
     const int nq = B - q0 < NB ? B - q0 : NB;
@@ -1471,8 +1559,18 @@ __global__ __launch_bounds__(256) void mask_scan_kernel(const void* __restrict__
     const int64_t begin = part * per < m ? part * per : m;
     const int64_t end = begin + per < m ? begin + per : m;
     // no mask: the list holds visible rows only.  Query b's part of the partial buffer: [query][part][k]
-    list_scan_body<DT, NB, NITER, SLOTS, true>(rows_, list, begin, end, dpad, q, nq, k, row_base, nullptr,
-                                               [&](int b) { return partial + ((int64_t)(q0 + b) * split + part) * k; });
+    list_scan_body<DT, NB, NITER, SLOTS, true, METRIC>(rows_, list, begin, end, dpad, q, nq, k, row_base, nullptr,
+                                                       [&](int b) { return partial + ((int64_t)(q0 + b) * split + part) * k; });
+}
+template <int DT, int NITER, int SLOTS>
+__global__ __launch_bounds__(256) void mask_scan_kernel(const void* __restrict__ rows_, const uint32_t* __restrict__ list, int64_t m, int B, int split,
+                                                        int dpad, const float* __restrict__ qn, int k, uint32_t row_base, u64* __restrict__ partial) {
+    mask_scan_body<DT, NITER, SLOTS, kMetricDot>(rows_, list, m, B, split, dpad, qn, k, row_base, partial);
+}
+template <int DT, int NITER, int SLOTS>
+__global__ __launch_bounds__(256) void mask_scan_l2(const void* __restrict__ rows_, const uint32_t* __restrict__ list, int64_t m, int B, int split,
+                                                    int dpad, const float* __restrict__ qn, int k, uint32_t row_base, u64* __restrict__ partial) {
+    mask_scan_body<DT, NITER, SLOTS, kMetricL2>(rows_, list, m, B, split, dpad, qn, k, row_base, partial);
 }
 
 }  // namespace
@@ -2016,6 +2114,34 @@ int launch_normalize(int dtype, const float* in, int64_t n, int d, int dpad, int
     return CODD_KNN_OK;
 }
 
+// raw_rows_kernel: vectors as given (non-finite and all-zero ones as zeros), padded and rounded to `dtype`
+int launch_raw_rows(int dtype, const float* in, int64_t n, int d, int dpad, const int64_t* slots, int64_t first_slot, void* out, hipStream_t st) {
+    if (n <= 0) return CODD_KNN_OK;
+    const dim3 grid((unsigned)((n + 3) / 4)), block(256);
+    const int rc = with_dtype(dtype, [&](auto dt) { return launch_kernel<raw_rows_kernel<dt>>(grid, block, 0, st, in, n, d, dpad, slots, first_slot, out); });
+    if (rc != 0) return rc;
+    HIP_TRY(hipGetLastError());
+    return CODD_KNN_OK;
+}
+
+// the metric of an index as its exact-score kernels see it: ip scores with the dot-product kernels that cosine runs
+static_assert(kMetricDot == CODD_KNN_METRIC_COSINE && kMetricL2 == CODD_KNN_METRIC_L2, "exact_score.h and codd_knn.h disagree");
+bool metric_is_cosine(const codd_knn_index* ix) { return ix->metric == CODD_KNN_METRIC_COSINE; }
+int kernel_metric(int metric) { return metric == CODD_KNN_METRIC_L2 ? kMetricL2 : kMetricDot; }
+
+// the ingest launch of every upsert.  normalize = 0 on an ip or l2 index still zeroes non-finite rows (the contract of those
+// spaces); on a cosine index it stores the values as they come, as it always did
+int launch_ingest(const codd_knn_index* ix, const float* in, int64_t n, int normalize, const int64_t* slots, int64_t first_slot, hipStream_t st) {
+    if (!normalize && !metric_is_cosine(ix)) return launch_raw_rows(ix->dtype, in, n, ix->dim, ix->dpad, slots, first_slot, ix->rows.get(), st);
+    return launch_normalize(ix->dtype, in, n, ix->dim, ix->dpad, normalize, slots, first_slot, ix->rows.get(), nullptr, st);
+}
+
+// the queries of an exact-score pass, fp32 [B][dpad] in ix->qn: normalised for cosine, as given for ip and l2
+int prep_exact_queries(codd_knn_index* ix, const float* dev_queries, int B, hipStream_t st) {
+    if (metric_is_cosine(ix)) return launch_normalize(DT_F32, dev_queries, B, ix->dim, ix->dpad, 1, nullptr, 0, ix->qn, nullptr, st);
+    return launch_raw_rows(DT_F32, dev_queries, B, ix->dim, ix->dpad, nullptr, 0, ix->qn.get(), st);
+}
+
 // ---- exact scan dispatch ---------------------------------------------------------------------
 
 struct ScanArgs {
@@ -2039,9 +2165,14 @@ struct ScanArgs {
 
 // queries per pass of the wide scan: 2-byte rows take at most 4 (8 would spill: the kernel walks a larger batch 4 queries at a time)
 constexpr int wide_scan_nb(int dt, int nb) { return dt == DT_F32 || nb < 4 ? nb : 4; }
+// ... and of the wide l2 scan: the same, but 2-byte rows with two list slots per lane (k > 64) take 2 (the subtraction's temporaries on top
+// of 4 queries' accumulators and 8 list registers spill one vector register in scan_topk_wide_l2<bf16, 4, 2>)
+constexpr int wide_scan_nb_l2(int dt, int nb, int slots) { return dt != DT_F32 && slots == 2 && nb >= 4 ? 2 : wide_scan_nb(dt, nb); }
 
 // one exact-scan launch, queries in groups of `nb` (1, 4 or 8) per pass over the rows
-int launch_scan(int dtype, int nb, int niter, dim3 grid, hipStream_t st, const ScanArgs& a) {
+// (l2: the squared-distance kernels, dense queries only)
+int launch_scan(int dtype, int nb, int niter, dim3 grid, hipStream_t st, const ScanArgs& a, int metric = kMetricDot) {
+    if (metric == kMetricL2 && (a.qlist || a.qcount)) return fail(CODD_KNN_EINVAL, "the l2 scan takes dense queries only%s");
     return with_dtype(dtype, [&](auto dt) {
         constexpr int DT = decltype(dt)::value;
         return with_int<1, 4, 8>(nb, "bad query group%s", [&](auto nbc) {
@@ -2054,6 +2185,14 @@ int launch_scan(int dtype, int nb, int niter, dim3 grid, hipStream_t st, const S
                         // rows of more than 4 chunks per lane: scan_topk_wide_kernel, one 8-wave workgroup per compute unit (scan_geometry sizes the grid)
                         constexpr int NBW = wide_scan_nb(DT, NB);
                         constexpr int E = RowTraits<DT>::E;
+                        if (metric == kMetricL2) {
+                            constexpr int NBL = wide_scan_nb_l2(DT, NB, SLOTS);
+                            const size_t qbytes = (size_t)NBL * wide_qfloats(a.dpad / E, E) * sizeof(float);
+                            const size_t lbytes = (size_t)kWideScanWaves * NBL * SLOTS * kWave * sizeof(u64);
+                            return launch_kernel<scan_topk_wide_l2<DT, NBL, SLOTS>>(grid, dim3(kWideScanWaves * kWave),
+                                                                                    Lds(qbytes > lbytes ? qbytes : lbytes, (size_t)NBL * kWideMaxFloats * sizeof(float)),
+                                                                                    st, a.rows, a.n, a.dpad, a.qn, a.nq, a.k, a.row_base, a.partial, a.stride_q, a.dead);
+                        }
                         const size_t qbytes = (size_t)NBW * wide_qfloats(a.dpad / E, E) * sizeof(float);
                         const size_t lbytes = (size_t)kWideScanWaves * NBW * SLOTS * kWave * sizeof(u64);
                         const size_t lds = qbytes > lbytes ? qbytes : lbytes;   // the lists take the queries' place once a group is scanned
@@ -2062,6 +2201,9 @@ int launch_scan(int dtype, int nb, int niter, dim3 grid, hipStream_t st, const S
                             a.k, a.row_base, a.partial, a.stride_q, a.qlist, a.qcount, a.merge_done, a.merged_keys, a.merged_dist, a.merged_rows, a.count_total, a.dead);
                     } else {
                         const size_t lds = (size_t)4 * NB * SLOTS * kWave * sizeof(u64);
+                        if (metric == kMetricL2)
+                            return launch_kernel<scan_topk_l2<DT, NB, NITER, SLOTS>>(grid, dim3(256), lds, st, a.rows, a.n, a.dpad, a.qn, a.nq, a.k, a.row_base,
+                                                                                     a.partial, a.stride_q, a.dead);
                         return launch_kernel<scan_topk_kernel<DT, NB, NITER, SLOTS>>(
                             grid, dim3(256), lds, st, a.rows, a.n, a.dpad, a.qn, a.nq, a.k, a.row_base, a.partial, a.stride_q, a.qlist, a.qcount,
                             a.merge_done, a.merged_keys, a.merged_dist, a.merged_rows, a.count_total, a.dead);
@@ -2074,15 +2216,23 @@ int launch_scan(int dtype, int nb, int niter, dim3 grid, hipStream_t st, const S
 
 int launch_merge(const u64* in, int B, int64_t m, int64_t in_stride, int k, u64* out_keys, float* out_dist, int64_t* out_rows,
                  hipStream_t st, const unsigned* out_list = nullptr, const unsigned* count_ptr = nullptr,
-                 unsigned long long* count_total = nullptr, int64_t seg_len = 0, int64_t seg_stride = 0) {
+                 unsigned long long* count_total = nullptr, int64_t seg_len = 0, int64_t seg_stride = 0, int metric = kMetricDot) {
     if (seg_len <= 0) seg_len = m > 0 ? m : 1;
+    if (metric == kMetricL2 && (out_list || count_ptr)) return fail(CODD_KNN_EINVAL, "the l2 merge takes no query list%s");
     const int rc = with_slots(k, [&](auto sl) {
+        if (metric == kMetricL2)
+            return launch_kernel<merge_keys_l2<sl>>(dim3(B), dim3(256), 0, st, in, m, in_stride, seg_len, seg_stride, k, out_keys, out_dist, out_rows);
         return launch_kernel<merge_keys_kernel<sl>>(dim3(B), dim3(256), 0, st, in, m, in_stride, seg_len, seg_stride, k, out_keys, out_dist, out_rows,
                                                     out_list, count_ptr, count_total);
     });
     if (rc != 0) return rc;
     HIP_TRY(hipGetLastError());
     return CODD_KNN_OK;
+}
+
+// the merge behind an index's own exact-score passes: distances by the index's metric
+int launch_merge_of(const codd_knn_index* ix, const u64* in, int B, int64_t m, int k, u64* out_keys, float* out_dist, int64_t* out_rows, hipStream_t st) {
+    return launch_merge(in, B, m, m, k, out_keys, out_dist, out_rows, st, nullptr, nullptr, nullptr, 0, 0, kernel_metric(ix->metric));
 }
 
 int scan_geometry(const codd_knn_index* ix, int64_t n, int* niter, int64_t* blocks) {
@@ -2120,18 +2270,18 @@ int exact_scan(codd_knn_index* ix, const float* qn, int nqueries, int k, uint32_
         // of 8 inside the kernel (small corpora stay L2-resident across the groups, and a batch costs one
         // launch instead of B/8)
         const int nb = nqueries == 1 ? 1 : (nqueries <= 4 ? 4 : 8);
-        ix->stat_last_scan_group = niter > 4 ? wide_scan_nb(ix->dtype, nb) : nb;
+        ix->stat_last_scan_group = niter <= 4 ? nb : (ix->metric == CODD_KNN_METRIC_L2 ? wide_scan_nb_l2(ix->dtype, nb, k <= 64 ? 1 : 2) : wide_scan_nb(ix->dtype, nb));
         ScanArgs a{ix->rows, n, ix->dpad, qn, nqueries, k, row_base, ix->partial, stride_q};
         a.dead = deny;
         {
             EvScope ev(ix, EV_SCAN, st);
-            rc = launch_scan(ix->dtype, nb, niter, dim3((unsigned)blocks), st, a);
+            rc = launch_scan(ix->dtype, nb, niter, dim3((unsigned)blocks), st, a, kernel_metric(ix->metric));
         }
         if (rc != 0) return rc;
         HIP_TRY(hipGetLastError());
         ix->stat_scan_launches++;
     }
-    return launch_merge(ix->partial, nqueries, stride_q, stride_q, k, keys_out, dist_out, rows_out, st);
+    return launch_merge_of(ix, ix->partial, nqueries, stride_q, k, keys_out, dist_out, rows_out, st);
 }
 
 // ---- filter path -----------------------------------------------------------------------------
@@ -2803,7 +2953,7 @@ int search_impl(codd_knn_index* ix, const float* dev_queries, int B, int k, uint
         hipLaunchKernelGGL(prep_queries_kernel, dim3(kTileQ / 4), dim3(256), 0, st, dev_queries, B, ix->dim, ix->dpad, ix->qn,
                            reinterpret_cast<uint2*>(ix->qfrag.get()), reinterpret_cast<unsigned*>(ix->ctl.get()), (int)(sizeof(FilterCtl) / 4));
         HIP_TRY(hipGetLastError());
-    } else if ((rc = launch_normalize(DT_F32, dev_queries, B, ix->dim, ix->dpad, 1, nullptr, 0, ix->qn, nullptr, st)) != 0) {
+    } else if ((rc = prep_exact_queries(ix, dev_queries, B, st)) != 0) {
         return rc;
     }
 
@@ -2923,7 +3073,8 @@ int codd_knn_create(codd_knn_index** out, int device, int dim, int dtype, int me
     *out = nullptr;
     if (dim < 1 || dim > 4096) return fail(CODD_KNN_EINVAL, "dim out of range [1,4096]%s");
     if (dtype != DT_F32 && dtype != DT_BF16 && dtype != DT_F16) return fail(CODD_KNN_EINVAL, "unknown dtype%s");
-    if (metric != CODD_KNN_METRIC_COSINE) return fail(CODD_KNN_ENOTSUP, "only the cosine metric exists on this path%s");
+    if (metric != CODD_KNN_METRIC_COSINE && metric != CODD_KNN_METRIC_IP && metric != CODD_KNN_METRIC_L2)
+        return fail(CODD_KNN_ENOTSUP, "unknown metric (cosine 0, ip 1, l2 2)%s");
     int ndev = 0;
     HIP_TRY(hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev) return fail(CODD_KNN_EINVAL, "no such device%s");
@@ -2935,6 +3086,8 @@ int codd_knn_create(codd_knn_index** out, int device, int dim, int dtype, int me
     ix->dpad = dpad;
     ix->dtype = dtype;
     ix->metric = metric;
+    // ip and l2 rows are no unit vectors, which both MFMA filters assume: such an index takes no filter leg, every batch the exact scan
+    if (metric != CODD_KNN_METRIC_COSINE) ix->all_normalized = false;
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) ix->num_cus = prop.multiProcessorCount;
     *out = ix;
@@ -2990,7 +3143,7 @@ int codd_knn_upsert_host(codd_knn_index* ix, const int64_t* host_slots, const fl
             rc = fail(CODD_KNN_EDEVICE, "staging copy failed: %s", hipGetErrorString(e));
             break;
         }
-        rc = launch_normalize(ix->dtype, dvec, m, ix->dim, ix->dpad, normalize, dslot, 0, ix->rows, nullptr, nullptr);
+        rc = launch_ingest(ix, dvec, m, normalize, dslot, 0, nullptr);
         // (one synchronisation per piece: the staging buffers are reused by the next piece, and the call is synchronous by contract)
         if (rc == 0 && hipDeviceSynchronize() != hipSuccess) rc = fail(CODD_KNN_EDEVICE, "ingest kernel failed%s");
     }
@@ -3029,7 +3182,7 @@ int codd_knn_upsert_device(codd_knn_index* ix, int64_t first_slot, const float* 
     if (ix->rows_event_set && ix->rows_stream != wst) HIP_TRY(hipStreamWaitEvent(wst, ix->rows_ready, 0));
     // ... and for streams that only READ rows outside a search (codd_knn_copy_rows_f32)
     if (ix->reader_event_set && ix->reader_stream != wst) HIP_TRY(hipStreamWaitEvent(wst, ix->reader_done, 0));
-    int rc = launch_normalize(ix->dtype, dev_vecs, n, ix->dim, ix->dpad, normalize, nullptr, first_slot, ix->rows, nullptr, wst);
+    int rc = launch_ingest(ix, dev_vecs, n, normalize, nullptr, first_slot, wst);
     if (rc != 0) return rc;
     // ... and searches on other streams wait for this write (wait_rows)
     HIP_TRY(ix->rows_ready.ensure());
@@ -3053,6 +3206,12 @@ int codd_knn_load_rows(codd_knn_index* ix, int64_t first_slot, const void* host_
     if (rc != 0) return rc;
     const size_t row_bytes = (size_t)ix->dpad * elem_size(ix->dtype);
     HIP_TRY(hipMemcpy(ix->rows + (size_t)first_slot * row_bytes, host_rows, (size_t)n * row_bytes, hipMemcpyHostToDevice));
+    if (!metric_is_cosine(ix)) {   // (ip, l2: rows of any norm, and no filter to keep on)
+        ix->rows_event_set = false;
+        if (first_slot + n > ix->count) ix->count = first_slot + n;
+        rows_written(ix, first_slot, first_slot + n);
+        return CODD_KNN_OK;
+    }
     // the loaded rows are taken as they are, so their norms are checked: the filters stay on only for unit rows
     // (tolerance = the storage type's rounding of a unit vector)
     DevBuf<unsigned> dev_bits;
@@ -3130,8 +3289,27 @@ int codd_knn_merge_shards(int device, const uint64_t* dev_keys_in, int G, int B,
                         nullptr, nullptr, k_in, (int64_t)B * k_in);
 }
 
+int codd_knn_merge_keys_metric(int device, const uint64_t* dev_keys_in, int B, int m, int k, int metric, uint64_t* dev_keys_out, float* dev_dist,
+                               int64_t* dev_rows, void* stream) {
+    if (!dev_keys_in || B < 1 || m < 1 || k < 1 || k > CODD_KNN_MAX_K) return fail(CODD_KNN_EINVAL, "bad merge arguments%s");
+    if (metric != CODD_KNN_METRIC_COSINE && metric != CODD_KNN_METRIC_IP && metric != CODD_KNN_METRIC_L2) return fail(CODD_KNN_ENOTSUP, "unknown metric (cosine 0, ip 1, l2 2)%s");
+    DeviceGuard guard(device);
+    return launch_merge((const u64*)dev_keys_in, B, m, m, k, (u64*)dev_keys_out, dev_dist, dev_rows, (hipStream_t)stream, nullptr, nullptr, nullptr, 0, 0,
+                        kernel_metric(metric));
+}
+
+int codd_knn_merge_shards_metric(int device, const uint64_t* dev_keys_in, int G, int B, int k_in, int k, int metric, uint64_t* dev_keys_out,
+                                 float* dev_dist, int64_t* dev_rows, void* stream) {
+    if (!dev_keys_in || G < 1 || B < 1 || k_in < 1 || k < 1 || k > CODD_KNN_MAX_K) return fail(CODD_KNN_EINVAL, "bad merge arguments%s");
+    if (metric != CODD_KNN_METRIC_COSINE && metric != CODD_KNN_METRIC_IP && metric != CODD_KNN_METRIC_L2) return fail(CODD_KNN_ENOTSUP, "unknown metric (cosine 0, ip 1, l2 2)%s");
+    DeviceGuard guard(device);
+    return launch_merge((const u64*)dev_keys_in, B, (int64_t)G * k_in, k_in, k, (u64*)dev_keys_out, dev_dist, dev_rows, (hipStream_t)stream, nullptr,
+                        nullptr, nullptr, k_in, (int64_t)B * k_in, kernel_metric(metric));
+}
+
 int codd_knn_approx_scores(codd_knn_index* ix, const float* dev_queries, int B, float* dev_scores, void* stream) {
     if (!ix || !dev_queries || !dev_scores || B < 1 || B > kTileQ) return fail(CODD_KNN_EINVAL, "bad debug arguments%s");
+    if (!metric_is_cosine(ix)) return fail(CODD_KNN_ENOTSUP, "approx_scores: the MFMA filters' scores exist for the cosine metric only%s");
     if (ix->count < 1) return fail(CODD_KNN_EINVAL, "empty index%s");
     DeviceGuard guard(ix->device);
     hipStream_t st = (hipStream_t)stream;
@@ -3199,6 +3377,7 @@ int codd_knn_copy_rows_f32(codd_knn_index* ix, int64_t first, int64_t n, float* 
 int codd_knn_ivf_install(codd_knn_index* ix, const float* dev_centroids, int nlist, const int64_t* dev_perm,
                          const int64_t* dev_offsets, void* stream) {
     if (!ix || !dev_centroids || !dev_perm || !dev_offsets || nlist < 1 || nlist > (1 << 20)) return fail(CODD_KNN_EINVAL, "bad ivf_install arguments%s");
+    if (!metric_is_cosine(ix)) return fail(CODD_KNN_ENOTSUP, "ivf_install: IVF exists for the cosine metric only (spherical k-means, bf16 assignment)%s");
     if (ix->count < 1) return fail(CODD_KNN_EINVAL, "empty index%s");
     DeviceGuard guard(ix->device);
     hipStream_t st = (hipStream_t)stream;
@@ -3283,6 +3462,7 @@ int empty_result(codd_knn_index* ix, int B, int k, uint64_t* dev_keys, float* de
 int ivf_check_args(const codd_knn_index* ix, const float* dev_queries, int B, int k, uint32_t row_base, int* nprobe) {
     int rc;
     if ((rc = search_check_args(ix, dev_queries, B, k, row_base)) != 0) return rc;
+    if (!metric_is_cosine(ix)) return fail(CODD_KNN_ENOTSUP, "IVF search exists for the cosine metric only%s");
     if (!ix->coarse || ix->ivf_epoch != ix->epoch) return fail(CODD_KNN_EINVAL, "no IVF layout, or rows changed since codd_knn_ivf_install%s");
     if (*nprobe < 1) return fail(CODD_KNN_EINVAL, "nprobe must be >= 1%s");
     if (*nprobe > ix->ivf_nlist) *nprobe = ix->ivf_nlist;
@@ -3442,7 +3622,7 @@ int codd_knn_search_scoped(codd_knn_index* ix, const float* dev_queries, const u
     HIP_TRY(ix->partial.ensure((int64_t)B * m));
     HIP_TRY(ix->scope_group.ensure((int64_t)2 * CODD_KNN_MAX_BATCH));
     if ((rc = ensure_scope_lists(ix, st)) != 0) return rc;
-    if ((rc = launch_normalize(DT_F32, dev_queries, B, ix->dim, ix->dpad, 1, nullptr, 0, ix->qn, nullptr, st)) != 0) return rc;
+    if ((rc = prep_exact_queries(ix, dev_queries, B, st)) != 0) return rc;
     unsigned* sorted_q = ix->scope_group;
     unsigned* rank = sorted_q + CODD_KNN_MAX_BATCH;
     hipLaunchKernelGGL(scope_group_kernel, dim3(1), dim3(1024), 0, st, dev_scopes, B, sorted_q, rank);
@@ -3450,6 +3630,10 @@ int codd_knn_search_scoped(codd_knn_index* ix, const float* dev_queries, const u
     {
         EvScope ev(ix, EV_SCAN, st);
         rc = with_row_form(ix, k, "row too wide for the scope scan%s", [&](auto dt, auto ni, auto sl) {
+            if (ix->metric == CODD_KNN_METRIC_L2)
+                return launch_kernel<scope_scan_l2<dt, ni, sl>>(dim3((unsigned)B, (unsigned)split), dim3(256), 0, st, ix->rows, ix->scope_perm, ix->scope_offsets,
+                                                                n - ix->dead_count, ix->max_scope, dev_scopes, sorted_q, rank, B, split, ix->dpad, ix->qn, k, row_base,
+                                                                ix->partial);
             return launch_kernel<scope_scan_kernel<dt, ni, sl>>(dim3((unsigned)B, (unsigned)split), dim3(256), 0, st, ix->rows, ix->scope_perm,
                                                                 ix->scope_offsets, n - ix->dead_count, ix->max_scope, dev_scopes, sorted_q, rank, B, split, ix->dpad,
                                                                 ix->qn, k, row_base, ix->partial);
@@ -3457,7 +3641,7 @@ int codd_knn_search_scoped(codd_knn_index* ix, const float* dev_queries, const u
     }
     if (rc != 0) return rc;
     HIP_TRY(hipGetLastError());
-    return launch_merge(ix->partial, B, m, m, k, (u64*)dev_keys, dev_dist, dev_rows, st);
+    return launch_merge_of(ix, ix->partial, B, m, k, (u64*)dev_keys, dev_dist, dev_rows, st);
 }
 
 }  // extern "C"
@@ -3528,18 +3712,21 @@ int masked_search_body(codd_knn_index* ix, const float* dev_queries, int B, int 
     const int64_t pm = (int64_t)split * k;
     HIP_TRY(ix->qn.ensure((int64_t)B * ix->dpad));
     HIP_TRY(ix->partial.ensure((int64_t)B * pm));
-    if ((rc = launch_normalize(DT_F32, dev_queries, B, ix->dim, ix->dpad, 1, nullptr, 0, ix->qn, nullptr, st)) != 0) return rc;
+    if ((rc = prep_exact_queries(ix, dev_queries, B, st)) != 0) return rc;
     {
         EvScope ev(ix, EV_SCAN, st);
         rc = with_row_form(ix, k, "row too wide for the mask scan%s", [&](auto dt, auto ni, auto sl) {
             constexpr int NB = scope_nb(decltype(dt)::value, decltype(ni)::value);
+            if (ix->metric == CODD_KNN_METRIC_L2)
+                return launch_kernel<mask_scan_l2<dt, ni, sl>>(dim3((unsigned)((B + NB - 1) / NB), (unsigned)split), dim3(256), 0, st, ix->rows, ix->mask_list, m, B,
+                                                               split, ix->dpad, ix->qn, k, row_base, ix->partial);
             return launch_kernel<mask_scan_kernel<dt, ni, sl>>(dim3((unsigned)((B + NB - 1) / NB), (unsigned)split), dim3(256), 0, st, ix->rows, ix->mask_list, m,
                                                                B, split, ix->dpad, ix->qn, k, row_base, ix->partial);
         });
     }
     if (rc != 0) return rc;
     HIP_TRY(hipGetLastError());
-    return launch_merge(ix->partial, B, pm, pm, k, (u64*)dev_keys, dev_dist, dev_rows, st);
+    return launch_merge_of(ix, ix->partial, B, pm, k, (u64*)dev_keys, dev_dist, dev_rows, st);
 }
 
 // The host words of a masked search (nwords > 0 of them): clipped to [0, n) into the workspace's pinned staging buffer and counted
@@ -4219,6 +4406,7 @@ int codd_knn_get_stat(const codd_knn_index* ix, const char* key, int64_t* out) {
     else if (strcmp(key, "shadow16_builds") == 0) *out = ix->stat_shadow_builds;
     else if (strcmp(key, "shadow16_alloc_failures") == 0) *out = ix->stat_shadow_nomem;
     else if (strcmp(key, "all_normalized") == 0) *out = ix->all_normalized ? 1 : 0;
+    else if (strcmp(key, "metric") == 0) *out = ix->metric;
     else if (strcmp(key, "shadow8_passes") == 0) *out = ix->stat_shadow8_passes;
     else if (strcmp(key, "i8v2_passes") == 0) *out = ix->stat_i8v2_passes;
     else if (strcmp(key, "f16_tile_passes") == 0) *out = ix->stat_f16_tile_passes;

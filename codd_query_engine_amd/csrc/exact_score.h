@@ -20,12 +20,25 @@
 
 namespace codd {
 
+// The metric of an exact-score function or body, a compile-time switch that defaults to the code as it always was:
+//   kMetricDot  the canonical dot product — cosine on normalised operands, ip (CODD_KNN_METRIC_IP) on raw ones
+//   kMetricL2   (== CODD_KNN_METRIC_L2) the squared distance by the direct difference: the chain step is t = q_e - c_e (one fp32
+//               subtraction), a = fmaf(t, t, a); the butterfly sum is the distance and the score is 0.0f - distance, so that
+//               larger is still better, an exact match scores +0, and the integer merges need no change
+constexpr int kMetricDot = 0;
+constexpr int kMetricL2 = 2;
+
 // the tail of the expression for four rows at once: a[r] = this lane's chain of row r.  packed4: the 16 lanes of group r hold the
 // score of row r; packed_score(y, r) hands it to every lane; reduce4 = both, sc[r] = the score of row r in every lane
-__device__ __forceinline__ float packed4(const float (&a)[4], const int& lane) { return butterfly_sum4(a[0], a[1], a[2], a[3], lane); }
+template <int METRIC = kMetricDot>
+__device__ __forceinline__ float packed4(const float (&a)[4], const int& lane) {
+    if constexpr (METRIC == kMetricL2) return 0.0f - butterfly_sum4(a[0], a[1], a[2], a[3], lane);
+    else return butterfly_sum4(a[0], a[1], a[2], a[3], lane);
+}
 __device__ __forceinline__ float packed_score(float y, const int& r) { return __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(y), 16 * r)); }
+template <int METRIC = kMetricDot>
 __device__ __forceinline__ void reduce4(const float (&a)[4], const int& lane, float (&sc)[4]) {
-    const float y = packed4(a, lane);
+    const float y = packed4<METRIC>(a, lane);
 #pragma unroll
     for (int r = 0; r < 4; ++r) sc[r] = packed_score(y, r);
 }
@@ -57,7 +70,7 @@ __device__ __forceinline__ void fetch4(const uint4* const (&p)[4], const int& nc
 
 // sc[b][r] = the score of row r against query b < nq (0 for b >= nq), in every lane.  Chunk-major: a chunk is widened when its
 // step comes (a widened bf16 / fp16 chunk is twice the registers) and serves every query.
-template <int DT, int NB, int NITER>
+template <int DT, int NB, int NITER, int METRIC = kMetricDot>
 __device__ __forceinline__ void score4(const uint4 (&c)[4][NITER], const float (&qf)[NB][NITER][RowTraits<DT>::E], const int& nq, const int& lane, float (&sc)[NB][4]) {
     typedef RowTraits<DT> RT;
     constexpr int E = RT::E;
@@ -76,13 +89,20 @@ __device__ __forceinline__ void score4(const uint4 (&c)[4][NITER], const float (
             for (int b = 0; b < NB; ++b)
                 if (b < nq) {
 #pragma unroll
-                    for (int e = 0; e < E; ++e) a[b][r] = __builtin_fmaf(qf[b][it][e], w[e], a[b][r]);
+                    for (int e = 0; e < E; ++e) {
+                        if constexpr (METRIC == kMetricL2) {
+                            const float t = qf[b][it][e] - w[e];
+                            a[b][r] = __builtin_fmaf(t, t, a[b][r]);
+                        } else {
+                            a[b][r] = __builtin_fmaf(qf[b][it][e], w[e], a[b][r]);
+                        }
+                    }
                 }
         }
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
         if (b < nq) {
-            reduce4(a[b], lane, sc[b]);
+            reduce4<METRIC>(a[b], lane, sc[b]);
         } else {
 #pragma unroll
             for (int r = 0; r < 4; ++r) sc[b][r] = 0.0f;
@@ -102,7 +122,7 @@ __device__ __forceinline__ void fetch4_widened(const uint4* const (&p)[4], const
             RowTraits<DT>::widen(c, w[r][it]);
         }
 }
-template <int NITER, int E>
+template <int NITER, int E, int METRIC = kMetricDot>
 __device__ __forceinline__ float score4_one(const float (&w)[4][NITER][E], const float (&qf)[NITER][E], const int& lane) {
     float a[4] = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
@@ -110,8 +130,15 @@ __device__ __forceinline__ float score4_one(const float (&w)[4][NITER][E], const
 #pragma unroll
         for (int it = 0; it < NITER; ++it)
 #pragma unroll
-            for (int e = 0; e < E; ++e) a[r] = __builtin_fmaf(qf[it][e], w[r][it][e], a[r]);
-    return packed4(a, lane);
+            for (int e = 0; e < E; ++e) {
+                if constexpr (METRIC == kMetricL2) {
+                    const float t = qf[it][e] - w[r][it][e];
+                    a[r] = __builtin_fmaf(t, t, a[r]);
+                } else {
+                    a[r] = __builtin_fmaf(qf[it][e], w[r][it][e], a[r]);
+                }
+            }
+    return packed4<METRIC>(a, lane);
 }
 
 // ---- wide rows: more than 4 chunks per lane (f32 rows above 1,024 elements, 2-byte rows above 2,048) ----
@@ -139,7 +166,7 @@ __device__ __forceinline__ void wide_stage_query(float* __restrict__ dst, const 
 // each lane's canonical fmaf chain over chunks lane + 64 (kSegIt s + it), it = 0 .. kSegIt-1.  f32: the segment widened as it lands,
 // one query's LDS values at a time; 2-byte rows: the 16-byte chunks stay raw until their step and chunk it's query values are read
 // once for all rows.  Either way the same fmaf sequence per (query, row).
-template <int DT, int NQ, int NR>
+template <int DT, int NQ, int NR, int METRIC = kMetricDot>
 __device__ __forceinline__ void wide_segment(const uint4* const (&p)[NR], const int& s, const int& nchunks, const int& lane, const float* qs, const int& qstride, float (&acc)[NQ][NR]) {
     typedef RowTraits<DT> RT;
     constexpr int E = RT::E;
@@ -167,7 +194,14 @@ __device__ __forceinline__ void wide_segment(const uint4* const (&p)[NR], const 
 #pragma unroll
                 for (int it = 0; it < kSegIt; ++it)
 #pragma unroll
-                    for (int e = 0; e < E; ++e) acc[b][r] = __builtin_fmaf(q[it][e], w[r][it][e], acc[b][r]);
+                    for (int e = 0; e < E; ++e) {
+                        if constexpr (METRIC == kMetricL2) {
+                            const float t = q[it][e] - w[r][it][e];
+                            acc[b][r] = __builtin_fmaf(t, t, acc[b][r]);
+                        } else {
+                            acc[b][r] = __builtin_fmaf(q[it][e], w[r][it][e], acc[b][r]);
+                        }
+                    }
         }
         return;
     }
@@ -199,14 +233,21 @@ __device__ __forceinline__ void wide_segment(const uint4* const (&p)[NR], const 
 #pragma unroll
             for (int b = 0; b < NQ; ++b)
 #pragma unroll
-                for (int e = 0; e < E; ++e) acc[b][r] = __builtin_fmaf(q[b][e], w[e], acc[b][r]);
+                for (int e = 0; e < E; ++e) {
+                    if constexpr (METRIC == kMetricL2) {
+                        const float t = q[b][e] - w[e];
+                        acc[b][r] = __builtin_fmaf(t, t, acc[b][r]);
+                    } else {
+                        acc[b][r] = __builtin_fmaf(q[b][e], w[e], acc[b][r]);
+                    }
+                }
         }
     }
 }
 
 // score4's wide twin for 4 G rows (G groups of four, every group's loads of a segment in flight together) against NQ staged queries:
 // sc[b][4 g + r] = the score of row r of group g against query b < nq (0 for b >= nq), in every lane
-template <int DT, int NQ, int G>
+template <int DT, int NQ, int G, int METRIC = kMetricDot>
 __device__ __forceinline__ void wide_scores(const uint4* const (&p)[4 * G], const int& nchunks, const int& lane, const float* qs, const int& qstride, const int& nq, float (&sc)[NQ][4 * G]) {
     float acc[NQ][4 * G];
 #pragma unroll
@@ -214,7 +255,7 @@ __device__ __forceinline__ void wide_scores(const uint4* const (&p)[4 * G], cons
 #pragma unroll
         for (int r = 0; r < 4 * G; ++r) acc[b][r] = 0.0f;
     const int nseg = wide_nseg(nchunks);
-    for (int s = 0; s < nseg; ++s) wide_segment<DT, NQ, 4 * G>(p, s, nchunks, lane, qs, qstride, acc);
+    for (int s = 0; s < nseg; ++s) wide_segment<DT, NQ, 4 * G, METRIC>(p, s, nchunks, lane, qs, qstride, acc);
 #pragma unroll
     for (int b = 0; b < NQ; ++b)
 #pragma unroll
@@ -222,7 +263,7 @@ __device__ __forceinline__ void wide_scores(const uint4* const (&p)[4 * G], cons
             float sg[4] = {0.0f, 0.0f, 0.0f, 0.0f};
             if (b < nq) {
                 const float a[4] = {acc[b][4 * g], acc[b][4 * g + 1], acc[b][4 * g + 2], acc[b][4 * g + 3]};
-                reduce4(a, lane, sg);
+                reduce4<METRIC>(a, lane, sg);
             }
 #pragma unroll
             for (int r = 0; r < 4; ++r) sc[b][4 * g + r] = sg[r];
@@ -256,8 +297,8 @@ __device__ __forceinline__ void write_keys(const WaveTopK<SLOTS>& M, int k, int 
         if (rank < k) keys[rank] = M.v[s];
     }
 }
-// ... to any of: packed keys, (distance = 1 - score, row); an empty rank reads (inf, -1)
-template <int SLOTS>
+// ... to any of: packed keys, (distance, row); distance = 1 - score, under kMetricL2 0 - score; an empty rank reads (inf, -1)
+template <int SLOTS, int METRIC = kMetricDot>
 __device__ __forceinline__ void write_ranks(const WaveTopK<SLOTS>& M, int k, int lane, u64* __restrict__ keys, float* __restrict__ dist, int64_t* __restrict__ rows) {
 #pragma unroll
     for (int s = 0; s < SLOTS; ++s) {
@@ -265,7 +306,7 @@ __device__ __forceinline__ void write_ranks(const WaveTopK<SLOTS>& M, int k, int
         if (rank < k) {
             const u64 key = M.v[s];
             if (keys) keys[rank] = key;
-            if (dist) dist[rank] = key ? 1.0f - key_score(key) : INFINITY;
+            if (dist) dist[rank] = key ? (METRIC == kMetricL2 ? 0.0f : 1.0f) - key_score(key) : INFINITY;
             if (rows) rows[rank] = key ? (int64_t)key_row(key) : (int64_t)-1;
         }
     }

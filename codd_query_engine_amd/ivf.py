@@ -22,6 +22,13 @@ from . import native
 from .knn_index import DeviceKnnIndex
 
 
+def _require_cosine(index) -> None:
+    """IVF is cosine-specific (spherical k-means, centroids assigned by the bf16 cosine GEMM): an ip or l2 index has none."""
+    space = getattr(index, "space", "cosine")
+    if space != "cosine":
+        raise native.NativeLibraryError(f"IVF exists for the cosine space only, this index is {space!r}: search it with the exact scan")
+
+
 def _assign(torch, centroid_index: DeviceKnnIndex, vecs) -> "torch.Tensor":
     """nearest centroid (by approximate cosine) of every row of `vecs` [n, dim] (device fp32)."""
     nlist = centroid_index.count()
@@ -41,6 +48,7 @@ def build_ivf(index: DeviceKnnIndex, nlist: int, iters: int = 8, sample: Optiona
     """
     import torch
 
+    _require_cosine(index)
     lib = native.load()
     n, dim, dev = index.count(), index.dim, index.device
     if n < nlist:
@@ -109,6 +117,7 @@ def search_ivf(index: DeviceKnnIndex, queries, k: int, nprobe: int, row_base: in
     probes; the mask only removes rows from them, so a small mask may leave fewer than k hits."""
     import torch
 
+    _require_cosine(index)
     row_base = native.check_row_base(row_base, index.count())
     if allow is not None:
         if _is_device_mask(allow):
@@ -132,6 +141,7 @@ def search_ivf_keys(index: DeviceKnnIndex, queries, k: int, nprobe: int, row_bas
     allow: as in search_ivf (the mask is over the shard's LOCAL row slots)."""
     import torch
 
+    _require_cosine(index)
     row_base = native.check_row_base(row_base, index.count())
     if allow is not None:
         if _is_device_mask(allow):
@@ -154,6 +164,7 @@ class IvfShardEngine:
     forms answer a shard-local `allow` under the same `nprobe` lists (search_ivf_keys(..., allow=))."""
 
     def __init__(self, index: DeviceKnnIndex, nprobe: int):
+        _require_cosine(index)
         self.index, self.nprobe = index, int(nprobe)
 
     def count(self) -> int:

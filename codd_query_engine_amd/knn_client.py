@@ -11,7 +11,15 @@ the C ABI of the HIP engine (knn_index.DeviceKnnIndex).  There is no CPU search 
 default engine factory raises if the library or the GPU is missing.
 
 `engine_factory(dim) -> engine` exists so that host-logic tests can stand the façade on a
-checker engine of their own (tests/_oracle_engine.py); products never pass it.
+checker engine of their own (tests/_oracle_engine.py); products never pass it.  A factory that can
+build engines for ChromaDB's other spaces says so with a `spaces` attribute (names of
+native.METRIC_CODES) and is then called as `engine_factory(dim, space=...)` for a collection whose
+metadata asks for one of them; a factory without the attribute serves cosine only.
+
+Spaces (`metadata={"hnsw:space": ...}`): "cosine" (the default here), "l2" (squared
+distance) and "ip" (1 - inner product), ChromaDB's definitions.  A non-cosine collection stores the
+embeddings as given (upsert with normalize=False) and `query` returns that space's distances;
+everything else — namespaces, `where`, `where_document`, delete, compact, persistence — is the same.
 
 Persistence (`KnnClient(path=...)`, the role of `SemanticStoreConfig.chromadb_path`, declared and
 never read in the reference, codd_lib/codd_lib/config/semantic_store_config.py:13): the indexer job
@@ -39,17 +47,28 @@ import numpy as np
 
 from .embedding import EmbeddingFunction, HashingEmbeddingFunction
 
-_SUPPORTED_SPACES = ("cosine",)
+_DEFAULT_SPACE = "cosine"
+_ALL_SPACES = ("cosine", "l2", "ip")
 FORMAT_VERSION = 1  # of the on-disk layout
 
 
-def _default_engine_factory(device: str, dtype: str) -> Callable[[int], Any]:
-    def make(dim: int):
+def _default_engine_factory(device: str, dtype: str) -> Callable[..., Any]:
+    def make(dim: int, space: str = _DEFAULT_SPACE):
         from .knn_index import DeviceKnnIndex  # raises NativeLibraryError without .so / GPU
 
-        return DeviceKnnIndex(dim, dtype=dtype, device=device)
+        return DeviceKnnIndex(dim, dtype=dtype, device=device, space=space)
 
+    make.spaces = _ALL_SPACES
     return make
+
+
+def _factory_spaces(engine_factory) -> tuple:
+    """The spaces a factory builds engines for: its `spaces` attribute, cosine only without one."""
+    return tuple(getattr(engine_factory, "spaces", (_DEFAULT_SPACE,)))
+
+
+def _space_of(metadata: Optional[dict]) -> str:
+    return (metadata or {}).get("hnsw:space", _DEFAULT_SPACE)
 
 
 class Collection:
@@ -93,9 +112,25 @@ class Collection:
         self._docs_fit_device: Optional[bool] = None   # no document holds NUL (None: not looked yet; one pass per change)
 
     # ------------------------------------------------------------------ helpers
+    @property
+    def space(self) -> str:
+        """The collection's `hnsw:space`: "cosine" unless its metadata names another."""
+        return _space_of(self.metadata)
+
+    def _make_engine(self, dim: int, space: str):
+        """A new engine of `space` from the factory; a cosine one by the plain call every factory answers."""
+        if space == _DEFAULT_SPACE:
+            return self._engine_factory(dim)
+        if space not in _factory_spaces(self._engine_factory):
+            raise ValueError(f"hnsw:space={space!r} is not on this path (supported: {_factory_spaces(self._engine_factory)})")
+        engine = self._engine_factory(dim, space=space)
+        if getattr(engine, "space", space) != space:
+            raise ValueError(f"the engine factory answered space {engine.space!r} for {space!r}")
+        return engine
+
     def _engine_for(self, dim: int):
         if self._engine is None:
-            self._engine = self._engine_factory(dim)
+            self._engine = self._make_engine(dim, self.space)
         elif self._engine.dim != dim:
             raise ValueError(f"embedding dimension {dim} does not match collection dimension {self._engine.dim}")
         return self._engine
@@ -423,11 +458,12 @@ class Collection:
                 next_slot += 1
                 fresh.append(doc_id)
             slots[i] = slot
-        # device first: host bookkeeping only changes if it succeeded
+        # device first: host bookkeeping only changes if it succeeded.  (l2 / ip: the vectors are stored as given)
+        raw = {} if self.space == _DEFAULT_SPACE else {"normalize": False}
         if isinstance(vecs, np.ndarray):
-            engine.upsert(slots, vecs)
+            engine.upsert(slots, vecs, **raw)
         else:
-            engine.upsert_device(int(slots[0]), vecs)
+            engine.upsert_device(int(slots[0]), vecs, **raw)
         for doc_id in fresh:
             self._slot_of[doc_id] = len(self._ids)
             self._ids.append(doc_id)
@@ -773,12 +809,16 @@ class Collection:
         n = manifest["count"]
         if not (len(ids) == len(metadatas) == len(documents) == n):
             raise ValueError(f"{gdir}: sidecar lengths disagree with the manifest")
+        # the space travels in the stored collection metadata; an engine this collection already has must be of that space
+        space = _space_of(manifest.get("metadata"))
+        if self._engine is not None and getattr(self._engine, "space", _DEFAULT_SPACE) != space:
+            raise ValueError(f"{gdir}: stored space {space} does not match the collection's space {getattr(self._engine, 'space', _DEFAULT_SPACE)}")
         engine = None
         if n and manifest["dim"]:
             dtype = manifest["dtype"]
             rows = np.fromfile(os.path.join(gdir, "rows.bin"), dtype=np.float32 if dtype == "f32" else np.uint16)
             rows = rows.reshape(n, manifest["padded_dim"])
-            engine = self._engine_factory(manifest["dim"])
+            engine = self._make_engine(manifest["dim"], space)
             if getattr(engine, "dtype", dtype) != dtype:
                 raise ValueError(f"{gdir}: stored dtype {dtype} does not match the client's dtype {engine.dtype}")
             engine.load_rows(rows, 0)
@@ -878,9 +918,9 @@ class KnnClient:
         existing = self._collections.get(name)
         if existing is not None:
             return existing
-        space = (metadata or {}).get("hnsw:space", "cosine")
-        if space not in _SUPPORTED_SPACES:
-            raise ValueError(f"hnsw:space={space!r} is not on this path (supported: {_SUPPORTED_SPACES})")
+        space = _space_of(metadata)
+        if space not in _factory_spaces(self._engine_factory):
+            raise ValueError(f"hnsw:space={space!r} is not on this path (supported: {_factory_spaces(self._engine_factory)})")
         col = Collection(name, metadata, embedding_function or self._embed, self._engine_factory)
         self._collections[name] = col
         return col

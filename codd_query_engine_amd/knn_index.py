@@ -31,7 +31,9 @@ def require_gpu(device: str = "cuda:0"):
 
 
 class DeviceKnnIndex:
-    """Device-resident, L2-normalised row store with exact cosine top-k search.
+    """Device-resident row store with exact top-k search: L2-normalised rows under cosine (the default `space`), rows as given
+    under ChromaDB's other two spaces, "ip" (distance 1 - <q, c>) and "l2" (squared distance).  Every search method's distances
+    follow the space; an ip or l2 index has no IVF and no approx_scores.
 
     Engine protocol consumed by knn_client.Collection:
         count() / upsert(slots, vecs) / search(queries, k) -> (dist, rows) as numpy;
@@ -41,9 +43,11 @@ class DeviceKnnIndex:
     out of a mask over global rows (sharded.py).
     """
 
-    def __init__(self, dim: int, dtype: str = "f32", device: str = "cuda:0"):
+    def __init__(self, dim: int, dtype: str = "f32", device: str = "cuda:0", space: str = "cosine"):
         if dtype not in native.DTYPE_CODES:
             raise ValueError(f"dtype must be one of {sorted(native.DTYPE_CODES)}")
+        metric = native.metric_code(space)
+        self.space = space
         self._lib = native.load()
         self.device = require_gpu(device)
         self.dim = int(dim)
@@ -51,7 +55,7 @@ class DeviceKnnIndex:
         self._dev_index = self.device.index if self.device.index is not None else _torch().cuda.current_device()
         h = ctypes.c_void_p()
         native.check(
-            self._lib.codd_knn_create(ctypes.byref(h), self._dev_index, self.dim, native.DTYPE_CODES[dtype], native.METRIC_COSINE),
+            self._lib.codd_knn_create(ctypes.byref(h), self._dev_index, self.dim, native.DTYPE_CODES[dtype], metric),
             "codd_knn_create",
         )
         self._h = h
@@ -397,11 +401,13 @@ class DeviceKnnIndex:
         return slice_mask(global_bits, global_rows, row_base, self.count(), self.device)
 
     def merge_keys(self, keys, k: int):
-        """Top-k of [B,m] packed keys -> (keys [B,k], dist [B,k], rows [B,k]) on device."""
-        return merge_keys(keys, k, self.device)
+        """Top-k of [B,m] packed keys -> (keys [B,k], dist [B,k], rows [B,k]) on device; distances by this index's space."""
+        return merge_keys(keys, k, self.device, space=self.space)
 
     def approx_scores(self, queries):
-        """Raw approximate scores of the MFMA filter: [256, count] fp32 tensor (diagnostics)."""
+        """Raw approximate scores of the MFMA filter: [256, count] fp32 tensor (diagnostics).  Cosine only."""
+        if self.space != "cosine":
+            raise native.NativeLibraryError(f"approx_scores: the MFMA filters exist for the cosine space only, this index is {self.space!r}")
         torch = _torch()
         q = self._queries_tensor(queries)
         out = torch.zeros((256, self.count()), dtype=torch.float32, device=self.device)
@@ -421,8 +427,9 @@ class DeviceKnnIndex:
         return out.value
 
 
-def merge_keys(keys, k: int, device=None):
-    """codd_knn_merge_keys on a [B,m] int64 CUDA tensor of packed keys."""
+def merge_keys(keys, k: int, device=None, space: str = "cosine"):
+    """codd_knn_merge_keys_metric on a [B,m] int64 CUDA tensor of packed keys; `space` decides the distances written."""
+    metric = native.metric_code(space)
     torch = _torch()
     lib = native.load()
     if not (isinstance(keys, torch.Tensor) and keys.is_cuda and keys.dtype == torch.int64 and keys.dim() == 2):
@@ -435,8 +442,8 @@ def merge_keys(keys, k: int, device=None):
     rows = torch.empty((B, k), dtype=torch.int64, device=dev)
     stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     native.check(
-        lib.codd_knn_merge_keys(dev.index or 0, keys.data_ptr(), B, m, int(k), out_keys.data_ptr(), dist.data_ptr(), rows.data_ptr(), stream),
-        "codd_knn_merge_keys",
+        lib.codd_knn_merge_keys_metric(dev.index or 0, keys.data_ptr(), B, m, int(k), metric, out_keys.data_ptr(), dist.data_ptr(), rows.data_ptr(), stream),
+        "codd_knn_merge_keys_metric",
     )
     return out_keys, dist, rows
 
@@ -465,8 +472,10 @@ def slice_mask(global_bits, global_rows: int, row_base: int, count: int, device=
     return out
 
 
-def merge_shards(gathered, world_size: int, k: int, device=None):
-    """codd_knn_merge_shards on the [G*B, k_in] int64 CUDA tensor an all_gather of the ranks' [B, k_in] keys delivers."""
+def merge_shards(gathered, world_size: int, k: int, device=None, space: str = "cosine"):
+    """codd_knn_merge_shards_metric on the [G*B, k_in] int64 CUDA tensor an all_gather of the ranks' [B, k_in] keys delivers;
+    `space` decides the distances written."""
+    metric = native.metric_code(space)
     torch = _torch()
     lib = native.load()
     if not (isinstance(gathered, torch.Tensor) and gathered.is_cuda and gathered.dtype == torch.int64 and gathered.dim() == 2
@@ -480,8 +489,8 @@ def merge_shards(gathered, world_size: int, k: int, device=None):
     rows = torch.empty((B, k), dtype=torch.int64, device=dev)
     stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     native.check(
-        lib.codd_knn_merge_shards(dev.index or 0, gathered.data_ptr(), int(world_size), B, k_in, int(k), out_keys.data_ptr(), dist.data_ptr(),
-                                  rows.data_ptr(), stream),
-        "codd_knn_merge_shards",
+        lib.codd_knn_merge_shards_metric(dev.index or 0, gathered.data_ptr(), int(world_size), B, k_in, int(k), metric, out_keys.data_ptr(),
+                                         dist.data_ptr(), rows.data_ptr(), stream),
+        "codd_knn_merge_shards_metric",
     )
     return out_keys, dist, rows

@@ -17,6 +17,11 @@ LIB_PATH = os.environ.get("CODD_KNN_LIB") or os.path.join(_HERE, "csrc", "libcod
 DTYPE_CODES = {"f32": 0, "bf16": 1, "f16": 2}
 DTYPE_NAMES = {v: k for k, v in DTYPE_CODES.items()}
 METRIC_COSINE = 0
+METRIC_IP = 1
+METRIC_L2 = 2
+# ChromaDB's `hnsw:space` names <-> CODD_KNN_METRIC_*
+METRIC_CODES = {"cosine": METRIC_COSINE, "ip": METRIC_IP, "l2": METRIC_L2}
+METRIC_NAMES = {v: k for k, v in METRIC_CODES.items()}
 MAX_K = 128
 MAX_BATCH = 1024
 MAX_SCOPE = 1048575
@@ -46,6 +51,8 @@ ABI = [
     ("codd_knn_search_keys", ctypes.c_int, [_c_idx, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]),
     ("codd_knn_merge_keys", ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     ("codd_knn_merge_shards", ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    ("codd_knn_merge_keys_metric", ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    ("codd_knn_merge_shards_metric", ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     ("codd_knn_approx_scores", ctypes.c_int, [_c_idx, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
     ("codd_knn_copy_rows_f32", ctypes.c_int, [_c_idx, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
     ("codd_knn_ivf_install", ctypes.c_int, [_c_idx, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
@@ -121,6 +128,13 @@ def last_error() -> str:
 def check(rc: int, what: str) -> None:
     if rc != 0:
         raise NativeLibraryError(f"{what} failed with code {rc}: {last_error()}")
+
+
+def metric_code(space: str) -> int:
+    """CODD_KNN_METRIC_* of a ChromaDB space name; ValueError for a name that is none of METRIC_CODES."""
+    if space not in METRIC_CODES:
+        raise ValueError(f"space must be one of {sorted(METRIC_CODES)}, got {space!r}")
+    return METRIC_CODES[space]
 
 
 def check_row_base(row_base: int, count: int) -> int:

@@ -59,8 +59,9 @@ class ShardedSearcher:
 
     engine.search_keys(queries, k, row_base) -> int64 tensor [B,k] of packed keys on the
     engine's device; merge(keys [B,m], k) -> (keys, dist, rows).  Products pass a
-    DeviceKnnIndex and leave `merge` unset (HIP merge kernel); the gloo tests pass the
-    checker engine and its merge.
+    DeviceKnnIndex and leave `merge` unset (HIP merge kernel, which writes the distances of the
+    engine's `space`: cosine where the engine names none); the gloo tests pass the checker engine
+    and its merge.
 
     Deletes need nothing here: tombstones are shard-local (engine.delete) and the keys carry
     global rows.  Compacting ONE shard (engine.compact) changes its local slots, so the
@@ -89,8 +90,10 @@ class ShardedSearcher:
             from .knn_index import merge_keys as hip_merge
             from .knn_index import merge_shards as hip_merge_shards
 
-            merge = hip_merge
-            self._merge_gathered = hip_merge_shards
+            # the keys merge alike under every space; the distance written beside them follows the engine's
+            space = getattr(engine, "space", "cosine")
+            merge = lambda keys, k: hip_merge(keys, k, space=space)  # noqa: E731
+            self._merge_gathered = lambda gathered, world, k: hip_merge_shards(gathered, world, k, space=space)  # noqa: E731
         self._merge = merge
         self._streams: list = []
         self._turn = 0

@@ -34,6 +34,23 @@
  *     zero vector: score 0, distance 1 against everything.
  *     score = <q/|q|, c/|c|> evaluated in fp32 in the canonical order of
  *     DESIGN.md §3; distance = 1 - score (fp32); ties -> lower row.
+ *   - the above is the cosine metric.  An index created with CODD_KNN_METRIC_IP or CODD_KNN_METRIC_L2
+ *     (ChromaDB's `hnsw:space` "ip" and "l2") uses rows and queries AS GIVEN: rounded to
+ *     the storage dtype and zero padded, never normalised (upsert with normalize = 0; normalize != 0
+ *     still normalises, the caller's choice).  A vector with a NaN or infinite element, or without a
+ *     non-zero one, is the zero vector here too.
+ *       ip: score = <q, c>, the canonical dot product of DESIGN.md §3; distance = 1 - score.
+ *       l2: distance = sum (q_i - c_i)^2, the SQUARED distance as hnswlib and ChromaDB report it, by the
+ *           direct difference in the same canonical order (per element one fp32 subtraction t, then
+ *           fmaf(t, t, a)); the score packed into a key is 0 - distance.  A query equal to a stored row
+ *           has distance +0.0 exactly.
+ *     Ties -> lower row, padding (row -1, distance +inf, key 0) and "a NaN score ranks as -inf" are as
+ *     for cosine.  Inputs whose fp32 sums overflow are outside the contract.  Such an index takes no
+ *     MFMA filter leg (both assume unit rows): every batch is answered by the exact scan, in groups of
+ *     up to 8 queries per pass over the rows; the "all_normalized" stat reads 0 from the start.  Every
+ *     search, delete, compact, load and read entry point keeps its contract word for word under these
+ *     metrics, except the IVF ones and codd_knn_approx_scores, which return ENOTSUP (spherical k-means
+ *     and the bf16 assignment are cosine-specific).
  *   - every entry point with a `row_base` (codd_knn_search_keys, _search_scoped, _search_masked,
  *     _search_masked_dev, _ivf_search, _ivf_search_masked, _ivf_search_masked_dev) writes global rows
  *     row_base + row, which must fit the low word of a packed key: the highest global row is
@@ -56,8 +73,10 @@ extern "C" {
 #define CODD_KNN_DTYPE_BF16 1
 #define CODD_KNN_DTYPE_F16 2
 
-/* `hnsw:space` of get_or_create_collection (store.py:63-68); only cosine exists on the path */
+/* `hnsw:space` of get_or_create_collection (store.py:63-68): "cosine", "ip", "l2" (see the conventions above) */
 #define CODD_KNN_METRIC_COSINE 0
+#define CODD_KNN_METRIC_IP 1
+#define CODD_KNN_METRIC_L2 2
 
 #define CODD_KNN_MAX_K 128        /* reference caps n_results at 100 (store.py:24) */
 #define CODD_KNN_MAX_BATCH 1024   /* queries per codd_knn_search call */
@@ -83,6 +102,7 @@ const char* codd_knn_last_error(void);
  *      rows (1536 / 3072 / 4096-wide embedders) by the wide forms of the exact-score kernels — the
  *      scan, finalize, the threshold anchors and the IVF scans — which stage the query in LDS and
  *      walk the row in segments: the same canonical scores.
+ * metric: CODD_KNN_METRIC_COSINE, _IP or _L2; any other value: ENOTSUP.
  */
 int codd_knn_create(codd_knn_index** out, int device, int dim, int dtype, int metric);
 int codd_knn_destroy(codd_knn_index* index);
@@ -116,7 +136,8 @@ int codd_knn_upsert_device(codd_knn_index* index, int64_t first_slot, const floa
  * codd_knn_read_rows returned them (storage dtype, padded width, already normalised); they are
  * copied into slots [first_slot, first_slot+n).  Their norms are checked on the device: if any row is
  * not a unit vector (within the storage type's rounding) the index behaves as after an upsert with
- * normalize = 0 — both filters off, every search an exact scan ("all_normalized" stat = 0).  Synchronous.
+ * normalize = 0 — both filters off, every search an exact scan ("all_normalized" stat = 0).  An ip or l2 index
+ * holds rows of any norm: nothing is checked, the rows load bit for bit.  Synchronous.
  */
 int codd_knn_load_rows(codd_knn_index* index, int64_t first_slot, const void* host_rows, int64_t n);
 
@@ -160,9 +181,20 @@ int codd_knn_merge_shards(int device, const uint64_t* dev_keys_in, int G, int B,
                           uint64_t* dev_keys_out, float* dev_dist, int64_t* dev_rows, void* stream);
 
 /*
+ * The two merges above for keys of any metric.  The keys merge alike (integers); `metric` decides the
+ * distance written to dev_dist: 1 - score for CODD_KNN_METRIC_COSINE and _IP, 0 - score for _L2
+ * (another value: ENOTSUP).  codd_knn_merge_keys and codd_knn_merge_shards are these with cosine.
+ */
+int codd_knn_merge_keys_metric(int device, const uint64_t* dev_keys_in, int B, int m, int k, int metric,
+                               uint64_t* dev_keys_out, float* dev_dist, int64_t* dev_rows, void* stream);
+int codd_knn_merge_shards_metric(int device, const uint64_t* dev_keys_in, int G, int B, int k_in, int k, int metric,
+                                 uint64_t* dev_keys_out, float* dev_dist, int64_t* dev_rows, void* stream);
+
+/*
  * The raw approximate (bf16 MFMA) scores of B <= 256 queries against every stored row:
  * dev_scores[q * count + row], q < 256 (rows of padding queries are zero).  Used by the IVF build
  * (row -> nearest centroid) and by tests that check the MFMA operand layouts in isolation.
+ * Cosine indexes only: ENOTSUP on an ip or l2 index, nothing enqueued.
  */
 int codd_knn_approx_scores(codd_knn_index* index, const float* dev_queries, int B,
                                  float* dev_scores, void* stream);
