@@ -1646,7 +1646,7 @@ struct codd_knn_index : WorkBufs {
     int scan_blocks_per_cu = 4;
     int64_t capacity = 0;  // row slots allocated
     int64_t count = 0;     // highest written slot + 1
-    DevBuf<unsigned char> rows;  // [capacity][dpad] storage dtype, as bytes
+    DevBuf<unsigned char> rows;  // [capacity][dpad] storage dtype, as bytes; zero at and past `count` (a never-written slot below the count is a zero row)
     // bf16 fragment-order copy, whole 256-row tiles.  Derived data like the int8 shadow: built lazily from the stored rows by the
     // first search that needs it (batches above 256 queries, an index with the int8 filter off or cooling down, the IVF
     // build), brought up to date incrementally over the rows written since
@@ -1851,6 +1851,18 @@ void rows_written(codd_knn_index* ix, int64_t lo, int64_t hi) {
         if (lo < ix->dirty16_lo) ix->dirty16_lo = lo;
         if (hi > ix->dirty16_hi) ix->dirty16_hi = hi;
     }
+}
+
+// the end of every write of row slots inside [lo, hi): raises the count, then rows_written.  A write that starts above the count
+// brings the slots in between into existence unwritten.  They are zero rows: the row store holds zeros at and
+// past the count (grow_rows, codd_knn_compact), but both shadows still hold there whatever they held — int8 block meta data that
+// reads NaN since the allocation, rows from before a compaction — so they are dirty from the old count on.
+void slots_written(codd_knn_index* ix, int64_t lo, int64_t hi) {
+    if (hi > ix->count) {
+        if (lo > ix->count) lo = ix->count;
+        ix->count = hi;
+    }
+    rows_written(ix, lo, hi);
 }
 
 #define HIP_TRY(expr)                                                                        \
@@ -3150,8 +3162,7 @@ int codd_knn_upsert_host(codd_knn_index* ix, const int64_t* host_slots, const fl
     ix->rows_event_set = false;  // (everything is complete on the device)
     ix->reader_event_set = false;
     if (rc == 0) {
-        if (max_slot + 1 > ix->count) ix->count = max_slot + 1;
-        rows_written(ix, min_slot, max_slot + 1);
+        slots_written(ix, min_slot, max_slot + 1);
         if (!normalize) ix->all_normalized = false;
     }
     return rc;
@@ -3189,8 +3200,7 @@ int codd_knn_upsert_device(codd_knn_index* ix, int64_t first_slot, const float* 
     HIP_TRY(hipEventRecord(ix->rows_ready, wst));
     ix->rows_stream = wst;
     ix->rows_event_set = true;
-    if (first_slot + n > ix->count) ix->count = first_slot + n;
-    rows_written(ix, first_slot, first_slot + n);
+    slots_written(ix, first_slot, first_slot + n);
     if (!normalize) ix->all_normalized = false;
     return CODD_KNN_OK;
 }
@@ -3208,8 +3218,7 @@ int codd_knn_load_rows(codd_knn_index* ix, int64_t first_slot, const void* host_
     HIP_TRY(hipMemcpy(ix->rows + (size_t)first_slot * row_bytes, host_rows, (size_t)n * row_bytes, hipMemcpyHostToDevice));
     if (!metric_is_cosine(ix)) {   // (ip, l2: rows of any norm, and no filter to keep on)
         ix->rows_event_set = false;
-        if (first_slot + n > ix->count) ix->count = first_slot + n;
-        rows_written(ix, first_slot, first_slot + n);
+        slots_written(ix, first_slot, first_slot + n);
         return CODD_KNN_OK;
     }
     // the loaded rows are taken as they are, so their norms are checked: the filters stay on only for unit rows
@@ -3230,8 +3239,7 @@ int codd_knn_load_rows(codd_knn_index* ix, int64_t first_slot, const void* host_
     const float tol = ix->dtype == DT_F32 ? 1e-4f : (ix->dtype == DT_BF16 ? 4e-3f : 6e-4f);
     if (!(worst <= tol)) ix->all_normalized = false;
     ix->rows_event_set = false;
-    if (first_slot + n > ix->count) ix->count = first_slot + n;
-    rows_written(ix, first_slot, first_slot + n);
+    slots_written(ix, first_slot, first_slot + n);
     return CODD_KNN_OK;
 }
 
@@ -4141,6 +4149,8 @@ int codd_knn_compact(codd_knn_index* ix, int64_t* new_count) {
         dbase += moved;
     }
     // the slots past the live rows are new slots again: no label, no tombstone; the int8 shadow's scales there read "no such row"
+    // ... and zero rows: a later write past the new count that does not regrow the store brings them back below the count
+    if (e == hipSuccess) e = hipMemsetAsync(ix->rows + (size_t)live * row_bytes, 0, (size_t)(n - live) * row_bytes, nullptr);
     if (e == hipSuccess && ix->scope_of) e = hipMemsetAsync(ix->scope_of + live, 0, (size_t)(n - live) * sizeof(uint32_t), nullptr);
     if (e == hipSuccess) e = hipMemsetAsync(ix->dead_bits, 0, (size_t)ix->dead_bits.bytes(), nullptr);
     if (e == hipSuccess && ix->rscale) {

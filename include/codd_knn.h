@@ -51,6 +51,10 @@
  *     search, delete, compact, load and read entry point keeps its contract word for word under these
  *     metrics, except the IVF ones and codd_knn_approx_scores, which return ENOTSUP (spherical k-means
  *     and the bf16 assignment are cosine-specific).
+ *   - the count is the highest written slot + 1, and a write may start above it.  A row slot below the count that was never
+ *     written (since creation, or since the last codd_knn_compact vacated it) holds the zero vector: it is live, has scope 0,
+ *     scores 0 (distance 1) under cosine and ip and lies at distance sum q_i^2 under l2 on every search path, reads back as
+ *     zeros from codd_knn_read_rows, and can be deleted.
  *   - every entry point with a `row_base` (codd_knn_search_keys, _search_scoped, _search_masked,
  *     _search_masked_dev, _ivf_search, _ivf_search_masked, _ivf_search_masked_dev) writes global rows
  *     row_base + row, which must fit the low word of a packed key: the highest global row is

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from oracle import knn_oracle as o
+from tests._int8_reference import quantise_like_the_kernels
 
 pytestmark = pytest.mark.gpu
 
@@ -29,25 +30,6 @@ def build8(Index, raw, dtype="f32"):
     ix.set_option("shadow8_max_batch", 32)
     ix.set_option("small_batch_max", 0)   # (these tests are about the filter chain; the single-launch kernel has tests/test_gpu_small_batch.py)
     return ix
-
-
-def quantise_like_the_kernels(x, is_query):
-    """fp32 arithmetic of shadow8_from_rows_kernel / prep_queries8_kernel.  Stored rows share ONE scale per 32-row block (the
-    block's largest magnitude / 127); a query has its own."""
-    x = x.astype(np.float32)
-    vmax = np.abs(x).max(axis=1).astype(np.float32)
-    if not is_query:
-        pad = (-len(vmax)) % 32
-        vmax = np.repeat(np.concatenate([vmax, np.zeros(pad, np.float32)]).reshape(-1, 32).max(axis=1), 32)[: x.shape[0]]
-    safe = np.where(vmax > 0, vmax, np.float32(1.0)).astype(np.float32)
-    if is_query:
-        scale = np.where(vmax > 0, vmax / np.float32(127.0), np.float32(0.0)).astype(np.float32)
-        inv = np.where(vmax > 0, np.float32(127.0) / safe, np.float32(0.0)).astype(np.float32)
-    else:
-        scale = np.where(vmax > 0, vmax / np.float32(127.0), np.float32(1.0)).astype(np.float32)
-        inv = (np.float32(1.0) / scale).astype(np.float32)
-    q8 = np.clip(np.rint((x * inv[:, None]).astype(np.float32)), -127, 127).astype(np.int32)
-    return q8, scale
 
 
 @pytest.mark.parametrize("n,d,B,dtype", [(1000, 768, 20, "f32"), (300, 100, 32, "f32"), (700, 384, 7, "bf16"), (513, 1024, 1, "f16")])
