@@ -476,6 +476,24 @@ __global__ __launch_bounds__(kWideScanWaves * kWave) void scan_topk_wide_l2(cons
                                                                         reinterpret_cast<u64*>(smem_raw), dead);
 }
 
+// The list-driven squared-distance scan: the exact-scan fallback of an l2 index's filter pass, for the queries
+// whose candidate lists were truncated.  scan_topk_body under kMetricL2 walking the device-side queue four queries at a time
+// (the role is rare), its last block merging; rows of 1 .. 4 chunks per lane.  A kernel of its own: the dense scans above stay
+// the instantiations they were.
+template <int DT, int NITER, int SLOTS>
+__global__ __launch_bounds__(256) void sqd_listed_scan_kernel(const void* __restrict__ rows_, int64_t n, int dpad, const float* __restrict__ qn, int k,
+                                                              uint32_t row_base, u64* __restrict__ partial, int64_t partial_stride_q,
+                                                              const unsigned* __restrict__ qlist, const unsigned* __restrict__ qcount_ptr,
+                                                              unsigned* __restrict__ merge_done, u64* __restrict__ merged_keys,
+                                                              float* __restrict__ merged_dist, int64_t* __restrict__ merged_rows,
+                                                              unsigned long long* __restrict__ count_total, const uint32_t* __restrict__ dead) {
+    static_assert(NITER != kWideRows, "the squared-distance filter leg serves rows of 1 .. 4 chunks per lane");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    scan_topk_body<DT, 4, NITER, SLOTS, 4, kMetricL2>(rows_, n, dpad, qn, (int)*qcount_ptr, k, row_base, partial, partial_stride_q, qlist, true, merge_done,
+                                                      merged_keys, merged_dist, merged_rows, count_total, (int)blockIdx.x, (int)gridDim.x,
+                                                      reinterpret_cast<u64*>(smem_raw), dead);
+}
+
 // ---------------------------------------------------------------------------------------------
 // finalize_fb_kernel: finalize and the exact-scan fallback of a filter pass in ONE launch (round 3: the fallback used to be a
 // launch of its own behind finalize — normally empty, still 4 us + a dependent-launch gap of ~10 us on every step).
@@ -810,6 +828,132 @@ __global__ __launch_bounds__(256) void prep_queries8_kernel(const float* __restr
         qmeta[512 + q] = slack_scale * (eq * 1.01f + 2e-6f);
         qmeta[768 + q] = slack_scale * (eq + 1.001f);
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// The int8 filter leg of an ip or l2 index ("space_filter"): rows and queries of ANY norm, so the two constants
+// above that stand for |c| and |q| of unit vectors become measured quantities.
+// row_sqnorm_kernel<DT>: one wave per stored row of [first, first + m): rnorm2[row] = the canonical sum of squares of the row AS
+// STORED (DESIGN.md §3's chain over chunks of RowTraits<DT>::E elements, the butterfly, + 0.0f), and *rmax_bits = max(*rmax_bits,
+// R(row)) with R(row) = sqrt(rnorm2) * 1.0001 + 1e-7 >= |c|_2: the chain and the root are off by < 2e-5 relative, squares that
+// underflow by < sqrt(dpad) 2^-63 absolute.  The bits of a non-negative float order like the float; a sum that overflowed (or a
+// row that is not a number) leaves +inf there, and every query of the index is then answered by the exact re-score of all rows.
+// ---------------------------------------------------------------------------------------------------------------
+template <int DT>
+__global__ __launch_bounds__(256) void row_sqnorm_kernel(const void* __restrict__ rows_, int64_t first, int64_t m, int dpad, float* __restrict__ rnorm2,
+                                                         unsigned* __restrict__ rmax_bits) {
+    typedef RowTraits<DT> RT;
+    constexpr int E = RT::E;
+    const int lane = lane_id();
+    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= m) return;
+    const int64_t row = first + r;
+    const int nchunks = dpad / E;
+    const uint4* p = reinterpret_cast<const uint4*>(rows_) + row * (int64_t)nchunks;
+    float a = 0.0f;
+    for (int j = lane; j < nchunks; j += kWave) {
+        float w[E];
+        RT::widen(p[j], w);
+#pragma unroll
+        for (int e = 0; e < E; ++e) a = __builtin_fmaf(w[e], w[e], a);
+    }
+    const float n2 = butterfly_sum(a);
+    if (lane == 0) {
+        rnorm2[row] = n2;
+        float R = __builtin_sqrtf(n2) * 1.0001f + 1e-7f;
+        if (!(R < INFINITY)) R = INFINITY;
+        atomicMax(rmax_bits, __float_as_uint(R));
+    }
+}
+
+// prep_queries8_raw_kernel: prep_queries8_kernel for an ip (l2 = 0) or l2 (l2 = 1) index.  qn = the query as raw_rows_kernel<f32>
+// cleans it (what the exact kernels consume); qfrag8 / qmeta[q]: the same vector quantised with its own scale s_q; qmeta[512 + q]
+// = n_q, its canonical sum of squares; qmeta[256 + q] = 2 eps(q) with, for every stored row c (DESIGN.md §21 derives both),
+//   e_q = |q - q~| measured, + 2^-23 Q for the fp32 rounding of the measurement, e_r likewise from the rows' measured *eps_r_bits,
+//   Q >= |q|, R = *rmax_bits >= |c|, m = dpad / 64 the length of a lane's chain, u = 2^-24:
+//   ip: eps = e_q (R + e_r) + Q e_r + (m + 9) u (Q + e_q)(R + e_r)               >= |acc s_blk s_q - score(q, c)|
+//   l2: eps = 2 (e_q (R + e_r) + Q e_r) + (2 m + 18) u (Q + R + e_q + e_r)^2     >= |fma(acc s_blk, 2 s_q, -rnorm2) - n_q - score(q, c)|
+// every term rounded upward; +inf when R or Q is not finite or the product term leaves [2^-100, 2^100] (the threshold is then
+// -inf, every row a hit, and the exact re-score or the overflow fallback answers the query).
+__global__ __launch_bounds__(256) void prep_queries8_raw_kernel(const float* __restrict__ in, int B, int d, int dpad, int dpad8, float* __restrict__ qn,
+                                                                uint32_t* __restrict__ qfrag8, float* __restrict__ qmeta,
+                                                                const unsigned* __restrict__ eps_r_bits, const unsigned* __restrict__ rmax_bits,
+                                                                unsigned* __restrict__ ctl, int ctl_words, int l2) {
+    const int lane = lane_id();
+    const int q = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+    for (int i = (int)blockIdx.x * 256 + (int)threadIdx.x; i < ctl_words; i += (int)gridDim.x * 256) ctl[i] = 0u;
+    const int nch = dpad >> 2, nch8 = dpad8 >> 2;
+    if (q >= B) {
+        for (int j = lane; j < nch8; j += kWave) qfrag8[codd::qfrag_piece_index(q, j >> 2) * 4 + (j & 3)] = 0u;
+        if (lane == 0) { qmeta[q] = 0.0f; qmeta[256 + q] = 0.0f; qmeta[512 + q] = 0.0f; qmeta[768 + q] = 0.0f; }
+        return;
+    }
+    const float* x = in + (int64_t)q * d;
+    bool bad = false, any = false;
+    for (int i = lane; i < d; i += kWave) {
+        const float v = x[i];
+        bad = bad || !(fabsf(v) < INFINITY);   // (NaN compares false too)
+        any = any || v != 0.0f;
+    }
+    const bool zero_row = __ballot(bad) != 0ull || __ballot(any) == 0ull;
+    float vmax = 0.0f, a2 = 0.0f;
+    for (int j = lane; j < nch; j += kWave) {
+        float v[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int i = j * 4 + e;
+            v[e] = (i < d && !zero_row) ? x[i] : 0.0f;
+            vmax = fmaxf(vmax, fabsf(v[e]));
+            a2 = __builtin_fmaf(v[e], v[e], a2);
+        }
+        reinterpret_cast<float4*>(qn)[(int64_t)q * nch + j] = make_float4(v[0], v[1], v[2], v[3]);
+    }
+    vmax = butterfly_max(vmax);
+    const float nq2 = butterfly_sum(a2);
+    const float scale = vmax > 0.0f ? vmax / 127.0f : 0.0f, inv_scale = vmax > 0.0f ? 127.0f / vmax : 0.0f;
+    float err2 = 0.0f;
+    for (int j = lane; j < nch8; j += kWave) {
+        float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (j < nch) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int i = j * 4 + e;
+                v[e] = (i < d && !zero_row) ? x[i] : 0.0f;
+            }
+        }
+        qfrag8[codd::qfrag_piece_index(q, j >> 2) * 4 + (j & 3)] = quantize4(v, inv_scale, scale, err2);
+    }
+    err2 = butterfly_sum(err2);
+    if (lane == 0) {
+        constexpr float up = 1.0001f, u = 5.9604645e-8f, u2 = 1.1920929e-7f;   // 2^-24, 2^-23
+        const float m = (float)(dpad >> 6);
+        const float R = __uint_as_float(*rmax_bits);
+        const float Q = __builtin_sqrtf(nq2) * up + 1e-7f;
+        const float eq = __builtin_sqrtf(err2) * up + u2 * Q + 1e-7f;
+        const float er = __uint_as_float(*eps_r_bits) * up + u2 * R;
+        const float a = (Q + eq) * up, b = (R + er) * up;
+        const float quant = (eq * b + Q * er * up) * up;
+        float eps, range;
+        if (l2) {
+            const float s = (a + b) * up;
+            range = s * s;
+            eps = (2.0f * quant + (2.0f * m + 18.0f) * u * 1.001f * range) * up + 1e-30f;
+        } else {
+            range = a * b;
+            eps = (quant + (m + 9.0f) * u * 1.001f * range) * up + 1e-30f;
+        }
+        if (!(range >= kNormBandLo && range <= kNormBandHi) || !(eps < INFINITY)) eps = INFINITY;
+        qmeta[q] = scale;
+        qmeta[256 + q] = 2.0f * eps;
+        qmeta[512 + q] = nq2;
+        qmeta[768 + q] = Q;
+    }
+}
+
+// codd_knn_filter_slack: out[q] = eps(q) of the device-wide bound, from the 2 eps(q) a preparation kernel left at two_eps_q[q]
+__global__ __launch_bounds__(256) void filter_slack_kernel(const float* __restrict__ two_eps_q, int B, float* __restrict__ out) {
+    const int q = (int)threadIdx.x;
+    if (q < B) out[q] = 0.5f * two_eps_q[q];
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1709,6 +1853,12 @@ struct codd_knn_index : WorkBufs {
     DevBuf<float> rscale;         // [shadow8_rows]
     DevBuf<float2> bmeta;         // [shadow8_rows / 32]: per 32-row block {scale, largest error norm |c - c~| of its rows}; NaN scale: no row of the block exists
     DevBuf<unsigned> eps_r_bits;     // device scalar: max row error norm (float bits)
+    // the int8 filter leg of an ip or l2 index ("space_filter" option, off by default).  Derived with the int8 shadow,
+    // over the same dirty rows, and only for such an index: rnorm2[row] = the row's canonical sum of squares; *rmax_bits = the float
+    // bits of R >= |c| for every row ever stored (it only grows: delete and compact never lower it)
+    int space_filter = 0;
+    DevBuf<float> rnorm2;            // [shadow8_rows]
+    DevBuf<unsigned> rmax_bits;
     int64_t shadow8_epoch = -1;
     int64_t dirty_lo = 0, dirty_hi = 0;  // rows written since the int8 shadow was last brought up to date: [lo, hi)
     hipStream_t shadow8_stream = nullptr;  // the stream the last rebuild ran on, and its completion
@@ -2457,6 +2607,11 @@ int ensure_shadow8(codd_knn_index* ix, hipStream_t st) {
         HIP_TRY(ix->eps_r_bits.reset(2));
         HIP_TRY(hipMemsetAsync(ix->eps_r_bits, 0, 2 * sizeof(unsigned), st));
     }
+    const bool norms = !metric_is_cosine(ix);  // (an ip or l2 index comes here through its filter leg only: the norms follow the shadow)
+    if (norms && !ix->rmax_bits) {
+        HIP_TRY(ix->rmax_bits.reset(1));
+        HIP_TRY(hipMemsetAsync(ix->rmax_bits, 0, sizeof(unsigned), st));
+    }
     if (need > ix->shadow8_rows) {
         // (every stream that may still read the old allocation has to be done with it)
         int rcw;
@@ -2474,6 +2629,10 @@ int ensure_shadow8(codd_knn_index* ix, hipStream_t st) {
         HIP_TRY(s8.reset(rows_al * dpad8 / (int64_t)sizeof(uint4)));
         HIP_TRY(rs.reset(rows_al));
         HIP_TRY(bm.reset(rows_al / 32 + 64));  // (+64: a wave's DMA reads 32 blocks from a tile's first one)
+        if (norms) {
+            (void)ix->rnorm2.reset();
+            HIP_TRY(ix->rnorm2.reset(rows_al));
+        }
         ix->shadow8 = std::move(s8);
         ix->rscale = std::move(rs);
         ix->bmeta = std::move(bm);
@@ -2501,6 +2660,14 @@ int ensure_shadow8(codd_knn_index* ix, hipStream_t st) {
         // the device-wide maximum of the block error norms, over the rows stored now (not a running maximum)
         hipLaunchKernelGGL(eps_max_kernel, dim3(1), dim3(1024), 0, st, ix->bmeta, (n + 31) / 32, ix->eps_r_bits, ix->shadow8_max_eps);
         HIP_TRY(hipGetLastError());
+        if (norms) {  // the same rows' sums of squares, and the bound on every row's norm
+            const int64_t mn = first + m > n ? n - first : m;
+            const int rcn = with_dtype(ix->dtype, [&](auto dt) {
+                return launch_kernel<row_sqnorm_kernel<dt>>(dim3((unsigned)((mn + 3) / 4)), block, 0, st, ix->rows, first, mn, ix->dpad, ix->rnorm2, ix->rmax_bits);
+            });
+            if (rcn != 0) return rcn;
+            HIP_TRY(hipGetLastError());
+        }
     }
     {
         // i8_tile_kernel reads whole tiles of scales: rows past the count carry NaN (`acc * NaN >= thr` is false for every
@@ -2536,20 +2703,25 @@ struct FilterProgram {
     Family family = GEMM;
     int nbq = 8;  // 32-query blocks the GEMM multiplies
     int ts = 0, res = 0, el = 0;
+    bool sqd = false;  // sqd_filter_kernel<MODE, nbq>: the squared-distance epilogue of an l2 index
 };
 
 FilterProgram filter_program(const codd_knn_index* ix, int nq, int nsteps, bool use8) {
     FilterProgram p;
     p.nbq = nq <= 32 ? 1 : (nq <= 64 ? 2 : (nq <= 128 ? 4 : 8));
     p.el = use8 ? 1 : 0;
-    const bool resident = use8 && nsteps <= 4 && ix->resident_q;
+    // an ip or l2 index: the GEMM family on int8 operands whatever "i8v2" / "f16_tile" say — the tile programs evaluate
+    // the per-block, unit-norm form of the bound — and for l2 its staged form with the squared-distance epilogue
+    const bool space = !metric_is_cosine(ix);
+    p.sqd = space && ix->metric == CODD_KNN_METRIC_L2;
+    const bool resident = use8 && nsteps <= 4 && ix->resident_q && !p.sqd;
     // 65..128 queries only: with <= 64 the kernel is a byte stream (nothing to gain); with 8 query blocks the six-step body
     // needs more than the 256 registers of a wave (hipcc spills, no gain measured)
-    const bool partial6 = use8 && nsteps == 6 && nq > 64 && nq <= 128 && ix->resident_q;
+    const bool partial6 = use8 && nsteps == 6 && nq > 64 && nq <= 128 && ix->resident_q && !p.sqd;
     // full query blocks: the second-generation int8 kernel (filter_i8.h); rows whose query block fits the LDS keep the resident one
-    const bool tile_v2 = use8 && (p.nbq == 8 || (p.nbq == 4 && ix->i8v2_half)) && ((ix->i8v2 == 1 && !resident && nsteps >= 3) || (ix->i8v2 == 2 && nsteps >= 3));
+    const bool tile_v2 = !space && use8 && (p.nbq == 8 || (p.nbq == 4 && ix->i8v2_half)) && ((ix->i8v2 == 1 && !resident && nsteps >= 3) || (ix->i8v2 == 2 && nsteps >= 3));
     // the 2-byte filter (dense clusters the int8 slack cannot separate, the int8 filter switched off): the same tile program on fp16 operands
-    const bool tile_f16 = CODD_SHADOW_F16 && CODD_MFMA16 && !use8 && p.nbq == 8 && nsteps % 6 == 0 && ix->f16_tile;
+    const bool tile_f16 = !space && CODD_SHADOW_F16 && CODD_MFMA16 && !use8 && p.nbq == 8 && nsteps % 6 == 0 && ix->f16_tile;
     if (tile_f16) {
         p.family = FilterProgram::TILE_F16;
         // rows of 768 elements are 12 K-steps of 64, rows of 384 are 6: the static forms of the tile program ("i8_pair" = 2); 18, 24, ...: run-time cursors
@@ -2593,6 +2765,8 @@ struct FilterArgs {
     const float* qscale;
     const float2* bmeta;  // i8_tile_kernel only
     float eb_scale;
+    const float* rnorm2 = nullptr;  // sqd_filter_kernel only: the rows' and the queries' sums of squares
+    const float* qn2 = nullptr;
 };
 
 // one launch of program `p` in pass MODE (MODE_SAMPLE or MODE_FILTER)
@@ -2611,6 +2785,13 @@ int launch_filter_program(const FilterProgram& p, dim3 grid, hipStream_t st, con
                                                                       a.ntiles_run, a.tile_stride, a.thr, a.bucket_key, a.hits, a.hit_cnt, a.cap_q,
                                                                       a.flags, a.rscale, a.qscale, a.bmeta, a.eb_scale);
     };
+    if (p.sqd) {
+        return with_nbq(p.nbq, [&](auto nbq) {
+            return launch_kernel<sqd_filter_kernel<MODE, nbq>>(grid, block, filter_lds_bytes(MODE), st, a.shadow, a.qfrag, a.n, a.nsteps, a.ntiles_run,
+                                                               a.tile_stride, a.thr, a.bucket_key, a.hits, a.hit_cnt, a.cap_q, a.flags, (float*)nullptr, a.rscale,
+                                                               a.qscale, a.rnorm2, a.qn2);
+        });
+    }
     if (p.family == FilterProgram::TILE) {
         return with_int<4, 8>(p.nbq, "bad query block count%s", [&](auto nbq) {
             const IntC<2 * decltype(nbq)::value> nqb;
@@ -2650,10 +2831,28 @@ int fallback_geometry(codd_knn_index* ix, int k, int64_t* blocks, int64_t* strid
 // the queue (an empty queue costs one empty launch), its last block merges the per-block partials and writes each answer into
 // its query's slot.  No host round trip: the whole search stays asynchronous on `st`.
 int listed_fallback(codd_knn_index* ix, const float* qn, int k, uint32_t row_base, u64* keys_out, float* dist_out, int64_t* rows_out,
-                    hipStream_t st, const uint32_t* deny) {
+                    hipStream_t st, const uint32_t* deny, int metric = kMetricDot) {
     int64_t blocks, stride_q;
     int rc;
     if ((rc = fallback_geometry(ix, k, &blocks, &stride_q)) != 0) return rc;
+    if (metric == kMetricL2) {  // the list-driven squared-distance scan (the dense l2 scans take no query list)
+        FilterCtl* c = ix->ctl;
+        {
+            EvScope ev(ix, EV_SCAN, st);
+            rc = with_row_form(ix, k, "row too wide for the listed squared-distance scan%s", [&](auto dt, auto ni, auto sl) {
+                if constexpr (decltype(ni)::value == kWideRows) {
+                    return fail(CODD_KNN_ENOTSUP, "row too wide for the listed squared-distance scan%s");
+                } else {
+                    return launch_kernel<sqd_listed_scan_kernel<dt, ni, sl>>(dim3((unsigned)blocks), dim3(256), (size_t)4 * 4 * decltype(sl)::value * kWave * sizeof(u64), st,
+                                                                            ix->rows, ix->count, ix->dpad, qn, k, row_base, ix->fb_partial, stride_q, c->fb_list,
+                                                                            &c->fb_count, &c->fb_done, keys_out, dist_out, rows_out, &ix->dstats[2], deny);
+                }
+            });
+        }
+        if (rc != 0) return rc;
+        HIP_TRY(hipGetLastError());
+        return CODD_KNN_OK;
+    }
     ScanArgs a{ix->rows, ix->count, ix->dpad, qn, 0, k, row_base, ix->fb_partial, stride_q, ix->ctl->fb_list, &ix->ctl->fb_count};
     a.merge_done = &ix->ctl->fb_done;
     a.merged_keys = keys_out;
@@ -2681,6 +2880,7 @@ int filter_pass(codd_knn_index* ix, const float* qn, int nq, int k, uint32_t row
     const float* slack_q = use8 ? ix->qmeta + 256 : nullptr;  // int8: 2*eps per query, written by prep_queries8_kernel
     const float* rscale = use8 ? ix->rscale : nullptr;
     const float* qscale = use8 ? ix->qmeta : nullptr;
+    const bool cosine = metric_is_cosine(ix);
     if (use8) ix->stat_shadow8_passes++;
     const int64_t ntiles = (n + kTileRows - 1) / kTileRows;
     const int slots = k <= 64 ? 1 : 2;
@@ -2703,12 +2903,18 @@ int filter_pass(codd_knn_index* ix, const float* qn, int nq, int k, uint32_t row
     {
         EvScope ev(ix, EV_SAMPLE, st);
         const dim3 g((unsigned)(ts < ix->num_cus ? ts : ix->num_cus));
-        const FilterArgs sa{shadow, qfrag, n, nsteps, ts, stride, nullptr, ix->bucket_max, nullptr, nullptr, 0, nullptr, rscale, qscale, nullptr, 1.0f};
+        FilterArgs sa{shadow, qfrag, n, nsteps, ts, stride, nullptr, ix->bucket_max, nullptr, nullptr, 0, nullptr, rscale, qscale, nullptr, 1.0f};
+        if (prog.sqd) { sa.rnorm2 = ix->rnorm2; sa.qn2 = ix->qmeta + 512; }
         if ((rc = launch_filter_program<MODE_SAMPLE>(prog, g, st, sa)) != 0) return rc;
     }
     HIP_TRY(hipGetLastError());
     // thresholds anchored on the exact scores of the k best sampled rows (anchor_thr_kernel)
     rc = with_row_form(ix, k, "row too wide for the threshold kernel%s", [&](auto dt, auto ni, auto sl) {
+        if constexpr (decltype(ni)::value != kWideRows) {
+            if (prog.sqd)
+                return launch_kernel<sqd_thr_kernel<dt, ni, sl>>(dim3(kTileQ), dim3(kAnchorWaves * kWave), 0, st, ix->bucket_max, ts, nq, k, ix->rows, ix->dpad,
+                                                                        qn, slack_q, ix->thr, deny);
+        }
         return launch_kernel<anchor_thr_kernel<dt, ni, sl>>(dim3(kTileQ), dim3(kAnchorWaves * kWave), 0, st, ix->bucket_max, ts, nq, k, ix->rows,
                                                             ix->dpad, qn, eps, slack_q, ix->thr, use8 ? ix->thr + kTileQ : nullptr, deny);
     });
@@ -2718,6 +2924,7 @@ int filter_pass(codd_knn_index* ix, const float* qn, int nq, int k, uint32_t row
         EvScope ev(ix, EV_FILTER, st);
         const dim3 g((unsigned)(ntiles < ix->num_cus ? ntiles : ix->num_cus));
         FilterArgs fa{shadow, qfrag, n, nsteps, ntiles, 1, ix->thr, nullptr, ix->hits, ix->ctl->hit_cnt, ix->hit_cap_q, ix->ctl->flags, rscale, qscale, nullptr, 0.0f};
+        if (prog.sqd) { fa.rnorm2 = ix->rnorm2; fa.qn2 = ix->qmeta + 512; }
         if (prog.family == FilterProgram::TILE) {
             // the per-block bound (per_block & 1): thr0[q] and the blocks' error norms
             fa.thr = (ix->per_block & 1) ? ix->thr + kTileQ : ix->thr;
@@ -2739,11 +2946,11 @@ int filter_pass(codd_knn_index* ix, const float* qn, int nq, int k, uint32_t row
     const int nparts = use8 ? (nq <= 8 ? 16 : (nq <= 32 ? 8 : (nq <= 64 ? 4 : 1))) : 1;
     ix->stat_last_finalize_parts = nparts;
     if (nparts > 1) HIP_TRY(ix->partial.ensure((int64_t)nq * nparts * k));
-    const float2* bm = slack_q && (ix->per_block & 2) ? ix->bmeta : nullptr;  // (the int8 passes: slack per 32-row block)
+    const float2* bm = slack_q && (ix->per_block & 2) && cosine ? ix->bmeta : nullptr;  // (the int8 passes: slack per 32-row block; ip, l2: the device-wide bound)
     FilterCtl* c = ix->ctl;
     // one list slot per lane and one workgroup per query (the large batches): finalize and the exact-scan fallback share ONE
     // launch — the scan workgroups derive the queue from the hit counters and leave at once when it is empty
-    if (slots == 1 && nparts == 1 && ix->fuse_fallback && niter <= 4 && !(ix->dtype != DT_F32 && niter == 4)) {  // (2-byte rows above 1536 elements: the fused kernel spills; wide rows take the separate fallback launch)
+    if (slots == 1 && nparts == 1 && ix->fuse_fallback && niter <= 4 && !(ix->dtype != DT_F32 && niter == 4) && !prog.sqd) {  // (2-byte rows above 1536 elements: the fused kernel spills; wide rows take the separate fallback launch)
         int64_t blocks, stride_q;
         if ((rc = fallback_geometry(ix, k, &blocks, &stride_q)) != 0) return rc;
         EvScope ev(ix, EV_FINALIZE, st);
@@ -2767,6 +2974,12 @@ int filter_pass(codd_knn_index* ix, const float* qn, int nq, int k, uint32_t row
     {
         EvScope ev(ix, EV_FINALIZE, st);
         rc = with_row_form(ix, k, "row too wide for the finalize kernel%s", [&](auto dt, auto ni, auto sl) {
+            if constexpr (decltype(ni)::value != kWideRows) {
+                if (prog.sqd)
+                    return launch_kernel<sqd_fin_kernel<dt, ni, sl>>(dim3(nq, nparts), dim3(kFinThreads), 0, st, ix->rows, ix->dpad, qn, ix->hits, c->hit_cnt,
+                                                                          ix->hit_cap_q, c->flags, k, row_base, keys_out, &c->fb_count, c->fb_list, ix->dstats, slack_q,
+                                                                          ix->partial, dist_out, rows_out, deny);
+            }
             return launch_kernel<finalize_kernel<dt, ni, sl>>(dim3(nq, nparts), dim3(kFinThreads), 0, st, ix->rows, ix->dpad, qn, ix->hits, c->hit_cnt,
                                                               ix->hit_cap_q, c->flags, k, 2.0f * eps, row_base, keys_out, &c->fb_count, c->fb_list,
                                                               ix->dstats, slack_q, ix->partial, dist_out, rows_out, bm, deny);
@@ -2774,8 +2987,10 @@ int filter_pass(codd_knn_index* ix, const float* qn, int nq, int k, uint32_t row
     }
     if (rc != 0) return rc;
     HIP_TRY(hipGetLastError());
-    if (nparts > 1 && (rc = launch_merge(ix->partial, nq, (int64_t)nparts * k, (int64_t)nparts * k, k, keys_out, dist_out, rows_out, st)) != 0) return rc;
-    return listed_fallback(ix, qn, k, row_base, keys_out, dist_out, rows_out, st, deny);
+    const int km = prog.sqd ? kMetricL2 : kMetricDot;
+    if (nparts > 1 && (rc = launch_merge(ix->partial, nq, (int64_t)nparts * k, (int64_t)nparts * k, k, keys_out, dist_out, rows_out, st, nullptr, nullptr, nullptr, 0, 0, km)) != 0)
+        return rc;
+    return listed_fallback(ix, qn, k, row_base, keys_out, dist_out, rows_out, st, deny, km);
 }
 
 // ---- one launch for a single query (small_batch_kernel) + the (normally empty) list-driven fallback scan ----
@@ -2843,6 +3058,52 @@ bool filter_applies(const codd_knn_index* ix, int B, int k) {
     return ix->count * (int64_t)B >= ix->filter_min_rows_small;
 }
 
+// The int8 filter leg of an ip or l2 index: opt-in ("space_filter"), batches of filter_min_batch queries and more
+// over filter_min_rows rows and more whose sample holds 2k tiles, both "filter" and "shadow8" on, a build with the int8 MFMA.
+// l2 rows wider than 4 chunks per lane stay on the scan.  No usefulness heuristic: a loose bound is slow, never wrong.
+bool space_filter_applies(const codd_knn_index* ix, int B, int k) {
+    if (metric_is_cosine(ix) || !ix->space_filter || !CODD_MFMA16 || !ix->filter_enabled || !ix->shadow8_enabled) return false;
+    if (ix->metric == CODD_KNN_METRIC_L2 && niter_of(ix) > 4) return false;
+    const int64_t ntiles = (ix->count + kTileRows - 1) / kTileRows;
+    if (sample_tile_count(ix, ntiles, k) < 2 * (int64_t)k) return false;
+    return B >= ix->filter_min_batch && ix->count >= ix->filter_min_rows;
+}
+
+int launch_prep_raw(codd_knn_index* ix, const float* dev_queries, int nq, float* qn, hipStream_t st) {
+    hipLaunchKernelGGL(prep_queries8_raw_kernel, dim3(kTileQ / 4), dim3(256), 0, st, dev_queries, nq, ix->dim, ix->dpad, dpad8_of(ix), qn,
+                       reinterpret_cast<uint32_t*>(ix->qfrag8.get()), ix->qmeta, ix->eps_r_bits, ix->rmax_bits, reinterpret_cast<unsigned*>(ix->ctl.get()),
+                       (int)(sizeof(FilterCtl) / 4), ix->metric == CODD_KNN_METRIC_L2 ? 1 : 0);
+    HIP_TRY(hipGetLastError());
+    return CODD_KNN_OK;
+}
+
+// what an int8 pass of an ip or l2 index needs beside the rows: the workspace, the shadow with the rows' norms, the query buffers
+int ensure_space_filter(codd_knn_index* ix, hipStream_t st) {
+    int rc;
+    if ((rc = ensure_filter_workspace(ix)) != 0) return rc;
+    if ((rc = ensure_shadow8(ix, st)) != 0) return rc;
+    HIP_TRY(ix->qfrag8.ensure((int64_t)kTileQ * (dpad8_of(ix) / 16)));
+    if (!ix->qmeta) HIP_TRY(ix->qmeta.reset(1024));
+    return CODD_KNN_OK;
+}
+
+// ... and the search: ceil(B / 256) passes, each with its own preparation.  The survivor watch, the cooldown and the eps_r switch to
+// the 2-byte filter never engage: they are unit-norm quantities, and the 2-byte filter's analytic bound does not hold here.
+int space_filter_search(codd_knn_index* ix, const float* dev_queries, int B, int k, uint32_t row_base, u64* out_keys, float* out_dist, int64_t* out_rows,
+                        hipStream_t st, const uint32_t* deny) {
+    int rc;
+    if ((rc = ensure_space_filter(ix, st)) != 0) return rc;
+    for (int q0 = 0; q0 < B; q0 += kTileQ) {
+        const int nq = B - q0 < kTileQ ? B - q0 : kTileQ;
+        float* qn = ix->qn + (int64_t)q0 * ix->dpad;
+        if ((rc = launch_prep_raw(ix, dev_queries + (int64_t)q0 * ix->dim, nq, qn, st)) != 0) return rc;
+        if ((rc = filter_pass(ix, qn, nq, k, row_base, out_keys ? out_keys + (int64_t)q0 * k : nullptr, out_dist ? out_dist + (int64_t)q0 * k : nullptr,
+                              out_rows ? out_rows + (int64_t)q0 * k : nullptr, st, deny, true, true)) != 0)
+            return rc;
+    }
+    return CODD_KNN_OK;
+}
+
 // the index looks at its own device counters now and then (one look in flight; after its first 32 searches only every 8th:
 // the copy is a launch of its own on the searching stream)
 int after_filter_search(codd_knn_index* ix, int B, bool use8, hipStream_t st) {
@@ -2877,6 +3138,7 @@ int search_impl(codd_knn_index* ix, const float* dev_queries, int B, int k, uint
     HIP_TRY(ix->qn.ensure((int64_t)B * ix->dpad));
     HIP_TRY(ix->keys_tmp.ensure((int64_t)B * k));
     if ((rc = wait_rows(ix, st)) != 0) return rc;
+    if (n > 0 && space_filter_applies(ix, B, k)) return space_filter_search(ix, dev_queries, B, k, row_base, out_keys, out_dist, out_rows, st, deny);
     bool use_filter = n > 0 && filter_applies(ix, B, k);
     if (ix->eps_r_copied) {
         if (hipEventQuery(ix->eps_r_copied) == hipSuccess) {
@@ -3317,7 +3579,11 @@ int codd_knn_merge_shards_metric(int device, const uint64_t* dev_keys_in, int G,
 
 int codd_knn_approx_scores(codd_knn_index* ix, const float* dev_queries, int B, float* dev_scores, void* stream) {
     if (!ix || !dev_queries || !dev_scores || B < 1 || B > kTileQ) return fail(CODD_KNN_EINVAL, "bad debug arguments%s");
-    if (!metric_is_cosine(ix)) return fail(CODD_KNN_ENOTSUP, "approx_scores: the MFMA filters' scores exist for the cosine metric only%s");
+    // an ip or l2 index: the values of its int8 filter leg, where that leg exists
+    const bool space = !metric_is_cosine(ix);
+    const bool space_ok = space && ix->space_filter && ix->shadow8_enabled && CODD_MFMA16 && B <= 32 && !(ix->metric == CODD_KNN_METRIC_L2 && niter_of(ix) > 4);
+    if (space && !space_ok)
+        return fail(CODD_KNN_ENOTSUP, "approx_scores: the MFMA filters' scores exist for the cosine metric only (ip, l2: with \"space_filter\" on, B <= 32)%s");
     if (ix->count < 1) return fail(CODD_KNN_EINVAL, "empty index%s");
     DeviceGuard guard(ix->device);
     hipStream_t st = (hipStream_t)stream;
@@ -3325,6 +3591,24 @@ int codd_knn_approx_scores(codd_knn_index* ix, const float* dev_queries, int B, 
     int rc;
     if ((rc = wait_rows(ix, st)) != 0) return rc;
     HIP_TRY(ix->qn.ensure((int64_t)B * ix->dpad));
+    if (space) {
+        if ((rc = ensure_space_filter(ix, st)) != 0) return rc;
+        if ((rc = launch_prep_raw(ix, dev_queries, B, ix->qn, st)) != 0) return rc;
+        const int dpad8 = dpad8_of(ix);
+        const int64_t ntiles8 = (ix->count + kTileRows - 1) / kTileRows;
+        const dim3 g8((unsigned)(ntiles8 < ix->num_cus ? ntiles8 : ix->num_cus));
+        if (ix->metric == CODD_KNN_METRIC_L2)
+            rc = launch_kernel<sqd_filter_kernel<MODE_DUMP, 1>>(g8, dim3(kFilterThreads), filter_lds_bytes(MODE_DUMP), st, ix->shadow8, ix->qfrag8, ix->count, dpad8 / 128,
+                                                                ntiles8, (int64_t)1, nullptr, nullptr, nullptr, nullptr, 0, nullptr, dev_scores, ix->rscale, ix->qmeta,
+                                                                ix->rnorm2, ix->qmeta + 512);
+        else
+            rc = launch_kernel<gemm_filter_kernel<MODE_DUMP, 1, 1>>(g8, dim3(kFilterThreads), filter_lds_bytes(MODE_DUMP), st, ix->shadow8, ix->qfrag8, ix->count,
+                                                                    dpad8 / 128, ntiles8, (int64_t)1, nullptr, nullptr, nullptr, nullptr, 0, nullptr, dev_scores, ix->rscale,
+                                                                    ix->qmeta);
+        if (rc != 0) return rc;
+        HIP_TRY(hipGetLastError());
+        return CODD_KNN_OK;
+    }
     if ((rc = ensure_filter_workspace(ix)) != 0) return rc;
     if (ix->shadow8_enabled && B <= 32 && CODD_MFMA16) {
         // the int8 filter's scores (what a batch of <= 32 queries is filtered with when "shadow8" is on)
@@ -3354,6 +3638,31 @@ int codd_knn_approx_scores(codd_knn_index* ix, const float* dev_queries, int B, 
                                                               ix->qfrag, ix->count, ix->dpad / 64, ntiles, (int64_t)1, nullptr, nullptr, nullptr, nullptr, 0,
                                                               nullptr, dev_scores, nullptr, nullptr)) != 0)
         return rc;
+    HIP_TRY(hipGetLastError());
+    return CODD_KNN_OK;
+}
+
+int codd_knn_filter_slack(codd_knn_index* ix, const float* dev_queries, int B, float* dev_slack, void* stream) {
+    if (!ix || !dev_queries || !dev_slack || B < 1 || B > kTileQ) return fail(CODD_KNN_EINVAL, "bad debug arguments%s");
+    const bool space = !metric_is_cosine(ix);
+    if (!ix->shadow8_enabled || !CODD_MFMA16 || (space && !ix->space_filter) || (space && ix->metric == CODD_KNN_METRIC_L2 && niter_of(ix) > 4))
+        return fail(CODD_KNN_ENOTSUP, "filter_slack: this index has no int8 filter leg (\"shadow8\"; ip, l2: \"space_filter\")%s");
+    if (ix->count < 1) return fail(CODD_KNN_EINVAL, "empty index%s");
+    DeviceGuard guard(ix->device);
+    hipStream_t st = (hipStream_t)stream;
+    WorkScope work(ix, st);
+    int rc;
+    if ((rc = wait_rows(ix, st)) != 0) return rc;
+    HIP_TRY(ix->qn.ensure((int64_t)B * ix->dpad));
+    if ((rc = ensure_space_filter(ix, st)) != 0) return rc;
+    if (space) {
+        if ((rc = launch_prep_raw(ix, dev_queries, B, ix->qn, st)) != 0) return rc;
+    } else {
+        hipLaunchKernelGGL(prep_queries8_kernel, dim3(kTileQ / 4), dim3(256), 0, st, dev_queries, B, ix->dim, ix->dpad, dpad8_of(ix), ix->qn,
+                           reinterpret_cast<uint32_t*>(ix->qfrag8.get()), ix->qmeta, ix->eps_r_bits, reinterpret_cast<unsigned*>(ix->ctl.get()),
+                           (int)(sizeof(FilterCtl) / 4), ix->exp_slack_scale);
+    }
+    hipLaunchKernelGGL(filter_slack_kernel, dim3(1), dim3(kTileQ), 0, st, ix->qmeta + 256, B, dev_slack);
     HIP_TRY(hipGetLastError());
     return CODD_KNN_OK;
 }
@@ -4218,6 +4527,11 @@ int codd_knn_set_option(codd_knn_index* ix, const char* key, int64_t value) {
         ix->shadow8_enabled = (int)value;
         return CODD_KNN_OK;
     }
+    if (strcmp(key, "space_filter") == 0) {  // the int8 filter leg of an ip or l2 index; no effect on a cosine index
+        if (value != 0 && value != 1) return fail(CODD_KNN_EINVAL, "space_filter must be 0 or 1%s");
+        ix->space_filter = (int)value;
+        return CODD_KNN_OK;
+    }
     if (strcmp(key, "shadow8_max_batch") == 0) {
         if (value < 1 || value > 256) return fail(CODD_KNN_EINVAL, "shadow8_max_batch must be in [1,256]%s");
         ix->shadow8_max_batch = (int)value;
@@ -4417,6 +4731,7 @@ int codd_knn_get_stat(const codd_knn_index* ix, const char* key, int64_t* out) {
     else if (strcmp(key, "shadow16_alloc_failures") == 0) *out = ix->stat_shadow_nomem;
     else if (strcmp(key, "all_normalized") == 0) *out = ix->all_normalized ? 1 : 0;
     else if (strcmp(key, "metric") == 0) *out = ix->metric;
+    else if (strcmp(key, "space_filter") == 0) *out = ix->space_filter;
     else if (strcmp(key, "shadow8_passes") == 0) *out = ix->stat_shadow8_passes;
     else if (strcmp(key, "i8v2_passes") == 0) *out = ix->stat_i8v2_passes;
     else if (strcmp(key, "f16_tile_passes") == 0) *out = ix->stat_f16_tile_passes;

@@ -20,6 +20,9 @@ Spaces (`metadata={"hnsw:space": ...}`): "cosine" (the default h
 distance) and "ip" (1 - inner product), ChromaDB's definitions.  A non-cosine collection stores the
 embeddings as given (upsert with normalize=False) and `query` returns that space's distances;
 everything else — namespaces, `where`, `where_document`, delete, compact, persistence — is the same.
+`metadata={"hnsw:space": "l2", "codd:space_filter": 1}` switches on the engine's int8 filter leg for
+such a collection (large batches, same answers), when the engine is created and again
+after `reload`; an engine without `set_option` ignores it.
 
 Persistence (`KnnClient(path=...)`, the role of `SemanticStoreConfig.chromadb_path`, declared and
 never read in the reference, codd_lib/codd_lib/config/semantic_store_config.py:13): the indexer job
@@ -65,6 +68,9 @@ def _default_engine_factory(device: str, dtype: str) -> Callable[..., Any]:
 def _factory_spaces(engine_factory) -> tuple:
     """The spaces a factory builds engines for: its `spaces` attribute, cosine only without one."""
     return tuple(getattr(engine_factory, "spaces", (_DEFAULT_SPACE,)))
+
+
+_SPACE_FILTER_KEY = "codd:space_filter"
 
 
 def _space_of(metadata: Optional[dict]) -> str:
@@ -117,16 +123,27 @@ class Collection:
         """The collection's `hnsw:space`: "cosine" unless its metadata names another."""
         return _space_of(self.metadata)
 
-    def _make_engine(self, dim: int, space: str):
-        """A new engine of `space` from the factory; a cosine one by the plain call every factory answers."""
+    def _make_engine(self, dim: int, space: str, metadata: Optional[dict] = None):
+        """A new engine of `space` from the factory; a cosine one by the plain call every factory answers.  `metadata`: the
+        collection metadata whose engine options apply (default: this collection's)."""
         if space == _DEFAULT_SPACE:
-            return self._engine_factory(dim)
-        if space not in _factory_spaces(self._engine_factory):
-            raise ValueError(f"hnsw:space={space!r} is not on this path (supported: {_factory_spaces(self._engine_factory)})")
-        engine = self._engine_factory(dim, space=space)
-        if getattr(engine, "space", space) != space:
-            raise ValueError(f"the engine factory answered space {engine.space!r} for {space!r}")
+            engine = self._engine_factory(dim)
+        else:
+            if space not in _factory_spaces(self._engine_factory):
+                raise ValueError(f"hnsw:space={space!r} is not on this path (supported: {_factory_spaces(self._engine_factory)})")
+            engine = self._engine_factory(dim, space=space)
+            if getattr(engine, "space", space) != space:
+                raise ValueError(f"the engine factory answered space {engine.space!r} for {space!r}")
+        self._apply_engine_options(engine, self.metadata if metadata is None else metadata)
         return engine
+
+    @staticmethod
+    def _apply_engine_options(engine, metadata: Optional[dict]) -> None:
+        """Collection metadata that is an engine option: "codd:space_filter" (the int8 filter leg of an ip or l2
+        collection) -> engine.set_option("space_filter", value).  Skipped on an engine without set_option."""
+        value = (metadata or {}).get(_SPACE_FILTER_KEY)
+        if value is not None and callable(getattr(engine, "set_option", None)):
+            engine.set_option("space_filter", int(value))
 
     def _engine_for(self, dim: int):
         if self._engine is None:
@@ -818,7 +835,7 @@ class Collection:
             dtype = manifest["dtype"]
             rows = np.fromfile(os.path.join(gdir, "rows.bin"), dtype=np.float32 if dtype == "f32" else np.uint16)
             rows = rows.reshape(n, manifest["padded_dim"])
-            engine = self._make_engine(manifest["dim"], space)
+            engine = self._make_engine(manifest["dim"], space, manifest.get("metadata") or {})
             if getattr(engine, "dtype", dtype) != dtype:
                 raise ValueError(f"{gdir}: stored dtype {dtype} does not match the client's dtype {engine.dtype}")
             engine.load_rows(rows, 0)

@@ -405,8 +405,9 @@ class DeviceKnnIndex:
         return merge_keys(keys, k, self.device, space=self.space)
 
     def approx_scores(self, queries):
-        """Raw approximate scores of the MFMA filter: [256, count] fp32 tensor (diagnostics).  Cosine only."""
-        if self.space != "cosine":
+        """Raw approximate scores of the MFMA filter: [256, count] fp32 tensor (diagnostics).  Cosine, or an ip / l2 index
+        with its int8 filter leg on ("space_filter", at most 32 queries: the values that leg filters with)."""
+        if self.space != "cosine" and not self.stat("space_filter"):
             raise native.NativeLibraryError(f"approx_scores: the MFMA filters exist for the cosine space only, this index is {self.space!r}")
         torch = _torch()
         q = self._queries_tensor(queries)
@@ -414,6 +415,17 @@ class DeviceKnnIndex:
         native.check(
             self._lib.codd_knn_approx_scores(self._h, q.data_ptr(), q.shape[0], out.data_ptr(), self._stream()),
             "codd_knn_approx_scores",
+        )
+        return out
+
+    def filter_slack(self, queries):
+        """eps(q) of the next int8 filter pass for up to 256 queries: [B] fp32 tensor (diagnostics; codd_knn_filter_slack)."""
+        torch = _torch()
+        q = self._queries_tensor(queries)
+        out = torch.zeros((q.shape[0],), dtype=torch.float32, device=self.device)
+        native.check(
+            self._lib.codd_knn_filter_slack(self._h, q.data_ptr(), q.shape[0], out.data_ptr(), self._stream()),
+            "codd_knn_filter_slack",
         )
         return out
 

@@ -47,7 +47,9 @@
  *     Ties -> lower row, padding (row -1, distance +inf, key 0) and "a NaN score ranks as -inf" are as
  *     for cosine.  Inputs whose fp32 sums overflow are outside the contract.  Such an index takes no
  *     MFMA filter leg (both assume unit rows): every batch is answered by the exact scan, in groups of
- *     up to 8 queries per pass over the rows; the "all_normalized" stat reads 0 from the start.  Every
+ *     up to 8 queries per pass over the rows; the "all_normalized" stat reads 0 from the start.  (Opt-in,
+ *     option "space_filter": an int8 filter leg with measured norms in its bound; the
+ *     answers are the same bits.)  Every
  *     search, delete, compact, load and read entry point keeps its contract word for word under these
  *     metrics, except the IVF ones and codd_knn_approx_scores, which return ENOTSUP (spherical k-means
  *     and the bf16 assignment are cosine-specific).
@@ -198,10 +200,22 @@ int codd_knn_merge_shards_metric(int device, const uint64_t* dev_keys_in, int G,
  * The raw approximate (bf16 MFMA) scores of B <= 256 queries against every stored row:
  * dev_scores[q * count + row], q < 256 (rows of padding queries are zero).  Used by the IVF build
  * (row -> nearest centroid) and by tests that check the MFMA operand layouts in isolation.
- * Cosine indexes only: ENOTSUP on an ip or l2 index, nothing enqueued.
+ * Cosine indexes only: ENOTSUP on an ip or l2 index, nothing enqueued — unless that index has its int8 filter
+ * leg switched on (option "space_filter" = 1) and B <= 32: then dev_scores holds the values that
+ * leg filters with, the int8 approximation of <q, c> (ip) or of -|q - c|^2 (l2: fma(acc s_row, 2 s_q, -|c|^2) - |q|^2),
+ * each within codd_knn_filter_slack's eps(q) of the exact score of (q, row).
  */
 int codd_knn_approx_scores(codd_knn_index* index, const float* dev_queries, int B,
                                  float* dev_scores, void* stream);
+
+/*
+ * Debug: dev_slack[q] = eps(q), q < B <= 256: the slack between an approximate and an exact score that the next int8
+ * filter pass over this index would use for these queries (the device-wide bound: measured |q - q~|, the rows'
+ * measured quantisation error and, on an ip or l2 index, the measured norms).  +inf: the bound
+ * cannot be evaluated finitely and the pass re-scores every row.  Builds the int8 shadow if rows changed.
+ * ENOTSUP where the index has no int8 leg: "shadow8" off, or an ip / l2 index without "space_filter".
+ */
+int codd_knn_filter_slack(codd_knn_index* index, const float* dev_queries, int B, float* dev_slack, void* stream);
 
 /*
  * Coarse-IVF with exact scores (BASELINE config 5: the small-batch, HBM-bound regime on corpora
@@ -456,6 +470,10 @@ int codd_knn_embed_texts_host(codd_knn_embedder* e, const uint8_t* host_bytes, c
  *            "mask_route" (0: codd_knn_search_masked chooses its route by the rule of DESIGN.md §15; 1: always the list route; 2: always the
  *            dense route), "mask_list_pct" (100: the weight of the dense side in that rule's cost comparison, in percent — above 100 more
  *            searches take the list route, 0 none that the rule decides by cost),
+ *            "space_filter" (0; 1: an ip or l2 index filters batches of "filter_min_batch" queries and more over "filter_min_rows" rows
+ *            and more through the int8 MFMA filter with measured norms in its bound, then re-scores exactly — same ids and distance
+ *            bits as the scan; needs "filter" and "shadow8" on, l2 rows of at most 4 chunks per lane; no effect on a cosine index;
+ *            DESIGN.md §21),
  *            "debug_fail_shadow_alloc" (tests: the next N allocations of the 2-byte shadow fail);
  *            "profile" = N keeps N (start, stop) HIP-event pairs, one per heavy-kernel launch,
  *            recorded on the launch stream (0 = off; resets the log)
@@ -475,7 +493,7 @@ int codd_knn_embed_texts_host(codd_knn_embedder* e, const uint8_t* host_bytes, c
  *            "device_bytes", "num_cus", "workspaces" (stream workspaces in use), "shadow8_builds", "shadow8_passes", "i8v2_passes",
  *            "shadow16_builds" (the bf16 shadow is built lazily, by the first search that needs it), "all_normalized",
  *            "shadow8_cooldowns", "shadow8_eps_r_micro", "shadow8_wide_blocks" (32-row blocks whose quantisation error is above
- *            0.04: tolerated up to 1 % of the blocks), "shadow16_alloc_failures", "small_batch_passes", "f16_tile_passes", and per kernel K in {scan, filter, sample, finalize}:
+ *            0.04: tolerated up to 1 % of the blocks), "shadow16_alloc_failures", "small_batch_passes", "f16_tile_passes", "space_filter" (the option), and per kernel K in {scan, filter, sample, finalize}:
  *            "events:K", "time_ns:K" (sum of the recorded launches; syncs on the last event)
  */
 int codd_knn_set_option(codd_knn_index* index, const char* key, int64_t value);

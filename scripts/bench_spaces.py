@@ -12,6 +12,13 @@ spread: the same code on the same box in the same loop.  Per B in {1, 8, 256} th
                  legs alternating per repetition; one launch serves the whole batch, ceil(B / 8) passes over the rows
   scan_bytes     passes x rows x row bytes; fraction_of_hbm_peak = scan_bytes / scan_launch time / 8 TB/s
 One JSON line per (B, leg).  Measures on the GPU only.
+
+    python scripts/bench_spaces.py --space-filter [--batches 16,64,256,512] --out profiles/space_filter/bench_space_filter.jsonl
+
+The opt-in int8 filter leg of the two spaces against the scan it replaces: an l2 and an ip index, each searched
+with "space_filter" on and off in the same loop (the same index, the option flipped per call), and a cosine index with "i8v2" = 0 —
+the first-generation int8 GEMM, the like-for-like kernel.  Per (B, leg): wall time per batch (p50, min), and from the device
+counters the hits and the survivors per query of the timed searches.
 """
 import argparse
 import json
@@ -47,6 +54,7 @@ def main():
     p.add_argument("--batches", default="1,8,256")
     p.add_argument("--warmup", type=int, default=3)
     p.add_argument("--reps", type=int, default=20)
+    p.add_argument("--space-filter", action="store_true", help="measure the int8 filter leg of l2 and ip against the scan (DESIGN.md §21)")
     p.add_argument("--commit", default=None, help="git rev-parse HEAD of the tree (when the tree is a copy without .git)")
     p.add_argument("--out", default=os.path.join(ROOT, "profiles", "spaces", "bench_spaces.jsonl"))
     a = p.parse_args()
@@ -58,6 +66,9 @@ def main():
     dev = "cuda:0"
     commit = head_commit(a.commit)
     n = a.rows
+
+    if a.space_filter:
+        return space_filter_bench(a, torch, DeviceKnnIndex, dev, commit)
 
     indexes = {}
     for leg, space in LEGS:
@@ -111,6 +122,64 @@ def main():
                     "scan_launch_ms": scan_ms, "passes_over_the_rows": passes, "scan_ms_per_pass": scan_ms / passes,
                     "scan_group": ix.stat("last_scan_group"), "scan_bytes": scan_bytes,
                     "fraction_of_hbm_peak": scan_bytes / (scan_ms * 1e-3) / HBM_PEAK, "warmup": a.warmup, "reps": a.reps,
+                }
+                out.write(json.dumps(line) + "\n")
+                out.flush()
+                print(json.dumps(line))
+    for ix in indexes.values():
+        ix.close()
+
+
+def space_filter_bench(a, torch, DeviceKnnIndex, dev, commit):
+    n = a.rows
+    indexes = {}
+    for space in ("l2", "ip", "cosine"):
+        ix = DeviceKnnIndex(a.dim, a.dtype, dev, space=space)
+        ix.reserve(n)
+        for c0 in range(0, n, CHUNK):
+            g = torch.Generator(device=dev).manual_seed(1234 + c0 // CHUNK)
+            ix.upsert_device(c0, torch.randn((min(CHUNK, n - c0), a.dim), generator=g, device=dev), normalize=space == "cosine")
+        if space == "cosine":
+            ix.set_option("i8v2", 0)
+        indexes[space] = ix
+    torch.cuda.synchronize()
+    legs = [("l2_on", "l2", 1), ("l2_off", "l2", 0), ("ip_on", "ip", 1), ("ip_off", "ip", 0), ("cosine_i8", "cosine", None)]
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as out:
+        for B in [int(b) for b in a.batches.split(",")]:
+            q = torch.randn((B, a.dim), generator=torch.Generator(device=dev).manual_seed(4321), device=dev)
+
+            def call(space, on):
+                ix = indexes[space]
+                if on is not None:
+                    ix.set_option("space_filter", on)
+                ix.search_tensors(q, a.k)
+
+            for _ in range(a.warmup):
+                for _leg, space, on in legs:
+                    timed(lambda: call(space, on))
+            wall = {leg: [] for leg, _, _ in legs}
+            counts = {leg: [0, 0, 0] for leg, _, _ in legs}
+            keys = ("filter_hits", "filter_survivors", "filter_passes")
+            for _ in range(a.reps):                            # alternating, so that a noisy neighbour hits every leg alike
+                for leg, space, on in legs:
+                    before = [indexes[space].stat(key) for key in keys]
+                    wall[leg].append(timed(lambda: call(space, on)))
+                    counts[leg] = [c + indexes[space].stat(key) - b for c, key, b in zip(counts[leg], keys, before)]
+            for leg, space, on in legs:
+                hits, surv, passes = counts[leg]
+                line = {
+                    "commit": commit, "leg": leg, "space": space, "space_filter": on, "B": B, "k": a.k, "rows": n, "dim": a.dim, "dtype": a.dtype,
+                    "wall_ms_p50": statistics.median(wall[leg]), "wall_ms_min": min(wall[leg]), "filter_passes_per_search": passes / a.reps,
+                    "hits_per_query": hits / (a.reps * B), "survivors_per_query": surv / (a.reps * B), "warmup": a.warmup, "reps": a.reps,
                 }
                 out.write(json.dumps(line) + "\n")
                 out.flush()
