@@ -1237,6 +1237,70 @@ __global__ __launch_bounds__(256) void ivf_scan_kernel(const void* __restrict__ 
     write_keys(L, k, lane, dst);
 }
 
+// ivf_scan_sq: ivf_scan_kernel for an l2 index ("space_ivf"): the same block per (query, probe rank, slice), the same
+// loads and lists, the score is §20's canonical squared distance (score4 / wide_scores under kMetricL2: key score 0 - distance) of the
+// RAW prepared query.  A kernel of its own beside its twin, not a shared body: ivf_scan_kernel keeps its resource line that way.
+// (waves per SIMD: wide f32 rows with two list slots come out at 130 VGPRs, two above the four waves of the twin, unless hipcc is told
+// to aim for four — then 128, no spill; every other form is left at the default, one wave at least)
+template <int DT, int NITER, int SLOTS>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DT == DT_F32 && NITER == kWideRows && SLOTS == 2 ? 4 : 1)))
+void ivf_scan_sq(const void* __restrict__ rows_, const uint32_t* __restrict__ ids, const int64_t* __restrict__ offsets,
+                 const u64* __restrict__ probe_keys, int nprobe, int split, int dpad, const float* __restrict__ qn, int k, uint32_t row_base,
+                 u64* __restrict__ partial, const uint32_t* __restrict__ dead) {
+    typedef RowTraits<DT> RT;
+    constexpr int E = RT::E;
+    const int lane = lane_id();
+    const int wave = (int)(threadIdx.x >> 6);
+    const int b = blockIdx.y, x = blockIdx.x;
+    const int nchunks = dpad / E;
+    u64* dst = partial + ((int64_t)b * nprobe * split + x) * k;
+
+    WaveTopK<SLOTS> L;
+    L.init();
+    const u64 pk = probe_keys[(int64_t)b * nprobe + x / split];
+    if (pk != 0ull) {  // block-uniform: fewer lists than nprobe leave empty probe slots
+        const uint32_t list = key_row(pk);
+        const int64_t lo = offsets[list], hi = offsets[list + 1];
+        const int64_t len = hi - lo, part = (len + split - 1) / split;
+        const int64_t begin = lo + (x % split) * part;
+        const int64_t end = begin + part < hi ? begin + part : hi;
+
+        const uint4* base = reinterpret_cast<const uint4*>(rows_);
+        [[maybe_unused]] float qf[1][NITER > 0 ? NITER : 1][E];
+        [[maybe_unused]] float* lds_q = nullptr;
+        if constexpr (NITER == kWideRows) {  // wide rows: the query in LDS
+            __shared__ __attribute__((aligned(16))) float lds_qw[kWideMaxFloats];
+            lds_q = lds_qw;
+            wide_stage_query(lds_q, qn + (int64_t)b * dpad, dpad, wide_qfloats(nchunks, E), (int)threadIdx.x, 256);
+            __syncthreads();
+        } else {
+            load_query_frags(qn + (int64_t)b * dpad, nchunks, lane, qf[0]);
+        }
+        for (int64_t g = begin + wave * 4; g < end; g += 16) {
+            const uint4* p[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) p[r] = base + (g + r < end ? g + r : end - 1) * (int64_t)nchunks + lane;
+            float sc[1][4];
+            if constexpr (NITER == kWideRows) {
+                wide_scores<DT, 1, 1, kMetricL2, 1>(p, nchunks, lane, lds_q, 0, 1, sc);   // (USER 1: an instantiation of its own, exact_score.h)
+            } else {
+                uint4 c[4][NITER];
+                fetch4(p, nchunks, lane, c);
+                score4<DT, 1, NITER, kMetricL2>(c, qf, 1, lane, sc);
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                if (g + r < end && !(dead && row_dead(dead, ids[g + r]))) L.offer(make_key(sc[0][r], row_base + ids[g + r]), k, lane);
+        }
+    }
+    __shared__ u64 lds[4 * SLOTS * kWave];
+    store_list(lds, wave, 1, 0, lane, L);
+    __syncthreads();
+    if (wave != 0) return;
+    merge_lists(L, lds, 1, 4, 1, 0, k, lane);
+    write_keys(L, k, lane, dst);
+}
+
 // ---------------------------------------------------------------------------------------------
 // IVF at batch (round 3): a probed list is scanned ONCE for all the queries of the batch that probe it.  ivf_scan_kernel reads a
 // list once per (query, list) pair — 256 queries x 32 probes over 2,048 lists read every list four times.  Here the pairs are
@@ -1440,6 +1504,33 @@ __global__ __launch_bounds__(256) void ivf_scan_shared_kernel(const void* __rest
     // the pair's own slot of the partial buffer: [query][probe rank][k]
     list_scan_body<DT, kIvfNB, NITER, SLOTS, false>(rows_, ids, offsets[list], offsets[list + 1], dpad, q, nq, k, row_base, dead,
                                                     [&](int b) { return partial + (int64_t)pair[b] * k; });
+}
+// ivf_shared_sq: the same work items for an l2 index: list_scan_body under kMetricL2
+template <int DT, int NITER, int SLOTS>
+__global__ __launch_bounds__(256) void ivf_shared_sq(const void* __restrict__ rows_, const uint32_t* __restrict__ ids, const int64_t* __restrict__ offsets,
+                                                     const unsigned* __restrict__ pair_start, const unsigned* __restrict__ item_start,
+                                                     const unsigned* __restrict__ sorted_pairs, int nlist, int nprobe, int dpad, const float* __restrict__ qn, int k,
+                                                     uint32_t row_base, u64* __restrict__ partial, const uint32_t* __restrict__ dead) {
+    const unsigned item = blockIdx.x;
+    if (item >= item_start[nlist]) return;   // (the grid is sized for the worst case: one item per pair)
+    int lo_l = 0, hi_l = nlist;              // the last list whose item_start <= item
+    while (hi_l - lo_l > 1) {
+        const int mid = (lo_l + hi_l) >> 1;
+        if (item_start[mid] <= item) lo_l = mid; else hi_l = mid;
+    }
+    const int list = lo_l;
+    const unsigned g = item - item_start[list];
+    const unsigned p0 = pair_start[list] + g * kIvfNB, p1e = pair_start[list + 1];
+    const int nq = (int)((p1e - p0) < (unsigned)kIvfNB ? (p1e - p0) : (unsigned)kIvfNB);
+    unsigned pair[kIvfNB];
+    const float* q[kIvfNB];
+#pragma unroll
+    for (int b = 0; b < kIvfNB; ++b) {
+        pair[b] = b < nq ? sorted_pairs[p0 + b] : 0u;
+        q[b] = b < nq ? qn + (int64_t)(pair[b] / (unsigned)nprobe) * dpad : nullptr;
+    }
+    list_scan_body<DT, kIvfNB, NITER, SLOTS, false, kMetricL2>(rows_, ids, offsets[list], offsets[list + 1], dpad, q, nq, k, row_base, dead,
+                                                               [&](int b) { return partial + (int64_t)pair[b] * k; });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1857,6 +1948,9 @@ struct codd_knn_index : WorkBufs {
     // over the same dirty rows, and only for such an index: rnorm2[row] = the row's canonical sum of squares; *rmax_bits = the float
     // bits of R >= |c| for every row ever stored (it only grows: delete and compact never lower it)
     int space_filter = 0;
+    // IVF on an ip or l2 index ("space_ivf" option, off by default): the coarse index in the index's own space, raw
+    // centroids, the list scans by the index's metric.  No effect on a cosine index.
+    int space_ivf = 0;
     DevBuf<float> rnorm2;            // [shadow8_rows]
     DevBuf<unsigned> rmax_bits;
     int64_t shadow8_epoch = -1;
@@ -2289,6 +2383,8 @@ int launch_raw_rows(int dtype, const float* in, int64_t n, int d, int dpad, cons
 // the metric of an index as its exact-score kernels see it: ip scores with the dot-product kernels that cosine runs
 static_assert(kMetricDot == CODD_KNN_METRIC_COSINE && kMetricL2 == CODD_KNN_METRIC_L2, "exact_score.h and codd_knn.h disagree");
 bool metric_is_cosine(const codd_knn_index* ix) { return ix->metric == CODD_KNN_METRIC_COSINE; }
+// IVF: cosine always; ip and l2 with "space_ivf" on
+bool ivf_allowed(const codd_knn_index* ix) { return metric_is_cosine(ix) || ix->space_ivf; }
 int kernel_metric(int metric) { return metric == CODD_KNN_METRIC_L2 ? kMetricL2 : kMetricDot; }
 
 // the ingest launch of every upsert.  normalize = 0 on an ip or l2 index still zeroes non-finite rows (the contract of those
@@ -3694,7 +3790,7 @@ int codd_knn_copy_rows_f32(codd_knn_index* ix, int64_t first, int64_t n, float* 
 int codd_knn_ivf_install(codd_knn_index* ix, const float* dev_centroids, int nlist, const int64_t* dev_perm,
                          const int64_t* dev_offsets, void* stream) {
     if (!ix || !dev_centroids || !dev_perm || !dev_offsets || nlist < 1 || nlist > (1 << 20)) return fail(CODD_KNN_EINVAL, "bad ivf_install arguments%s");
-    if (!metric_is_cosine(ix)) return fail(CODD_KNN_ENOTSUP, "ivf_install: IVF exists for the cosine metric only (spherical k-means, bf16 assignment)%s");
+    if (!ivf_allowed(ix)) return fail(CODD_KNN_ENOTSUP, "ivf_install: IVF exists for the cosine metric only (spherical k-means, bf16 assignment)%s");
     if (ix->count < 1) return fail(CODD_KNN_EINVAL, "empty index%s");
     DeviceGuard guard(ix->device);
     hipStream_t st = (hipStream_t)stream;
@@ -3740,8 +3836,9 @@ int codd_knn_ivf_install(codd_knn_index* ix, const float* dev_centroids, int nli
         drop_ivf(ix);
         return fail(he == hipErrorOutOfMemory ? CODD_KNN_ENOMEM : CODD_KNN_EDEVICE, "ivf_install: building the list layout failed: %s", hipGetErrorString(he));
     }
-    rc = codd_knn_create(&ix->coarse, ix->device, ix->dim, DT_F32, CODD_KNN_METRIC_COSINE);
-    if (rc == 0) rc = codd_knn_upsert_device(ix->coarse, 0, dev_centroids, nlist, 1, stream);
+    // the coarse index lives in the index's own space: unit centroids for cosine, the centroids as given for ip and l2 (§22)
+    rc = codd_knn_create(&ix->coarse, ix->device, ix->dim, DT_F32, ix->metric);
+    if (rc == 0) rc = codd_knn_upsert_device(ix->coarse, 0, dev_centroids, nlist, metric_is_cosine(ix) ? 1 : 0, stream);
     if (rc == 0 && hipStreamSynchronize(st) != hipSuccess) rc = fail(CODD_KNN_EDEVICE, "ivf_install: device work failed%s");
     if (rc != 0) {
         drop_ivf(ix);
@@ -3779,7 +3876,7 @@ int empty_result(codd_knn_index* ix, int B, int k, uint64_t* dev_keys, float* de
 int ivf_check_args(const codd_knn_index* ix, const float* dev_queries, int B, int k, uint32_t row_base, int* nprobe) {
     int rc;
     if ((rc = search_check_args(ix, dev_queries, B, k, row_base)) != 0) return rc;
-    if (!metric_is_cosine(ix)) return fail(CODD_KNN_ENOTSUP, "IVF search exists for the cosine metric only%s");
+    if (!ivf_allowed(ix)) return fail(CODD_KNN_ENOTSUP, "IVF search exists for the cosine metric only%s");
     if (!ix->coarse || ix->ivf_epoch != ix->epoch) return fail(CODD_KNN_EINVAL, "no IVF layout, or rows changed since codd_knn_ivf_install%s");
     if (*nprobe < 1) return fail(CODD_KNN_EINVAL, "nprobe must be >= 1%s");
     if (*nprobe > ix->ivf_nlist) *nprobe = ix->ivf_nlist;
@@ -3796,8 +3893,9 @@ int ivf_search_body(codd_knn_index* ix, const float* dev_queries, int B, int k, 
     if ((rc = wait_rows(ix, st)) != 0) return rc;
     HIP_TRY(ix->qn.ensure((int64_t)B * ix->dpad));
     HIP_TRY(ix->probe_keys.ensure((int64_t)B * nprobe));
-    if ((rc = launch_normalize(DT_F32, dev_queries, B, ix->dim, ix->dpad, 1, nullptr, 0, ix->qn, nullptr, st)) != 0) return rc;
-    // 1. coarse: the nprobe best lists per query (exact scan of the centroids, tiny)
+    if ((rc = prep_exact_queries(ix, dev_queries, B, st)) != 0) return rc;
+    const bool sq = ix->metric == CODD_KNN_METRIC_L2;  // the squared-distance list scans (§22); ip runs the dot-product ones on the raw query
+    // 1. coarse: the nprobe best lists per query (exact scan of the centroids in the index's space, tiny)
     if ((rc = exact_scan(ix->coarse, ix->qn, B, nprobe, 0u, ix->probe_keys, nullptr, nullptr, st, ix->coarse->dead_bits)) != 0) return rc;
     const int niter = niter_of(ix);
     // 2a. a batch with enough (query, list) pairs to fill the chip without splitting lists: group the pairs by list on the
@@ -3825,6 +3923,15 @@ int ivf_search_body(codd_knn_index* ix, const float* dev_queries, int B, int k, 
         // work items <= sum over lists of ceil(pairs / kIvfNB) <= min(pairs, lists + pairs / kIvfNB): the grid covers the bound, surplus workgroups leave at once
         const int64_t bound = std::min<int64_t>(npairs, (int64_t)nlist + npairs / kIvfNB);
         rc = with_row_form(ix, k, "row too wide for the IVF scan%s", [&](auto dt, auto ni, auto sl) {
+            if (sq) {
+                // (2-byte rows of 4 chunks per lane never come here, see the condition above: that form is not built)
+                if constexpr (decltype(dt)::value != DT_F32 && decltype(ni)::value == 4) {
+                    return fail(CODD_KNN_EINVAL, "the shared squared-distance scan takes no 2-byte rows of 4 chunks per lane%s");
+                } else {
+                    return launch_kernel<ivf_shared_sq<dt, ni, sl>>(dim3((unsigned)bound), dim3(256), 0, st, ix->rows_ivf, ix->ivf_ids, ix->ivf_offsets, pair_start,
+                                                                    item_start, sorted_pairs, nlist, nprobe, ix->dpad, ix->qn, k, row_base, ix->ivf_partial, deny);
+                }
+            }
             return launch_kernel<ivf_scan_shared_kernel<dt, ni, sl>>(dim3((unsigned)bound), dim3(256), 0, st, ix->rows_ivf, ix->ivf_ids, ix->ivf_offsets,
                                                                      pair_start, item_start, sorted_pairs, nlist, nprobe, ix->dpad, ix->qn, k, row_base,
                                                                      ix->ivf_partial, deny);
@@ -3833,7 +3940,7 @@ int ivf_search_body(codd_knn_index* ix, const float* dev_queries, int B, int k, 
         HIP_TRY(hipGetLastError());
         }
         const int64_t ms = (int64_t)nprobe * k;
-        return launch_merge(ix->ivf_partial, B, ms, ms, k, (u64*)dev_keys, dev_dist, dev_rows, st);
+        return launch_merge_of(ix, ix->ivf_partial, B, ms, k, (u64*)dev_keys, dev_dist, dev_rows, st);
     }
     // 2. scan the probed lists; split each list over several blocks when the batch alone cannot fill the chip
     int split = (int)((4 * (int64_t)ix->num_cus + (int64_t)B * nprobe - 1) / ((int64_t)B * nprobe));
@@ -3844,6 +3951,9 @@ int ivf_search_body(codd_knn_index* ix, const float* dev_queries, int B, int k, 
     {
         EvScope ev(ix, EV_SCAN, st);
         rc = with_row_form(ix, k, "row too wide for the IVF scan%s", [&](auto dt, auto ni, auto sl) {
+            if (sq)
+                return launch_kernel<ivf_scan_sq<dt, ni, sl>>(grid, block, 0, st, ix->rows_ivf, ix->ivf_ids, ix->ivf_offsets, ix->probe_keys, nprobe, split, ix->dpad,
+                                                              ix->qn, k, row_base, ix->ivf_partial, deny);
             return launch_kernel<ivf_scan_kernel<dt, ni, sl>>(grid, block, 0, st, ix->rows_ivf, ix->ivf_ids, ix->ivf_offsets, ix->probe_keys, nprobe, split,
                                                               ix->dpad, ix->qn, k, row_base, ix->ivf_partial, deny);
         });
@@ -3851,7 +3961,7 @@ int ivf_search_body(codd_knn_index* ix, const float* dev_queries, int B, int k, 
     if (rc != 0) return rc;
     HIP_TRY(hipGetLastError());
     // 3. top-k of the nprobe*split partial lists
-    return launch_merge(ix->ivf_partial, B, m, m, k, (u64*)dev_keys, dev_dist, dev_rows, st);
+    return launch_merge_of(ix, ix->ivf_partial, B, m, k, (u64*)dev_keys, dev_dist, dev_rows, st);
 }
 
 }  // namespace
@@ -4532,6 +4642,11 @@ int codd_knn_set_option(codd_knn_index* ix, const char* key, int64_t value) {
         ix->space_filter = (int)value;
         return CODD_KNN_OK;
     }
+    if (strcmp(key, "space_ivf") == 0) {  // IVF on an ip or l2 index; no effect on a cosine index
+        if (value != 0 && value != 1) return fail(CODD_KNN_EINVAL, "space_ivf must be 0 or 1%s");
+        ix->space_ivf = (int)value;
+        return CODD_KNN_OK;
+    }
     if (strcmp(key, "shadow8_max_batch") == 0) {
         if (value < 1 || value > 256) return fail(CODD_KNN_EINVAL, "shadow8_max_batch must be in [1,256]%s");
         ix->shadow8_max_batch = (int)value;
@@ -4732,6 +4847,7 @@ int codd_knn_get_stat(const codd_knn_index* ix, const char* key, int64_t* out) {
     else if (strcmp(key, "all_normalized") == 0) *out = ix->all_normalized ? 1 : 0;
     else if (strcmp(key, "metric") == 0) *out = ix->metric;
     else if (strcmp(key, "space_filter") == 0) *out = ix->space_filter;
+    else if (strcmp(key, "space_ivf") == 0) *out = ix->space_ivf;
     else if (strcmp(key, "shadow8_passes") == 0) *out = ix->stat_shadow8_passes;
     else if (strcmp(key, "i8v2_passes") == 0) *out = ix->stat_i8v2_passes;
     else if (strcmp(key, "f16_tile_passes") == 0) *out = ix->stat_f16_tile_passes;

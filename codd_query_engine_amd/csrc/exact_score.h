@@ -166,7 +166,9 @@ __device__ __forceinline__ void wide_stage_query(float* __restrict__ dst, const 
 // each lane's canonical fmaf chain over chunks lane + 64 (kSegIt s + it), it = 0 .. kSegIt-1.  f32: the segment widened as it lands,
 // one query's LDS values at a time; 2-byte rows: the 16-byte chunks stay raw until their step and chunk it's query values are read
 // once for all rows.  Either way the same fmaf sequence per (query, row).
-template <int DT, int NQ, int NR, int METRIC = kMetricDot>
+// USER only names the instantiation (the code is the same): a kernel added later asks for a copy of its own where sharing one would
+// move hipcc's register allocation of the kernels that already use it (ivf_scan_sq beside scan_topk_wide_l2<DT, 1, SLOTS>: DESIGN.md §22).
+template <int DT, int NQ, int NR, int METRIC = kMetricDot, int USER = 0>
 __device__ __forceinline__ void wide_segment(const uint4* const (&p)[NR], const int& s, const int& nchunks, const int& lane, const float* qs, const int& qstride, float (&acc)[NQ][NR]) {
     typedef RowTraits<DT> RT;
     constexpr int E = RT::E;
@@ -247,7 +249,7 @@ __device__ __forceinline__ void wide_segment(const uint4* const (&p)[NR], const 
 
 // score4's wide twin for 4 G rows (G groups of four, every group's loads of a segment in flight together) against NQ staged queries:
 // sc[b][4 g + r] = the score of row r of group g against query b < nq (0 for b >= nq), in every lane
-template <int DT, int NQ, int G, int METRIC = kMetricDot>
+template <int DT, int NQ, int G, int METRIC = kMetricDot, int USER = 0>
 __device__ __forceinline__ void wide_scores(const uint4* const (&p)[4 * G], const int& nchunks, const int& lane, const float* qs, const int& qstride, const int& nq, float (&sc)[NQ][4 * G]) {
     float acc[NQ][4 * G];
 #pragma unroll
@@ -255,7 +257,7 @@ __device__ __forceinline__ void wide_scores(const uint4* const (&p)[4 * G], cons
 #pragma unroll
         for (int r = 0; r < 4 * G; ++r) acc[b][r] = 0.0f;
     const int nseg = wide_nseg(nchunks);
-    for (int s = 0; s < nseg; ++s) wide_segment<DT, NQ, 4 * G, METRIC>(p, s, nchunks, lane, qs, qstride, acc);
+    for (int s = 0; s < nseg; ++s) wide_segment<DT, NQ, 4 * G, METRIC, USER>(p, s, nchunks, lane, qs, qstride, acc);
 #pragma unroll
     for (int b = 0; b < NQ; ++b)
 #pragma unroll

@@ -6,6 +6,9 @@ row is assigned to its nearest centroid and the rows are regrouped by list.
   * the heavy part of every step — scores of 256 rows against all centroids — is the engine's own
     bf16 MFMA GEMM (`codd_knn_approx_scores` on an index that holds the centroids);
   * torch supplies argmax / index_add / sort on the device: bookkeeping around the GEMM, not search.
+An ip or l2 index (opt-in, option "space_ivf") is clustered in its own space instead: a centroid is the plain
+mean of its members, and every assignment is the exact search of a centroid index of that space (nearest centroid by squared
+distance for l2 — Lloyd's algorithm — and largest inner product for ip, the usual inner-product IVF).
 Search: `codd_knn_ivf_search` (HIP): exact top-nprobe lists per query, canonical exact scores over
 those lists, original row slots; `nprobe == nlist` reproduces the flat search bit for bit.
 
@@ -23,9 +26,10 @@ from .knn_index import DeviceKnnIndex
 
 
 def _require_cosine(index) -> None:
-    """IVF is cosine-specific (spherical k-means, centroids assigned by the bf16 cosine GEMM): an ip or l2 index has none."""
+    """IVF serves a cosine index, and an ip or l2 index whose "space_ivf" option is on; by default an ip or l2
+    index has none (spherical k-means and the bf16 cosine GEMM of the assignment are cosine-specific)."""
     space = getattr(index, "space", "cosine")
-    if space != "cosine":
+    if space != "cosine" and not index.stat("space_ivf"):
         raise native.NativeLibraryError(f"IVF exists for the cosine space only, this index is {space!r}: search it with the exact scan")
 
 
@@ -37,6 +41,16 @@ def _assign(torch, centroid_index: DeviceKnnIndex, vecs) -> "torch.Tensor":
         chunk = vecs[a : a + 256]
         scores = centroid_index.approx_scores(chunk)[: chunk.shape[0], :nlist]
         out[a : a + chunk.shape[0]] = torch.argmax(scores, dim=1)
+    return out
+
+
+def _assign_exact(torch, centroid_index: DeviceKnnIndex, vecs) -> "torch.Tensor":
+    """the best centroid of every row of `vecs` [n, dim] (device fp32) by the exact search of the centroid index's own space:
+    smallest canonical squared distance (l2), largest canonical inner product (ip); ties to the lower list."""
+    out = torch.empty(vecs.shape[0], dtype=torch.int64, device=vecs.device)
+    for a in range(0, vecs.shape[0], 1024):
+        chunk = vecs[a : a + 1024]
+        out[a : a + chunk.shape[0]] = centroid_index.search_tensors(chunk.contiguous(), 1)[1][:, 0]
     return out
 
 
@@ -69,25 +83,41 @@ def build_ivf(index: DeviceKnnIndex, nlist: int, iters: int = 8, sample: Optiona
     train = torch.cat([rows_f32(s, per) for s in starts])
     cent = train[torch.randperm(train.shape[0], generator=g)[:nlist].to(dev)].clone()
 
+    space = getattr(index, "space", "cosine")
+    spherical = space == "cosine"
+
+    def centroid_index(cent):
+        # cosine: unit centroids under the approximate GEMM; ip, l2: the centroids as they are, searched exactly in the index's space
+        if spherical:
+            cidx = DeviceKnnIndex(dim, "f32", str(dev))
+            cidx.upsert_device(0, cent.contiguous())
+        else:
+            cidx = DeviceKnnIndex(dim, "f32", str(dev), space=space)
+            cidx.upsert_device(0, cent.contiguous(), normalize=False)
+        return cidx
+
+    assign_rows = _assign if spherical else _assign_exact
+
     for _ in range(iters):
-        cidx = DeviceKnnIndex(dim, "f32", str(dev))
-        cidx.upsert_device(0, cent.contiguous())
-        a = _assign(torch, cidx, train)
+        cidx = centroid_index(cent)
+        a = assign_rows(torch, cidx, train)
         cidx.close()
         sums = torch.zeros((nlist, dim), dtype=torch.float32, device=dev).index_add_(0, a, train)
         counts = torch.bincount(a, minlength=nlist)
         empty = counts == 0
         if empty.any():  # reseed empty lists from random training rows
             sums[empty] = train[torch.randint(0, train.shape[0], (int(empty.sum()),), generator=g).to(dev)]
-        cent = torch.nn.functional.normalize(sums, dim=1)
+        if spherical:
+            cent = torch.nn.functional.normalize(sums, dim=1)
+        else:  # the mean of the members (a reseeded list: the one row it was given)
+            cent = sums / counts.clamp(min=1).to(torch.float32).unsqueeze(1)
 
     # assign every stored row, chunk by chunk, then group rows by list (stable: ascending slot inside a list)
-    cidx = DeviceKnnIndex(dim, "f32", str(dev))
-    cidx.upsert_device(0, cent.contiguous())
+    cidx = centroid_index(cent)
     assign = torch.empty(n, dtype=torch.int64, device=dev)
     for a0 in range(0, n, chunk_rows):
         c = min(chunk_rows, n - a0)
-        assign[a0 : a0 + c] = _assign(torch, cidx, rows_f32(a0, c))
+        assign[a0 : a0 + c] = assign_rows(torch, cidx, rows_f32(a0, c))
     cidx.close()
     perm = torch.sort(assign, stable=True).indices.contiguous()
     sizes = torch.bincount(assign, minlength=nlist)
@@ -166,6 +196,11 @@ class IvfShardEngine:
     def __init__(self, index: DeviceKnnIndex, nprobe: int):
         _require_cosine(index)
         self.index, self.nprobe = index, int(nprobe)
+
+    @property
+    def space(self) -> str:
+        """the index's space: ShardedSearcher's merges write that space's distances"""
+        return getattr(self.index, "space", "cosine")
 
     def count(self) -> int:
         return self.index.count()

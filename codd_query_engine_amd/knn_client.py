@@ -22,7 +22,9 @@ embeddings as given (upsert with normalize=False) and `query` returns that space
 everything else — namespaces, `where`, `where_document`, delete, compact, persistence — is the same.
 `metadata={"hnsw:space": "l2", "codd:space_filter": 1}` switches on the engine's int8 filter leg for
 such a collection (large batches, same answers), when the engine is created and again
-after `reload`; an engine without `set_option` ignores it.
+after `reload`; an engine without `set_option` ignores it.  `"codd:space_ivf": 1` sets the engine's
+"space_ivf" option the same way (codd_query_engine_amd.ivf accepts that engine; `query`
+itself never takes the IVF route).
 
 Persistence (`KnnClient(path=...)`, the role of `SemanticStoreConfig.chromadb_path`, declared and
 never read in the reference, codd_lib/codd_lib/config/semantic_store_config.py:13): the indexer job
@@ -71,6 +73,7 @@ def _factory_spaces(engine_factory) -> tuple:
 
 
 _SPACE_FILTER_KEY = "codd:space_filter"
+_SPACE_IVF_KEY = "codd:space_ivf"
 
 
 def _space_of(metadata: Optional[dict]) -> str:
@@ -140,10 +143,12 @@ class Collection:
     @staticmethod
     def _apply_engine_options(engine, metadata: Optional[dict]) -> None:
         """Collection metadata that is an engine option: "codd:space_filter" (the int8 filter leg of an ip or l2
-        collection) -> engine.set_option("space_filter", value).  Skipped on an engine without set_option."""
-        value = (metadata or {}).get(_SPACE_FILTER_KEY)
-        if value is not None and callable(getattr(engine, "set_option", None)):
-            engine.set_option("space_filter", int(value))
+        collection) -> engine.set_option("space_filter", value); "codd:space_ivf" (IVF on such an engine) ->
+        engine.set_option("space_ivf", value).  Skipped on an engine without set_option."""
+        for key, option in ((_SPACE_FILTER_KEY, "space_filter"), (_SPACE_IVF_KEY, "space_ivf")):
+            value = (metadata or {}).get(key)
+            if value is not None and callable(getattr(engine, "set_option", None)):
+                engine.set_option(option, int(value))
 
     def _engine_for(self, dim: int):
         if self._engine is None:

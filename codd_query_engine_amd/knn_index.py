@@ -33,7 +33,7 @@ def require_gpu(device: str = "cuda:0"):
 class DeviceKnnIndex:
     """Device-resident row store with exact top-k search: L2-normalised rows under cosine (the default `space`), rows as given
     under ChromaDB's other two spaces, "ip" (distance 1 - <q, c>) and "l2" (squared distance).  Every search method's distances
-    follow the space; an ip or l2 index has no IVF and no approx_scores.
+    follow the space; an ip or l2 index has no approx_scores and takes IVF with its "space_ivf" option on (§22).
 
     Engine protocol consumed by knn_client.Collection:
         count() / upsert(slots, vecs) / search(queries, k) -> (dist, rows) as numpy;

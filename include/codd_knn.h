@@ -51,8 +51,9 @@
  *     option "space_filter": an int8 filter leg with measured norms in its bound; the
  *     answers are the same bits.)  Every
  *     search, delete, compact, load and read entry point keeps its contract word for word under these
- *     metrics, except the IVF ones and codd_knn_approx_scores, which return ENOTSUP (spherical k-means
- *     and the bf16 assignment are cosine-specific).
+ *     metrics, except the IVF ones and codd_knn_approx_scores, which return ENOTSUP by default (spherical
+ *     k-means and the bf16 assignment are cosine-specific).  (Opt-in, option "space_ivf": the IVF entry
+ *     points accept an ip or l2 index, with a coarse index in the index's own space)
  *   - the count is the highest written slot + 1, and a write may start above it.  A row slot below the count that was never
  *     written (since creation, or since the last codd_knn_compact vacated it) holds the zero vector: it is live, has scope 0,
  *     scores 0 (distance 1) under cosine and ip and lies at distance sum q_i^2 under l2 on every search path, reads back as
@@ -230,6 +231,14 @@ int codd_knn_filter_slack(codd_knn_index* index, const float* dev_queries, int B
  * ivf_search: nprobe (<= 128) best lists per query by exact centroid score, canonical exact scores
  * over those lists, top-k with ORIGINAL row slots; with nprobe == nlist the result is bit-identical
  * to codd_knn_search.  Any of dev_keys / dev_dist / dev_rows may be NULL.
+ * An ip or l2 index: ENOTSUP from install and from every IVF search, nothing enqueued or allocated, unless
+ * option "space_ivf" is 1.  Then the centroids are RAW vectors (stored as given, f32, not
+ * normalised: for l2 the means of their lists), the coarse index has the index's own metric, and ivf_search
+ * probes the nprobe lists of smallest canonical squared distance to the centroid (l2) or largest canonical
+ * dot product with it (ip), ties to the lower list number; the lists are scored with the index's canonical
+ * expression on the raw query.  The contract is the cosine one word for word: the exact canonical top-k among
+ * the allowed live rows of the probed lists, min(k, rows there) hits, padding (row -1, distance +inf, key 0),
+ * and nprobe >= nlist is codd_knn_search bit for bit.  The same holds for the two masked forms below.
  */
 /* Stored rows [first, first+n) widened to fp32, device to device, asynchronously on `stream` (the IVF build's
  * input).  Ordered like a search: behind every upsert enqueued before it on any stream, and a later upsert waits
@@ -474,6 +483,8 @@ int codd_knn_embed_texts_host(codd_knn_embedder* e, const uint8_t* host_bytes, c
  *            and more through the int8 MFMA filter with measured norms in its bound, then re-scores exactly — same ids and distance
  *            bits as the scan; needs "filter" and "shadow8" on, l2 rows of at most 4 chunks per lane; no effect on a cosine index;
  *            DESIGN.md §21),
+ *            "space_ivf" (0; 1: codd_knn_ivf_install and the IVF searches accept an ip or l2 index — raw centroids, a coarse index
+ *            and list scans in the index's own space; 0: they return ENOTSUP there; no effect on a cosine index),
  *            "debug_fail_shadow_alloc" (tests: the next N allocations of the 2-byte shadow fail);
  *            "profile" = N keeps N (start, stop) HIP-event pairs, one per heavy-kernel launch,
  *            recorded on the launch stream (0 = off; resets the log)
@@ -493,7 +504,7 @@ int codd_knn_embed_texts_host(codd_knn_embedder* e, const uint8_t* host_bytes, c
  *            "device_bytes", "num_cus", "workspaces" (stream workspaces in use), "shadow8_builds", "shadow8_passes", "i8v2_passes",
  *            "shadow16_builds" (the bf16 shadow is built lazily, by the first search that needs it), "all_normalized",
  *            "shadow8_cooldowns", "shadow8_eps_r_micro", "shadow8_wide_blocks" (32-row blocks whose quantisation error is above
- *            0.04: tolerated up to 1 % of the blocks), "shadow16_alloc_failures", "small_batch_passes", "f16_tile_passes", "space_filter" (the option), and per kernel K in {scan, filter, sample, finalize}:
+ *            0.04: tolerated up to 1 % of the blocks), "shadow16_alloc_failures", "small_batch_passes", "f16_tile_passes", "space_filter", "space_ivf" (the options), and per kernel K in {scan, filter, sample, finalize}:
  *            "events:K", "time_ns:K" (sum of the recorded launches; syncs on the last event)
  */
 int codd_knn_set_option(codd_knn_index* index, const char* key, int64_t value);
