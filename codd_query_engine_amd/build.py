@@ -20,7 +20,7 @@ _ROOT = os.path.dirname(_PKG)
 CSRC = os.path.join(_PKG, "csrc")
 LIB_PATH = os.path.join(CSRC, "libcodd_knn.so")
 SOURCES = ["codd_knn.hip"]
-HEADERS = ["wave_topk.h", "row_traits.h", "exact_score.h", "filter_gemm.h", "filter_gemm_body.inc", "filter_i8.h", "doc_match.h", "text_embed.h", "device_mem.h", os.path.join(_ROOT, "include", "codd_knn.h")]
+INCLUDE = os.path.join(_ROOT, "include")
 
 HIPCC_FLAGS = [
     "--offload-arch=gfx950",
@@ -49,13 +49,33 @@ def _hipcc() -> str:
     return "hipcc"
 
 
+def dependencies() -> list[str]:
+    """Every file the library is compiled from: SOURCES and whatever they reach through #include "...", resolved against
+    csrc/ and include/ (absolute paths, sources first, each file once).  A textual walk: an #include inside #if 0 or a block
+    comment counts too, so the list can only be too long, never too short.  An include that resolves nowhere raises (the
+    compile would fail on it anyway), so build() can raise FileNotFoundError before it reaches hipcc."""
+    todo = [os.path.join(CSRC, s) for s in SOURCES]
+    seen = []
+    while todo:
+        path = todo.pop(0)
+        if path in seen:
+            continue
+        seen.append(path)
+        with open(path, encoding="utf-8") as f:
+            names = re.findall(r'^[ \t]*#[ \t]*include[ \t]*"([^"]+)"', f.read(), re.M)
+        for name in names:
+            found = [p for p in (os.path.join(d, name) for d in (os.path.dirname(path), CSRC, INCLUDE)) if os.path.exists(p)]
+            if not found:
+                raise FileNotFoundError(f'{path} includes "{name}", which is neither under csrc/ nor under include/')
+            todo.append(os.path.abspath(found[0]))
+    return seen
+
+
 def _stale() -> bool:
     if not os.path.exists(LIB_PATH):
         return True
     t = os.path.getmtime(LIB_PATH)
-    deps = [os.path.join(CSRC, s) for s in SOURCES] + [h if os.path.isabs(h) else os.path.join(CSRC, h) for h in HEADERS]
-    deps.append(os.path.abspath(__file__))
-    return any(os.path.getmtime(d) > t for d in deps if os.path.exists(d))
+    return any(os.path.getmtime(d) > t for d in dependencies() + [os.path.abspath(__file__)])
 
 
 def build(force: bool = False, report: bool = False) -> str:

@@ -1,21 +1,21 @@
-// codd_knn.hip — HIP kernels (gfx950 / CDNA4, wave64) and the C ABI of include/codd_knn.h.
+// codd_knn.hip — the one translation unit of libcodd_knn.so: HIP kernels (gfx950 / CDNA4, wave64) and the C ABI of include/codd_knn.h.
 //
 // What runs here is the arithmetic half of ChromaDB on Codd's search_relevant_metrics path
 // (reference call sites: codd_dal/metrics/metrics_semantic_metadata_store.py:60-69 create,
-// :236-238 upsert, :314-316 query; scoring :336).  Kernels:
+// :236-238 upsert, :314-316 query; scoring :336).  In this order (one translation unit, kernels in the
+// anonymous namespace, definition order is part of the build):
 //
-//   normalize_rows_kernel   ingest + query prep: c <- c/|c| (canonical sum of squares, IEEE sqrt/div),
-//                           writes the stored row AND its bf16 shadow in MFMA-fragment order
-//   prep_queries_kernel     one launch per batch of <= 256 queries: normalise, pack the MFMA fragments,
-//                           clear the pass's control block
-//   scan_topk_kernel        exact streaming scan (small batches, fallback): one wave owns 4 rows per
-//                           step, 16-B/lane coalesced loads, fmaf chains in canonical order,
-//                           wave-distributed top-k lists
-//   merge_keys_kernel       integer top-k of packed keys (per-block partials, shard partials)
-//   raw_rows_kernel         ingest + query prep of an ip or l2 index: vectors as given, non-finite ones as zeros
-//   scan_topk_l2, scan_topk_wide_l2, scope_scan_l2, mask_scan_l2, merge_keys_l2
-//                           the squared-L2 forms of the exact-score kernels; ip runs the dot-product ones
-//   filter_gemm.h           large batches: bf16 MFMA filter + exact fp32 re-score (finalize)
+//   ingest_kernels.h     caller vectors -> stored rows and the bf16 shadow (normalised or raw), query preparation, row read-back
+//   scan_kernels.h       the exact scan of the whole row store (dot product and squared L2), finalize + fallback, the key merges
+//   shadow8_kernels.h    the int8 shadow, the int8 filter leg's query preparation and bounds, small_batch_kernel
+//   list_scan_kernels.h  scans of row lists and what builds the lists: IVF, scopes, tombstones and compaction, masks
+//   (here)               host side: the index object, its workspaces and guards
+//   dispatch.h           with_* (run-time value -> template argument), Lds, launch_kernel, launch_by_metric
+//   (here)               the exact pass, the filter pass, scopes, then the extern "C" entry points with the bodies of the IVF and
+//                        masked searches between them
+//
+// The other headers (exact_score.h, wave_topk.h, row_traits.h, filter_gemm.h, filter_i8.h, doc_match.h, text_embed.h,
+// device_mem.h) are interfaces in namespace codd and come first.
 //
 // HBM-bound byte streaming throughout: the corpus is read once per pass, each row by exactly one
 // wave, straight into registers; results leave as 8-byte keys.
@@ -46,1769 +46,10 @@
 
 using namespace codd;
 
-// =============================================================================================
-// device code
-// =============================================================================================
-
-namespace {
-
-// ---------------------------------------------------------------------------------------------
-// normalize_rows_kernel: one wave per input vector.  in: n x d fp32 (row stride d).
-// out row = slots ? slots[r] : first_slot + r, width dpad, storage dtype DT.
-// Sum of squares in the canonical order with E = 4 (the input is fp32), then IEEE sqrt and
-// IEEE division per element; a zero / non-finite norm stores an all-zero row.
-// shadow (optional): the bf16 rounding of the STORED value, in fragment order (filter_gemm.h).
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ float butterfly_max(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, kWave));
-    return v;
-}
-// |x| of one vector by the canonical sum of squares: chunk j of 4 elements belongs to lane j % 64
-//
-// The squares are taken in fp32, so a vector of finite elements can have a sum of squares that underflows (elements near 1e-23
-// and below: the few bits left of a subnormal sum put the stored norm at 0.8 .. 1.2, or at 0) or overflows (elements near 1e18
-// and above).  Cosine does not depend on scale: where the sum leaves [2^-100, 2^100] the vector is scaled by the exact power of
-// two `sh` that brings its largest magnitude into [1, 2) and the same chain runs on the scaled values; the caller divides
-// scaled(x[i], sh) by the returned norm.  Inside the band (every ordinary vector) sh = 0 and nothing changes.  The branch is
-// wave-uniform: butterfly_sum and butterfly_max leave the same value in every lane.
-// Returns 0 for a vector with a non-finite element or without a non-zero one (the callers' zero row).
-constexpr float kNormBandLo = 0x1p-100f, kNormBandHi = 0x1p+100f;
-__device__ __forceinline__ float scaled(float t, int sh) { return sh ? __builtin_ldexpf(t, sh) : t; }
-// floor(log2 m) of a finite m > 0 from its bits, subnormals included
-__device__ __forceinline__ int floor_log2_f32(float m) {
-    const uint32_t u = __float_as_uint(m) & 0x7fffffffu;
-    const int e = (int)(u >> 23);
-    return e ? e - 127 : (31 - __builtin_clz(u)) - 149;
-}
-__device__ __forceinline__ float canonical_norm(const float* __restrict__ x, int d, int nch, int lane, int& sh) {
-    sh = 0;
-    float acc = 0.0f;
-    for (int j = lane; j < nch; j += kWave) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int i = j * 4 + e;
-            const float v = i < d ? x[i] : 0.0f;
-            acc = __builtin_fmaf(v, v, acc);
-        }
-    }
-    float n2 = butterfly_sum(acc);
-    if (!(n2 >= kNormBandLo && n2 <= kNormBandHi)) {
-        float m = 0.0f;
-        for (int j = lane; j < nch; j += kWave) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int i = j * 4 + e;
-                m = fmaxf(m, fabsf(i < d ? x[i] : 0.0f));
-            }
-        }
-        m = butterfly_max(m);
-        // a NaN element makes n2 NaN (fmaxf would skip it); an infinite one makes m infinite
-        if (n2 != n2 || !(m > 0.0f) || !(m < INFINITY)) return 0.0f;
-        sh = -floor_log2_f32(m);
-        acc = 0.0f;
-        for (int j = lane; j < nch; j += kWave) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int i = j * 4 + e;
-                const float v = i < d ? __builtin_ldexpf(x[i], sh) : 0.0f;
-                acc = __builtin_fmaf(v, v, acc);
-            }
-        }
-        n2 = butterfly_sum(acc);
-    }
-    return __builtin_sqrtf(n2);
-}
-
-// Query preparation of one filter pass in ONE launch (B <= 256): q <- q/|q| exactly as normalize_rows_kernel<f32> does
-// (qn, for finalize's exact re-scoring), the same values rounded into the MFMA fragment order (qfrag; queries >= B
-// are zero), and the pass's control block cleared.  One wave per query slot, 64 blocks.
-__global__ __launch_bounds__(256) void prep_queries_kernel(const float* __restrict__ in, int B, int d, int dpad, float* __restrict__ qn,
-                                                           uint2* __restrict__ qfrag, unsigned* __restrict__ ctl, int ctl_words) {
-    const int lane = lane_id();
-    const int q = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
-    for (int i = (int)blockIdx.x * 256 + (int)threadIdx.x; i < ctl_words; i += (int)gridDim.x * 256) ctl[i] = 0u;
-    const int nch = dpad >> 2;
-    if (q >= B) {
-        for (int j = lane; j < nch; j += kWave) qfrag[codd::qfrag_piece_index(q, j >> 1) * 2 + (j & 1)] = make_uint2(0u, 0u);
-        return;
-    }
-    const float* x = in + (int64_t)q * d;
-    int sh;
-    const float nrm = canonical_norm(x, d, nch, lane, sh);
-    const bool zero_row = !(nrm > 0.0f) || !(nrm < INFINITY);
-    for (int j = lane; j < nch; j += kWave) {
-        float v[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int i = j * 4 + e;
-            const float t = i < d ? x[i] : 0.0f;
-            v[e] = zero_row ? 0.0f : scaled(t, sh) / nrm;
-        }
-        reinterpret_cast<float4*>(qn)[(int64_t)q * nch + j] = make_float4(v[0], v[1], v[2], v[3]);
-        qfrag[codd::qfrag_piece_index(q, j >> 1) * 2 + (j & 1)] = make_uint2(codd::pack_bf16x2(v[0], v[1]), codd::pack_bf16x2(v[2], v[3]));
-    }
-}
-
-template <int DT>
-__global__ __launch_bounds__(256) void normalize_rows_kernel(const float* __restrict__ in, int64_t n, int d, int dpad,
-                                                             int normalize, const int64_t* __restrict__ slots,
-                                                             int64_t first_slot, void* __restrict__ out_,
-                                                             uint2* __restrict__ shadow) {
-    const int lane = lane_id();
-    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= n) return;
-    const float* x = in + r * (int64_t)d;
-    const int nch = dpad >> 2;
-    const int nsteps = dpad >> 6;
-    float scale_div = 1.0f;
-    int sh = 0;
-    bool zero_row = false;
-    if (normalize) {
-        const float nrm = canonical_norm(x, d, nch, lane, sh);
-        zero_row = !(nrm > 0.0f) || !(nrm < INFINITY);
-        scale_div = nrm;
-    }
-    const int64_t orow = slots ? slots[r] : first_slot + r;
-    for (int j = lane; j < nch; j += kWave) {
-        float v[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int i = j * 4 + e;
-            float t = i < d ? x[i] : 0.0f;
-            if (normalize) t = zero_row ? 0.0f : scaled(t, sh) / scale_div;
-            v[e] = t;
-        }
-        if (DT == DT_F32) {
-            float4* o = reinterpret_cast<float4*>(out_) + orow * (int64_t)nch + j;
-            *o = make_float4(v[0], v[1], v[2], v[3]);
-        } else {
-            uint16_t hb[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                hb[e] = DT == DT_BF16 ? f32_to_bf16_rne(v[e]) : f32_to_f16_rne(v[e]);
-                // the shadow approximates the STORED value, whatever the shadow element type is
-                v[e] = DT == DT_F16 ? f16_bits_to_f32(hb[e]) : __uint_as_float((uint32_t)hb[e] << 16);
-            }
-            uint2* o = reinterpret_cast<uint2*>(out_) + orow * (int64_t)nch + j;
-            *o = make_uint2((uint32_t)hb[0] | ((uint32_t)hb[1] << 16), (uint32_t)hb[2] | ((uint32_t)hb[3] << 16));
-        }
-        if (shadow) {
-            // elements [4j, 4j+4) = half (j&1) of 16-byte piece c8 = j>>1
-            const int64_t piece = shadow_piece_index(orow, j >> 1, nsteps);
-            shadow[piece * 2 + (j & 1)] = make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
-        }
-    }
-}
-
-// raw_rows_kernel: ingest and query prep of an ip or l2 index, one wave per input vector: the vector is used as
-// given — padded with zeros to dpad, rounded to the storage dtype DT, not normalised — except that a vector with a NaN or infinite
-// element, or without a non-zero one, is stored as zeros.  out row = slots ? slots[r] : first_slot + r, as normalize_rows_kernel.
-template <int DT>
-__global__ __launch_bounds__(256) void raw_rows_kernel(const float* __restrict__ in, int64_t n, int d, int dpad, const int64_t* __restrict__ slots,
-                                                       int64_t first_slot, void* __restrict__ out_) {
-    const int lane = lane_id();
-    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= n) return;
-    const float* x = in + r * (int64_t)d;
-    const int nch = dpad >> 2;
-    bool bad = false, any = false;
-    for (int i = lane; i < d; i += kWave) {
-        const float v = x[i];
-        bad = bad || !(fabsf(v) < INFINITY);   // (NaN compares false too)
-        any = any || v != 0.0f;
-    }
-    const bool zero_row = __ballot(bad) != 0ull || __ballot(any) == 0ull;
-    const int64_t orow = slots ? slots[r] : first_slot + r;
-    for (int j = lane; j < nch; j += kWave) {
-        float v[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int i = j * 4 + e;
-            v[e] = (i < d && !zero_row) ? x[i] : 0.0f;
-        }
-        if (DT == DT_F32) {
-            reinterpret_cast<float4*>(out_)[orow * (int64_t)nch + j] = make_float4(v[0], v[1], v[2], v[3]);
-        } else {
-            uint16_t hb[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) hb[e] = DT == DT_BF16 ? f32_to_bf16_rne(v[e]) : f32_to_f16_rne(v[e]);
-            reinterpret_cast<uint2*>(out_)[orow * (int64_t)nch + j] = make_uint2((uint32_t)hb[0] | ((uint32_t)hb[1] << 16), (uint32_t)hb[2] | ((uint32_t)hb[3] << 16));
-        }
-    }
-}
-
-// shadow_from_rows_kernel: rebuild the bf16 fragment-order shadow of rows [first, first+n) from the
-// stored rows themselves (index load from disk: the rows arrive already normalised and rounded).
-template <int DT>
-__global__ __launch_bounds__(256) void shadow_from_rows_kernel(const void* __restrict__ rows_, int64_t first, int64_t n, int dpad,
-                                                               uint2* __restrict__ shadow) {
-    const int lane = lane_id();
-    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= n) return;
-    const int64_t row = first + r;
-    const int nch = dpad >> 2, nsteps = dpad >> 6;
-    for (int j = lane; j < nch; j += kWave) {
-        float v[4];
-        if (DT == DT_F32) {
-            const float4 x = reinterpret_cast<const float4*>(rows_)[row * (int64_t)nch + j];
-            v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
-        } else {
-            const uint2 x = reinterpret_cast<const uint2*>(rows_)[row * (int64_t)nch + j];
-            const uint16_t hb[4] = {(uint16_t)(x.x & 0xffffu), (uint16_t)(x.x >> 16), (uint16_t)(x.y & 0xffffu), (uint16_t)(x.y >> 16)};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = DT == DT_BF16 ? __uint_as_float((uint32_t)hb[e] << 16) : f16_bits_to_f32(hb[e]);
-        }
-        const int64_t piece = shadow_piece_index(row, j >> 1, nsteps);
-        shadow[piece * 2 + (j & 1)] = make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// scan_topk_kernel<DT, NB, NITER, SLOTS>: exact canonical-score scan of the whole row store for
-// up to NB queries at once.
-//   - a wave owns row group g = 4 consecutive rows per step; NITER 16-byte loads per row per lane
-//     (chunk j = lane + 64*it), i.e. 4*NITER loads in flight per lane before the first use;
-//   - the NB query fragments live in registers for the whole kernel;
-//   - per (row, query): one fmaf chain per lane in canonical order, then the 4-row butterfly;
-//   - per (wave, query): a top-k list distributed over the lanes (wave_topk.h);
-//   - per block: the 4 wave lists are merged through LDS and written as k packed keys to
-//     partial[q][block][0..k).
-// ---------------------------------------------------------------------------------------------
-// scan_topk_body: the scan as a workgroup of NW waves sees it — workgroup `bid` of `nblocks`, lds = NW * NB * SLOTS * 64 u64.
-// `total` queries, dense from qn (qlist == nullptr) or listed (qlist[i] = query slot; `listed` also selects the one-launch
-// hand-off to the last block, see below).  Shared by scan_topk_kernel and by the scan role of finalize_fb_kernel.
-// the tombstone bits of row group g (rows 4g .. 4g+3: one bitmap word, 4 | 32) in bits 0..3; 0 without a load while nothing was ever
-// deleted.  g is wave-uniform: said so to the compiler, the word is a scalar load into a scalar register, not one more vector register
-// in a loop that lives at the register limit.
-__device__ __forceinline__ uint32_t group_dead_bits(const uint32_t* __restrict__ dead, int64_t g) {
-    if (!dead) return 0u;
-    const uint32_t gu = (uint32_t)__builtin_amdgcn_readfirstlane((int)g);
-    return dead[gu >> 3] >> ((gu & 7u) * 4u);
-}
-
-template <int DT, int NB, int NITER, int SLOTS, int NW, int METRIC = kMetricDot>
-__device__ __forceinline__ void scan_topk_body(const void* __restrict__ rows_, int64_t n, int dpad, const float* __restrict__ qn, int total, int k,
-                                               uint32_t row_base, u64* __restrict__ partial, int64_t partial_stride_q,
-                                               const unsigned* __restrict__ qlist, bool listed, unsigned* __restrict__ merge_done,
-                                               u64* __restrict__ merged_keys, float* __restrict__ merged_dist, int64_t* __restrict__ merged_rows,
-                                               unsigned long long* __restrict__ count_total, int bid, int nblocks, u64* __restrict__ lds,
-                                               const uint32_t* __restrict__ dead) {
-    typedef RowTraits<DT> RT;
-    constexpr int E = RT::E;
-    const int lane = lane_id();
-    const int wave = (int)(threadIdx.x >> 6);
-    const int nchunks = dpad / E;
-
-    // Two ways in: (a) the host names a dense group of nq_arg <= NB queries starting at qn (one pass);
-    // (b) LISTED: qcount_ptr / qlist live on the device (the filter's fallback queue) and the kernel walks
-    // the queue NB queries at a time — zero queued queries is the common case and costs one empty launch.
-    for (int g0 = 0; g0 < total; g0 += NB) {
-    const int nq = total - g0 < NB ? total - g0 : NB;
-
-    WaveTopK<SLOTS> L[NB];
-    if constexpr (NITER == kWideRows) {
-        // wide rows: the group's queries in LDS (where the block merge keeps its lists: the previous group is done with them),
-        // every row group walked segment by segment (wide_segment)
-        float* qs = reinterpret_cast<float*>(lds);
-        const int qstride = wide_qfloats(nchunks, E);
-#pragma unroll
-        for (int b = 0; b < NB; ++b) {
-            const float* src = b < nq ? qn + (qlist ? (int64_t)qlist[g0 + b] : (int64_t)(g0 + b)) * dpad : nullptr;
-            wide_stage_query(qs + b * qstride, src, dpad, qstride, (int)threadIdx.x, NW * kWave);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int b = 0; b < NB; ++b) L[b].init();
-        const uint4* base = reinterpret_cast<const uint4*>(rows_);
-        const int64_t ngroups = (n + 3) >> 2;
-        const int64_t W = (int64_t)nblocks * NW;
-        const int nseg = wide_nseg(nchunks);
-        for (int64_t g = (int64_t)bid * NW + wave; g < ngroups; g += W) {
-            const uint4* p[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int64_t row = g * 4 + r < n ? g * 4 + r : n - 1;
-                p[r] = base + row * (int64_t)nchunks + lane;
-            }
-            float acc[NB][4];
-#pragma unroll
-            for (int b = 0; b < NB; ++b)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) acc[b][r] = 0.0f;
-            for (int s = 0; s < nseg; ++s) wide_segment<DT, NB, 4, METRIC>(p, s, nchunks, lane, qs, qstride, acc);
-            const uint32_t dm = group_dead_bits(dead, g);
-#pragma unroll
-            for (int b = 0; b < NB; ++b) {   // (one query's tail and offers at a time: NB x 4 scores at once spill scalar registers)
-                const float y = packed4<METRIC>(acc[b], lane);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int64_t row = g * 4 + r;
-                    if (row < n && !((dm >> r) & 1u)) L[b].offer(make_key(packed_score(y, r), row_base + (uint32_t)row), k, lane);
-                }
-            }
-        }
-        __syncthreads();  // every wave is done with the queries: the lists take their place
-    } else {
-    float qf[NB][NITER][E];
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-        load_query_frags(b < nq ? qn + (qlist ? (int64_t)qlist[g0 + b] : (int64_t)(g0 + b)) * dpad : nullptr, nchunks, lane, qf[b]);
-        L[b].init();
-    }
-
-    const uint4* base = reinterpret_cast<const uint4*>(rows_);
-    const int64_t ngroups = (n + 3) >> 2;
-    const int64_t W = (int64_t)nblocks * NW;
-    for (int64_t g = (int64_t)bid * NW + wave; g < ngroups; g += W) {
-        const uint4* p[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) p[r] = base + (g * 4 + r < n ? g * 4 + r : n - 1) * (int64_t)nchunks + lane;
-        float w[4][NITER][E];
-        fetch4_widened<DT>(p, nchunks, lane, w);
-        const uint32_t dm = group_dead_bits(dead, g);
-#pragma unroll
-        for (int b = 0; b < NB; ++b) {   // (an absent query's fragments are zeros: its list is never read)
-            const float y = score4_one<NITER, E, METRIC>(w, qf[b], lane);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int64_t row = g * 4 + r;
-                if (row < n && !((dm >> r) & 1u)) L[b].offer(make_key(packed_score(y, r), row_base + (uint32_t)row), k, lane);
-            }
-        }
-    }
-    }  // (NITER)
-
-    // block merge through LDS: wave b collects query b's list
-#pragma unroll
-    for (int b = 0; b < NB; ++b) store_list(lds, wave, NB, b, lane, L[b]);
-    __syncthreads();
-    for (int b = wave; b < nq; b += NW) {
-        WaveTopK<SLOTS> M;
-        M.init();
-        merge_lists(M, lds, 0, NW, NB, b, k, lane);
-        write_keys(M, k, lane, partial + (int64_t)(g0 + b) * partial_stride_q + (int64_t)bid * k);
-    }
-    __syncthreads();  // the LDS lists are rewritten by the next group
-    }  // group loop
-
-    // LISTED mode with `merge_done`: the block that finishes last merges every queued query's per-block partials and writes
-    // the answers into the queries' own slots — the fallback is ONE launch (an empty queue, the normal case, costs one
-    // empty launch and touches no counter).  Hand-off: every block's stores, a device-scope fence, the arrival ticket;
-    // the last arriver fences again before it reads the other blocks' partials.
-    if (listed && merge_done && total > 0) {
-        __shared__ unsigned s_last;
-        __threadfence();
-        __syncthreads();
-        if (threadIdx.x == 0) s_last = atomicAdd(merge_done, 1u) == (unsigned)nblocks - 1u ? 1u : 0u;
-        __syncthreads();
-        if (!s_last) return;
-        __threadfence();
-        if (threadIdx.x == 0) *merge_done = 0u;  // (ready for the next list-driven launch without a clearing pass)
-        if (threadIdx.x == 0 && count_total) atomicAdd(count_total, (unsigned long long)total);
-        const int64_t m = (int64_t)nblocks * k;
-        for (int qi = wave; qi < total; qi += NW) {
-            const u64* src = partial + (int64_t)qi * partial_stride_q;
-            WaveTopK<SLOTS> M;
-            M.init();
-            for (int64_t i0 = 0; i0 < m; i0 += kWave) {
-                const int64_t i = i0 + lane;
-                M.offer_lanes(i < m ? src[i] : 0ull, k, lane);
-            }
-            const int64_t o = (int64_t)qlist[qi] * k;
-            write_ranks<SLOTS, METRIC>(M, k, lane, merged_keys ? merged_keys + o : nullptr, merged_dist ? merged_dist + o : nullptr, merged_rows ? merged_rows + o : nullptr);
-        }
-    }
-}
-
-template <int DT, int NB, int NITER, int SLOTS>
-__global__ __launch_bounds__(256) void scan_topk_kernel(const void* __restrict__ rows_, int64_t n, int dpad,
-                                                        const float* __restrict__ qn, int nq_arg, int k,
-                                                        uint32_t row_base, u64* __restrict__ partial,
-                                                        int64_t partial_stride_q, const unsigned* __restrict__ qlist,
-                                                        const unsigned* __restrict__ qcount_ptr, unsigned* __restrict__ merge_done = nullptr,
-                                                        u64* __restrict__ merged_keys = nullptr, float* __restrict__ merged_dist = nullptr,
-                                                        int64_t* __restrict__ merged_rows = nullptr,
-                                                        unsigned long long* __restrict__ count_total = nullptr,
-                                                        const uint32_t* __restrict__ dead = nullptr) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    const int total = qcount_ptr ? (int)*qcount_ptr : nq_arg;
-    scan_topk_body<DT, NB, NITER, SLOTS, 4>(rows_, n, dpad, qn, total, k, row_base, partial, partial_stride_q, qlist, qcount_ptr != nullptr, merge_done, merged_keys,
-                                            merged_dist, merged_rows, count_total, (int)blockIdx.x, (int)gridDim.x, reinterpret_cast<u64*>(smem_raw), dead);
-}
-
-// scan_topk_kernel's wide form (more than 4 chunks per lane): the NB queries' full rows are staged in LDS, up to 128 KiB, so ONE
-// workgroup of 8 waves per compute unit shares them (2 waves per SIMD, 8 row groups per LDS copy of the queries)
-constexpr int kWideScanWaves = 8;
-template <int DT, int NB, int SLOTS>
-__global__ __launch_bounds__(kWideScanWaves * kWave) void scan_topk_wide_kernel(const void* __restrict__ rows_, int64_t n, int dpad,
-                                                                                const float* __restrict__ qn, int nq_arg, int k,
-                                                                                uint32_t row_base, u64* __restrict__ partial,
-                                                                                int64_t partial_stride_q, const unsigned* __restrict__ qlist,
-                                                                                const unsigned* __restrict__ qcount_ptr, unsigned* __restrict__ merge_done,
-                                                                                u64* __restrict__ merged_keys, float* __restrict__ merged_dist,
-                                                                                int64_t* __restrict__ merged_rows, unsigned long long* __restrict__ count_total,
-                                                                                const uint32_t* __restrict__ dead) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    const int total = qcount_ptr ? (int)*qcount_ptr : nq_arg;
-    scan_topk_body<DT, NB, kWideRows, SLOTS, kWideScanWaves>(rows_, n, dpad, qn, total, k, row_base, partial, partial_stride_q, qlist, qcount_ptr != nullptr,
-                                                             merge_done, merged_keys, merged_dist, merged_rows, count_total, (int)blockIdx.x, (int)gridDim.x,
-                                                             reinterpret_cast<u64*>(smem_raw), dead);
-}
-
-// The squared-L2 scans: scan_topk_body under kMetricL2, dense queries only (an l2 index takes no filter leg, so
-// the list-driven fallback forms are not built).  Kernels of their own, so that every dot-product kernel stays the code it was.
-template <int DT, int NB, int NITER, int SLOTS>
-__global__ __launch_bounds__(256) void scan_topk_l2(const void* __restrict__ rows_, int64_t n, int dpad, const float* __restrict__ qn, int nq, int k,
-                                                    uint32_t row_base, u64* __restrict__ partial, int64_t partial_stride_q,
-                                                    const uint32_t* __restrict__ dead) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    scan_topk_body<DT, NB, NITER, SLOTS, 4, kMetricL2>(rows_, n, dpad, qn, nq, k, row_base, partial, partial_stride_q, nullptr, false, nullptr, nullptr, nullptr,
-                                                       nullptr, nullptr, (int)blockIdx.x, (int)gridDim.x, reinterpret_cast<u64*>(smem_raw), dead);
-}
-template <int DT, int NB, int SLOTS>
-__global__ __launch_bounds__(kWideScanWaves * kWave) void scan_topk_wide_l2(const void* __restrict__ rows_, int64_t n, int dpad, const float* __restrict__ qn,
-                                                                            int nq, int k, uint32_t row_base, u64* __restrict__ partial,
-                                                                            int64_t partial_stride_q, const uint32_t* __restrict__ dead) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    scan_topk_body<DT, NB, kWideRows, SLOTS, kWideScanWaves, kMetricL2>(rows_, n, dpad, qn, nq, k, row_base, partial, partial_stride_q, nullptr, false, nullptr,
-                                                                        nullptr, nullptr, nullptr, nullptr, (int)blockIdx.x, (int)gridDim.x,
-                                                                        reinterpret_cast<u64*>(smem_raw), dead);
-}
-
-// The list-driven squared-distance scan: the exact-scan fallback of an l2 index's filter pass, for the queries
-// whose candidate lists were truncated.  scan_topk_body under kMetricL2 walking the device-side queue four queries at a time
-// (the role is rare), its last block merging; rows of 1 .. 4 chunks per lane.  A kernel of its own: the dense scans above stay
-// the instantiations they were.
-template <int DT, int NITER, int SLOTS>
-__global__ __launch_bounds__(256) void sqd_listed_scan_kernel(const void* __restrict__ rows_, int64_t n, int dpad, const float* __restrict__ qn, int k,
-                                                              uint32_t row_base, u64* __restrict__ partial, int64_t partial_stride_q,
-                                                              const unsigned* __restrict__ qlist, const unsigned* __restrict__ qcount_ptr,
-                                                              unsigned* __restrict__ merge_done, u64* __restrict__ merged_keys,
-                                                              float* __restrict__ merged_dist, int64_t* __restrict__ merged_rows,
-                                                              unsigned long long* __restrict__ count_total, const uint32_t* __restrict__ dead) {
-    static_assert(NITER != kWideRows, "the squared-distance filter leg serves rows of 1 .. 4 chunks per lane");
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    scan_topk_body<DT, 4, NITER, SLOTS, 4, kMetricL2>(rows_, n, dpad, qn, (int)*qcount_ptr, k, row_base, partial, partial_stride_q, qlist, true, merge_done,
-                                                      merged_keys, merged_dist, merged_rows, count_total, (int)blockIdx.x, (int)gridDim.x,
-                                                      reinterpret_cast<u64*>(smem_raw), dead);
-}
-
-// ---------------------------------------------------------------------------------------------
-// finalize_fb_kernel: finalize and the exact-scan fallback of a filter pass in ONE launch (round 3: the fallback used to be a
-// launch of its own behind finalize — normally empty, still 4 us + a dependent-launch gap of ~10 us on every step).
-//   workgroups x < nq  : finalize_kernel's work for query x (share blockIdx.y of its candidates);
-//   workgroups x >= nq : the exact scan over the queries whose candidate lists were truncated (hit_cnt > cap_q).  They need
-//     nothing from the finalize workgroups: each derives the queue from the counters itself (same order in every workgroup)
-//     and leaves at once when it is empty — the normal case.  Otherwise: scan_topk_body over the queue, the last scan
-//     workgroup to finish merges the per-workgroup partials and writes the answers into the queries' slots.
-// k <= 64 only (one list slot per lane); wider k keeps the two launches.
-// ---------------------------------------------------------------------------------------------
-template <int DT, int NITER>
-__global__ __launch_bounds__(kFinThreads) void finalize_fb_kernel(const void* __restrict__ rows_, int dpad, const float* __restrict__ qn, const u64* __restrict__ hits,
-                                                                   const unsigned* __restrict__ hit_cnt, int cap_q, unsigned* __restrict__ flags, int k, float two_eps,
-                                                                   uint32_t row_base, u64* __restrict__ out_keys, unsigned long long* __restrict__ stats,
-                                                                   const float* __restrict__ two_eps_q, u64* __restrict__ part_keys, float* __restrict__ out_dist,
-                                                                   int64_t* __restrict__ out_rows, const float2* __restrict__ bmeta, int nq, int64_t n,
-                                                                   u64* __restrict__ fb_partial, int64_t fb_stride_q, unsigned* __restrict__ fb_done,
-                                                                   const uint32_t* __restrict__ dead) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    constexpr int kWavesHere = kFinThreads / kWave;
-    if ((int)blockIdx.x < nq) {
-        const int q = blockIdx.x;
-        const unsigned total = hit_cnt[q * kHitCntStride];
-        const unsigned part = blockIdx.y, nparts = gridDim.y;
-        if (total > (unsigned)cap_q) {  // the candidate list was truncated: the scan workgroups answer this query
-            if (threadIdx.x == 0 && part == 0) atomicOr(&flags[FLAG_NEED_FALLBACK], 1u);
-            return;
-        }
-        const float eps1 = bmeta ? two_eps_q[256 + q] : 0.5f * (two_eps_q ? two_eps_q[q] : two_eps);
-        const float bq = bmeta ? two_eps_q[512 + q] : 0.0f;
-        finalize_body<DT, NITER, 1>(rows_, dpad, qn + (int64_t)q * dpad, hits + (int64_t)q * cap_q, total, part, nparts, k, eps1, bq, bmeta, row_base,
-                                    out_keys ? out_keys + (int64_t)q * k : nullptr, out_dist ? out_dist + (int64_t)q * k : nullptr,
-                                    out_rows ? out_rows + (int64_t)q * k : nullptr, part_keys ? part_keys + ((int64_t)q * nparts + part) * k : nullptr, stats, dead);
-        return;
-    }
-    if (blockIdx.y != 0) return;
-    // the queue: queries with a truncated list, in query order (every scan workgroup computes the same list)
-    __shared__ unsigned s_fb[kTileQ];
-    __shared__ unsigned s_cnt[kWavesHere + 1];
-    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const bool over = tid < nq && hit_cnt[tid * kHitCntStride] > (unsigned)cap_q;   // (nq <= 256 < kFinThreads)
-    const u64 mask = __ballot(over);
-    if (lane == 0) s_cnt[wave] = (unsigned)__popcll(mask);
-    __syncthreads();
-    unsigned base = 0, total = 0;
-    for (int w = 0; w < kWavesHere; ++w) {
-        if (w < wave) base += s_cnt[w];
-        total += s_cnt[w];
-    }
-    if (total == 0) return;   // (uniform: nothing was truncated — the normal case)
-    if (over) s_fb[base + (unsigned)__popcll(mask & ((1ull << lane) - 1ull))] = (unsigned)tid;
-    __syncthreads();
-    // (4 queries per pass over the rows, not 8: the role is rare, and its query registers must not push the finalize role into scratch)
-    scan_topk_body<DT, 4, NITER, 1, kWavesHere>(rows_, n, dpad, qn, (int)total, k, row_base, fb_partial, fb_stride_q, s_fb, true, fb_done, out_keys, out_dist, out_rows,
-                                                 stats ? stats + 2 : nullptr, (int)blockIdx.x - nq, (int)gridDim.x - nq, reinterpret_cast<u64*>(smem_raw), dead);
-}
-
-// ---------------------------------------------------------------------------------------------
-// merge_keys_kernel: block b reduces in[b][0..m) to its k largest keys (descending) and writes
-// keys and/or (distance, row).  Used for the per-block partials of a scan, for the all-gathered
-// shard partials, and (m == k) to unpack final keys.
-// ---------------------------------------------------------------------------------------------
-template <int SLOTS, int METRIC>
-__device__ __forceinline__ void merge_keys_body(const u64* __restrict__ in, int64_t m, int64_t in_stride, int64_t seg_len,
-                                                int64_t seg_stride, int k, u64* __restrict__ out_keys, float* __restrict__ out_dist,
-                                                int64_t* __restrict__ out_rows, const unsigned* __restrict__ out_list,
-                                                const unsigned* __restrict__ count_ptr,
-                                                unsigned long long* __restrict__ count_total) {
-    const int lane = lane_id();
-    const int wave = (int)(threadIdx.x >> 6);
-    // LISTED (fallback queue): only the first *count_ptr blocks work, block i answers query out_list[i]
-    if (count_ptr) {
-        const unsigned cnt = *count_ptr;
-        if (blockIdx.x == 0 && threadIdx.x == 0 && count_total && cnt) atomicAdd(count_total, (unsigned long long)cnt);
-        if (blockIdx.x >= cnt) return;
-    }
-    const int64_t oblock = out_list ? (int64_t)out_list[blockIdx.x] : (int64_t)blockIdx.x;
-    const u64* src = in + (int64_t)blockIdx.x * in_stride;
-    WaveTopK<SLOTS> L;
-    L.init();
-    for (int64_t i0 = (int64_t)wave * kWave; i0 < m; i0 += 256) {
-        const int64_t i = i0 + lane;
-        // a query's m keys are m / seg_len runs of seg_len keys, seg_stride apart (one run when seg_len == m;
-        // one run per shard when the input is an all_gather of [B][k] partials)
-        const u64 cand = i < m ? src[(i / seg_len) * seg_stride + (i % seg_len)] : 0ull;
-        L.offer_lanes(cand, k, lane);
-    }
-    __shared__ u64 lds[4 * SLOTS * kWave];
-    store_list(lds, wave, 1, 0, lane, L);
-    __syncthreads();
-    if (wave != 0) return;
-    merge_lists(L, lds, 1, 4, 1, 0, k, lane);
-    const int64_t o = oblock * k;
-    write_ranks<SLOTS, METRIC>(L, k, lane, out_keys ? out_keys + o : nullptr, out_dist ? out_dist + o : nullptr, out_rows ? out_rows + o : nullptr);
-}
-template <int SLOTS>
-__global__ __launch_bounds__(256) void merge_keys_kernel(const u64* __restrict__ in, int64_t m, int64_t in_stride, int64_t seg_len,
-                                                         int64_t seg_stride, int k, u64* __restrict__ out_keys, float* __restrict__ out_dist,
-                                                         int64_t* __restrict__ out_rows, const unsigned* __restrict__ out_list,
-                                                         const unsigned* __restrict__ count_ptr,
-                                                         unsigned long long* __restrict__ count_total) {
-    merge_keys_body<SLOTS, kMetricDot>(in, m, in_stride, seg_len, seg_stride, k, out_keys, out_dist, out_rows, out_list, count_ptr, count_total);
-}
-// the same merge for keys of squared-L2 scores: the distance written is 0 - score
-template <int SLOTS>
-__global__ __launch_bounds__(256) void merge_keys_l2(const u64* __restrict__ in, int64_t m, int64_t in_stride, int64_t seg_len, int64_t seg_stride, int k,
-                                                     u64* __restrict__ out_keys, float* __restrict__ out_dist, int64_t* __restrict__ out_rows) {
-    merge_keys_body<SLOTS, kMetricL2>(in, m, in_stride, seg_len, seg_stride, k, out_keys, out_dist, out_rows, nullptr, nullptr, nullptr);
-}
-
-// ---------------------------------------------------------------------------------------------
-// IVF (coarse lists + exact scores), SURVEY.md §8(f)4 / BASELINE config 5.
-// gather_rows_kernel: rows_ivf[i] = rows[perm[i]] (rows regrouped by coarse list), one wave per row.
-// widen_rows_kernel : stored rows -> fp32 [n][dim] (index build reads the corpus back through it).
-// ivf_scan_kernel   : block (x, b) scans slice x%split of the list that query b probes at rank x/split,
-//                     canonical exact scores, per-wave top-k, keys carry the ORIGINAL row slot.
-// ---------------------------------------------------------------------------------------------
-// perm_check_kernel: sets *bad when any perm[i] lies outside [0, n) (codd_knn_ivf_install trusts no caller-built table:
-// gather_rows_kernel and ivf_scan_kernel index rows with these values)
-__global__ __launch_bounds__(256) void perm_check_kernel(const int64_t* __restrict__ perm, int64_t n, unsigned* __restrict__ bad) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n && (perm[i] < 0 || perm[i] >= n)) atomicOr(bad, 1u);
-}
-
-__global__ __launch_bounds__(256) void gather_rows_kernel(const uint4* __restrict__ src, const int64_t* __restrict__ perm, int64_t n,
-                                                          int chunks_per_row, uint4* __restrict__ dst, uint32_t* __restrict__ ids) {
-    const int lane = lane_id();
-    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= n) return;
-    const int64_t from = perm[r];
-    for (int j = lane; j < chunks_per_row; j += kWave) dst[r * chunks_per_row + j] = src[from * chunks_per_row + j];
-    if (lane == 0) ids[r] = (uint32_t)from;
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// int8 shadow (half the bytes of the bf16 shadow).  Row r is stored as round(c_i / scale_b), scale_b = the largest |c_i| of
-// its 32-row block / 127 (rscale[] holds it once per row), in the same fragment order as the bf16 shadow with 16-element pieces and 128-element K-steps.  The
-// filter's error bound needs |c - c~| for the worst row: every wave folds its row's error norm into *eps_r (ordered bits).
-// ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t quantize4(const float (&v)[4], float inv_scale, float scale, float& err2) {
-    uint32_t packed = 0;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        float t = __builtin_rintf(v[e] * inv_scale);
-        t = fminf(fmaxf(t, -127.0f), 127.0f);
-        const float d = v[e] - t * scale;
-        err2 = __builtin_fmaf(d, d, err2);
-        packed |= ((uint32_t)(int)t & 0xffu) << (8 * e);
-    }
-    return packed;
-}
-// One workgroup quantises one 32-row corpus block (a wave's rows in the filter GEMMs) with ONE scale for the whole block:
-// max |c_i| over its 32 rows / 127.  (Round 1 scaled every row by its own maximum.  A scale that is uniform inside a block
-// lets the filter's epilogue test accumulators against an integer threshold before any conversion; the price, a coarser
-// grid for rows whose own maximum is smaller, is in the measured error norm *eps_r like every other quantisation error.)
-// Pass 1 finds the block maximum, pass 2 quantises the block in two halves of 16 rows (4 rows per wave), collects each half in
-// LDS and writes its pieces out in fragment order: 16 consecutive lanes = the 16 rows of one piece column = 256 contiguous
-// bytes (a wave per row writing its own 16-byte pieces, 256 bytes apart, ran at a tenth of the HBM rate).
-template <int DT>
-__global__ __launch_bounds__(256) void shadow8_from_rows_kernel(const void* __restrict__ rows_, int64_t first32, int64_t n, int dpad, int dpad8,
-                                                                uint4* __restrict__ shadow8, float* __restrict__ rscale,
-                                                                float2* __restrict__ bmeta) {
-    constexpr int kRowDwords = 516;  // 512 + 4: sixteen rows read column-wise hit 64 different banks
-    __shared__ __attribute__((aligned(16))) uint32_t tile[16 * kRowDwords];
-    __shared__ float s_max[4];
-    __shared__ float s_err[4];
-    const int lane = lane_id(), wave = (int)(threadIdx.x >> 6);
-    const int64_t row32 = first32 + (int64_t)blockIdx.x * 32;
-    const int nch = dpad >> 2, nch8 = dpad8 >> 2, nsteps8 = dpad8 >> 7;
-    const int nit = (nch8 + kWave - 1) / kWave;  // chunks of 4 elements per lane and row
-    // chunk j = lane + 64 * it of a row (zeros past the row's end and for rows past n)
-    auto load_chunk = [&](int64_t row, int it, float (&v)[4]) __attribute__((always_inline)) {
-        const int j = lane + kWave * it;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = 0.0f;
-        if (j < nch && row < n) {
-            if (DT == DT_F32) {
-                const float4 x = reinterpret_cast<const float4*>(rows_)[row * (int64_t)nch + j];
-                v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
-            } else {
-                const uint2 x = reinterpret_cast<const uint2*>(rows_)[row * (int64_t)nch + j];
-                const uint16_t hb[4] = {(uint16_t)(x.x & 0xffffu), (uint16_t)(x.x >> 16), (uint16_t)(x.y & 0xffffu), (uint16_t)(x.y >> 16)};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = DT == DT_BF16 ? __uint_as_float((uint32_t)hb[e] << 16) : f16_bits_to_f32(hb[e]);
-            }
-        }
-    };
-    // pass 1: the block's largest magnitude.  Chunk-major, the wave's 8 rows inside: eight independent loads in flight per
-    // lane (row-major with one row at a time, the kernel was a chain of HBM round trips: 26 ms for 10M x 768 rows)
-    float vmax = 0.0f;
-    for (int it = 0; it < nit; ++it) {
-        float v[8][4];
-#pragma unroll
-        for (int rr = 0; rr < 8; ++rr) load_chunk(row32 + wave * 8 + rr, it, v[rr]);
-#pragma unroll
-        for (int rr = 0; rr < 8; ++rr)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) vmax = fmaxf(vmax, fabsf(v[rr][e]));
-    }
-    vmax = butterfly_max(vmax);
-    if (lane == 0) s_max[wave] = vmax;
-    __syncthreads();
-    vmax = fmaxf(fmaxf(s_max[0], s_max[1]), fmaxf(s_max[2], s_max[3]));
-    const float scale = vmax > 0.0f ? vmax / 127.0f : 1.0f, inv_scale = 1.0f / scale;
-    // pass 2: quantise (the rows come from L2 this time), 16 rows at a time, 4 rows per wave; rows wider than the tile (2,048
-    // elements) in column slices of kTileDwords dwords.  The scale above and each row's error norm below span the WHOLE row.
-    constexpr int kTileDwords = 512;
-    float wave_err = 0.0f;  // largest error norm among this wave's rows
-    for (int half = 0; half < 2; ++half) {
-        const int64_t row16 = row32 + 16 * half;
-        float err2[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        for (int c0 = 0; c0 < nch8; c0 += kTileDwords) {
-            const int it1 = (c0 + kTileDwords) / kWave < nit ? (c0 + kTileDwords) / kWave : nit;
-            for (int it = c0 / kWave; it < it1; ++it) {
-                float v[4][4];
-#pragma unroll
-                for (int rr = 0; rr < 4; ++rr) load_chunk(row16 + wave * 4 + rr, it, v[rr]);
-                const int j = lane + kWave * it;
-#pragma unroll
-                for (int rr = 0; rr < 4; ++rr)
-                    if (j < nch8) tile[(wave * 4 + rr) * kRowDwords + (j - c0)] = quantize4(v[rr], inv_scale, scale, err2[rr]);  // (rows past n, chunks past the row: zeros)
-            }
-            __syncthreads();
-            // piece (c16, r) of the half block: 16 bytes of row r at byte 16*c16 (c16 counted from the slice's first piece)
-            const int npieces = (nch8 - c0 < kTileDwords ? nch8 - c0 : kTileDwords) >> 2;
-            for (int p = (int)threadIdx.x; p < 16 * npieces; p += 256) {
-                const int r = p & 15, c16 = p >> 4;
-                shadow8[codd::shadow_piece_index(row16 + r, (c0 >> 2) + c16, nsteps8)] = *reinterpret_cast<const uint4*>(&tile[r * kRowDwords + c16 * 4]);
-            }
-            __syncthreads();
-        }
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) {
-            const int64_t row = row16 + wave * 4 + rr;
-            const float e2 = butterfly_sum(err2[rr]);
-            if (row < n) {
-                if (lane == 0) rscale[row] = scale;
-                wave_err = fmaxf(wave_err, __builtin_sqrtf(e2) * 1.0001f + 1e-7f);  // inflated a little: the norm itself was accumulated in fp32
-            }
-        }
-    }
-    // The block's meta data: its scale and the largest quantisation error norm |c - c~| among its rows.  The filter's bound is
-    // evaluated PER BLOCK with this norm (round 2 folded every row's norm into one device-wide maximum that could only grow: one
-    // badly quantising row widened every query's slack for the life of the index); the device-wide maximum that the
-    // first-generation kernels and the host's "is int8 usable at all" test still use is re-derived from these after every
-    // build (eps_max_kernel), so it follows the rows that are stored NOW.
-    if (lane == 0) s_err[wave] = wave_err;
-    __syncthreads();
-    if (threadIdx.x == 0 && row32 < n) bmeta[row32 >> 5] = make_float2(scale, fmaxf(fmaxf(s_err[0], s_err[1]), fmaxf(s_err[2], s_err[3])));
-}
-
-// eps_max_kernel: *eps_r_bits = the largest block error norm over blocks [0, nblocks) (one workgroup; after every shadow build)
-// eps_r_bits[1] = how many blocks lie above `wide` (the host's "int8 bound useless" level): the per-block kernels only pay for those blocks
-__global__ __launch_bounds__(1024) void eps_max_kernel(const float2* __restrict__ bmeta, int64_t nblocks, unsigned* __restrict__ eps_r_bits, float wide) {
-    __shared__ float s_part[16];
-    __shared__ unsigned s_wide;
-    if (threadIdx.x == 0) s_wide = 0u;
-    __syncthreads();
-    float m = 0.0f;
-    unsigned nw = 0;
-    for (int64_t i = threadIdx.x; i < nblocks; i += 1024) {
-        const float e = bmeta[i].y;
-        m = fmaxf(m, e);
-        nw += e > wide ? 1u : 0u;
-    }
-    m = butterfly_max(m);
-    if (nw) atomicAdd(&s_wide, nw);
-    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 16; ++w) m = fmaxf(m, s_part[w]);
-        eps_r_bits[0] = __float_as_uint(m);
-        eps_r_bits[1] = s_wide;
-    }
-}
-
-// prep_queries_kernel for the int8 filter: qn as always; the query quantised like a row (qfrag8, scale in qmeta[q]);
-// qmeta[256 + q] = 2 * eps(q) with eps(q) = |q - q~| (1.01 + eps_r) + 1.001 eps_r + 2e-6 >= |<q~, c~> - <q, c>| for every
-// stored row c (|c| <= 1.004 whatever the storage type, |c - c~| <= eps_r, |q| <= 1 + 1e-6; the integer accumulation
-// is exact and the two scale multiplications cost < 4e-7)
-__global__ __launch_bounds__(256) void prep_queries8_kernel(const float* __restrict__ in, int B, int d, int dpad, int dpad8,
-                                                            float* __restrict__ qn, uint32_t* __restrict__ qfrag8, float* __restrict__ qmeta,
-                                                            const unsigned* __restrict__ eps_r_bits, unsigned* __restrict__ ctl, int ctl_words,
-                                                            float slack_scale) {
-    const int lane = lane_id();
-    const int q = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
-    for (int i = (int)blockIdx.x * 256 + (int)threadIdx.x; i < ctl_words; i += (int)gridDim.x * 256) ctl[i] = 0u;
-    const int nch = dpad >> 2, nch8 = dpad8 >> 2;
-    if (q >= B) {
-        for (int j = lane; j < nch8; j += kWave) qfrag8[codd::qfrag_piece_index(q, j >> 2) * 4 + (j & 3)] = 0u;
-        if (lane == 0) { qmeta[q] = 0.0f; qmeta[256 + q] = 0.0f; qmeta[512 + q] = 0.0f; qmeta[768 + q] = 0.0f; }
-        return;
-    }
-    const float* x = in + (int64_t)q * d;
-    int sh;
-    const float nrm = canonical_norm(x, d, nch, lane, sh);
-    const bool zero_row = !(nrm > 0.0f) || !(nrm < INFINITY);
-    float vmax = 0.0f;
-    for (int j = lane; j < nch; j += kWave) {
-        float v[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int i = j * 4 + e;
-            const float t = i < d ? x[i] : 0.0f;
-            v[e] = zero_row ? 0.0f : scaled(t, sh) / nrm;
-            vmax = fmaxf(vmax, fabsf(v[e]));
-        }
-        reinterpret_cast<float4*>(qn)[(int64_t)q * nch + j] = make_float4(v[0], v[1], v[2], v[3]);
-    }
-    vmax = butterfly_max(vmax);
-    const float scale = vmax > 0.0f ? vmax / 127.0f : 0.0f, inv_scale = vmax > 0.0f ? 127.0f / vmax : 0.0f;
-    float err2 = 0.0f;
-    for (int j = lane; j < nch8; j += kWave) {
-        float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        if (j < nch) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int i = j * 4 + e;
-                const float t = i < d ? x[i] : 0.0f;
-                v[e] = zero_row ? 0.0f : scaled(t, sh) / nrm;
-            }
-        }
-        qfrag8[codd::qfrag_piece_index(q, j >> 2) * 4 + (j & 3)] = quantize4(v, inv_scale, scale, err2);
-    }
-    err2 = butterfly_sum(err2);
-    if (lane == 0) {
-        const float eq = __builtin_sqrtf(err2) * 1.0001f + 1e-7f, er = __uint_as_float(*eps_r_bits);
-        qmeta[q] = scale;
-        qmeta[256 + q] = slack_scale * 2.0f * (eq * (1.01f + er) + 1.001f * er + 2e-6f);
-        // the same bound split by what it depends on: eps(q, block) = A(q) + B(q) * e_block, e_block = the block's own error norm
-        // (bmeta[].y) in place of the device-wide maximum er — what i8_tile_kernel and finalize evaluate per 32-row block
-        qmeta[512 + q] = slack_scale * (eq * 1.01f + 2e-6f);
-        qmeta[768 + q] = slack_scale * (eq + 1.001f);
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// The int8 filter leg of an ip or l2 index ("space_filter"): rows and queries of ANY norm, so the two constants
-// above that stand for |c| and |q| of unit vectors become measured quantities.
-// row_sqnorm_kernel<DT>: one wave per stored row of [first, first + m): rnorm2[row] = the canonical sum of squares of the row AS
-// STORED (DESIGN.md §3's chain over chunks of RowTraits<DT>::E elements, the butterfly, + 0.0f), and *rmax_bits = max(*rmax_bits,
-// R(row)) with R(row) = sqrt(rnorm2) * 1.0001 + 1e-7 >= |c|_2: the chain and the root are off by < 2e-5 relative, squares that
-// underflow by < sqrt(dpad) 2^-63 absolute.  The bits of a non-negative float order like the float; a sum that overflowed (or a
-// row that is not a number) leaves +inf there, and every query of the index is then answered by the exact re-score of all rows.
-// ---------------------------------------------------------------------------------------------------------------
-template <int DT>
-__global__ __launch_bounds__(256) void row_sqnorm_kernel(const void* __restrict__ rows_, int64_t first, int64_t m, int dpad, float* __restrict__ rnorm2,
-                                                         unsigned* __restrict__ rmax_bits) {
-    typedef RowTraits<DT> RT;
-    constexpr int E = RT::E;
-    const int lane = lane_id();
-    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= m) return;
-    const int64_t row = first + r;
-    const int nchunks = dpad / E;
-    const uint4* p = reinterpret_cast<const uint4*>(rows_) + row * (int64_t)nchunks;
-    float a = 0.0f;
-    for (int j = lane; j < nchunks; j += kWave) {
-        float w[E];
-        RT::widen(p[j], w);
-#pragma unroll
-        for (int e = 0; e < E; ++e) a = __builtin_fmaf(w[e], w[e], a);
-    }
-    const float n2 = butterfly_sum(a);
-    if (lane == 0) {
-        rnorm2[row] = n2;
-        float R = __builtin_sqrtf(n2) * 1.0001f + 1e-7f;
-        if (!(R < INFINITY)) R = INFINITY;
-        atomicMax(rmax_bits, __float_as_uint(R));
-    }
-}
-
-// prep_queries8_raw_kernel: prep_queries8_kernel for an ip (l2 = 0) or l2 (l2 = 1) index.  qn = the query as raw_rows_kernel<f32>
-// cleans it (what the exact kernels consume); qfrag8 / qmeta[q]: the same vector quantised with its own scale s_q; qmeta[512 + q]
-// = n_q, its canonical sum of squares; qmeta[256 + q] = 2 eps(q) with, for every stored row c (DESIGN.md §21 derives both),
-//   e_q = |q - q~| measured, + 2^-23 Q for the fp32 rounding of the measurement, e_r likewise from the rows' measured *eps_r_bits,
-//   Q >= |q|, R = *rmax_bits >= |c|, m = dpad / 64 the length of a lane's chain, u = 2^-24:
-//   ip: eps = e_q (R + e_r) + Q e_r + (m + 9) u (Q + e_q)(R + e_r)               >= |acc s_blk s_q - score(q, c)|
-//   l2: eps = 2 (e_q (R + e_r) + Q e_r) + (2 m + 18) u (Q + R + e_q + e_r)^2     >= |fma(acc s_blk, 2 s_q, -rnorm2) - n_q - score(q, c)|
-// every term rounded upward; +inf when R or Q is not finite or the product term leaves [2^-100, 2^100] (the threshold is then
-// -inf, every row a hit, and the exact re-score or the overflow fallback answers the query).
-__global__ __launch_bounds__(256) void prep_queries8_raw_kernel(const float* __restrict__ in, int B, int d, int dpad, int dpad8, float* __restrict__ qn,
-                                                                uint32_t* __restrict__ qfrag8, float* __restrict__ qmeta,
-                                                                const unsigned* __restrict__ eps_r_bits, const unsigned* __restrict__ rmax_bits,
-                                                                unsigned* __restrict__ ctl, int ctl_words, int l2) {
-    const int lane = lane_id();
-    const int q = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
-    for (int i = (int)blockIdx.x * 256 + (int)threadIdx.x; i < ctl_words; i += (int)gridDim.x * 256) ctl[i] = 0u;
-    const int nch = dpad >> 2, nch8 = dpad8 >> 2;
-    if (q >= B) {
-        for (int j = lane; j < nch8; j += kWave) qfrag8[codd::qfrag_piece_index(q, j >> 2) * 4 + (j & 3)] = 0u;
-        if (lane == 0) { qmeta[q] = 0.0f; qmeta[256 + q] = 0.0f; qmeta[512 + q] = 0.0f; qmeta[768 + q] = 0.0f; }
-        return;
-    }
-    const float* x = in + (int64_t)q * d;
-    bool bad = false, any = false;
-    for (int i = lane; i < d; i += kWave) {
-        const float v = x[i];
-        bad = bad || !(fabsf(v) < INFINITY);   // (NaN compares false too)
-        any = any || v != 0.0f;
-    }
-    const bool zero_row = __ballot(bad) != 0ull || __ballot(any) == 0ull;
-    float vmax = 0.0f, a2 = 0.0f;
-    for (int j = lane; j < nch; j += kWave) {
-        float v[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int i = j * 4 + e;
-            v[e] = (i < d && !zero_row) ? x[i] : 0.0f;
-            vmax = fmaxf(vmax, fabsf(v[e]));
-            a2 = __builtin_fmaf(v[e], v[e], a2);
-        }
-        reinterpret_cast<float4*>(qn)[(int64_t)q * nch + j] = make_float4(v[0], v[1], v[2], v[3]);
-    }
-    vmax = butterfly_max(vmax);
-    const float nq2 = butterfly_sum(a2);
-    const float scale = vmax > 0.0f ? vmax / 127.0f : 0.0f, inv_scale = vmax > 0.0f ? 127.0f / vmax : 0.0f;
-    float err2 = 0.0f;
-    for (int j = lane; j < nch8; j += kWave) {
-        float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        if (j < nch) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int i = j * 4 + e;
-                v[e] = (i < d && !zero_row) ? x[i] : 0.0f;
-            }
-        }
-        qfrag8[codd::qfrag_piece_index(q, j >> 2) * 4 + (j & 3)] = quantize4(v, inv_scale, scale, err2);
-    }
-    err2 = butterfly_sum(err2);
-    if (lane == 0) {
-        constexpr float up = 1.0001f, u = 5.9604645e-8f, u2 = 1.1920929e-7f;   // 2^-24, 2^-23
-        const float m = (float)(dpad >> 6);
-        const float R = __uint_as_float(*rmax_bits);
-        const float Q = __builtin_sqrtf(nq2) * up + 1e-7f;
-        const float eq = __builtin_sqrtf(err2) * up + u2 * Q + 1e-7f;
-        const float er = __uint_as_float(*eps_r_bits) * up + u2 * R;
-        const float a = (Q + eq) * up, b = (R + er) * up;
-        const float quant = (eq * b + Q * er * up) * up;
-        float eps, range;
-        if (l2) {
-            const float s = (a + b) * up;
-            range = s * s;
-            eps = (2.0f * quant + (2.0f * m + 18.0f) * u * 1.001f * range) * up + 1e-30f;
-        } else {
-            range = a * b;
-            eps = (quant + (m + 9.0f) * u * 1.001f * range) * up + 1e-30f;
-        }
-        if (!(range >= kNormBandLo && range <= kNormBandHi) || !(eps < INFINITY)) eps = INFINITY;
-        qmeta[q] = scale;
-        qmeta[256 + q] = 2.0f * eps;
-        qmeta[512 + q] = nq2;
-        qmeta[768 + q] = Q;
-    }
-}
-
-// codd_knn_filter_slack: out[q] = eps(q) of the device-wide bound, from the 2 eps(q) a preparation kernel left at two_eps_q[q]
-__global__ __launch_bounds__(256) void filter_slack_kernel(const float* __restrict__ two_eps_q, int B, float* __restrict__ out) {
-    const int q = (int)threadIdx.x;
-    if (q < B) out[q] = 0.5f * two_eps_q[q];
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// small_batch_kernel<DT, NITER, NS>: ONE query answered in ONE launch (BASELINE configs[1]: 1M x 768, B = 1).  The filter chain
-// of a batch is six dependent launches (query preparation, sample, thresholds, filter, finalize, merge); at B = 1 over 1M rows
-// they cost as much again as streaming the int8 shadow once.  Here:
-//   every workgroup : wave 0 quantises the query (same arithmetic as prep_queries8_kernel) into LDS while the other waves' first
-//     loads are already in flight; then every wave streams its share of the int8 shadow — 16 rows x dpad8 bytes at a time
-//     (2 NS contiguous 1-KiB chunks of the fragment order, the next unit's loads issued before this unit's arithmetic);
-//     lane (kq, r) holds 16 elements of row r: v_dot4 against the query's 16 bytes from LDS, two cross-lane adds — keeps
-//     its best 64 approximate scores (WaveTopK) and publishes the best kSbKeep of them plus `dropmax`, the best key it did NOT
-//     publish (0: none);
-//   the workgroup that finishes LAST (device-scope fence + arrival ticket) : finalize_body over the published candidates — the
-//     k best approximate ones re-scored exactly give L' <= s_k, every row whose approximate score is >= L' - eps(q) is
-//     re-scored exactly (canonical fp32 expression), top-k written.  MARGIN TEST: if some wave's dropmax is >= L' - eps(q) a
-//     candidate may have been dropped: the query goes to the exact-scan fallback queue (the list-driven scan launch behind
-//     this kernel: normally empty).  No thresholds, no sample pass: the bound is the same eps(q) = |q - q~| (1.01 + eps_r) +
-//     1.001 eps_r + 2e-6 as the int8 filter's (device-wide eps_r).
-// Results are bit-identical to every other path: the survivors' scores are the canonical ones.
-// ---------------------------------------------------------------------------------------------------------------
-#if !CODD_EXPERIMENTS && (defined(CODD_SB_EXP_NOOFFER) || defined(CODD_SB_EXP_NOSTREAM) || defined(CODD_SB_EXP_NOFINAL))
-#error "the CODD_SB_EXP_* switches return wrong results: they exist only in -DCODD_EXPERIMENTS=1 builds (build_variant)"
-#endif
-constexpr int kSbKeep = 8;        // keys a wave publishes
-constexpr int kSbThreads = kFinThreads;
-static_assert(kSbThreads == 512, "finalize_body's workgroup");
-template <int DT, int NITER, int NS>
-__global__ __launch_bounds__(kSbThreads) void small_batch_kernel(const uint4* __restrict__ shadow8, const float2* __restrict__ bmeta, const void* __restrict__ rows_,
-                                                                  int64_t n, int d, int dpad, const float* __restrict__ in, int k, uint32_t row_base,
-                                                                  const unsigned* __restrict__ eps_r_bits, float* __restrict__ qn, u64* __restrict__ cand,
-                                                                  u64* __restrict__ dropmax, unsigned* __restrict__ ticket, unsigned* __restrict__ fb_count,
-                                                                  unsigned* __restrict__ fb_list, u64* __restrict__ out_keys, float* __restrict__ out_dist,
-                                                                  int64_t* __restrict__ out_rows, unsigned long long* __restrict__ stats,
-                                                                  const uint32_t* __restrict__ dead) {
-    constexpr int kWaves = kSbThreads / kWave;
-    constexpr int kDpad8 = NS * 128;
-    typedef unsigned sb_u32x4 __attribute__((ext_vector_type(4)));
-    __shared__ __attribute__((aligned(16))) unsigned char s_q8[kDpad8];   // the query's int8 bytes, natural order
-    __shared__ float s_qscale, s_eps, s_lo;
-    __shared__ unsigned s_last;
-    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int nch = dpad >> 2;
-    const int64_t G = gridDim.x;
-    const int64_t nunits = (n + 15) >> 4;
-    const int64_t W = G * kWaves;
-    const int64_t wave_global = (int64_t)blockIdx.x * kWaves + wave;
-
-    // the chunks of unit u (16 rows): read-once stream, non-temporal.  A unit index past the end is clamped (the loads are
-    // unconditional: a conditional load makes hipcc drain the queue at every join); its results are never offered.
-    auto load_unit = [&](sb_u32x4(&c)[2 * NS], float& scale, int64_t u) __attribute__((always_inline)) {
-        const int64_t uu = u < nunits ? u : nunits - 1;
-        scale = bmeta[uu >> 1].x;   // (in front of the chunks: the queue retires in order, a load issued behind them would drain the prefetch)
-        const uint4* src = shadow8 + ((uu >> 1) * NS * 4 + (uu & 1) * 2) * 64 + lane;   // chunk (s, ks) at + (s * 4 + ks) * 64 pieces
-#pragma unroll
-        for (int j = 0; j < 2 * NS; ++j) c[j] = __builtin_nontemporal_load(reinterpret_cast<const sb_u32x4*>(src + ((j >> 1) * 4 + (j & 1)) * 64));
-    };
-    sb_u32x4 ca[2 * NS], cb[2 * NS];
-    float sa = 0.0f, sb = 0.0f;
-    int64_t u = wave_global;
-    load_unit(ca, sa, u);
-
-    // ---- the query: normalise (block 0 also stores qn: the last workgroup and the fallback scan read it) and quantise ----
-    if (wave == 0) {
-        int sh;
-        const float nrm = canonical_norm(in, d, nch, lane, sh);
-        const bool zero_row = !(nrm > 0.0f) || !(nrm < INFINITY);
-        float vmax = 0.0f;
-        for (int j = lane; j < nch; j += kWave) {
-            float v[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int i = j * 4 + e;
-                const float t = i < d ? in[i] : 0.0f;
-                v[e] = zero_row ? 0.0f : scaled(t, sh) / nrm;
-                vmax = fmaxf(vmax, fabsf(v[e]));
-            }
-            if (blockIdx.x == 0) reinterpret_cast<float4*>(qn)[j] = make_float4(v[0], v[1], v[2], v[3]);
-        }
-        vmax = butterfly_max(vmax);
-        const float scale = vmax > 0.0f ? vmax / 127.0f : 0.0f, inv_scale = vmax > 0.0f ? 127.0f / vmax : 0.0f;
-        float err2 = 0.0f;
-        for (int j = lane; j < kDpad8 / 4; j += kWave) {
-            float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-            if (j < nch) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int i = j * 4 + e;
-                    const float t = i < d ? in[i] : 0.0f;
-                    v[e] = zero_row ? 0.0f : scaled(t, sh) / nrm;
-                }
-            }
-            reinterpret_cast<uint32_t*>(s_q8)[j] = quantize4(v, inv_scale, scale, err2);
-        }
-        err2 = butterfly_sum(err2);
-        if (lane == 0) {
-            const float eq = __builtin_sqrtf(err2) * 1.0001f + 1e-7f, er = __uint_as_float(*eps_r_bits);
-            s_qscale = scale;
-            s_eps = eq * (1.01f + er) + 1.001f * er + 2e-6f;
-        }
-    }
-    __syncthreads();
-    const float qscale = s_qscale;
-
-    // ---- the stream ----
-    WaveTopK<1> L;
-    L.init();
-    const int kq = lane >> 4, r = lane & 15;
-    auto score_unit = [&](const sb_u32x4(&c)[2 * NS], float scale, int64_t uu) __attribute__((always_inline)) {
-        int acc = 0;
-#pragma unroll
-        for (int j = 0; j < 2 * NS; ++j) {
-            const uint4 b = *reinterpret_cast<const uint4*>(s_q8 + j * 64 + kq * 16);
-            acc = __builtin_amdgcn_sdot4((int)c[j][0], (int)b.x, acc, false);
-            acc = __builtin_amdgcn_sdot4((int)c[j][1], (int)b.y, acc, false);
-            acc = __builtin_amdgcn_sdot4((int)c[j][2], (int)b.z, acc, false);
-            acc = __builtin_amdgcn_sdot4((int)c[j][3], (int)b.w, acc, false);
-        }
-        acc += __shfl_xor(acc, 16);
-        acc += __shfl_xor(acc, 32);
-        const int64_t block = uu >> 1;
-        const int64_t row = (block << 5) + 16 * (uu & 1) + r;
-        const float score = (float)acc * scale * qscale;
-        // (a deleted row is no candidate: it would only crowd the wave's kSbKeep published keys and trip the margin test)
-        const bool live = lane < 16 && row < n && !(dead && row_dead(dead, (uint32_t)row));
-        const u64 key = live ? make_key(score, (uint32_t)row) : 0ull;
-#ifdef CODD_SB_EXP_NOOFFER
-        asm volatile("" ::"v"(key));  // diagnostic: scores computed, no top-k insert
-#else
-        L.offer_lanes(key, kWave, lane);
-#endif
-    };
-#ifdef CODD_SB_EXP_NOSTREAM
-    u = nunits;  // diagnostic: no stream at all
-#endif
-    while (u < nunits) {
-        load_unit(cb, sb, u + W);
-        score_unit(ca, sa, u);
-        u += W;
-        if (u >= nunits) break;
-        load_unit(ca, sa, u + W);
-        score_unit(cb, sb, u);
-        u += W;
-    }
-
-    // ---- publish: the wave's best kSbKeep keys and the best key it keeps to itself ----
-    if (lane < kSbKeep) cand[wave_global * kSbKeep + lane] = L.v[0];
-    const u64 dropped = readlane_u64(L.v[0], kSbKeep);
-    if (lane == 0) dropmax[wave_global] = dropped;
-
-    // ---- the last workgroup to arrive answers the query ----
-    __threadfence();
-    __syncthreads();
-    if (tid == 0) s_last = atomicAdd(ticket, 1u) == (unsigned)(G - 1) ? 1u : 0u;
-    __syncthreads();
-    if (!s_last) return;
-    __threadfence();
-#ifdef CODD_SB_EXP_NOFINAL
-    if (tid == 0) { *ticket = 0u; *fb_count = 0u; }
-    return;  // diagnostic: nothing behind the arrival ticket (results are garbage)
-#endif
-    if (tid == 0) {
-        *ticket = 0u;    // (the next search finds the ticket at zero: no clearing launch)
-        *fb_count = 0u;  // (the fallback queue of THIS search starts empty; the scan behind this kernel reads it)
-    }
-    __syncthreads();
-    finalize_body<DT, NITER, 1>(rows_, dpad, qn, cand, (unsigned)(W * kSbKeep), 0u, 1u, k, s_eps, 0.0f, nullptr, row_base, out_keys, out_dist, out_rows, nullptr, stats,
-                                dead, &s_lo);
-    // margin test: could a wave have kept a row to itself that belongs among the survivors?
-    const float lo = s_lo;
-    unsigned bad = 0;
-    for (int64_t i = tid; i < W; i += kSbThreads) {
-        const u64 dm = dropmax[i];
-        if (dm && key_score(dm) >= lo) bad = 1u;
-    }
-    if (__syncthreads_or((int)bad) && tid == 0) fb_list[atomicAdd(fb_count, 1u)] = 0u;
-}
-
-// row_norm_check_kernel: largest | |c| - 1 | over stored rows [first, first + n) that are not all-zero, folded into *dev_bits
-// (non-negative floats order as their bits).  codd_knn_load_rows trusts nothing it is handed: both filters' bounds assume unit
-// rows, and rows written with normalize = 0 (or a damaged rows.bin) must switch them off, not return wrong neighbours.
-template <int DT>
-__global__ __launch_bounds__(256) void row_norm_check_kernel(const void* __restrict__ rows_, int64_t first, int64_t n, int dpad,
-                                                             unsigned* __restrict__ dev_bits) {
-    typedef RowTraits<DT> RT;
-    constexpr int E = RT::E;
-    const int lane = lane_id();
-    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= n) return;
-    const int nchunks = dpad / E;
-    const uint4* p = reinterpret_cast<const uint4*>(rows_) + (first + r) * (int64_t)nchunks;
-    float acc = 0.0f;
-    for (int j = lane; j < nchunks; j += kWave) {
-        float w[E];
-        RT::widen(p[j], w);
-#pragma unroll
-        for (int e = 0; e < E; ++e) acc = __builtin_fmaf(w[e], w[e], acc);
-    }
-    const float nrm = __builtin_sqrtf(butterfly_sum(acc));
-    if (lane == 0 && nrm != 0.0f) {
-        const float dev = nrm == nrm ? fabsf(nrm - 1.0f) : INFINITY;  // NaN rows count as infinitely far from unit
-        atomicMax(dev_bits, __float_as_uint(dev));
-    }
-}
-
-template <int DT>
-__global__ __launch_bounds__(256) void widen_rows_kernel(const void* __restrict__ rows_, int64_t first, int64_t n, int dim, int dpad,
-                                                         float* __restrict__ out) {
-    typedef RowTraits<DT> RT;
-    constexpr int E = RT::E;
-    const int lane = lane_id();
-    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= n) return;
-    const int nchunks = dpad / E;
-    const uint4* p = reinterpret_cast<const uint4*>(rows_) + (first + r) * (int64_t)nchunks;
-    for (int j = lane; j < nchunks; j += kWave) {
-        float w[E];
-        RT::widen(p[j], w);
-#pragma unroll
-        for (int e = 0; e < E; ++e)
-            if (j * E + e < dim) out[r * (int64_t)dim + j * E + e] = w[e];
-    }
-}
-
-template <int DT, int NITER, int SLOTS>
-__global__ __launch_bounds__(256) void ivf_scan_kernel(const void* __restrict__ rows_, const uint32_t* __restrict__ ids,
-                                                       const int64_t* __restrict__ offsets, const u64* __restrict__ probe_keys,
-                                                       int nprobe, int split, int dpad, const float* __restrict__ qn, int k,
-                                                       uint32_t row_base, u64* __restrict__ partial, const uint32_t* __restrict__ dead) {
-    // dead: the tombstone bits of the ORIGINAL row slots (ids[] carries them), null = none: a delete leaves the list layout valid
-    typedef RowTraits<DT> RT;
-    constexpr int E = RT::E;
-    const int lane = lane_id();
-    const int wave = (int)(threadIdx.x >> 6);
-    const int b = blockIdx.y, x = blockIdx.x;
-    const int nchunks = dpad / E;
-    u64* dst = partial + ((int64_t)b * nprobe * split + x) * k;
-
-    WaveTopK<SLOTS> L;
-    L.init();
-    const u64 pk = probe_keys[(int64_t)b * nprobe + x / split];
-    if (pk != 0ull) {  // block-uniform: fewer lists than nprobe leave empty probe slots
-        const uint32_t list = key_row(pk);
-        const int64_t lo = offsets[list], hi = offsets[list + 1];
-        const int64_t len = hi - lo, part = (len + split - 1) / split;
-        const int64_t begin = lo + (x % split) * part;
-        const int64_t end = begin + part < hi ? begin + part : hi;
-
-        const uint4* base = reinterpret_cast<const uint4*>(rows_);
-        [[maybe_unused]] float qf[1][NITER > 0 ? NITER : 1][E];
-        [[maybe_unused]] float* lds_q = nullptr;
-        if constexpr (NITER == kWideRows) {  // wide rows: the query in LDS
-            __shared__ __attribute__((aligned(16))) float lds_qw[kWideMaxFloats];
-            lds_q = lds_qw;
-            wide_stage_query(lds_q, qn + (int64_t)b * dpad, dpad, wide_qfloats(nchunks, E), (int)threadIdx.x, 256);
-            __syncthreads();
-        } else {
-            load_query_frags(qn + (int64_t)b * dpad, nchunks, lane, qf[0]);
-        }
-        for (int64_t g = begin + wave * 4; g < end; g += 16) {
-            const uint4* p[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) p[r] = base + (g + r < end ? g + r : end - 1) * (int64_t)nchunks + lane;
-            float sc[1][4];
-            if constexpr (NITER == kWideRows) {
-                wide_scores<DT, 1, 1>(p, nchunks, lane, lds_q, 0, 1, sc);
-            } else {
-                uint4 c[4][NITER];
-                fetch4(p, nchunks, lane, c);
-                score4<DT, 1, NITER>(c, qf, 1, lane, sc);
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                if (g + r < end && !(dead && row_dead(dead, ids[g + r]))) L.offer(make_key(sc[0][r], row_base + ids[g + r]), k, lane);
-        }
-    }
-    __shared__ u64 lds[4 * SLOTS * kWave];
-    store_list(lds, wave, 1, 0, lane, L);
-    __syncthreads();
-    if (wave != 0) return;
-    merge_lists(L, lds, 1, 4, 1, 0, k, lane);
-    write_keys(L, k, lane, dst);
-}
-
-// ivf_scan_sq: ivf_scan_kernel for an l2 index ("space_ivf"): the same block per (query, probe rank, slice), the same
-// loads and lists, the score is §20's canonical squared distance (score4 / wide_scores under kMetricL2: key score 0 - distance) of the
-// RAW prepared query.  A kernel of its own beside its twin, not a shared body: ivf_scan_kernel keeps its resource line that way.
-// (waves per SIMD: wide f32 rows with two list slots come out at 130 VGPRs, two above the four waves of the twin, unless hipcc is told
-// to aim for four — then 128, no spill; every other form is left at the default, one wave at least)
-template <int DT, int NITER, int SLOTS>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DT == DT_F32 && NITER == kWideRows && SLOTS == 2 ? 4 : 1)))
-void ivf_scan_sq(const void* __restrict__ rows_, const uint32_t* __restrict__ ids, const int64_t* __restrict__ offsets,
-                 const u64* __restrict__ probe_keys, int nprobe, int split, int dpad, const float* __restrict__ qn, int k, uint32_t row_base,
-                 u64* __restrict__ partial, const uint32_t* __restrict__ dead) {
-    typedef RowTraits<DT> RT;
-    constexpr int E = RT::E;
-    const int lane = lane_id();
-    const int wave = (int)(threadIdx.x >> 6);
-    const int b = blockIdx.y, x = blockIdx.x;
-    const int nchunks = dpad / E;
-    u64* dst = partial + ((int64_t)b * nprobe * split + x) * k;
-
-    WaveTopK<SLOTS> L;
-    L.init();
-    const u64 pk = probe_keys[(int64_t)b * nprobe + x / split];
-    if (pk != 0ull) {  // block-uniform: fewer lists than nprobe leave empty probe slots
-        const uint32_t list = key_row(pk);
-        const int64_t lo = offsets[list], hi = offsets[list + 1];
-        const int64_t len = hi - lo, part = (len + split - 1) / split;
-        const int64_t begin = lo + (x % split) * part;
-        const int64_t end = begin + part < hi ? begin + part : hi;
-
-        const uint4* base = reinterpret_cast<const uint4*>(rows_);
-        [[maybe_unused]] float qf[1][NITER > 0 ? NITER : 1][E];
-        [[maybe_unused]] float* lds_q = nullptr;
-        if constexpr (NITER == kWideRows) {  // wide rows: the query in LDS
-            __shared__ __attribute__((aligned(16))) float lds_qw[kWideMaxFloats];
-            lds_q = lds_qw;
-            wide_stage_query(lds_q, qn + (int64_t)b * dpad, dpad, wide_qfloats(nchunks, E), (int)threadIdx.x, 256);
-            __syncthreads();
-        } else {
-            load_query_frags(qn + (int64_t)b * dpad, nchunks, lane, qf[0]);
-        }
-        for (int64_t g = begin + wave * 4; g < end; g += 16) {
-            const uint4* p[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) p[r] = base + (g + r < end ? g + r : end - 1) * (int64_t)nchunks + lane;
-            float sc[1][4];
-            if constexpr (NITER == kWideRows) {
-                wide_scores<DT, 1, 1, kMetricL2, 1>(p, nchunks, lane, lds_q, 0, 1, sc);   // (USER 1: an instantiation of its own, exact_score.h)
-            } else {
-                uint4 c[4][NITER];
-                fetch4(p, nchunks, lane, c);
-                score4<DT, 1, NITER, kMetricL2>(c, qf, 1, lane, sc);
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                if (g + r < end && !(dead && row_dead(dead, ids[g + r]))) L.offer(make_key(sc[0][r], row_base + ids[g + r]), k, lane);
-        }
-    }
-    __shared__ u64 lds[4 * SLOTS * kWave];
-    store_list(lds, wave, 1, 0, lane, L);
-    __syncthreads();
-    if (wave != 0) return;
-    merge_lists(L, lds, 1, 4, 1, 0, k, lane);
-    write_keys(L, k, lane, dst);
-}
-
-// ---------------------------------------------------------------------------------------------
-// IVF at batch (round 3): a probed list is scanned ONCE for all the queries of the batch that probe it.  ivf_scan_kernel reads a
-// list once per (query, list) pair — 256 queries x 32 probes over 2,048 lists read every list four times.  Here the pairs are
-// grouped by list on the device (count, prefix sums, scatter: three tiny launches), every work item is (list, up to kIvfNB
-// pairs): the list's rows enter registers once and are scored against the item's queries with the canonical exact expression.
-// The item writes each pair's top-k to the pair's own slot of the partial buffer, so the merge behind it is the same launch
-// as for the unshared scan and the results are the same bits.
-// ---------------------------------------------------------------------------------------------
-constexpr int kIvfNB = 4;  // queries per work item
-__global__ __launch_bounds__(256) void ivf_pair_count_kernel(const u64* __restrict__ probe_keys, int npairs, unsigned* __restrict__ cnt) {
-    const int p = (int)blockIdx.x * 256 + (int)threadIdx.x;
-    if (p < npairs && probe_keys[p] != 0ull) atomicAdd(&cnt[key_row(probe_keys[p])], 1u);
-}
-// one workgroup: exclusive prefix sums over the lists — pair_start[l] (where list l's pairs go) and item_start[l] (its work
-// items: ceil(cnt / kIvfNB)); cnt[] is cleared on the way (the scatter reuses it as its fill counters); nitems at item_start[nlist]
-__global__ __launch_bounds__(1024) void ivf_pair_offsets_kernel(unsigned* __restrict__ cnt, int nlist, unsigned* __restrict__ pair_start,
-                                                                unsigned* __restrict__ item_start) {
-    __shared__ unsigned s_p[1024], s_i[1024];
-    const int tid = (int)threadIdx.x;
-    const int per = (nlist + 1023) / 1024;
-    unsigned sp = 0, si = 0;
-    for (int j = 0; j < per; ++j) {
-        const int l = tid * per + j;
-        const unsigned c = l < nlist ? cnt[l] : 0u;
-        sp += c;
-        si += (c + kIvfNB - 1) / kIvfNB;
-    }
-    s_p[tid] = sp;
-    s_i[tid] = si;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {   // Hillis-Steele inclusive scan
-        const unsigned a = tid >= off ? s_p[tid - off] : 0u, b = tid >= off ? s_i[tid - off] : 0u;
-        __syncthreads();
-        s_p[tid] += a;
-        s_i[tid] += b;
-        __syncthreads();
-    }
-    unsigned bp = s_p[tid] - sp, bi = s_i[tid] - si;   // exclusive bases of this thread's lists
-    for (int j = 0; j < per; ++j) {
-        const int l = tid * per + j;
-        if (l < nlist) {
-            const unsigned c = cnt[l];
-            pair_start[l] = bp;
-            item_start[l] = bi;
-            bp += c;
-            bi += (c + kIvfNB - 1) / kIvfNB;
-            cnt[l] = 0u;
-        }
-    }
-    if (tid == 1023) {
-        pair_start[nlist] = s_p[1023];
-        item_start[nlist] = s_i[1023];
-    }
-}
-__global__ __launch_bounds__(256) void ivf_pair_scatter_kernel(const u64* __restrict__ probe_keys, int npairs, const unsigned* __restrict__ pair_start,
-                                                               unsigned* __restrict__ fill, unsigned* __restrict__ sorted_pairs) {
-    const int p = (int)blockIdx.x * 256 + (int)threadIdx.x;
-    if (p >= npairs || probe_keys[p] == 0ull) return;
-    const uint32_t l = key_row(probe_keys[p]);
-    sorted_pairs[pair_start[l] + atomicAdd(&fill[l], 1u)] = (unsigned)p;
-}
-// list_scan_body: one workgroup of 4 waves scores positions [begin, end) of a row list against up to NB queries (q[b]: the query's
-// normalised row, null = absent) and writes query b's k best keys to dst_of(b); a wave owns 4 positions per step.
-//   GATHER = false (IVF): position i IS row i of the regrouped store and reports ids[i]; the next step's rows are on their way while
-//                  this step is scored (raw 16-byte chunks: half the registers of widened rows)
-//   GATHER = true (scopes): position i names row ids[i] of the original store and reports it.  Two steps of look-ahead: the row
-//                  slots of step g + 32 and the rows of step g + 16 (whose slots arrived a step ago) are in flight
-//   dead: the tombstone bits of the reported ids, null = no mask
-template <int DT, int NB, int NITER, int SLOTS, bool GATHER, int METRIC = kMetricDot, class DstOf>
-__device__ __forceinline__ void list_scan_body(const void* __restrict__ rows_, const uint32_t* __restrict__ ids, int64_t begin, int64_t end, int dpad,
-                                               const float* const (&q)[NB], int nq, int k, uint32_t row_base, const uint32_t* __restrict__ dead,
-                                               DstOf dst_of) {
-    typedef RowTraits<DT> RT;
-    constexpr int E = RT::E;
-    const int lane = lane_id();
-    const int wave = (int)(threadIdx.x >> 6);
-    const int nchunks = dpad / E;
-    const uint4* base = reinterpret_cast<const uint4*>(rows_);
-    WaveTopK<SLOTS> L[NB];
-#pragma unroll
-    for (int b = 0; b < NB; ++b) L[b].init();
-    auto load_ids = [&](int64_t g, uint32_t (&dst)[4]) {   // (g < end)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) dst[r] = ids[g + r < end ? g + r : end - 1];
-    };
-    // where the rows of step g are: by position (clamped into the list), or by the slots `id` that load_ids(g) brought
-    auto row_ptrs = [&](int64_t g, const uint32_t (&id)[4], const uint4* (&p)[4]) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            int64_t row = id[r];
-            if constexpr (!GATHER) {
-                row = g + r < end ? g + r : end - 1;
-                row = row < begin ? begin : row;
-            }
-            p[r] = base + row * (int64_t)nchunks + lane;
-        }
-    };
-    auto offer4 = [&](int64_t g, const uint32_t (&id)[4], const float (&sc)[NB][4]) {
-#pragma unroll
-        for (int b = 0; b < NB; ++b)
-            if (b < nq) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    if constexpr (GATHER) {
-                        if (g + r < end && !(dead && row_dead(dead, id[r]))) L[b].offer(make_key(sc[b][r], row_base + id[r]), k, lane);
-                    } else {
-                        if (g + r < end && !(dead && row_dead(dead, ids[g + r]))) L[b].offer(make_key(sc[b][r], row_base + ids[g + r]), k, lane);
-                    }
-                }
-            }
-    };
-    const int64_t g0 = begin + wave * 4;
-    uint32_t id0[4] = {0u, 0u, 0u, 0u}, id1[4] = {0u, 0u, 0u, 0u};
-    if constexpr (NITER == kWideRows) {  // wide rows: the queries in LDS (64 KiB at most); the next step's row slots on their way
-        __shared__ __attribute__((aligned(16))) float lds_q[NB * kWideMaxFloats];
-        const int qstride = wide_qfloats(nchunks, E);
-#pragma unroll
-        for (int b = 0; b < NB; ++b) wide_stage_query(lds_q + b * qstride, q[b], dpad, qstride, (int)threadIdx.x, 256);
-        __syncthreads();
-        if (GATHER && g0 < end) load_ids(g0, id0);
-        for (int64_t g = g0; g < end; g += 16) {
-            if (GATHER && g + 16 < end) load_ids(g + 16, id1);
-            const uint4* p[4];
-            row_ptrs(g, id0, p);
-            float sc[NB][4];
-            wide_scores<DT, NB, 1, METRIC>(p, nchunks, lane, lds_q, qstride, nq, sc);
-            offer4(g, id0, sc);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) id0[r] = id1[r];
-        }
-    } else {
-        float qf[NB][NITER][E];
-#pragma unroll
-        for (int b = 0; b < NB; ++b) load_query_frags(q[b], nchunks, lane, qf[b]);
-        uint4 cur[4][NITER], nxt[4][NITER];
-        const uint4* p[4];
-        if (g0 < end) {
-            if constexpr (GATHER) {
-                load_ids(g0, id0);
-                if (g0 + 16 < end) load_ids(g0 + 16, id1);
-            }
-            row_ptrs(g0, id0, p);
-            fetch4(p, nchunks, lane, cur);
-        }
-        for (int64_t g = g0; g < end; g += 16) {
-            uint32_t id2[4] = {0u, 0u, 0u, 0u};
-            if (GATHER && g + 32 < end) load_ids(g + 32, id2);
-            if (g + 16 < end) {
-                row_ptrs(g + 16, id1, p);
-                fetch4(p, nchunks, lane, nxt);
-            }
-            float sc[NB][4];
-            score4<DT, NB, NITER, METRIC>(cur, qf, nq, lane, sc);
-            offer4(g, id0, sc);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-#pragma unroll
-                for (int it = 0; it < NITER; ++it) cur[r][it] = nxt[r][it];
-                id0[r] = id1[r];
-                id1[r] = id2[r];
-            }
-        }
-    }
-    __shared__ u64 lds[4 * NB * SLOTS * kWave];
-#pragma unroll
-    for (int b = 0; b < NB; ++b) store_list(lds, wave, NB, b, lane, L[b]);
-    __syncthreads();
-    for (int b = wave; b < nq; b += 4) {
-        WaveTopK<SLOTS> M;
-        M.init();
-        merge_lists(M, lds, 0, 4, NB, b, k, lane);
-        write_keys(M, k, lane, dst_of(b));
-    }
-}
-
-// one work item per workgroup: item -> (list, its kIvfNB-pair group) by binary search in item_start
-template <int DT, int NITER, int SLOTS>
-__global__ __launch_bounds__(256) void ivf_scan_shared_kernel(const void* __restrict__ rows_, const uint32_t* __restrict__ ids, const int64_t* __restrict__ offsets,
-                                                              const unsigned* __restrict__ pair_start, const unsigned* __restrict__ item_start,
-                                                              const unsigned* __restrict__ sorted_pairs, int nlist, int nprobe, int dpad,
-                                                              const float* __restrict__ qn, int k, uint32_t row_base, u64* __restrict__ partial,
-                                                              const uint32_t* __restrict__ dead) {
-    const unsigned item = blockIdx.x;
-    if (item >= item_start[nlist]) return;   // (the grid is sized for the worst case: one item per pair)
-    int lo_l = 0, hi_l = nlist;              // the last list whose item_start <= item
-    while (hi_l - lo_l > 1) {
-        const int mid = (lo_l + hi_l) >> 1;
-        if (item_start[mid] <= item) lo_l = mid; else hi_l = mid;
-    }
-    const int list = lo_l;
-    const unsigned g = item - item_start[list];
-    const unsigned p0 = pair_start[list] + g * kIvfNB, p1e = pair_start[list + 1];
-    const int nq = (int)((p1e - p0) < (unsigned)kIvfNB ? (p1e - p0) : (unsigned)kIvfNB);
-    unsigned pair[kIvfNB];
-    const float* q[kIvfNB];
-#pragma unroll
-    for (int b = 0; b < kIvfNB; ++b) {
-        pair[b] = b < nq ? sorted_pairs[p0 + b] : 0u;
-        q[b] = b < nq ? qn + (int64_t)(pair[b] / (unsigned)nprobe) * dpad : nullptr;
-    }
-    // the pair's own slot of the partial buffer: [query][probe rank][k]
-    list_scan_body<DT, kIvfNB, NITER, SLOTS, false>(rows_, ids, offsets[list], offsets[list + 1], dpad, q, nq, k, row_base, dead,
-                                                    [&](int b) { return partial + (int64_t)pair[b] * k; });
-}
-// ivf_shared_sq: the same work items for an l2 index: list_scan_body under kMetricL2
-template <int DT, int NITER, int SLOTS>
-__global__ __launch_bounds__(256) void ivf_shared_sq(const void* __restrict__ rows_, const uint32_t* __restrict__ ids, const int64_t* __restrict__ offsets,
-                                                     const unsigned* __restrict__ pair_start, const unsigned* __restrict__ item_start,
-                                                     const unsigned* __restrict__ sorted_pairs, int nlist, int nprobe, int dpad, const float* __restrict__ qn, int k,
-                                                     uint32_t row_base, u64* __restrict__ partial, const uint32_t* __restrict__ dead) {
-    const unsigned item = blockIdx.x;
-    if (item >= item_start[nlist]) return;   // (the grid is sized for the worst case: one item per pair)
-    int lo_l = 0, hi_l = nlist;              // the last list whose item_start <= item
-    while (hi_l - lo_l > 1) {
-        const int mid = (lo_l + hi_l) >> 1;
-        if (item_start[mid] <= item) lo_l = mid; else hi_l = mid;
-    }
-    const int list = lo_l;
-    const unsigned g = item - item_start[list];
-    const unsigned p0 = pair_start[list] + g * kIvfNB, p1e = pair_start[list + 1];
-    const int nq = (int)((p1e - p0) < (unsigned)kIvfNB ? (p1e - p0) : (unsigned)kIvfNB);
-    unsigned pair[kIvfNB];
-    const float* q[kIvfNB];
-#pragma unroll
-    for (int b = 0; b < kIvfNB; ++b) {
-        pair[b] = b < nq ? sorted_pairs[p0 + b] : 0u;
-        q[b] = b < nq ? qn + (int64_t)(pair[b] / (unsigned)nprobe) * dpad : nullptr;
-    }
-    list_scan_body<DT, kIvfNB, NITER, SLOTS, false, kMetricL2>(rows_, ids, offsets[list], offsets[list + 1], dpad, q, nq, k, row_base, dead,
-                                                               [&](int b) { return partial + (int64_t)pair[b] * k; });
-}
-
-// ---------------------------------------------------------------------------------------------
-// Scopes: a 32-bit label per row slot, 0 = none.  A scoped query sees only the rows of its scope.
-//   scope_of[capacity]          the label of every slot (codd_knn_set_scopes_host)
-//   scope_perm[count]           row slots grouped by scope, scope_offsets[nlist + 1] where each group starts (nlist = highest
-//                               scope + 1; group 0 = the unlabelled rows).  Built lazily by the first scoped search after labels
-//                               or the row count changed: count, prefix sums, scatter.  The order inside a group is whatever the
-//                               atomics give: keys carry the row, so the top-k does not depend on it.
-//   scope_scan_kernel           (scope, up to NB of the batch's queries with that scope, one of `split` parts of its group):
-//                               gathers the group's rows from the ORIGINAL row store by slot and scores them with the canonical
-//                               expression; one partial list per (query, part), merge_keys_kernel behind it.
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void scope_set_kernel(const int64_t* __restrict__ packed, int64_t n, uint32_t* __restrict__ scope_of) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + (int64_t)threadIdx.x;
-    if (i < n) scope_of[(uint32_t)(packed[i] & 0xffffffffll)] = (uint32_t)((u64)packed[i] >> 32);   // (slot in the low word, scope in the high one)
-}
-// A wave whose 64 rows carry one scope (labels assigned in runs, as the indexer job writes them) costs one atomic, not 64.
-// (dead: the tombstone bits, null = none: deleted rows are left out of the lists, so scope_scan_kernel needs no mask of its own)
-__global__ __launch_bounds__(256) void scope_count_kernel(const uint32_t* __restrict__ scope_of, int64_t n, int nlist, unsigned* __restrict__ cnt,
-                                                          const uint32_t* __restrict__ dead) {
-    const int64_t r = (int64_t)blockIdx.x * 256 + (int64_t)threadIdx.x;
-    const bool valid = r < n && !(dead && row_dead(dead, (uint32_t)r));
-    uint32_t s = valid ? scope_of[r] : 0u;
-    if (s >= (uint32_t)nlist) s = 0u;   // (cannot happen: nlist covers every label ever set)
-    const uint32_t first = (uint32_t)__builtin_amdgcn_readfirstlane((int)s);
-    const u64 act = __ballot(valid), same = __ballot(valid && s == first);
-    if (same == act) {
-        if (lane_id() == 0 && act != 0ull) atomicAdd(&cnt[first], (unsigned)__popcll(act));
-    } else if (valid) {
-        atomicAdd(&cnt[s], 1u);
-    }
-}
-// one workgroup: start[l] = exclusive prefix sum of cnt[], the total at start[nlist]; cnt[] is cleared on the way (the scatter's fill counters)
-__global__ __launch_bounds__(1024) void scope_offsets_kernel(unsigned* __restrict__ cnt, int nlist, unsigned* __restrict__ start) {
-    __shared__ unsigned s_p[1024];
-    const int tid = (int)threadIdx.x;
-    const int per = (nlist + 1023) / 1024;
-    unsigned sp = 0;
-    for (int j = 0; j < per; ++j) {
-        const int l = tid * per + j;
-        sp += l < nlist ? cnt[l] : 0u;
-    }
-    s_p[tid] = sp;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {   // Hillis-Steele inclusive scan
-        const unsigned a = tid >= off ? s_p[tid - off] : 0u;
-        __syncthreads();
-        s_p[tid] += a;
-        __syncthreads();
-    }
-    unsigned bp = s_p[tid] - sp;
-    for (int j = 0; j < per; ++j) {
-        const int l = tid * per + j;
-        if (l < nlist) {
-            const unsigned c = cnt[l];
-            start[l] = bp;
-            bp += c;
-            cnt[l] = 0u;
-        }
-    }
-    if (tid == 1023) start[nlist] = s_p[1023];
-}
-__global__ __launch_bounds__(256) void scope_scatter_kernel(const uint32_t* __restrict__ scope_of, int64_t n, int nlist, const unsigned* __restrict__ start,
-                                                            unsigned* __restrict__ fill, uint32_t* __restrict__ perm, const uint32_t* __restrict__ dead) {
-    const int64_t r = (int64_t)blockIdx.x * 256 + (int64_t)threadIdx.x;
-    const bool valid = r < n && !(dead && row_dead(dead, (uint32_t)r));
-    uint32_t s = valid ? scope_of[r] : 0u;
-    if (s >= (uint32_t)nlist) s = 0u;
-    const uint32_t first = (uint32_t)__builtin_amdgcn_readfirstlane((int)s);
-    const u64 act = __ballot(valid), same = __ballot(valid && s == first);
-    if (same == act) {   // (a valid lane's place: its rank among the valid lanes — deleted rows leave gaps)
-        unsigned base = 0u;
-        if (lane_id() == 0 && act != 0ull) base = atomicAdd(&fill[first], (unsigned)__popcll(act));
-        base = (unsigned)__builtin_amdgcn_readfirstlane((int)base);
-        if (valid) perm[start[first] + base + (unsigned)__popcll(act & ((1ull << lane_id()) - 1ull))] = (uint32_t)r;
-    } else if (valid) {
-        perm[start[s] + atomicAdd(&fill[s], 1u)] = (uint32_t)r;
-    }
-}
-// One workgroup groups the batch's queries by scope: position p of the order (scope, query) holds query sorted_q[p], the rank[p]-th of its
-// scope.  Counting ranks over LDS (B <= 1,024 broadcast reads per thread): the cost does not depend on how many scopes exist, where
-// the count / prefix-sum / scatter of ivf_pair_* would walk a table of up to 2^20 scopes per search.
-__global__ __launch_bounds__(1024) void scope_group_kernel(const uint32_t* __restrict__ scopes, int B, unsigned* __restrict__ sorted_q, unsigned* __restrict__ rank) {
-    __shared__ uint32_t s_sc[CODD_KNN_MAX_BATCH];
-    const int tid = (int)threadIdx.x;
-    const uint32_t mine = tid < B ? scopes[tid] : 0xffffffffu;
-    s_sc[tid] = mine;
-    __syncthreads();
-    if (tid >= B) return;
-    unsigned lower = 0u, before = 0u;   // queries of a lower scope; ... plus those of this scope that come earlier in the batch
-    for (int j = 0; j < B; ++j) {
-        const uint32_t sj = s_sc[j];
-        lower += sj < mine ? 1u : 0u;
-        before += (sj < mine || (sj == mine && j < tid)) ? 1u : 0u;
-    }
-    sorted_q[before] = (unsigned)tid;
-    rank[before] = before - lower;
-}
-
-// queries per work item: four, as in ivf_scan_shared_kernel; two for 2-byte rows of 4 chunks per lane (four queries' registers would spill)
-constexpr int scope_nb(int dt, int niter) { return (dt != DT_F32 && niter == 4) ? 2 : 4; }
-// rows per part: a whole number of workgroup steps (4 waves x 4 rows)
-__host__ __device__ constexpr int64_t scope_part_rows(int64_t len, int split) { return ((len + split - 1) / split + 15) / 16 * 16; }
-
-// grid (B, split): workgroup (p, part) serves the queries at positions p .. p + NB-1 of the grouped order when p opens a group of NB
-// (rank[p] % NB == 0) and leaves at once otherwise.
-template <int DT, int NITER, int SLOTS, int METRIC>
-__device__ __forceinline__ void scope_scan_body(const void* __restrict__ rows_, const uint32_t* __restrict__ perm, const unsigned* __restrict__ offsets,
-                                                int64_t count, uint32_t max_scope, const uint32_t* __restrict__ scopes,
-                                                const unsigned* __restrict__ sorted_q, const unsigned* __restrict__ rank, int B, int split, int dpad,
-                                                const float* __restrict__ qn, int k, uint32_t row_base, u64* __restrict__ partial) {
-    constexpr int NB = scope_nb(DT, NITER);
-    const int p0 = (int)blockIdx.x, part = (int)blockIdx.y;
-    const unsigned r0 = rank[p0];
-    if (r0 % NB != 0u) return;
-    int nq = 1;
-    while (nq < NB && p0 + nq < B && rank[p0 + nq] == r0 + (unsigned)nq) ++nq;   // (ranks count up inside a scope and restart at 0)
-    const float* q[NB];
-#pragma unroll
-    for (int b = 0; b < NB; ++b) q[b] = b < nq ? qn + (int64_t)sorted_q[p0 + b] * dpad : nullptr;
-    const uint32_t scope = scopes[sorted_q[p0]];
-    int64_t lo = 0, hi = 0;   // the scope's rows: scope_perm[lo, hi); scope 0 = every listed row (`count`: the live rows); a scope nobody carries = none
-    if (scope == 0u) hi = count;
-    else if (scope <= max_scope) { lo = offsets[scope]; hi = offsets[scope + 1]; }
-    const int64_t per = scope_part_rows(hi - lo, split);
-    const int64_t begin = lo + part * per < hi ? lo + part * per : hi;
-    const int64_t end = begin + per < hi ? begin + per : hi;
-    // no mask: the lists hold live rows only.  Query b's part of the partial buffer: [query][part][k]
-    list_scan_body<DT, NB, NITER, SLOTS, true, METRIC>(rows_, perm, begin, end, dpad, q, nq, k, row_base, nullptr,
-                                                       [&](int b) { return partial + ((int64_t)sorted_q[p0 + b] * split + part) * k; });
-}
-template <int DT, int NITER, int SLOTS>
-__global__ __launch_bounds__(256) void scope_scan_kernel(const void* __restrict__ rows_, const uint32_t* __restrict__ perm, const unsigned* __restrict__ offsets,
-                                                         int64_t count, uint32_t max_scope, const uint32_t* __restrict__ scopes,
-                                                         const unsigned* __restrict__ sorted_q, const unsigned* __restrict__ rank, int B, int split, int dpad,
-                                                         const float* __restrict__ qn, int k, uint32_t row_base, u64* __restrict__ partial) {
-    scope_scan_body<DT, NITER, SLOTS, kMetricDot>(rows_, perm, offsets, count, max_scope, scopes, sorted_q, rank, B, split, dpad, qn, k, row_base, partial);
-}
-template <int DT, int NITER, int SLOTS>
-__global__ __launch_bounds__(256) void scope_scan_l2(const void* __restrict__ rows_, const uint32_t* __restrict__ perm, const unsigned* __restrict__ offsets,
-                                                     int64_t count, uint32_t max_scope, const uint32_t* __restrict__ scopes,
-                                                     const unsigned* __restrict__ sorted_q, const unsigned* __restrict__ rank, int B, int split, int dpad,
-                                                     const float* __restrict__ qn, int k, uint32_t row_base, u64* __restrict__ partial) {
-    scope_scan_body<DT, NITER, SLOTS, kMetricL2>(rows_, perm, offsets, count, max_scope, scopes, sorted_q, rank, B, split, dpad, qn, k, row_base, partial);
-}
-
-// ---------------------------------------------------------------------------------------------
-// Tombstones and compaction.
-//   dead_set_kernel        sets the bits of n row slots (vector atomics: several slots may share a word)
-//   live_prefix_kernel     per bitmap word: the live slots of its 256-word block that lie below it (popcount, Hillis-Steele scan
-//                          in LDS), and the block's total; scope_offsets_kernel turns the totals into block bases.  New slot of a
-//                          live row r = base[block] + prefix[word] + live bits of its word below r: its rank among the live rows.
-//   compact_gather_kernel  one wave per source row of a chunk [s0, s1), whole 16-byte pieces as gather_rows_kernel moves them: a
-//                          live row goes to the bounce buffer at (new slot - dbase), dbase = the chunk's first destination; its
-//                          scope label goes along.  The host then copies the bounce buffer to rows [dbase, dbase + live rows of
-//                          the chunk): rows only move down, and that range ends at or before s1, the next chunk's first source.
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void dead_set_kernel(const int64_t* __restrict__ slots, int64_t n, uint32_t* __restrict__ dead) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + (int64_t)threadIdx.x;
-    if (i < n) atomicOr(&dead[slots[i] >> 5], 1u << (uint32_t)(slots[i] & 31));
-}
-// live slots of bitmap word w among rows [0, n)
-__device__ __forceinline__ uint32_t live_bits(const uint32_t* __restrict__ dead, int64_t w, int64_t n) {
-    const int64_t left = n - w * 32;
-    const uint32_t in_range = left >= 32 ? 0xffffffffu : (left > 0 ? (1u << (uint32_t)left) - 1u : 0u);
-    return ~dead[w] & in_range;
-}
-__global__ __launch_bounds__(256) void live_prefix_kernel(const uint32_t* __restrict__ dead, int64_t n, int64_t nwords, unsigned* __restrict__ prefix,
-                                                          unsigned* __restrict__ block_total) {
-    __shared__ unsigned s_p[256];
-    const int tid = (int)threadIdx.x;
-    const int64_t w = (int64_t)blockIdx.x * 256 + tid;
-    const unsigned mine = w < nwords ? (unsigned)__popc(live_bits(dead, w, n)) : 0u;
-    s_p[tid] = mine;
-    __syncthreads();
-    for (int off = 1; off < 256; off <<= 1) {   // Hillis-Steele inclusive scan
-        const unsigned a = tid >= off ? s_p[tid - off] : 0u;
-        __syncthreads();
-        s_p[tid] += a;
-        __syncthreads();
-    }
-    if (w < nwords) prefix[w] = s_p[tid] - mine;
-    if (tid == 255) block_total[blockIdx.x] = s_p[255];
-}
-__global__ __launch_bounds__(256) void compact_gather_kernel(const uint4* __restrict__ rows, const uint32_t* __restrict__ dead, int64_t n,
-                                                             const unsigned* __restrict__ prefix, const unsigned* __restrict__ block_base,
-                                                             const uint32_t* __restrict__ scope_of, int64_t s0, int64_t s1, int64_t dbase,
-                                                             int64_t bounce_rows, int chunks_per_row, uint4* __restrict__ bounce,
-                                                             uint32_t* __restrict__ bounce_scope) {
-    const int lane = lane_id();
-    const int64_t r = s0 + (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= s1 || row_dead(dead, (uint32_t)r)) return;
-    const int64_t w = r >> 5;
-    const int64_t to = (int64_t)block_base[w >> 8] + prefix[w] + __popc(live_bits(dead, w, n) & ((1u << (uint32_t)(r & 31)) - 1u)) - dbase;
-    if (to < 0 || to >= bounce_rows) return;   // (cannot happen: the host sized the chunk from the same bits)
-    for (int j = lane; j < chunks_per_row; j += kWave) bounce[to * chunks_per_row + j] = rows[r * chunks_per_row + j];
-    if (lane == 0 && scope_of) bounce_scope[to] = scope_of[r];
-}
-
-// ---------------------------------------------------------------------------------------------
-// Masked search: one bitmap of ALLOWED row slots per call, shared by the batch's queries.
-//   mask_deny_kernel     dense route: deny[w] = ~allow[w] | dead[w], all ones from the mask's last word on — the bitmap every
-//                        exact-score kernel takes where it takes the tombstone bits (§14 with "dead" read as "denied")
-//   mask_prefix_kernel   list route: per bitmap word the visible (allowed, live) slots of its 256-word block that lie below it, and
-//                        the block's total (live_prefix_kernel's shape); scope_offsets_kernel turns the totals into block bases
-//   mask_scatter_kernel  ... and each word writes its visible slots, ascending, from base[block] + prefix[word]: the list is the
-//                        visible row slots in slot order, the same for every run
-//   mask_scan_kernel     (group of up to NB of the batch's queries, one of `split` parts of the list): list_scan_body's gathering
-//                        form, as scope_scan_kernel runs it; one partial list per (query, part), merge_keys_kernel behind it
-// ---------------------------------------------------------------------------------------------
-// the slots of bitmap word w among rows [0, n) that a masked search may return (dead: the tombstone bits, null = none)
-__device__ __forceinline__ uint32_t visible_bits(const uint32_t* __restrict__ allow, const uint32_t* __restrict__ dead, int64_t w, int64_t n) {
-    const int64_t left = n - w * 32;
-    const uint32_t in_range = left >= 32 ? 0xffffffffu : (left > 0 ? (1u << (uint32_t)left) - 1u : 0u);
-    return allow[w] & in_range & ~(dead ? dead[w] : 0u);
-}
-__global__ __launch_bounds__(256) void mask_deny_kernel(const uint32_t* __restrict__ allow, const uint32_t* __restrict__ dead, int64_t n, int64_t nwords,
-                                                        int64_t total_words, uint32_t* __restrict__ deny) {
-    const int64_t w = (int64_t)blockIdx.x * 256 + (int64_t)threadIdx.x;
-    if (w < total_words) deny[w] = w < nwords ? ~visible_bits(allow, dead, w, n) : 0xffffffffu;
-}
-__global__ __launch_bounds__(256) void mask_prefix_kernel(const uint32_t* __restrict__ allow, const uint32_t* __restrict__ dead, int64_t n, int64_t nwords,
-                                                          unsigned* __restrict__ prefix, unsigned* __restrict__ block_total) {
-    __shared__ unsigned s_p[256];
-    const int tid = (int)threadIdx.x;
-    const int64_t w = (int64_t)blockIdx.x * 256 + tid;
-    const unsigned mine = w < nwords ? (unsigned)__popc(visible_bits(allow, dead, w, n)) : 0u;
-    s_p[tid] = mine;
-    __syncthreads();
-    for (int off = 1; off < 256; off <<= 1) {   // Hillis-Steele inclusive scan
-        const unsigned a = tid >= off ? s_p[tid - off] : 0u;
-        __syncthreads();
-        s_p[tid] += a;
-        __syncthreads();
-    }
-    if (w < nwords) prefix[w] = s_p[tid] - mine;
-    if (tid == 255) block_total[blockIdx.x] = s_p[255];
-}
-__global__ __launch_bounds__(256) void mask_scatter_kernel(const uint32_t* __restrict__ allow, const uint32_t* __restrict__ dead, int64_t n, int64_t nwords,
-                                                           const unsigned* __restrict__ prefix, const unsigned* __restrict__ block_base, int64_t m,
-                                                           uint32_t* __restrict__ list) {
-    const int64_t w = (int64_t)blockIdx.x * 256 + (int64_t)threadIdx.x;
-    if (w >= nwords) return;
-    uint32_t v = visible_bits(allow, dead, w, n);
-    int64_t at = (int64_t)block_base[w >> 8] + prefix[w];
-    for (; v != 0u; v &= v - 1u, ++at)
-        if (at < m) list[at] = (uint32_t)(w * 32) + (uint32_t)(__ffs((int)v) - 1);   // (at < m always: the host counted the same bits)
-}
-// grid (ceil(B / NB), split): workgroup (g, part) serves queries g * NB .. g * NB + NB-1 over part `part` of list[0, m)
-template <int DT, int NITER, int SLOTS, int METRIC>
-__device__ __forceinline__ void mask_scan_body(const void* __restrict__ rows_, const uint32_t* __restrict__ list, int64_t m, int B, int split,
-                                               int dpad, const float* __restrict__ qn, int k, uint32_t row_base, u64* __restrict__ partial) {
-    constexpr int NB = scope_nb(DT, NITER);
-    const int q0 = (int)blockIdx.x * NB, part = (int)blockIdx.y;
-    const int nq = B - q0 < NB ? B - q0 : NB;
-    const float* q[NB];
-#pragma unroll
-    for (int b = 0; b < NB; ++b) q[b] = b < nq ? qn + (int64_t)(q0 + b) * dpad : nullptr;
-    const int64_t per = scope_part_rows(m, split);
-    const int64_t begin = part * per < m ? part * per : m;
-    const int64_t end = begin + per < m ? begin + per : m;
-    // no mask: the list holds visible rows only.  Query b's part of the partial buffer: [query][part][k]
-    list_scan_body<DT, NB, NITER, SLOTS, true, METRIC>(rows_, list, begin, end, dpad, q, nq, k, row_base, nullptr,
-                                                       [&](int b) { return partial + ((int64_t)(q0 + b) * split + part) * k; });
-}
-template <int DT, int NITER, int SLOTS>
-__global__ __launch_bounds__(256) void mask_scan_kernel(const void* __restrict__ rows_, const uint32_t* __restrict__ list, int64_t m, int B, int split,
-                                                        int dpad, const float* __restrict__ qn, int k, uint32_t row_base, u64* __restrict__ partial) {
-    mask_scan_body<DT, NITER, SLOTS, kMetricDot>(rows_, list, m, B, split, dpad, qn, k, row_base, partial);
-}
-template <int DT, int NITER, int SLOTS>
-__global__ __launch_bounds__(256) void mask_scan_l2(const void* __restrict__ rows_, const uint32_t* __restrict__ list, int64_t m, int B, int split,
-                                                    int dpad, const float* __restrict__ qn, int k, uint32_t row_base, u64* __restrict__ partial) {
-    mask_scan_body<DT, NITER, SLOTS, kMetricL2>(rows_, list, m, B, split, dpad, qn, k, row_base, partial);
-}
-
-}  // namespace
+#include "ingest_kernels.h"
+#include "scan_kernels.h"
+#include "shadow8_kernels.h"
+#include "list_scan_kernels.h"
 
 // =============================================================================================
 // host side: the index object and the C ABI
@@ -2262,101 +503,11 @@ int64_t live_in_range(const codd_knn_index* ix, int64_t lo, int64_t hi) {
     return (hi - lo) - dead;
 }
 
-// ---- kernel dispatch -------------------------------------------------------------------------
-// Each run-time choice of a template argument is made in one place: a with_* helper calls the generic lambda `f` with a
-// std::integral_constant of the chosen value (usable as a template argument inside f) and returns what f returns (a
-// CODD_KNN_* code).  A value no kernel is built for is an error.
+}  // namespace
 
-template <int V>
-using IntC = std::integral_constant<int, V>;
+#include "dispatch.h"
 
-// f(IntC<V>) for the V of Vs that equals v, else EINVAL with `unsupported` (a fail() format)
-template <int... Vs, typename F>
-int with_int(int v, const char* unsupported, F&& f) {
-    bool found = false;
-    int rc = CODD_KNN_OK;
-    ((v == Vs ? (found = true, rc = f(IntC<Vs>{})) : 0), ...);
-    return found ? rc : fail(CODD_KNN_EINVAL, unsupported);
-}
-
-template <typename F>
-int with_dtype(int dtype, F&& f) {
-    return with_int<DT_F32, DT_BF16, DT_F16>(dtype, "unknown dtype%s", f);
-}
-
-// the NITER values the wide forms serve: rows of 5 .. 16 chunks per lane (f32: 1,025 .. 4,096 elements; 2-byte: 2,049 .. 4,096)
-constexpr int kMaxNiter = 16;
-
-// chunks of the padded row per lane: the NITER of the exact-score row kernels
-int niter_of(const codd_knn_index* ix) { return (ix->dpad / elems_per_chunk(ix->dtype) + kWave - 1) / kWave; }
-
-// 1 .. 4 chunks per lane: NITER itself; 5 .. kMaxNiter: the wide form (kWideRows); wider: ENOTSUP with `too_wide`
-template <typename F>
-int with_niter(int niter, const char* too_wide, F&& f) {
-    switch (niter) {
-        case 1: return f(IntC<1>{});
-        case 2: return f(IntC<2>{});
-        case 3: return f(IntC<3>{});
-        case 4: return f(IntC<4>{});
-    }
-    if (niter > 4 && niter <= kMaxNiter) return f(IntC<kWideRows>{});
-    return fail(CODD_KNN_ENOTSUP, too_wide);
-}
-
-// list slots per lane of a top-k list: one for k <= 64, else two
-template <typename F>
-int with_slots(int k, F&& f) {
-    return k <= 64 ? f(IntC<1>{}) : f(IntC<2>{});
-}
-
-// 32-query blocks of a filter pass
-template <typename F>
-int with_nbq(int nbq, F&& f) {
-    return with_int<1, 2, 4, 8>(nbq, "bad query block count%s", f);
-}
-
-// f(DT, NITER, SLOTS): the form of an exact-score row kernel for the index's rows and k
-template <typename F>
-int with_row_form(const codd_knn_index* ix, int k, const char* too_wide, F&& f) {
-    return with_dtype(ix->dtype, [&](auto dt) {
-        return with_niter(niter_of(ix), too_wide, [&](auto ni) {
-            return with_slots(k, [&](auto sl) { return f(dt, ni, sl); });
-        });
-    });
-}
-
-// Dynamic LDS above 64 KiB needs the instantiation's opt-in, once per device (the caller's DeviceGuard has made the index's
-// device current).  `bytes` must be at least what any launch of `Kernel` asks for.
-template <auto Kernel>
-int opt_in_lds(size_t bytes) {
-    static std::atomic<uint64_t> done{0};  // one bit per device
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    const uint64_t bit = dev < 64 ? 1ull << dev : 0ull;
-    if (!bit || !(done.load(std::memory_order_acquire) & bit)) {
-        HIP_TRY(hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-        done.fetch_or(bit, std::memory_order_acq_rel);
-    }
-    return CODD_KNN_OK;
-}
-
-// dynamic LDS of a launch, and what its kernel opts in to when that is above 64 KiB (by default the same: a kernel launched
-// with one size only)
-struct Lds {
-    size_t bytes, opt_in;
-    Lds(size_t b) : bytes(b), opt_in(b) {}
-    Lds(size_t b, size_t most) : bytes(b), opt_in(most) {}
-};
-constexpr size_t kLdsNoOptIn = 64 * 1024;
-
-// every launch of a template kernel, and every launch with dynamic LDS; the caller checks hipGetLastError
-template <auto Kernel, typename... Args>
-int launch_kernel(dim3 grid, dim3 block, Lds lds, hipStream_t st, Args&&... args) {  // (by reference: an owning buffer converts to its pointer at the launch itself)
-    int rc;
-    if (lds.bytes > kLdsNoOptIn && (rc = opt_in_lds<Kernel>(lds.opt_in)) != 0) return rc;
-    hipLaunchKernelGGL(Kernel, grid, block, lds.bytes, st, args...);
-    return CODD_KNN_OK;
-}
+namespace {
 
 int launch_normalize(int dtype, const float* in, int64_t n, int d, int dpad, int normalize, const int64_t* slots,
                      int64_t first_slot, void* out, uint2* shadow, hipStream_t st) {
@@ -3951,11 +2102,9 @@ int ivf_search_body(codd_knn_index* ix, const float* dev_queries, int B, int k, 
     {
         EvScope ev(ix, EV_SCAN, st);
         rc = with_row_form(ix, k, "row too wide for the IVF scan%s", [&](auto dt, auto ni, auto sl) {
-            if (sq)
-                return launch_kernel<ivf_scan_sq<dt, ni, sl>>(grid, block, 0, st, ix->rows_ivf, ix->ivf_ids, ix->ivf_offsets, ix->probe_keys, nprobe, split, ix->dpad,
-                                                              ix->qn, k, row_base, ix->ivf_partial, deny);
-            return launch_kernel<ivf_scan_kernel<dt, ni, sl>>(grid, block, 0, st, ix->rows_ivf, ix->ivf_ids, ix->ivf_offsets, ix->probe_keys, nprobe, split,
-                                                              ix->dpad, ix->qn, k, row_base, ix->ivf_partial, deny);
+            return launch_by_metric<ivf_scan_sq<dt, ni, sl>, ivf_scan_kernel<dt, ni, sl>>(sq ? kMetricL2 : kMetricDot, grid, block, 0, st, ix->rows_ivf, ix->ivf_ids,
+                                                                                          ix->ivf_offsets, ix->probe_keys, nprobe, split, ix->dpad, ix->qn, k, row_base,
+                                                                                          ix->ivf_partial, deny);
         });
     }
     if (rc != 0) return rc;
@@ -4057,13 +2206,9 @@ int codd_knn_search_scoped(codd_knn_index* ix, const float* dev_queries, const u
     {
         EvScope ev(ix, EV_SCAN, st);
         rc = with_row_form(ix, k, "row too wide for the scope scan%s", [&](auto dt, auto ni, auto sl) {
-            if (ix->metric == CODD_KNN_METRIC_L2)
-                return launch_kernel<scope_scan_l2<dt, ni, sl>>(dim3((unsigned)B, (unsigned)split), dim3(256), 0, st, ix->rows, ix->scope_perm, ix->scope_offsets,
-                                                                n - ix->dead_count, ix->max_scope, dev_scopes, sorted_q, rank, B, split, ix->dpad, ix->qn, k, row_base,
-                                                                ix->partial);
-            return launch_kernel<scope_scan_kernel<dt, ni, sl>>(dim3((unsigned)B, (unsigned)split), dim3(256), 0, st, ix->rows, ix->scope_perm,
-                                                                ix->scope_offsets, n - ix->dead_count, ix->max_scope, dev_scopes, sorted_q, rank, B, split, ix->dpad,
-                                                                ix->qn, k, row_base, ix->partial);
+            return launch_by_metric<scope_scan_l2<dt, ni, sl>, scope_scan_kernel<dt, ni, sl>>(
+                kernel_metric(ix->metric), dim3((unsigned)B, (unsigned)split), dim3(256), 0, st, ix->rows, ix->scope_perm, ix->scope_offsets,
+                n - ix->dead_count, ix->max_scope, dev_scopes, sorted_q, rank, B, split, ix->dpad, ix->qn, k, row_base, ix->partial);
         });
     }
     if (rc != 0) return rc;
@@ -4144,11 +2289,9 @@ int masked_search_body(codd_knn_index* ix, const float* dev_queries, int B, int 
         EvScope ev(ix, EV_SCAN, st);
         rc = with_row_form(ix, k, "row too wide for the mask scan%s", [&](auto dt, auto ni, auto sl) {
             constexpr int NB = scope_nb(decltype(dt)::value, decltype(ni)::value);
-            if (ix->metric == CODD_KNN_METRIC_L2)
-                return launch_kernel<mask_scan_l2<dt, ni, sl>>(dim3((unsigned)((B + NB - 1) / NB), (unsigned)split), dim3(256), 0, st, ix->rows, ix->mask_list, m, B,
-                                                               split, ix->dpad, ix->qn, k, row_base, ix->partial);
-            return launch_kernel<mask_scan_kernel<dt, ni, sl>>(dim3((unsigned)((B + NB - 1) / NB), (unsigned)split), dim3(256), 0, st, ix->rows, ix->mask_list, m,
-                                                               B, split, ix->dpad, ix->qn, k, row_base, ix->partial);
+            return launch_by_metric<mask_scan_l2<dt, ni, sl>, mask_scan_kernel<dt, ni, sl>>(kernel_metric(ix->metric), dim3((unsigned)((B + NB - 1) / NB), (unsigned)split),
+                                                                                            dim3(256), 0, st, ix->rows, ix->mask_list, m, B, split, ix->dpad, ix->qn, k,
+                                                                                            row_base, ix->partial);
         });
     }
     if (rc != 0) return rc;

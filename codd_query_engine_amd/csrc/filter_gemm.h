@@ -354,7 +354,7 @@ constexpr int kFinThreads = kFinWaves * kWave; // round trips (hit list, k ancho
 //   dead : the tombstone bits (null: no row was ever deleted).  A dead hit is dropped BEFORE the k best approximate hits are
 //          chosen — L' must be the smallest exact score of k LIVE rows, or rows between a dead anchor's score and the live
 //          k-th best would be cut off — and it is never re-scored into the answer.
-// Shared by finalize_kernel and by the last workgroup of small_batch_kernel (codd_knn.hip).
+// Shared by finalize_kernel and by the last workgroup of small_batch_kernel (shadow8_kernels.h).
 template <int DT, int NITER, int SLOTS, int METRIC = kMetricDot>
 __device__ __forceinline__ void finalize_body(const void* __restrict__ rows_, int dpad, const float* __restrict__ qn_q, const u64* __restrict__ my,
                                               unsigned total, unsigned part, unsigned nparts, int k, float eps1, float bq,

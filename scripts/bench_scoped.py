@@ -26,7 +26,7 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK = 8.0e12  # bytes/s
 CHUNK = 250_000
-QUERIES_PER_ITEM = 4  # f32 / narrow rows (scope_nb in csrc/codd_knn.hip)
+QUERIES_PER_ITEM = 4  # f32 / narrow rows (scope_nb in csrc/list_scan_kernels.h)
 
 
 def head_commit(given):
