@@ -69,11 +69,23 @@ struct FilterCtl {
     unsigned fb_list[kTileQ];  // ... and which ones
 };
 
+// What the last filter_pass on a workspace ran, for codd_knn_debug_last_pass: host fields only, no device state
+struct LastPass {
+    bool valid = false;
+    int family = 0, nbq = 0, ts = 0, res = 0, el = 0, sqd = 0;
+    int nq = 0, k = 0;
+    int64_t n = 0, sample_tiles = 0, sample_stride = 0;
+    int hit_cap = 0;
+    float eps = 0.0f;
+    int per_block_filter = 0, per_block_finalize = 0;
+};
+
 // Search workspace.  An index keeps up to kMaxWork of them, one per HIP stream that searches it, so that searches
 // issued on different streams (the next batch while this batch's small kernels and its collective are still in
 // flight) never share scratch memory.  The index inherits one set of these fields: WorkScope loads the calling
 // stream's set into them for the duration of one call and stores it back (a swap each way: one owner at any time).
 struct WorkBufs {
+    LastPass last;                // the last filter_pass that ran on this workspace (codd_knn_debug_last_pass)
     // (grown on demand, never inside a captured region after warm-up)
     DevBuf<float> qn;             // [B][dpad] normalised queries
     DevBuf<u64> partial;          // [B][blocks][k]
@@ -1147,6 +1159,15 @@ int filter_pass(codd_knn_index* ix, const float* qn, int nq, int k, uint32_t row
     // sample: every `stride`-th tile
     const int64_t ts = sample_tile_count(ix, ntiles, k, use8, prog.nbq);
     const int64_t stride = ntiles / ts;
+    {
+        LastPass& lp = ix->last;
+        lp.valid = true;
+        lp.family = (int)prog.family; lp.nbq = prog.nbq; lp.ts = prog.ts; lp.res = prog.res; lp.el = prog.el; lp.sqd = prog.sqd ? 1 : 0;
+        lp.nq = nq; lp.k = k; lp.n = n; lp.sample_tiles = ts; lp.sample_stride = stride; lp.hit_cap = ix->hit_cap_q;
+        lp.eps = eps;
+        lp.per_block_filter = prog.family == FilterProgram::TILE && (ix->per_block & 1) ? 1 : 0;
+        lp.per_block_finalize = slack_q && (ix->per_block & 2) && cosine ? 1 : 0;
+    }
     {
         EvScope ev(ix, EV_SAMPLE, st);
         const dim3 g((unsigned)(ts < ix->num_cus ? ts : ix->num_cus));
@@ -2763,6 +2784,55 @@ int codd_knn_exp_read_stamps(codd_knn_index* ix, unsigned long long* host_out, i
     return CODD_KNN_OK;
 }
 #endif
+
+int codd_knn_debug_last_pass(codd_knn_index* ix, void* stream, codd_knn_last_pass* info, float* thr, float* qmeta, uint32_t* hit_counts,
+                             uint32_t* fb_list, uint64_t* keys, int64_t keys_per_query, uint64_t* bucket_max, int64_t bucket_max_cap,
+                             float* bmeta, int64_t bmeta_blocks) {
+    if (keys_per_query < 0 || bucket_max_cap < 0 || bmeta_blocks < 0) return fail(CODD_KNN_EINVAL, "negative buffer size%s");
+    if (!ix) return fail(CODD_KNN_EINVAL, "null index%s");
+    hipStream_t st = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lock(ix->mu);
+    // the stream's workspace where it rests between calls (no WorkScope: a stream that never searched must not take a slot)
+    const WorkBufs* w = nullptr;
+    for (const WorkSlot& s : ix->slots)
+        if (s.used && s.stream == st) w = &s.bufs;
+    if (!w || !w->last.valid) return fail(CODD_KNN_EINVAL, "no filter pass has run on this stream's workspace%s");
+    const LastPass& lp = w->last;
+    if (bucket_max && bucket_max_cap < (int64_t)kTileQ * lp.sample_tiles) return fail(CODD_KNN_EINVAL, "bucket_max buffer below 256 x sampled tiles%s");
+    DeviceGuard guard(ix->device);
+    HIP_TRY(hipStreamSynchronize(st));
+    FilterCtl ctl;
+    HIP_TRY(hipMemcpy(&ctl, w->ctl.get(), sizeof(FilterCtl), hipMemcpyDeviceToHost));
+    if (info) {
+        info->family = lp.family; info->nbq = lp.nbq; info->ts = lp.ts; info->res = lp.res; info->el = lp.el; info->sqd = lp.sqd;
+        info->nq = lp.nq; info->k = lp.k; info->hit_cap = lp.hit_cap;
+        info->per_block_filter = lp.per_block_filter; info->per_block_finalize = lp.per_block_finalize;
+        info->eps = lp.eps;
+        info->n = lp.n; info->sample_tiles = lp.sample_tiles; info->sample_stride = lp.sample_stride;
+        for (int i = 0; i < 4; ++i) info->flags[i] = i < FLAG_WORDS ? ctl.flags[i] : 0u;
+        info->fb_count = ctl.fb_count;
+    }
+    if (thr) HIP_TRY(hipMemcpy(thr, w->thr.get(), 2 * kTileQ * sizeof(float), hipMemcpyDeviceToHost));
+    if (qmeta && lp.el && w->qmeta) HIP_TRY(hipMemcpy(qmeta, w->qmeta.get(), 1024 * sizeof(float), hipMemcpyDeviceToHost));
+    if (hit_counts)
+        for (int q = 0; q < kTileQ; ++q) hit_counts[q] = ctl.hit_cnt[q * kHitCntStride];
+    if (fb_list) memcpy(fb_list, ctl.fb_list, sizeof(ctl.fb_list));
+    if (keys && keys_per_query > 0) {
+        for (int q = 0; q < kTileQ; ++q) {
+            int64_t m = ctl.hit_cnt[q * kHitCntStride];
+            if (m > lp.hit_cap) m = lp.hit_cap;
+            if (m > keys_per_query) m = keys_per_query;
+            if (m > 0) HIP_TRY(hipMemcpy(keys + (int64_t)q * keys_per_query, w->hits.get() + (int64_t)q * lp.hit_cap, (size_t)m * sizeof(u64), hipMemcpyDeviceToHost));
+        }
+    }
+    if (bucket_max) HIP_TRY(hipMemcpy(bucket_max, w->bucket_max.get(), (size_t)kTileQ * lp.sample_tiles * sizeof(u64), hipMemcpyDeviceToHost));
+    if (bmeta && lp.el && ix->bmeta) {
+        int64_t nb = (lp.n + 31) / 32;
+        if (nb > bmeta_blocks) nb = bmeta_blocks;
+        if (nb > 0) HIP_TRY(hipMemcpy(bmeta, ix->bmeta.get(), (size_t)nb * sizeof(float2), hipMemcpyDeviceToHost));
+    }
+    return CODD_KNN_OK;
+}
 
 int codd_knn_set_option(codd_knn_index* ix, const char* key, int64_t value) {
     if (!ix || !key) return fail(CODD_KNN_EINVAL, "bad option arguments%s");

@@ -429,6 +429,37 @@ class DeviceKnnIndex:
         )
         return out
 
+    def last_pass(self, keys_per_query: int | None = None, want_bmeta: bool = True) -> dict:
+        """What the last filter pass on this stream's workspace left behind (diagnostics; codd_knn_debug_last_pass): a dict of
+        the program and shape fields of codd_knn_last_pass ("family" as its name), "flags", "fb_count", and numpy arrays "thr" [256],
+        "thr0" [256], "qmeta" [1024] (int8 passes, else None), "hit_counts" [256], "fb_list" [256], "keys" (a list of 256 u64
+        arrays: each query's first min(counter, hit_cap, keys_per_query) candidate keys), "bucket_max" [256, sample_tiles] and
+        "bmeta" [ceil(n / 32), 2] (int8 passes, else None).  keys_per_query: None = the largest list the pass left."""
+        info = native.LastPassInfo()
+        ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+        thr = np.zeros(512, dtype=np.float32)
+        qmeta = np.zeros(1024, dtype=np.float32)
+        counts = np.zeros(256, dtype=np.uint32)
+        fb_list = np.zeros(256, dtype=np.uint32)
+        call = self._lib.codd_knn_debug_last_pass
+        native.check(call(self._h, self._stream(), ctypes.byref(info), ptr(thr), ptr(qmeta), ptr(counts), ptr(fb_list), None, 0, None, 0, None, 0),
+                     "codd_knn_debug_last_pass")
+        kept = np.minimum(counts.astype(np.int64), info.hit_cap)
+        per_q = int(kept.max()) if keys_per_query is None else int(keys_per_query)
+        kept = np.minimum(kept, per_q)
+        keys = np.zeros((256, max(per_q, 1)), dtype=np.uint64)
+        buckets = np.zeros((256, info.sample_tiles), dtype=np.uint64)
+        nblocks = (info.n + 31) // 32 if (want_bmeta and info.el) else 0
+        bmeta = np.zeros((max(nblocks, 1), 2), dtype=np.float32)
+        native.check(call(self._h, self._stream(), None, None, None, None, None, ptr(keys), per_q, ptr(buckets), buckets.size, ptr(bmeta) if nblocks else None, nblocks),
+                     "codd_knn_debug_last_pass")
+        out = {name: getattr(info, name) for name, _ in native.LastPassInfo._fields_ if name not in ("flags", "reserved_", "family")}
+        out["family"] = native.FILTER_FAMILIES[info.family]
+        out["flags"] = list(info.flags)
+        out.update(thr=thr[:256].copy(), thr0=thr[256:].copy(), qmeta=qmeta if info.el else None, hit_counts=counts, fb_list=fb_list,
+                   keys=[keys[q, : kept[q]].copy() for q in range(256)], bucket_max=buckets, bmeta=bmeta[:nblocks] if nblocks else None)
+        return out
+
     # ------------------------------------------------------------------ knobs
     def set_option(self, key: str, value: int) -> None:
         native.check(self._lib.codd_knn_set_option(self._h, key.encode(), int(value)), f"set_option({key})")

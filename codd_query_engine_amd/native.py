@@ -76,7 +76,22 @@ ABI = [
     ("codd_knn_set_option", ctypes.c_int, [_c_idx, ctypes.c_char_p, ctypes.c_int64]),
     ("codd_knn_get_stat", ctypes.c_int, [_c_idx, ctypes.c_char_p, _i64p]),
     ("codd_knn_debug_live_allocations", ctypes.c_int, [_i64p, _i64p, _i64p]),
+    ("codd_knn_debug_last_pass", ctypes.c_int, [_c_idx, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64]),
 ]
+
+
+class LastPassInfo(ctypes.Structure):
+    """codd_knn_last_pass of include/codd_knn.h"""
+
+    _fields_ = (
+        [(name, ctypes.c_int32) for name in ("family", "nbq", "ts", "res", "el", "sqd", "nq", "k", "hit_cap", "per_block_filter", "per_block_finalize")]
+        + [("eps", ctypes.c_float)]
+        + [(name, ctypes.c_int64) for name in ("n", "sample_tiles", "sample_stride")]
+        + [("flags", ctypes.c_uint32 * 4), ("fb_count", ctypes.c_uint32), ("reserved_", ctypes.c_uint32)]
+    )
+
+
+FILTER_FAMILIES = ("GEMM", "TILE", "TILE_F16")
 
 
 class NativeLibraryError(RuntimeError):

@@ -515,6 +515,46 @@ int codd_knn_get_stat(const codd_knn_index* index, const char* key, int64_t* out
  * codd_knn_create (tests compare against such a baseline: other indexes may be alive).  No device call; EINVAL for a null pointer. */
 int codd_knn_debug_live_allocations(int64_t* buffers, int64_t* bytes, int64_t* events);
 
+/*
+ * Debug: what the LAST filter pass (sample -> anchor -> filter -> finalize) on `stream`'s workspace left behind,
+ * copied to the host.  Takes that workspace, synchronises the stream, copies; launches no kernel and changes no state (a stream
+ * that never searched this index takes no workspace).  A search of more than 256 queries runs one pass per 256 queries over the
+ * same workspace: only its last pass is left.  EINVAL, nothing copied: null index, a negative size, no filter pass has run on that
+ * workspace, or bucket_max_cap too small.  Any output pointer may be NULL.
+ * "That workspace" is the slot, not the stream: an index keeps four, and a fifth stream takes over the least recently used one
+ * with the record of its previous owner's last pass, until its own first filter pass replaces it.
+ * The record is written on the host when the pass is enqueued, so replaying a captured graph does not refresh it; and the call
+ * synchronises the stream, so it must not be made while that stream is capturing.
+ *   info        the program that ran and the pass's shape (below)
+ *   thr         [512]   thr[q], then thr0[q] (thr0: int8 passes only)
+ *   qmeta       [1024]  int8 passes only (info->el = 1; untouched otherwise): q-scale, 2 eps(q), A(q), B(q) — for an l2 index
+ *                       [512 + q] is the query's sum of squares
+ *   hit_counts  [256]   the raw candidate counters as they are: above hit_cap where a list was cut
+ *   fb_list     [256]   the fallback queue's words (info->fb_count of them are entries where finalize ran as its own launch; the
+ *                       fused finalize derives the queue from the counters and writes neither)
+ *   keys        [256][keys_per_query]  the first min(counter, hit_cap, keys_per_query) candidate keys of each query (approximate
+ *                       score in the high word, 0xFFFFFFFF - local row in the low one); the rest is untouched
+ *   bucket_max  [256][info->sample_tiles]  the sample pass's best key per (query, sampled tile); bucket_max_cap: u64 the buffer holds
+ *   bmeta       [min(bmeta_blocks, ceil(n / 32))][2]  int8 passes only: {scale, error norm} of the index's 32-row blocks as they are now
+ */
+typedef struct codd_knn_last_pass {
+    int32_t family;             /* 0 GEMM (gemm_filter_kernel, sqd_filter_kernel), 1 TILE (i8_tile_kernel), 2 TILE_F16 */
+    int32_t nbq, ts, res, el, sqd;
+    int32_t nq, k;
+    int32_t hit_cap;
+    int32_t per_block_filter;   /* the filter launch evaluated the int8 bound per 32-row block (thr0, bmeta) */
+    int32_t per_block_finalize; /* ... and so did finalize */
+    float eps;                  /* filter_eps(): the 2-byte filter's slack (recorded for every pass) */
+    int64_t n;                  /* rows the pass ran over */
+    int64_t sample_tiles, sample_stride;
+    uint32_t flags[4];          /* FLAG_* words of the control block: [0] a workgroup hit list filled up, [1] a query was queued */
+    uint32_t fb_count;
+    uint32_t reserved_;
+} codd_knn_last_pass;
+int codd_knn_debug_last_pass(codd_knn_index* index, void* stream, codd_knn_last_pass* info, float* thr, float* qmeta,
+                             uint32_t* hit_counts, uint32_t* fb_list, uint64_t* keys, int64_t keys_per_query,
+                             uint64_t* bucket_max, int64_t bucket_max_cap, float* bmeta, int64_t bmeta_blocks);
+
 #ifdef __cplusplus
 }
 #endif

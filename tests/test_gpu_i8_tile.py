@@ -2,7 +2,11 @@
 8-query-block instantiation; rows of more than 512
 elements; from 384 elements on with the option i8v2 = 2).  Hand-ordered LDS-DMA staging, a lagging half of the
 workgroup, deferred epilogues with an integer pre-test: all of it may only change SPEED.  Ids and distances must equal
-the oracle's bit for bit, and the candidate lists must be the ones the first-generation kernel writes."""
+the oracle's bit for bit.  The candidate lists: under the device-wide bound ("per_block" = 0) they hold the first-generation
+kernel's list row for row, plus rows whose accumulator is within three levels of the threshold (the integer test's slack); under
+the per-block bound, the default, they are the rows the per-block cut names, up to the roundings of its threshold
+(test_tile_kernel_writes_the_same_candidate_lists_as_the_first_generation here; every tile program by name, with the sample keys
+and the thresholds, in tests/test_gpu_filter_stages.py)."""
 
 import numpy as np
 import pytest
@@ -133,28 +137,55 @@ def test_tile_kernel_writes_the_same_candidate_lists_as_the_first_generation(Ind
     """Same sample, same anchors: the results must not depend on which kernel ran.  Since round 3 the tile kernel evaluates the
     int8 bound per 32-row block (each block's own quantisation error norm instead of the corpus's worst), so its candidate list
     is a SUBSET-sized one: fewer candidates than the first-generation kernel's (device-wide bound), never more than a
-    hair above it (its integer per-value test has two accumulator levels of slack); `per_block` = 0 gives the old lists back."""
+    hair above it (its integer per-value test has two accumulator levels of slack); `per_block` = 0 gives the old lists back.
+
+    The lists themselves, read back after each search (tests/test_gpu_filter_stages.py states and derives every statement):
+    the three runs leave the same sample keys and thresholds, bit for bit; the first-generation list is exactly
+    {fp32(acc s_row) >= fp32(thr / s_q)}; the tile kernel's list under `per_block` = 0 holds every row of it, and each of its other
+    rows has an accumulator at most three levels below the smallest one that reaches thr; its list under the per-block bound holds
+    every row with margin m > delta and none with m < -delta - 3 scale_b s_q."""
+    import copy
+
+    from tests import _filter_stage_reference as fs
+
     rng = np.random.default_rng(77)
     n, d, B, k = 120_000, 768, 256, 10
     raw = rng.standard_normal((n, d)).astype(np.float32)
     q = rng.standard_normal((B, d)).astype(np.float32)
-    stats = []
-    for v in (0, 1):
+    cases = {
+        "first": (fs.Case("first-generation", "GEMM", 8, d, B, n=n), 0, 7),
+        "tile": (fs.Case("tile", "TILE", 8, d, B, ts=3, n=n), 1, 7),
+        "tile-pb0": (fs.Case("tile-pb0", "TILE", 8, d, B, ts=3, n=n, options={"per_block": 0}), 1, 0),
+    }
+    base, runs = None, {}
+    for name, (case, v, per_block) in cases.items():
         ix = build(Index, raw, "f32", v)
+        ix.set_option("per_block", per_block)
         dist, rows = ix.search(q, k)
         assert ix.stat("i8v2_passes") == v
-        stats.append((ix.stat("filter_hits"), ix.stat("filter_survivors"), dist.copy(), rows.copy()))
+        lp = ix.last_pass()
+        assert {key: lp[key] for key in case.program()} == case.program(), (name, "another program ran")
+        if base is None:
+            base = fs.Pass(case, ix.read_rows(), q)
+        p = copy.copy(base)
+        p.case = case
+        fs.check_sample(p, lp)
+        L, thr, thr0 = fs.check_thresholds(p, lp)
+        fs.check_candidates(p, lp, L, thr, thr0)
+        runs[name] = (ix.stat("filter_hits"), ix.stat("filter_survivors"), dist.copy(), rows.copy(), lp)
         ix.close()
-    assert stats[0][0] * 0.4 <= stats[1][0] <= stats[0][0] * 1.01 + 8, (stats[0][0], stats[1][0])
-    assert stats[1][1] <= stats[0][1] * 1.01 + 8, (stats[0][1], stats[1][1])
-    assert np.array_equal(stats[0][2], stats[1][2]) and np.array_equal(stats[0][3], stats[1][3])
-    # the device-wide bound in both kernels: the tile kernel's list holds the first-generation kernel's, plus a hair
-    ix = build(Index, raw, "f32", 1)
-    ix.set_option("per_block", 0)
-    dist, rows = ix.search(q, k)
-    assert stats[0][0] <= ix.stat("filter_hits") <= stats[0][0] * 1.01 + 8
-    assert np.array_equal(dist, stats[0][2]) and np.array_equal(rows, stats[0][3])
-    ix.close()
+    first, tile, pb0 = runs["first"], runs["tile"], runs["tile-pb0"]
+    for other in (tile, pb0):
+        assert np.array_equal(other[4]["bucket_max"], first[4]["bucket_max"])
+        assert np.array_equal(other[4]["thr"].view(np.uint32), first[4]["thr"].view(np.uint32))
+        assert np.array_equal(other[2], first[2]) and np.array_equal(other[3], first[3])
+    for z in range(B):
+        a, c = set(fs.key_rows(first[4]["keys"][z]).tolist()), set(fs.key_rows(pb0[4]["keys"][z]).tolist())
+        assert a <= c, (z, sorted(a - c)[:8])      # (the rows of c - a: within the integer slack, check_candidates above)
+    assert tile[0] <= first[0] * 1.01 + 8, (first[0], tile[0])
+    assert tile[1] <= first[1] * 1.01 + 8, (first[1], tile[1])
+    assert first[0] <= pb0[0] <= first[0] * 1.01 + 8
+    assert first[0] == sum(len(x) for x in first[4]["keys"]) and pb0[0] == sum(len(x) for x in pb0[4]["keys"])
 
 
 def test_tile_kernel_negative_and_zero_thresholds_and_zero_queries(Index):
