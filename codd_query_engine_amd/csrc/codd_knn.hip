@@ -14,7 +14,7 @@
 //   (here)               the exact pass, the filter pass, scopes, then the extern "C" entry points with the bodies of the IVF and
 //                        masked searches between them
 //
-// The other headers (exact_score.h, wave_topk.h, row_traits.h, filter_gemm.h, filter_i8.h, doc_match.h, text_embed.h,
+// The other headers (exact_score.h, wave_topk.h, row_traits.h, filter_gemm.h, filter_i8.h, doc_match.h, doc_regex.h, text_embed.h,
 // device_mem.h) are interfaces in namespace codd and come first.
 //
 // HBM-bound byte streaming throughout: the corpus is read once per pass, each row by exactly one
@@ -37,6 +37,7 @@
 #define CODD_EXPERIMENTS 0  // 1 (build_variant only): the diagnostic switches that can return wrong results exist
 #endif
 #include "doc_match.h"
+#include "doc_regex.h"
 #include "exact_score.h"
 #include "filter_gemm.h"
 #include "filter_i8.h"
@@ -113,6 +114,11 @@ struct WorkBufs {
     // codd_knn_search_masked_dev: the visible rows of a device mask, counted on the device and read back through pinned memory
     DevBuf<unsigned long long> mask_m_dev;
     PinnedBuf<unsigned long long> mask_m_host;
+    // codd_knn_match_documents_dfa: the call's class map and table, staged in pinned memory and copied to the device
+    // on the calling stream — per stream, so two threads' patterns cannot overwrite each other
+    PinnedBuf<uint32_t> dfa_host;   // [kRegexTableWords]; dfa_uploaded: its last copy to the device
+    Event dfa_uploaded; bool dfa_upload_pending = false;
+    DevBuf<uint32_t> dfa_dev;       // [kRegexTableWords]
 };
 static_assert(!std::is_copy_constructible<WorkBufs>::value, "a workspace has one owner (WorkScope swaps, never copies)");
 constexpr int kMaxWork = 4;
@@ -276,6 +282,7 @@ struct codd_knn_index : WorkBufs {
     int64_t doc_bytes = 0;             // the arena: the documents' bytes plus one separator each
     int64_t doc_count = -1, doc_epoch = -1;
     int64_t stat_doc_matches = 0;
+    int64_t stat_doc_regex_matches = 0;   // codd_knn_match_documents_dfa calls that launched
 
     // tombstones: one bit per row slot, set = deleted.  Null until the first codd_knn_delete_host — the kernels
     // take a null pointer as "nothing was ever deleted" and load nothing.  The host keeps a mirror: the write paths refuse dead
@@ -2539,6 +2546,57 @@ int codd_knn_match_documents(codd_knn_index* ix, const uint8_t* host_needle, int
     return CODD_KNN_OK;
 }
 
+int codd_knn_match_documents_dfa(codd_knn_index* ix, const uint8_t* host_class_of, const uint8_t* host_next, int nstates, int nclasses, int start, int accept,
+                                 uint32_t* dev_bits, int64_t nwords, void* stream) {
+    if (!ix || !host_class_of || !host_next) return fail(CODD_KNN_EINVAL, "match_documents_dfa: null index, class map or table%s");
+    static_assert(kRegexMaxStates == CODD_KNN_MAX_DFA_STATES && kRegexMaxTable == CODD_KNN_MAX_DFA_TABLE, "doc_regex.h and codd_knn.h disagree");
+    // the table is checked here, entry by entry, before anything is enqueued: on the device no entry leads outside it
+    if (nstates < 1 || nstates > CODD_KNN_MAX_DFA_STATES) return fail(CODD_KNN_EINVAL, "match_documents_dfa: nstates out of range [1,255]%s");
+    if (nclasses < 1 || nclasses > 256) return fail(CODD_KNN_EINVAL, "match_documents_dfa: nclasses out of range [1,256]%s");
+    const int entries = nstates * nclasses;
+    if (entries > CODD_KNN_MAX_DFA_TABLE) return fail(CODD_KNN_EINVAL, "match_documents_dfa: the table exceeds CODD_KNN_MAX_DFA_TABLE bytes%s");
+    if (start < 0 || start >= nstates || accept < 0 || accept >= nstates) return fail(CODD_KNN_EINVAL, "match_documents_dfa: start or accept is not a state%s");
+    for (int b = 0; b < 256; ++b)
+        if (host_class_of[b] >= nclasses) return fail(CODD_KNN_EINVAL, "match_documents_dfa: a byte's class is not below nclasses%s");
+    for (int i = 0; i < entries; ++i)
+        if (host_next[i] >= nstates) return fail(CODD_KNN_EINVAL, "match_documents_dfa: a table entry is not a state%s");
+    for (int c = 0; c < nclasses; ++c)
+        if (host_next[accept * nclasses + c] != accept) return fail(CODD_KNN_EINVAL, "match_documents_dfa: the accepting state must be absorbing%s");
+    int reject = -1;   // an absorbing state other than accept, if the table has one: a lane stops reading there too
+    for (int s = 0; s < nstates && reject < 0; ++s) {
+        bool absorbing = s != accept;
+        for (int c = 0; c < nclasses && absorbing; ++c) absorbing = host_next[s * nclasses + c] == s;
+        if (absorbing) reject = s;
+    }
+    DeviceGuard guard(ix->device);
+    hipStream_t st = (hipStream_t)stream;
+    WorkScope work(ix, st);   // (holds the index's enqueue lock from the checks below to the launch: the snapshot checked is the snapshot read)
+    if (!docs_valid(ix)) return fail(CODD_KNN_EINVAL, "match_documents_dfa: no document snapshot, or a stale one (rows changed since codd_knn_set_documents_host)%s");
+    if (nwords != (ix->count + 31) / 32) return fail(CODD_KNN_EINVAL, "match_documents_dfa: nwords must be ceil(count / 32)%s");
+    if (nwords == 0) return CODD_KNN_OK;
+    if (!dev_bits) return fail(CODD_KNN_EINVAL, "match_documents_dfa: null bits%s");
+    // the class map and the table: into the stream's pinned staging buffer (its previous copy is waited for first), one copy on `st`
+    if (ix->dfa_upload_pending) HIP_TRY(hipEventSynchronize(ix->dfa_uploaded));
+    ix->dfa_upload_pending = false;
+    HIP_TRY(ix->dfa_host.ensure(kRegexTableWords));
+    HIP_TRY(ix->dfa_dev.ensure(kRegexTableWords));
+    HIP_TRY(ix->dfa_uploaded.ensure());
+    const int table_words = (entries + 3) / 4, words = kRegexClassWords + table_words;
+    memset(ix->dfa_host.get(), 0, (size_t)words * sizeof(uint32_t));
+    memcpy(ix->dfa_host.get(), host_class_of, 256);
+    memcpy(ix->dfa_host.get() + kRegexClassWords, host_next, (size_t)entries);
+    HIP_TRY(hipMemcpyAsync(ix->dfa_dev, ix->dfa_host, (size_t)words * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(ix->dfa_uploaded, st));
+    ix->dfa_upload_pending = true;
+    const int64_t runs = (ix->count + kRegexDocs - 1) / kRegexDocs;
+    const int rc = launch_kernel<doc_regex_kernel>(dim3((unsigned)runs), dim3(kRegexDocs), 0, st, reinterpret_cast<const uint4*>(ix->doc_arena.get()), ix->doc_offsets,
+                                                   ix->count, ix->dfa_dev, table_words, nclasses, start, accept, reject, dev_bits, nwords);
+    if (rc != 0) return rc;
+    HIP_TRY(hipGetLastError());
+    ix->stat_doc_regex_matches++;
+    return CODD_KNN_OK;
+}
+
 int codd_knn_embedder_create(codd_knn_embedder** out, int device, int dim, float trigram_weight) {
     if (!out) return fail(CODD_KNN_EINVAL, "embedder_create: null out pointer%s");
     *out = nullptr;
@@ -3050,6 +3108,9 @@ int codd_knn_get_stat(const codd_knn_index* ix, const char* key, int64_t* out) {
     else if (strcmp(key, "doc_bytes") == 0) *out = ix->doc_arena ? ix->doc_bytes : 0;
     else if (strcmp(key, "doc_tile_bytes") == 0) *out = kDocTile;
     else if (strcmp(key, "doc_matches") == 0) *out = ix->stat_doc_matches;
+    else if (strcmp(key, "doc_regex_tile_bytes") == 0) *out = kRegexTile;
+    else if (strcmp(key, "doc_regex_run_docs") == 0) *out = kRegexDocs;
+    else if (strcmp(key, "doc_regex_matches") == 0) *out = ix->stat_doc_regex_matches;
     else if (strcmp(key, "dead_rows") == 0) *out = ix->dead_count;
     else if (strcmp(key, "delete_calls") == 0) *out = ix->stat_delete_calls;
     else if (strcmp(key, "compactions") == 0) *out = ix->stat_compactions;

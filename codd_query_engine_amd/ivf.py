@@ -217,5 +217,8 @@ class IvfShardEngine:
     def match_documents(self, needle: bytes):
         return self.index.match_documents(needle)
 
+    def match_documents_dfa(self, dfa):
+        return self.index.match_documents_dfa(dfa)
+
     def slice_mask(self, global_bits, global_rows: int, row_base: int):
         return self.index.slice_mask(global_bits, global_rows, row_base)

@@ -44,12 +44,14 @@ from __future__ import annotations
 
 import json
 import os
+import re
 import shutil
 import time
 from typing import Any, Callable, Optional, Sequence
 
 import numpy as np
 
+from . import regex_dfa
 from .embedding import EmbeddingFunction, HashingEmbeddingFunction
 
 _DEFAULT_SPACE = "cosine"
@@ -74,6 +76,7 @@ def _factory_spaces(engine_factory) -> tuple:
 
 _SPACE_FILTER_KEY = "codd:space_filter"
 _SPACE_IVF_KEY = "codd:space_ivf"
+_DOCUMENT_REGEX_KEY = "codd:document_regex"   # collection metadata: 1 = where_document knows $regex / $not_regex
 
 
 def _space_of(metadata: Optional[dict]) -> str:
@@ -96,8 +99,9 @@ class Collection:
     DEVICE_EMBED_MIN_TEXTS = 2
 
     def __init__(self, name: str, metadata: Optional[dict], embedding_function: EmbeddingFunction,
-                 engine_factory: Callable[[int], Any]):
+                 engine_factory: Callable[[int], Any], document_regex: bool = False):
         self.name = name
+        self._client_document_regex = bool(document_regex)   # KnnClient(document_regex=True): the opt-in without the metadata key
         self.metadata = dict(metadata or {})
         self._embed = embedding_function
         self._engine_factory = engine_factory
@@ -116,9 +120,11 @@ class Collection:
         # `where_document`: host masks by canonical filter; on a device engine the needles' bitmaps (packed words on the GPU) by needle
         # bytes, and whether the engine holds the current documents.  Dropped with the two above.
         self._doc_mask_cache: dict[str, np.ndarray] = {}
-        self._doc_bits_cache: dict[bytes, Any] = {}
+        # ... and under ("re", pattern) a $regex pattern's, under ("has document",) the records that have one
+        self._doc_bits_cache: dict[Any, Any] = {}
         self._docs_on_device = False
         self._docs_fit_device: Optional[bool] = None   # no document holds NUL (None: not looked yet; one pass per change)
+        self._docs_ascii: Optional[bool] = None        # every document is ASCII (found by the same pass)
 
     # ------------------------------------------------------------------ helpers
     @property
@@ -318,14 +324,25 @@ class Collection:
         self._doc_bits_cache.clear()
         self._docs_on_device = False
         self._docs_fit_device = None
+        self._docs_ascii = None
 
     # ------------------------------------------------------------------ where_document -> row mask
     _WHERE_DOCUMENT_GRAMMAR = ('{"$contains": "text"}, {"$not_contains": "text"}, {"$and": [filters]}, {"$or": [filters]}; '
                                'text is a non-empty str, matched case-sensitively as a substring of the stored document')
+    # ... on a collection that opted in to regular expressions ("codd:document_regex": 1, or KnnClient(document_regex=True))
+    _WHERE_DOCUMENT_GRAMMAR_REGEX = ('{"$contains": "text"}, {"$not_contains": "text"}, {"$regex": "pattern"}, {"$not_regex": "pattern"}, '
+                                     '{"$and": [filters]}, {"$or": [filters]}; text is a non-empty str, matched case-sensitively as a substring of '
+                                     'the stored document; pattern is a non-empty str that re.compile accepts, matched as re.search(pattern, document)')
     _DEVICE_NEEDLE_MAX = 256  # CODD_KNN_MAX_NEEDLE: longer needles, and needles holding NUL, are evaluated on the host
 
+    @property
+    def document_regex(self) -> bool:
+        """Whether `where_document` knows $regex / $not_regex here: the collection's metadata says so, or its client does."""
+        return self._client_document_regex or bool(self.metadata.get(_DOCUMENT_REGEX_KEY))
+
     def _where_document_error(self, where_document, why: str) -> ValueError:
-        return ValueError(f"unsupported where_document filter {where_document!r}: {why}; supported: {self._WHERE_DOCUMENT_GRAMMAR}")
+        grammar = self._WHERE_DOCUMENT_GRAMMAR_REGEX if self.document_regex else self._WHERE_DOCUMENT_GRAMMAR
+        return ValueError(f"unsupported where_document filter {where_document!r}: {why}; supported: {grammar}")
 
     def _check_where_document(self, wd, top=None) -> None:
         """ValueError unless `wd` is a filter of ChromaDB's document grammar."""
@@ -341,6 +358,13 @@ class Collection:
         elif op in ("$contains", "$not_contains"):
             if not isinstance(arg, str) or arg == "":
                 raise self._where_document_error(top, f"{op} takes a non-empty str")
+        elif op in ("$regex", "$not_regex") and self.document_regex:
+            if not isinstance(arg, str) or arg == "":
+                raise self._where_document_error(top, f"{op} takes a non-empty str")
+            try:
+                re.compile(arg)
+            except (re.error, RecursionError, OverflowError) as e:
+                raise self._where_document_error(top, f"{op} pattern {arg!r} does not compile: {e}") from None
         else:
             raise self._where_document_error(top, f"unknown operator {op!r}")
 
@@ -355,13 +379,18 @@ class Collection:
         """bool over the row slots: the stored document contains `needle` (a record without a document contains nothing)."""
         return np.fromiter((doc is not None and needle in doc for doc in self._documents), dtype=bool, count=len(self._documents))
 
+    def _regex_mask(self, pattern: str) -> np.ndarray:
+        """bool over the row slots: re.search(pattern, document) finds something (a record without a document matches nothing)."""
+        search = re.compile(pattern).search
+        return np.fromiter((doc is not None and search(doc) is not None for doc in self._documents), dtype=bool, count=len(self._documents))
+
     def _eval_where_document(self, wd) -> np.ndarray:
         (op, arg), = wd.items()
         if op in ("$and", "$or"):
             masks = [self._eval_where_document(sub) for sub in arg]
             return np.logical_and.reduce(masks) if op == "$and" else np.logical_or.reduce(masks)
-        hit = self._contains_mask(arg)
-        return hit if op == "$contains" else self._live_mask() & ~hit   # (a deleted slot never passes)
+        hit = self._regex_mask(arg) if op in ("$regex", "$not_regex") else self._contains_mask(arg)
+        return hit if op in ("$contains", "$regex") else self._live_mask() & ~hit   # (a deleted slot never passes)
 
     def _where_document_mask(self, wd) -> np.ndarray:
         """The checked filter as a bool array over the row slots, evaluated on the host (`needle in doc`); cached by canonical JSON."""
@@ -406,6 +435,43 @@ class Collection:
             self._doc_bits_cache[raw] = bits
         return bits
 
+    def _cache_doc_bits(self, key, bits):
+        if len(self._doc_bits_cache) >= self._MASK_CACHE_SIZE:
+            self._doc_bits_cache.pop(next(iter(self._doc_bits_cache)))
+        self._doc_bits_cache[key] = bits
+        return bits
+
+    def _has_document_bits(self):
+        """The records that have a document, as words on the device (the arena stores None as an empty document)."""
+        bits = self._doc_bits_cache.get(("has document",))
+        if bits is None:
+            has = np.fromiter((doc is not None for doc in self._documents), dtype=bool, count=len(self._documents))
+            bits = self._cache_doc_bits(("has document",), self._words_on_device(has))
+        return bits
+
+    def _regex_bits(self, pattern: str):
+        """The bitmap of one $regex pattern on the device, from the cache (under ("re", pattern): no needle's bytes) or made now.
+        A pattern that is plain text after parsing is a needle (doc_match_kernel); one inside the device subset runs as a byte
+        DFA (regex_dfa.compile_search_dfa, doc_regex_kernel); any other is evaluated here by re and uploaded as a mask."""
+        key = ("re", pattern)
+        bits = self._doc_bits_cache.get(key)
+        if bits is not None:
+            return bits
+        text = regex_dfa.literal_of(pattern)
+        if text is not None:
+            return self._cache_doc_bits(key, self._needle_bits(text))
+        dfa = regex_dfa.compile_search_dfa(pattern, bool(self._docs_ascii)) if hasattr(self._engine, "match_documents_dfa") else None
+        if dfa is None:
+            return self._cache_doc_bits(key, self._words_on_device(self._regex_mask(pattern)))
+        if not self._docs_on_device:
+            self._engine.set_documents([None if doc is None else self._utf8(doc) for doc in self._documents])
+            self._docs_on_device = True
+        bits = self._engine.match_documents_dfa(dfa)
+        # the arena holds a record without a document as an empty one: where the pattern matches "", such records are taken out
+        if re.search(pattern, "") is not None and any(doc is None and doc_id is not None for doc, doc_id in zip(self._documents, self._ids)):
+            bits = bits & self._has_document_bits()
+        return self._cache_doc_bits(key, bits)
+
     def _where_document_bits(self, wd):
         (op, arg), = wd.items()
         if op in ("$and", "$or"):
@@ -414,14 +480,22 @@ class Collection:
             for part in parts[1:]:
                 out = out & part if op == "$and" else out | part
             return out
-        bits = self._needle_bits(arg)
-        return bits if op == "$contains" else ~bits   # (the engine clips the words to the count and drops dead rows)
+        bits = self._regex_bits(arg) if op in ("$regex", "$not_regex") else self._needle_bits(arg)
+        return bits if op in ("$contains", "$regex") else ~bits   # (the engine clips the words to the count and drops dead rows)
 
     def _documents_fit_device(self) -> bool:
         """The engine's arena separates documents by NUL: a collection whose documents hold one is filtered on the host.  One pass
-        over the documents per change of the collection (the flag is dropped with the snapshot's), not one per query."""
+        over the documents per change of the collection (the flag is dropped with the snapshot's), not one per query.  The same
+        pass finds out whether every document is ASCII: the condition for \\d \\w \\s and (?i) in a device pattern."""
         if self._docs_fit_device is None:
-            self._docs_fit_device = not any(doc is not None and "\x00" in doc for doc in self._documents)
+            fit = ascii_only = True
+            for doc in self._documents:
+                if doc is not None:
+                    if fit and "\x00" in doc:
+                        fit = False
+                    if ascii_only and not doc.isascii():
+                        ascii_only = False
+            self._docs_fit_device, self._docs_ascii = fit, ascii_only
         return self._docs_fit_device
 
     def _where_scopes(self, where, B: int) -> Optional[np.ndarray]:
@@ -613,7 +687,14 @@ class Collection:
         needle's bitmap is cached (32 entries), $and / $or / $not_contains and a `where` mask are combined there, and one
         search_masked_dev answers; a needle above 256 bytes or holding NUL is evaluated here and uploaded as a mask.  On an engine
         with search_masked only, the filter is evaluated here (`needle in doc`) and goes through search_masked.  An engine with
-        neither raises ValueError, as does anything outside the grammar (an empty string, a non-string, an unknown operator)."""
+        neither raises ValueError, as does anything outside the grammar (an empty string, a non-string, an unknown operator).
+
+        On a collection that opted in — metadata "codd:document_regex": 1, or KnnClient(document_regex=True) — the grammar also has
+        {"$regex": "pattern"} and {"$not_regex": "pattern"}: the document passes $regex iff re.search(pattern,
+        document) finds something, Python's semantics; a record without a document fails $regex and passes $not_regex.  On the
+        device path a pattern inside the device subset runs as a byte DFA (match_documents_dfa), plain text as a needle, and
+        anything else (back-references, look-around, \\b, flags, Unicode classes on non-ASCII documents) is evaluated here by re
+        and uploaded as a mask.  Without the opt-in the two operators are unknown operators, as before."""
         if (query_texts is None) == (query_embeddings is None):
             raise ValueError("give exactly one of query_texts / query_embeddings")
         if where_document is not None:
@@ -871,11 +952,14 @@ class KnnClient:
         dtype: storage dtype of the rows: "f32" | "bf16" | "f16".
         embedding_function: list[str] -> [n,d] float32; default HashingEmbeddingFunction(384).
         engine_factory: test seam, see module docstring.
+        document_regex: every collection of this client answers `where_document` {"$regex": ...} / {"$not_regex": ...} (DESIGN.md
+            §24); without it only a collection whose metadata carries "codd:document_regex": 1 does.
     """
 
     def __init__(self, device: str = "cuda:0", dtype: str = "f32", embedding_function: Optional[EmbeddingFunction] = None,
-                 engine_factory: Optional[Callable[[int], Any]] = None, path: Optional[str] = None):
+                 engine_factory: Optional[Callable[[int], Any]] = None, path: Optional[str] = None, document_regex: bool = False):
         self.device = device
+        self.document_regex = bool(document_regex)
         self.dtype = dtype
         self.path = path
         self._embed = embedding_function or HashingEmbeddingFunction()
@@ -887,7 +971,7 @@ class KnnClient:
                 cdir = os.path.join(path, entry)
                 gen = Collection._current_generation(cdir) if os.path.isdir(cdir) else None
                 if gen:
-                    col = Collection(entry, None, self._embed, self._engine_factory)
+                    col = Collection(entry, None, self._embed, self._engine_factory, self.document_regex)
                     col._load_generation(cdir, gen)
                     self._collections[col.name] = col
 
@@ -922,7 +1006,7 @@ class KnnClient:
                 continue
             col = self._collections.get(entry)
             if col is None:
-                col = Collection(entry, None, self._embed, self._engine_factory)
+                col = Collection(entry, None, self._embed, self._engine_factory, self.document_regex)
                 self._collections[entry] = col
             if int(gen.split("-")[1]) > col._generation:
                 col._load_generation(cdir, gen)
@@ -943,7 +1027,7 @@ class KnnClient:
         space = _space_of(metadata)
         if space not in _factory_spaces(self._engine_factory):
             raise ValueError(f"hnsw:space={space!r} is not on this path (supported: {_factory_spaces(self._engine_factory)})")
-        col = Collection(name, metadata, embedding_function or self._embed, self._engine_factory)
+        col = Collection(name, metadata, embedding_function or self._embed, self._engine_factory, self.document_regex)
         self._collections[name] = col
         return col
 

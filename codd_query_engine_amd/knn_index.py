@@ -38,7 +38,7 @@ class DeviceKnnIndex:
     Engine protocol consumed by knn_client.Collection:
         count() / upsert(slots, vecs) / search(queries, k) -> (dist, rows) as numpy;
         optionally set_scopes / search_scoped (`where=` by namespace), search_masked (any other `where=`), set_documents /
-        match_documents / search_masked_dev (`where_document=` on the device) and delete / live_count / compact (`Collection.delete`).
+        match_documents / match_documents_dfa / search_masked_dev (`where_document=` on the device) and delete / live_count / compact (`Collection.delete`).
     The ivf_search_*masked* methods are the same masks under an installed IVF layout (ivf.py), slice_mask cuts a shard's words
     out of a mask over global rows (sharded.py).
     """
@@ -314,6 +314,24 @@ class DeviceKnnIndex:
         native.check(
             self._lib.codd_knn_match_documents(self._h, needle, len(needle), bits.data_ptr() if nwords else None, nwords, self._stream()),
             "codd_knn_match_documents",
+        )
+        return bits
+
+    def match_documents_dfa(self, dfa):
+        """The row slots whose document a byte DFA accepts (regex_dfa.ByteDfa, or anything with its class_of / next / nstates /
+        nclasses / start / accept): the walk over the document's bytes and one 0x00 ends in `accept`.  The words match_documents
+        returns.  The engine checks the table before it uploads it; a malformed one is EINVAL."""
+        torch = _torch()
+        class_of, table, nstates, nclasses = bytes(dfa.class_of), bytes(dfa.next), int(dfa.nstates), int(dfa.nclasses)
+        # (the library reads 256 and nstates * nclasses host bytes before it can check anything else)
+        if len(class_of) != 256 or nstates < 1 or nclasses < 1 or len(table) != nstates * nclasses:
+            raise ValueError(f"malformed DFA: class_of holds {len(class_of)} bytes (256 wanted), next {len(table)} for {nstates} x {nclasses} states x classes")
+        nwords = (self.count() + 31) // 32
+        bits = torch.empty((nwords,), dtype=torch.int32, device=self.device)
+        native.check(
+            self._lib.codd_knn_match_documents_dfa(self._h, class_of, table, nstates, nclasses, int(dfa.start),
+                                                   int(dfa.accept), bits.data_ptr() if nwords else None, nwords, self._stream()),
+            "codd_knn_match_documents_dfa",
         )
         return bits
 

@@ -26,6 +26,8 @@ MAX_K = 128
 MAX_BATCH = 1024
 MAX_SCOPE = 1048575
 MAX_NEEDLE = 256
+MAX_DFA_STATES = 255  # CODD_KNN_MAX_DFA_STATES
+MAX_DFA_TABLE = 8192  # CODD_KNN_MAX_DFA_TABLE: bytes of a DFA's next[nstates][nclasses]
 MAX_EMBED_DIM = 4096       # codd_knn_embedder_create: dim in [8, 4096]
 MAX_EMBED_BYTES = 1 << 28  # CODD_KNN_MAX_EMBED_BYTES: text bytes per codd_knn_embed_texts_host call
 MAX_EMBED_TEXTS = 1 << 24  # CODD_KNN_MAX_EMBED_TEXTS
@@ -64,6 +66,8 @@ ABI = [
     ("codd_knn_search_masked_dev", ctypes.c_int, [_c_idx, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     ("codd_knn_set_documents_host", ctypes.c_int, [_c_idx, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]),
     ("codd_knn_match_documents", ctypes.c_int, [_c_idx, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
+    ("codd_knn_match_documents_dfa", ctypes.c_int, [_c_idx, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                    ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
     ("codd_knn_ivf_search_masked", ctypes.c_int, [_c_idx, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     ("codd_knn_ivf_search_masked_dev", ctypes.c_int, [_c_idx, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     ("codd_knn_slice_mask", ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),

@@ -21,7 +21,7 @@
  *   - `stream` is a hipStream_t passed as void* (NULL = the null stream).  Calls
  *     are asynchronous with respect to the host unless stated otherwise.
  *   - thread-safety: the search entry points (codd_knn_search, _search_keys, _search_scoped,
- *     _search_masked, _search_masked_dev, _match_documents, _ivf_search, _ivf_search_masked, _ivf_search_masked_dev, _approx_scores) may be called from several host threads and on
+ *     _search_masked, _search_masked_dev, _match_documents, _match_documents_dfa, _ivf_search, _ivf_search_masked, _ivf_search_masked_dev, _approx_scores) may be called from several host threads and on
  *     several streams of one index: the index keeps one workspace per stream (up to
  *     4; a fifth stream takes over the least recently used one, ordered behind its
  *     previous owner on the device) and serialises only the enqueueing.  Searches on
@@ -344,6 +344,20 @@ int codd_knn_compact(codd_knn_index* index, int64_t* new_count);
  *           returns.  Asynchronous on `stream`: one hipMemsetAsync of dev_bits and one launch of doc_match_kernel (csrc/doc_match.h),
  *           which streams the arena once, "doc_tile_bytes" start positions per workgroup step — its cost is the arena's bytes whatever
  *           the documents' lengths are.  May be called from several host threads and streams, like a search.
+ * match_documents_dfa: the `$regex` of the same filter grammar.  What crosses this boundary is a byte DFA, compiled from
+ *           the pattern by the façade (codd_query_engine_amd/regex_dfa.py): host_class_of[256] maps a byte to its class, host_next is
+ *           next[nstates][nclasses], one uint8 per entry.  Sets bit (r & 31) of dev_bits[r >> 5] iff the walk
+ *           state = next[state][class_of[byte]] over document r's bytes and then one 0x00 (the arena's separator), from `start`, ends in
+ *           `accept`; every other bit of the nwords words is zero.  The contract of match_documents otherwise: a current snapshot and
+ *           nwords == ceil(count / 32), else EINVAL; a dead slot's document is matched as it stands; the host pointers are consumed
+ *           before the call returns; callable from several host threads and streams.  THE TABLE IS VALIDATED ON THE HOST before anything
+ *           is enqueued, so that no entry leads outside it on the device: nstates in [1, CODD_KNN_MAX_DFA_STATES], nclasses in [1, 256],
+ *           nstates * nclasses <= CODD_KNN_MAX_DFA_TABLE, every class < nclasses, every entry < nstates, start and accept states,
+ *           accept absorbing (next[accept][c] == accept for every c); a violation is EINVAL and changes nothing.  The table does not
+ *           fit a kernel's argument segment: it is staged in pinned memory of the calling stream's workspace and copied on `stream`.
+ *           Asynchronous on `stream`: that copy and one launch of doc_regex_kernel (csrc/doc_regex.h) — document-parallel, one lane per
+ *           document, "doc_regex_run_docs" consecutive documents per workgroup, their arena range staged "doc_regex_tile_bytes" at a
+ *           time; the bitmap is written by wave ballots, every word once: no memset, no atomics.
  * search_masked_dev: codd_knn_search_masked under a mask that is already on the device — the same answer contract, word for word: the
  *           exact canonical top-k among the rows that are allowed AND live, min(k, m) hits, m == 0 an all-empty result with no scan, the
  *           same two routes chosen by the same rule from m, B and the index size, the same "mask_route" / "mask_list_pct" options and
@@ -358,6 +372,10 @@ int codd_knn_compact(codd_knn_index* index, int64_t* new_count);
 int codd_knn_set_documents_host(codd_knn_index* index, const uint8_t* host_bytes, const int64_t* host_offsets, int64_t n);
 int codd_knn_match_documents(codd_knn_index* index, const uint8_t* host_needle, int needle_len,
                              uint32_t* dev_bits, int64_t nwords, void* stream);
+#define CODD_KNN_MAX_DFA_STATES 255
+#define CODD_KNN_MAX_DFA_TABLE 8192   /* bytes of next[nstates][nclasses] */
+int codd_knn_match_documents_dfa(codd_knn_index* index, const uint8_t* host_class_of, const uint8_t* host_next, int nstates, int nclasses,
+                                 int start, int accept, uint32_t* dev_bits, int64_t nwords, void* stream);
 int codd_knn_search_masked_dev(codd_knn_index* index, const float* dev_queries, int B, int k, const uint32_t* dev_allow_bits,
                                int64_t nwords, uint32_t row_base, uint64_t* dev_keys, float* dev_dist, int64_t* dev_rows, void* stream);
 
@@ -499,7 +517,9 @@ int codd_knn_embed_texts_host(codd_knn_embedder* e, const uint8_t* host_bytes, c
  *            apart from the three below), "masked_dev_searches" (the masked searches among them that came through
  *            codd_knn_search_masked_dev), "docs_valid" (1: a document snapshot exists and is not stale), "doc_bytes" (its arena: the
  *            documents' bytes plus one separator each), "doc_tile_bytes" (arena bytes per workgroup step of doc_match_kernel),
- *            "doc_matches" (codd_knn_match_documents calls that launched), "filter_passes",
+ *            "doc_matches" (codd_knn_match_documents calls that launched), "doc_regex_matches" (codd_knn_match_documents_dfa calls that
+ *            launched), "doc_regex_tile_bytes" (arena bytes per segment of doc_regex_kernel), "doc_regex_run_docs" (documents per
+ *            workgroup of it), "filter_passes",
  *            "fallback_queries", "filter_hits", "filter_survivors", "capacity_rows",
  *            "device_bytes", "num_cus", "workspaces" (stream workspaces in use), "shadow8_builds", "shadow8_passes", "i8v2_passes",
  *            "shadow16_builds" (the bf16 shadow is built lazily, by the first search that needs it), "all_normalized",
