@@ -9,13 +9,15 @@
 //   scan_kernels.h       the exact scan of the whole row store (dot product and squared L2), finalize + fallback, the key merges
 //   shadow8_kernels.h    the int8 shadow, the int8 filter leg's query preparation and bounds, small_batch_kernel
 //   list_scan_kernels.h  scans of row lists and what builds the lists: IVF, scopes, tombstones and compaction, masks
-//   (here)               host side: the index object, its workspaces and guards
+//   (here)               host side: the index object (its option knobs and filter watch are search_plan.h's), its workspaces and guards
 //   dispatch.h           with_* (run-time value -> template argument), Lds, launch_kernel, launch_by_metric
-//   (here)               the exact pass, the filter pass, scopes, then the extern "C" entry points with the bodies of the IVF and
-//                        masked searches between them
+//   (here)               the exact pass, the filter pass, search_impl, scopes, then the extern "C" entry points with the bodies of the
+//                        IVF and masked searches between them
 //
 // The other headers (exact_score.h, wave_topk.h, row_traits.h, filter_gemm.h, filter_i8.h, doc_match.h, doc_regex.h, text_embed.h,
-// device_mem.h) are interfaces in namespace codd and come first.
+// device_mem.h) are interfaces in namespace codd and come first.  Two of them take no HIP: geometry.h (the sizes kernels and host
+// share) and search_plan.h, where the ROUTE of a search is decided — plan_search, filter_program, mask_takes_dense and their helpers,
+// pure functions of (FilterKnobs, IndexShape, batch).  search_impl and filter_pass launch what those name and decide nothing.
 //
 // HBM-bound byte streaming throughout: the corpus is read once per pass, each row by exactly one
 // wave, straight into registers; results leave as 8-byte keys.
@@ -42,6 +44,7 @@
 #include "filter_gemm.h"
 #include "filter_i8.h"
 #include "row_traits.h"
+#include "search_plan.h"
 #include "text_embed.h"
 #include "wave_topk.h"
 
@@ -137,7 +140,6 @@ struct codd_knn_index : WorkBufs {
     int dtype = 0;
     int metric = 0;
     int num_cus = 256;
-    int scan_blocks_per_cu = 4;
     int64_t capacity = 0;  // row slots allocated
     int64_t count = 0;     // highest written slot + 1
     DevBuf<unsigned char> rows;  // [capacity][dpad] storage dtype, as bytes; zero at and past `count` (a never-written slot below the count is a zero row)
@@ -167,37 +169,12 @@ struct codd_knn_index : WorkBufs {
     DevBuf<int64_t> stage_slot;
     bool all_normalized = true;    // false once a caller stored rows with normalize = 0
 
-    // filter path knobs
-    int filter_enabled = 1;
-    int64_t filter_min_rows = 1;             // batches >= filter_min_batch: only the tile-count condition applies
-    int64_t filter_min_rows_small = 100000;  // batches below filter_min_batch: filter when rows * B reaches this
-    int filter_min_batch = 9;
-    int sample_tiles = 4096;  // upper bound on sampled tiles (reached from 42M rows on)
-    int sample_div = 40;      // sample about 1/40 of the tiles (2.5 % extra GEMM work), see sample_tile_count()
-    int hit_cap_q = 131072;  // candidates kept per query before it falls back to the exact scan (256 MiB per searching stream at 256 queries:
-                             // a cluster of 60,000 near-identical rows — closer to each other than either filter's slack — stays on the filter path)
+    FilterKnobs knobs;   // the option-settable integers of the filter path (search_plan.h: plan_search reads them, never the index)
 
     DevBuf<unsigned long long> dstats;                     // device counters: hits, survivors, fallback queries
 
     // int8 shadow for small batches (optional; rebuilt lazily from the stored rows when they have changed)
-    int shadow8_enabled = 1;
-    int shadow8_max_batch = 256;  // batches up to this size (one query pass) take the int8 filter
-    int resident_q = 1;           // rows of <= 512 int8 elements: the query block stays in LDS ("resident_q" option)
-    int i8v2 = 2;                 // batches of 65..256 queries on rows of >= 384 elements (3 K-steps) take i8_tile_kernel (filter_i8.h); 1: only rows of
-                                  // more than 512 elements (below, the first-generation kernel keeps the query block resident in LDS: 6-12 % slower); 0: never
-    int i8v2_half = 1;            // ... and so do batches of 65..128 queries (its 8-query-block instantiation)
-    int ivf_share = 1;            // IVF search: from 1,024 (query, list) pairs on, a probed list is scanned once for all its queries ("ivf_share": 0 = per pair)
-    int fuse_fallback = 1;        // batches above 64 queries, k <= 64: finalize and the exact-scan fallback in one launch ("fuse_fallback": 0 = two launches)
-    int small_batch_max = 0;      // 1: a single query is answered in one launch by small_batch_kernel where it applies.  OFF by default: measured SLOWER than the
-                                  // six-launch chain (1M x 768, B = 1: kernel 0.27 ms, p50 0.33 ms against 0.25 ms; profiles/r3/small_batch_latency.txt)
     int64_t stat_small_batch = 0;
-    int per_block = 7;            // the int8 bound per 32-row block: bit 0 in i8_tile_kernel, bit 1 in finalize ("per_block" option; 0 = the device-wide bound everywhere;
-                                  // bit 2 chose between block metadata and per-row scales in the tile kernel's filter pass until the per-row path was removed: ignored)
-    int i8_pair = 2;              // rows of 6, 12, ... K-steps: the staged tile program with one workgroup barrier per two K-steps ("i8_pair" option: 0 = one per K-step;
-                                  // 2 = ... and rows of exactly 6 K-steps its static form, i8_tile_kernel<., 3, ., false>)
-    int sample_div8 = 28;         // its thresholds come from a larger sample (the int8 slack is ~5x the bf16 one)
-    int sample_rounds8 = 2;       // ... of at least this many rounds of workgroups (one tile each) when the batch has more than 32 queries (3 until the round-3 epilogue:
-                                  // at 1.25M rows two rounds trade 13 us of sample for 7 us of filter, gpurun_out/r3n/ab_sample_1p25m.txt)
     DevBuf<uint4> shadow8;
     int64_t shadow8_rows = 0;     // rows the allocation covers (multiple of 256)
     DevBuf<float> rscale;         // [shadow8_rows]
@@ -206,10 +183,6 @@ struct codd_knn_index : WorkBufs {
     // the int8 filter leg of an ip or l2 index ("space_filter" option, off by default).  Derived with the int8 shadow,
     // over the same dirty rows, and only for such an index: rnorm2[row] = the row's canonical sum of squares; *rmax_bits = the float
     // bits of R >= |c| for every row ever stored (it only grows: delete and compact never lower it)
-    int space_filter = 0;
-    // IVF on an ip or l2 index ("space_ivf" option, off by default): the coarse index in the index's own space, raw
-    // centroids, the list scans by the index's metric.  No effect on a cosine index.
-    int space_ivf = 0;
     DevBuf<float> rnorm2;            // [shadow8_rows]
     DevBuf<unsigned> rmax_bits;
     int64_t shadow8_epoch = -1;
@@ -217,8 +190,6 @@ struct codd_knn_index : WorkBufs {
     hipStream_t shadow8_stream = nullptr;  // the stream the last rebuild ran on, and its completion
     Event shadow8_ready;
     int64_t stat_shadow8_builds = 0, stat_shadow8_passes = 0, stat_i8v2_passes = 0, stat_f16_tile_passes = 0;
-    int f16_tile = 1;             // the 2-byte filter of 129..256 queries over rows of 6, 12, ... 64-element K-steps (768 elements: 12) runs the tile program of
-                                  // filter_i8.h on fp16 operands ("f16_tile" option; 0 = gemm_filter_kernel)
     // the worst row's quantisation error, copied back asynchronously after every build: a corpus with badly
     // quantisable rows (one large element, many small ones) would make the int8 bound useless and send every small batch
     // to the exact-scan fallback, so such an index keeps the bf16 filter.  Performance only: never needed for exactness.
@@ -226,25 +197,10 @@ struct codd_knn_index : WorkBufs {
     Event eps_r_copied;
     float eps_r_known = 0.0f;
     int64_t wide_blocks_known = 0;      // blocks whose error norm exceeds shadow8_max_eps, as last read back
-    float shadow8_max_eps = 0.04f;
-    // Which filter suits the DATA is watched too: on corpora with dense clusters the wider int8 slack lets thousands of
-    // rows per query through to the exact re-scoring, where the bf16 filter (a fifth of the slack) is the faster one
-    // (profiles/r1/clustered_data_check.txt).  The device counters of the filter passes are copied back
-    // asynchronously; when the int8 passes since the last look left more than shadow8_max_surv survivors per query, or
-    // sent queries to the fallback, the next shadow8_cooldown searches take the bf16 filter, then the int8 one is
-    // tried again.  Performance only: either filter returns the same bits.
-    PinnedBuf<unsigned long long> watch_host;  // copy of dstats[0..3]
+    // the filter watch (search_plan.h): its state, and the asynchronous copy of dstats[0..3] that feeds it
+    FilterWatch watch;
+    PinnedBuf<unsigned long long> watch_host;
     Event watch_copied;
-    bool watch_pending = false;
-    unsigned long long watch_surv = 0, watch_fb = 0;  // counter values at the last look
-    int64_t watch_q8 = 0, watch_q16 = 0;              // queries filtered since then, by path
-    int64_t watch_q8_sent = 0, watch_q16_sent = 0;    // ... as of the copy in flight
-    int shadow8_max_surv = 4000;
-    int shadow8_cooldown = 256;
-    int cooldown_left = 0;
-    int64_t stat_cooldowns = 0;
-    double cooldown_surv8 = 0.0;          // survivors per query of the int8 passes that started the current cooldown
-    int64_t cooldown_useless_epoch = -1;  // row epoch at which the bf16 filter was seen to leave as many survivors as the int8 one: no more cooldowns until rows change
     float exp_slack_scale = 1.0f;  // always 1 in the shipped library; "exp_slack_pct" exists only in -DCODD_EXPERIMENTS=1 builds
 
     // IVF (optional): rows regrouped by coarse list, original slots, list offsets, the coarse index
@@ -268,8 +224,6 @@ struct codd_knn_index : WorkBufs {
     int64_t stat_scoped_searches = 0, stat_scope_builds = 0;
 
     // masked search
-    int mask_route = 0;        // "mask_route": 0 = by the routing rule, 1 = always the list route, 2 = always the dense route
-    int mask_list_pct = 100;   // "mask_list_pct": the list route's side of the cost comparison, in percent (100 = the derived rule)
     DevBuf<unsigned long long> mask_dstats;     // the device counters of the dense masked passes: kept apart from dstats, which the filter watch reads
     int64_t stat_masked_searches = 0, stat_mask_list = 0, stat_mask_dense = 0, stat_last_mask_rows = 0;
     int64_t stat_masked_dev = 0;   // ... those of them whose mask was on the device already (codd_knn_search_masked_dev)
@@ -316,6 +270,14 @@ struct codd_knn_index : WorkBufs {
     ~codd_knn_index() { (void)codd_knn_destroy(coarse); }
 };
 static_assert(!std::is_copy_constructible<codd_knn_index>::value, "an index owns its device memory");
+
+// what the route rules of search_plan.h see of an index
+inline IndexShape shape_of(const codd_knn_index* ix) {
+    IndexShape s;
+    s.count = ix->count; s.dim = ix->dim; s.dpad = ix->dpad; s.dtype = ix->dtype; s.metric = ix->metric; s.num_cus = ix->num_cus;
+    s.all_normalized = ix->all_normalized;
+    return s;
+}
 
 // The device embedder: no index behind it — an index does not exist before the first upsert fixes the width.
 // One pinned staging buffer and its device copy, both laid out [n + 1 offsets][bytes]; `uploaded` frees the staging buffer for
@@ -447,9 +409,6 @@ struct WorkScope {
     WorkScope& operator=(const WorkScope&) = delete;
 };
 
-size_t elem_size(int dtype) { return dtype == DT_F32 ? 4 : 2; }
-int elems_per_chunk(int dtype) { return dtype == DT_F32 ? 4 : 8; }
-
 int grow_dead_bits(codd_knn_index* ix, int64_t slots);
 
 // (re)allocate row storage for at least `need` slots, preserving contents (the shadows are derived data with their own
@@ -554,7 +513,7 @@ int launch_raw_rows(int dtype, const float* in, int64_t n, int d, int dpad, cons
 static_assert(kMetricDot == CODD_KNN_METRIC_COSINE && kMetricL2 == CODD_KNN_METRIC_L2, "exact_score.h and codd_knn.h disagree");
 bool metric_is_cosine(const codd_knn_index* ix) { return ix->metric == CODD_KNN_METRIC_COSINE; }
 // IVF: cosine always; ip and l2 with "space_ivf" on
-bool ivf_allowed(const codd_knn_index* ix) { return metric_is_cosine(ix) || ix->space_ivf; }
+bool ivf_allowed(const codd_knn_index* ix) { return metric_is_cosine(ix) || ix->knobs.space_ivf; }
 int kernel_metric(int metric) { return metric == CODD_KNN_METRIC_L2 ? kMetricL2 : kMetricDot; }
 
 // the ingest launch of every upsert.  normalize = 0 on an ip or l2 index still zeroes non-finite rows (the contract of those
@@ -664,7 +623,7 @@ int launch_merge_of(const codd_knn_index* ix, const u64* in, int B, int64_t m, i
 }
 
 int scan_geometry(const codd_knn_index* ix, int64_t n, int* niter, int64_t* blocks) {
-    *niter = niter_of(ix);
+    *niter = niter_of(shape_of(ix));
     if (*niter > kMaxNiter) return fail(CODD_KNN_ENOTSUP, "dim too large (<= 4096 elements)%s");
     const int64_t ngroups = (n + 3) / 4;
     if (*niter > 4) {  // scan_topk_wide_kernel: workgroups of 8 waves, one per compute unit (its query block fills the LDS)
@@ -674,7 +633,7 @@ int scan_geometry(const codd_knn_index* ix, int64_t n, int* niter, int64_t* bloc
         return CODD_KNN_OK;
     }
     int64_t b = (ngroups + 3) / 4;
-    const int64_t cap_blocks = (int64_t)ix->num_cus * ix->scan_blocks_per_cu;
+    const int64_t cap_blocks = (int64_t)ix->num_cus * ix->knobs.scan_blocks_per_cu;
     if (b > cap_blocks) b = cap_blocks;
     if (b < 1) b = 1;
     *blocks = b;
@@ -745,8 +704,8 @@ size_t filter_lds_bytes(int mode) {
 
 int ensure_filter_workspace(codd_knn_index* ix) {
     HIP_TRY(ix->qfrag.ensure((int64_t)kTileQ * (ix->dpad / 8)));
-    HIP_TRY(ix->bucket_max.ensure((int64_t)ix->sample_tiles * kTileQ));
-    HIP_TRY(ix->hits.ensure((int64_t)kTileQ * ix->hit_cap_q));
+    HIP_TRY(ix->bucket_max.ensure((int64_t)ix->knobs.sample_tiles * kTileQ));
+    HIP_TRY(ix->hits.ensure((int64_t)kTileQ * ix->knobs.hit_cap_q));
     if (!ix->thr) HIP_TRY(ix->thr.reset(2 * kTileQ));  // thr[q], then thr0[q] (per-block form, int8 tile kernel)
     if (!ix->ctl) {
         HIP_TRY(ix->ctl.reset(1));
@@ -758,33 +717,6 @@ int ensure_filter_workspace(codd_knn_index* ix) {
     }
     return CODD_KNN_OK;
 }
-
-// how many evenly spaced tiles set the thresholds: ~ntiles/sample_div (so the sample costs a fixed
-// fraction of the main pass at every shard size and the hit volume per query stays ~k*sample_div),
-// at least max(64, 4k) where the corpus has that many tiles, at most sample_tiles
-int64_t sample_tile_count(const codd_knn_index* ix, int64_t ntiles, int k, bool use8 = false, int nbq = 8) {
-    int64_t ts = ntiles / (use8 ? (nbq == 1 ? 2 * ix->sample_div8 : ix->sample_div8) : ix->sample_div);
-    if (use8) {
-        // the int8 filter pays more per hit (wider slack, more of them) and less per sampled tile: "sample_rounds8" rounds of
-        // workgroups (2 since round 3's cheaper epilogue; 3 before) where that is still under a quarter of the corpus
-        // (1/10 of a 1.25M-row shard, 1/28 of 10M rows; twice as sparse for <= 32 queries, whose sample is a pure byte stream)
-        const int64_t rounds = (nbq == 1 ? 1 : ix->sample_rounds8) * (int64_t)ix->num_cus;
-        const int64_t floor8 = rounds < ntiles / 4 ? rounds : ntiles / 4;
-        if (ts < floor8) ts = floor8;
-    }
-    const int64_t lo = 4 * (int64_t)k > 64 ? 4 * (int64_t)k : 64;
-    if (ts < lo) ts = lo;
-    // a sample of fewer tiles than there are CUs takes as long as one full round of workgroups (one tile each), and a
-    // bigger sample means a tighter threshold: fewer hits for the filter's epilogue (scripts/rows_sweep.py)
-    if (ts < ix->num_cus && ntiles >= 2 * (int64_t)ix->num_cus) ts = ix->num_cus;
-    // whole rounds of workgroups: the last round costs a round whether it is full or not
-    if (ts > ix->num_cus) ts = (ts + ix->num_cus - 1) / ix->num_cus * ix->num_cus;
-    if (ts > ix->sample_tiles) ts = ix->sample_tiles;
-    if (ts > ntiles) ts = ntiles;
-    return ts < 1 ? 1 : ts;
-}
-
-int dpad8_of(const codd_knn_index* ix) { return (ix->dpad + 127) / 128 * 128; }
 
 // Searches on a stream other than the one rows were last written on (codd_knn_upsert_device is asynchronous on the caller's
 // stream) wait for that write on the device before they read rows or rebuild a shadow from them.
@@ -815,7 +747,7 @@ int ensure_shadow(codd_knn_index* ix, hipStream_t st) {
         if (st != ix->shadow_stream && ix->shadow_ready) HIP_TRY(hipStreamWaitEvent(st, ix->shadow_ready, 0));
         return CODD_KNN_OK;
     }
-    const int64_t need = (n + kTileRows - 1) / kTileRows * kTileRows;
+    const int64_t need = tiles_of(n) * kTileRows;
     int64_t first = ix->dirty16_lo, m = ix->dirty16_hi - ix->dirty16_lo;
     if (first + m > n) m = n > first ? n - first : 0;  // (never past the count: the allocation below is only checked against it)
     if (need > ix->shadow_rows) {
@@ -827,7 +759,7 @@ int ensure_shadow(codd_knn_index* ix, hipStream_t st) {
         (void)ix->shadow.reset();
         ix->shadow_rows = 0;
         const int64_t rows = need + need / 8;
-        const int64_t rows_al = (rows + kTileRows - 1) / kTileRows * kTileRows;
+        const int64_t rows_al = tiles_of(rows) * kTileRows;
         hipError_t me = ix->debug_fail_shadow_alloc ? hipErrorOutOfMemory : ix->shadow.reset(rows_al * ix->dpad * 2 / (int64_t)sizeof(uint4));
         if (me != hipSuccess) {
             (void)hipGetLastError();
@@ -861,12 +793,12 @@ int ensure_shadow(codd_knn_index* ix, hipStream_t st) {
 // written since the last build.  Other streams that search before the build has finished wait for it on the device.
 int ensure_shadow8(codd_knn_index* ix, hipStream_t st) {
     const int64_t n = ix->count;
-    const int dpad8 = dpad8_of(ix);
+    const int dpad8 = dpad8_of(shape_of(ix));
     if (ix->shadow8_epoch == ix->epoch && ix->shadow8) {
         if (st != ix->shadow8_stream && ix->shadow8_ready) HIP_TRY(hipStreamWaitEvent(st, ix->shadow8_ready, 0));
         return CODD_KNN_OK;
     }
-    const int64_t need = (n + kTileRows - 1) / kTileRows * kTileRows;
+    const int64_t need = tiles_of(n) * kTileRows;
     int64_t first = ix->dirty_lo, m = ix->dirty_hi - ix->dirty_lo;  // rows to (re)quantise
     if (first + m > n) m = n > first ? n - first : 0;  // (never past the count: the allocation below is only checked against it)
     if (!ix->eps_r_bits) {
@@ -887,7 +819,7 @@ int ensure_shadow8(codd_knn_index* ix, hipStream_t st) {
         (void)ix->bmeta.reset();
         ix->shadow8_rows = 0;
         const int64_t rows = need + need / 8;  // head room: appends do not reallocate every time
-        const int64_t rows_al = (rows + kTileRows - 1) / kTileRows * kTileRows;
+        const int64_t rows_al = tiles_of(rows) * kTileRows;
         // the three belong together: built in locals, handed over together (a failure leaves the index without an int8 shadow, not with a third of one)
         DevBuf<uint4> s8;
         DevBuf<float> rs;
@@ -924,7 +856,7 @@ int ensure_shadow8(codd_knn_index* ix, hipStream_t st) {
         if (rc != 0) return rc;
         HIP_TRY(hipGetLastError());
         // the device-wide maximum of the block error norms, over the rows stored now (not a running maximum)
-        hipLaunchKernelGGL(eps_max_kernel, dim3(1), dim3(1024), 0, st, ix->bmeta, (n + 31) / 32, ix->eps_r_bits, ix->shadow8_max_eps);
+        hipLaunchKernelGGL(eps_max_kernel, dim3(1), dim3(1024), 0, st, ix->bmeta, (n + 31) / 32, ix->eps_r_bits, ix->knobs.shadow8_max_eps);
         HIP_TRY(hipGetLastError());
         if (norms) {  // the same rows' sums of squares, and the bound on every row's norm
             const int64_t mn = first + m > n ? n - first : m;
@@ -955,63 +887,6 @@ int ensure_shadow8(codd_knn_index* ix, hipStream_t st) {
     ix->dirty_lo = ix->dirty_hi = 0;
     ix->stat_shadow8_builds++;
     return CODD_KNN_OK;
-}
-
-// The program a filter pass runs, chosen once per pass (filter_program); its sample launch and its filter launch both read it.
-//   GEMM      gemm_filter_kernel<MODE, nbq, el, res>: el = 1 int8 operands; res = 1 the whole int8 query block resident in LDS,
-//             res = 2 two of its six slices (768 elements, 4 query blocks)
-//   TILE      i8_tile_kernel<MODE, ts, 2 * nbq, res> (filter_i8.h: the int8 tile program, 16-query blocks; res: the query block
-//             resident in LDS); the sample pass runs ts = 0
-//   TILE_F16  i8_tile_kernel<MODE_FILTER, ts, 16, false, true>: the same program on fp16 operands; the sample pass is GEMM's
-//             gemm_filter_kernel<MODE_SAMPLE, 8>
-struct FilterProgram {
-    enum Family { GEMM, TILE, TILE_F16 };
-    Family family = GEMM;
-    int nbq = 8;  // 32-query blocks the GEMM multiplies
-    int ts = 0, res = 0, el = 0;
-    bool sqd = false;  // sqd_filter_kernel<MODE, nbq>: the squared-distance epilogue of an l2 index
-};
-
-FilterProgram filter_program(const codd_knn_index* ix, int nq, int nsteps, bool use8) {
-    FilterProgram p;
-    p.nbq = nq <= 32 ? 1 : (nq <= 64 ? 2 : (nq <= 128 ? 4 : 8));
-    p.el = use8 ? 1 : 0;
-    // an ip or l2 index: the GEMM family on int8 operands whatever "i8v2" / "f16_tile" say — the tile programs evaluate
-    // the per-block, unit-norm form of the bound — and for l2 its staged form with the squared-distance epilogue
-    const bool space = !metric_is_cosine(ix);
-    p.sqd = space && ix->metric == CODD_KNN_METRIC_L2;
-    const bool resident = use8 && nsteps <= 4 && ix->resident_q && !p.sqd;
-    // 65..128 queries only: with <= 64 the kernel is a byte stream (nothing to gain); with 8 query blocks the six-step body
-    // needs more than the 256 registers of a wave (hipcc spills, no gain measured)
-    const bool partial6 = use8 && nsteps == 6 && nq > 64 && nq <= 128 && ix->resident_q && !p.sqd;
-    // full query blocks: the second-generation int8 kernel (filter_i8.h); rows whose query block fits the LDS keep the resident one
-    const bool tile_v2 = !space && use8 && (p.nbq == 8 || (p.nbq == 4 && ix->i8v2_half)) && ((ix->i8v2 == 1 && !resident && nsteps >= 3) || (ix->i8v2 == 2 && nsteps >= 3));
-    // the 2-byte filter (dense clusters the int8 slack cannot separate, the int8 filter switched off): the same tile program on fp16 operands
-    const bool tile_f16 = !space && CODD_SHADOW_F16 && CODD_MFMA16 && !use8 && p.nbq == 8 && nsteps % 6 == 0 && ix->f16_tile;
-    if (tile_f16) {
-        p.family = FilterProgram::TILE_F16;
-        // rows of 768 elements are 12 K-steps of 64, rows of 384 are 6: the static forms of the tile program ("i8_pair" = 2); 18, 24, ...: run-time cursors
-        if (nsteps == 12 && ix->i8_pair == 2) p.ts = 4;
-        else if (nsteps == 6 && ix->i8_pair == 2) p.ts = 3;
-        else p.ts = 2;
-    } else if (tile_v2) {
-        p.family = FilterProgram::TILE;
-        p.res = i8_tile_resident(nsteps, p.nbq) && ix->resident_q;  // the query block fits the four LDS slices: loaded once per workgroup
-        // tile structure: rows of 6, 12, ... K-steps (768 elements: the headline shape) run the staged program with one barrier
-        // per TWO K-steps; other multiples of 3 one per K-step; the rest the generic interval loop
-        // ("i8_pair" = 2, the default: rows of exactly 6 K-steps take that program with every cursor a compile-time constant)
-        const bool pair = nsteps % 6 == 0 && ix->i8_pair;
-        const bool static6 = nsteps == 6 && ix->i8_pair == 2;
-        if (p.res) p.ts = nsteps % 3 == 0 ? 1 : 0;
-        else if (static6) p.ts = 3;
-        else if (pair) p.ts = 2;
-        else p.ts = nsteps % 3 == 0 ? 1 : 0;
-    } else if (partial6) {  // 768 int8 elements: two of the six query slices stay in LDS
-        p.res = 2;
-    } else if (resident) {  // the whole int8 query block fits the LDS slices: loaded once per workgroup
-        p.res = 1;
-    }
-    return p;
 }
 
 // the arguments gemm_filter_kernel and i8_tile_kernel share, in their order; each launch expands them into its kernel's list
@@ -1128,7 +1003,7 @@ int listed_fallback(codd_knn_index* ix, const float* qn, int k, uint32_t row_bas
     a.dead = deny;
     {
         EvScope ev(ix, EV_SCAN, st);
-        rc = launch_scan(ix->dtype, 8, niter_of(ix), dim3((unsigned)blocks), st, a);
+        rc = launch_scan(ix->dtype, 8, niter_of(shape_of(ix)), dim3((unsigned)blocks), st, a);
     }
     if (rc != 0) return rc;
     HIP_TRY(hipGetLastError());
@@ -1140,7 +1015,9 @@ int listed_fallback(codd_knn_index* ix, const float* qn, int k, uint32_t row_bas
 int filter_pass(codd_knn_index* ix, const float* qn, int nq, int k, uint32_t row_base, u64* keys_out, float* dist_out, int64_t* rows_out,
                 hipStream_t st, const uint32_t* deny, bool prepared = false, bool use8 = false) {
     const int64_t n = ix->count;
-    const int nsteps = use8 ? dpad8_of(ix) / 128 : ix->dpad / 64;
+    const IndexShape shape = shape_of(ix);
+    const FilterKnobs& knobs = ix->knobs;
+    const int nsteps = use8 ? dpad8_of(shape) / 128 : ix->dpad / 64;
     const uint4* shadow = use8 ? ix->shadow8 : ix->shadow;
     const uint4* qfrag = use8 ? ix->qfrag8 : ix->qfrag;
     const float* slack_q = use8 ? ix->qmeta + 256 : nullptr;  // int8: 2*eps per query, written by prep_queries8_kernel
@@ -1148,7 +1025,7 @@ int filter_pass(codd_knn_index* ix, const float* qn, int nq, int k, uint32_t row
     const float* qscale = use8 ? ix->qmeta : nullptr;
     const bool cosine = metric_is_cosine(ix);
     if (use8) ix->stat_shadow8_passes++;
-    const int64_t ntiles = (n + kTileRows - 1) / kTileRows;
+    const int64_t ntiles = tiles_of(n);
     const int slots = k <= 64 ? 1 : 2;
     const float eps = filter_eps(ix);
     int rc;
@@ -1160,20 +1037,20 @@ int filter_pass(codd_knn_index* ix, const float* qn, int nq, int k, uint32_t row
         HIP_TRY(hipGetLastError());
     }
 
-    const FilterProgram prog = filter_program(ix, nq, nsteps, use8);
+    const FilterProgram prog = filter_program(knobs, shape, nq, nsteps, use8);
     if (prog.family == FilterProgram::TILE) ix->stat_i8v2_passes++;
     if (prog.family == FilterProgram::TILE_F16) ix->stat_f16_tile_passes++;
     // sample: every `stride`-th tile
-    const int64_t ts = sample_tile_count(ix, ntiles, k, use8, prog.nbq);
+    const int64_t ts = sample_tile_count(knobs, shape, ntiles, k, use8, prog.nbq);
     const int64_t stride = ntiles / ts;
     {
         LastPass& lp = ix->last;
         lp.valid = true;
         lp.family = (int)prog.family; lp.nbq = prog.nbq; lp.ts = prog.ts; lp.res = prog.res; lp.el = prog.el; lp.sqd = prog.sqd ? 1 : 0;
-        lp.nq = nq; lp.k = k; lp.n = n; lp.sample_tiles = ts; lp.sample_stride = stride; lp.hit_cap = ix->hit_cap_q;
+        lp.nq = nq; lp.k = k; lp.n = n; lp.sample_tiles = ts; lp.sample_stride = stride; lp.hit_cap = ix->knobs.hit_cap_q;
         lp.eps = eps;
-        lp.per_block_filter = prog.family == FilterProgram::TILE && (ix->per_block & 1) ? 1 : 0;
-        lp.per_block_finalize = slack_q && (ix->per_block & 2) && cosine ? 1 : 0;
+        lp.per_block_filter = prog.family == FilterProgram::TILE && (ix->knobs.per_block & 1) ? 1 : 0;
+        lp.per_block_finalize = slack_q && (ix->knobs.per_block & 2) && cosine ? 1 : 0;
     }
     {
         EvScope ev(ix, EV_SAMPLE, st);
@@ -1198,13 +1075,13 @@ int filter_pass(codd_knn_index* ix, const float* qn, int nq, int k, uint32_t row
     {
         EvScope ev(ix, EV_FILTER, st);
         const dim3 g((unsigned)(ntiles < ix->num_cus ? ntiles : ix->num_cus));
-        FilterArgs fa{shadow, qfrag, n, nsteps, ntiles, 1, ix->thr, nullptr, ix->hits, ix->ctl->hit_cnt, ix->hit_cap_q, ix->ctl->flags, rscale, qscale, nullptr, 0.0f};
+        FilterArgs fa{shadow, qfrag, n, nsteps, ntiles, 1, ix->thr, nullptr, ix->hits, ix->ctl->hit_cnt, ix->knobs.hit_cap_q, ix->ctl->flags, rscale, qscale, nullptr, 0.0f};
         if (prog.sqd) { fa.rnorm2 = ix->rnorm2; fa.qn2 = ix->qmeta + 512; }
         if (prog.family == FilterProgram::TILE) {
             // the per-block bound (per_block & 1): thr0[q] and the blocks' error norms
-            fa.thr = (ix->per_block & 1) ? ix->thr + kTileQ : ix->thr;
+            fa.thr = (ix->knobs.per_block & 1) ? ix->thr + kTileQ : ix->thr;
             fa.bmeta = ix->bmeta;
-            fa.eb_scale = (ix->per_block & 1) ? 1.0f : 0.0f;
+            fa.eb_scale = (ix->knobs.per_block & 1) ? 1.0f : 0.0f;
 #ifdef CODD_I8_EXP_STAMPS  // (diagnostic build: the filter pass writes its per-wave phase stamps over the sample's bucket keys, which anchor_thr has consumed)
             fa.bucket_key = ix->bucket_max;
 #endif
@@ -1215,17 +1092,16 @@ int filter_pass(codd_knn_index* ix, const float* qn, int nq, int k, uint32_t row
         if ((rc = launch_filter_program<MODE_FILTER>(prog, g, st, fa)) != 0) return rc;
     }
     HIP_TRY(hipGetLastError());
-    const int niter = niter_of(ix);
-    // the int8 filter leaves thousands of survivors per query and is only used for a handful of queries: share each
-    // query's re-scoring out between several workgroups, then merge their lists
-    const int nparts = use8 ? (nq <= 8 ? 16 : (nq <= 32 ? 8 : (nq <= 64 ? 4 : 1))) : 1;
+    const int niter = niter_of(shape);
+    // (an int8 pass of a handful of queries: several workgroups per query, their lists merged below)
+    const int nparts = finalize_parts(use8, nq);
     ix->stat_last_finalize_parts = nparts;
     if (nparts > 1) HIP_TRY(ix->partial.ensure((int64_t)nq * nparts * k));
-    const float2* bm = slack_q && (ix->per_block & 2) && cosine ? ix->bmeta : nullptr;  // (the int8 passes: slack per 32-row block; ip, l2: the device-wide bound)
+    const float2* bm = slack_q && (ix->knobs.per_block & 2) && cosine ? ix->bmeta : nullptr;  // (the int8 passes: slack per 32-row block; ip, l2: the device-wide bound)
     FilterCtl* c = ix->ctl;
     // one list slot per lane and one workgroup per query (the large batches): finalize and the exact-scan fallback share ONE
     // launch — the scan workgroups derive the queue from the hit counters and leave at once when it is empty
-    if (slots == 1 && nparts == 1 && ix->fuse_fallback && niter <= 4 && !(ix->dtype != DT_F32 && niter == 4) && !prog.sqd) {  // (2-byte rows above 1536 elements: the fused kernel spills; wide rows take the separate fallback launch)
+    if (slots == 1 && nparts == 1 && ix->knobs.fuse_fallback && niter <= 4 && !(ix->dtype != DT_F32 && niter == 4) && !prog.sqd) {  // (2-byte rows above 1536 elements: the fused kernel spills; wide rows take the separate fallback launch)
         int64_t blocks, stride_q;
         if ((rc = fallback_geometry(ix, k, &blocks, &stride_q)) != 0) return rc;
         EvScope ev(ix, EV_FINALIZE, st);
@@ -1237,7 +1113,7 @@ int filter_pass(codd_knn_index* ix, const float* qn, int nq, int k, uint32_t row
                     return fail(CODD_KNN_ENOTSUP, "row too wide for the finalize kernel%s");
                 } else {
                     return launch_kernel<finalize_fb_kernel<decltype(dt)::value, ni>>(
-                        grid, dim3(kFinThreads), lds, st, ix->rows, ix->dpad, qn, ix->hits, c->hit_cnt, ix->hit_cap_q, c->flags, k, 2.0f * eps, row_base,
+                        grid, dim3(kFinThreads), lds, st, ix->rows, ix->dpad, qn, ix->hits, c->hit_cnt, ix->knobs.hit_cap_q, c->flags, k, 2.0f * eps, row_base,
                         keys_out, ix->dstats, slack_q, (u64*)nullptr, dist_out, rows_out, bm, nq, n, ix->fb_partial, stride_q, &c->fb_done, deny);
                 }
             });
@@ -1252,11 +1128,11 @@ int filter_pass(codd_knn_index* ix, const float* qn, int nq, int k, uint32_t row
             if constexpr (decltype(ni)::value != kWideRows) {
                 if (prog.sqd)
                     return launch_kernel<sqd_fin_kernel<dt, ni, sl>>(dim3(nq, nparts), dim3(kFinThreads), 0, st, ix->rows, ix->dpad, qn, ix->hits, c->hit_cnt,
-                                                                          ix->hit_cap_q, c->flags, k, row_base, keys_out, &c->fb_count, c->fb_list, ix->dstats, slack_q,
+                                                                          ix->knobs.hit_cap_q, c->flags, k, row_base, keys_out, &c->fb_count, c->fb_list, ix->dstats, slack_q,
                                                                           ix->partial, dist_out, rows_out, deny);
             }
             return launch_kernel<finalize_kernel<dt, ni, sl>>(dim3(nq, nparts), dim3(kFinThreads), 0, st, ix->rows, ix->dpad, qn, ix->hits, c->hit_cnt,
-                                                              ix->hit_cap_q, c->flags, k, 2.0f * eps, row_base, keys_out, &c->fb_count, c->fb_list,
+                                                              ix->knobs.hit_cap_q, c->flags, k, 2.0f * eps, row_base, keys_out, &c->fb_count, c->fb_list,
                                                               ix->dstats, slack_q, ix->partial, dist_out, rows_out, bm, deny);
         });
     }
@@ -1293,14 +1169,10 @@ int launch_small_batch(int64_t nunits, hipStream_t st, const codd_knn_index* ix,
                                                             dev_queries, k, row_base, ix->eps_r_bits, ix->qn, cand, dropmax, &c->sb_ticket, &c->fb_count,
                                                             c->fb_list, out_keys, out_dist, out_rows, ix->dstats, deny);
 }
-bool small_batch_applies(const codd_knn_index* ix, int B, int k) {
-    const int ns = dpad8_of(ix) / 128;
-    return ix->small_batch_max > 0 && B == 1 && k <= kWave && (ns == 3 || ns == 4 || ns == 6 || ns == 8) && ix->count >= 4096;
-}
 int small_batch_search(codd_knn_index* ix, const float* dev_queries, int B, int k, uint32_t row_base, u64* out_keys, float* out_dist, int64_t* out_rows,
                        hipStream_t st, const uint32_t* deny) {
     (void)B;
-    const int ns = dpad8_of(ix) / 128;
+    const int ns = dpad8_of(shape_of(ix)) / 128;
     const int64_t n = ix->count;
     constexpr int kWavesPerWg = kSbThreads / kWave;
     const int64_t nunits = (n + 15) / 16;
@@ -1322,30 +1194,8 @@ int small_batch_search(codd_knn_index* ix, const float* dev_queries, int B, int 
     return listed_fallback(ix, ix->qn, k, row_base, out_keys, out_dist, out_rows, st, deny);
 }
 
-bool filter_applies(const codd_knn_index* ix, int B, int k) {
-    // the thresholds come from the k-th largest of the sampled tile maxima: need comfortably more tiles than k
-    const int64_t ntiles = (ix->count + kTileRows - 1) / kTileRows;
-    const int64_t ts = sample_tile_count(ix, ntiles, k);
-    if (!(ix->filter_enabled && ix->all_normalized) || ts < 2 * (int64_t)k) return false;
-    // measured on MI355X (scripts/crossover.py, d = 768): with more than 8 queries the filter wins at every size
-    // it is sound for; up to 8 queries the exact scan's single launch wins until rows * B reaches ~100k
-    if (B >= ix->filter_min_batch) return ix->count >= ix->filter_min_rows;
-    return ix->count * (int64_t)B >= ix->filter_min_rows_small;
-}
-
-// The int8 filter leg of an ip or l2 index: opt-in ("space_filter"), batches of filter_min_batch queries and more
-// over filter_min_rows rows and more whose sample holds 2k tiles, both "filter" and "shadow8" on, a build with the int8 MFMA.
-// l2 rows wider than 4 chunks per lane stay on the scan.  No usefulness heuristic: a loose bound is slow, never wrong.
-bool space_filter_applies(const codd_knn_index* ix, int B, int k) {
-    if (metric_is_cosine(ix) || !ix->space_filter || !CODD_MFMA16 || !ix->filter_enabled || !ix->shadow8_enabled) return false;
-    if (ix->metric == CODD_KNN_METRIC_L2 && niter_of(ix) > 4) return false;
-    const int64_t ntiles = (ix->count + kTileRows - 1) / kTileRows;
-    if (sample_tile_count(ix, ntiles, k) < 2 * (int64_t)k) return false;
-    return B >= ix->filter_min_batch && ix->count >= ix->filter_min_rows;
-}
-
 int launch_prep_raw(codd_knn_index* ix, const float* dev_queries, int nq, float* qn, hipStream_t st) {
-    hipLaunchKernelGGL(prep_queries8_raw_kernel, dim3(kTileQ / 4), dim3(256), 0, st, dev_queries, nq, ix->dim, ix->dpad, dpad8_of(ix), qn,
+    hipLaunchKernelGGL(prep_queries8_raw_kernel, dim3(kTileQ / 4), dim3(256), 0, st, dev_queries, nq, ix->dim, ix->dpad, dpad8_of(shape_of(ix)), qn,
                        reinterpret_cast<uint32_t*>(ix->qfrag8.get()), ix->qmeta, ix->eps_r_bits, ix->rmax_bits, reinterpret_cast<unsigned*>(ix->ctl.get()),
                        (int)(sizeof(FilterCtl) / 4), ix->metric == CODD_KNN_METRIC_L2 ? 1 : 0);
     HIP_TRY(hipGetLastError());
@@ -1357,7 +1207,7 @@ int ensure_space_filter(codd_knn_index* ix, hipStream_t st) {
     int rc;
     if ((rc = ensure_filter_workspace(ix)) != 0) return rc;
     if ((rc = ensure_shadow8(ix, st)) != 0) return rc;
-    HIP_TRY(ix->qfrag8.ensure((int64_t)kTileQ * (dpad8_of(ix) / 16)));
+    HIP_TRY(ix->qfrag8.ensure((int64_t)kTileQ * (dpad8_of(shape_of(ix)) / 16)));
     if (!ix->qmeta) HIP_TRY(ix->qmeta.reset(1024));
     return CODD_KNN_OK;
 }
@@ -1379,25 +1229,41 @@ int space_filter_search(codd_knn_index* ix, const float* dev_queries, int B, int
     return CODD_KNN_OK;
 }
 
-// the index looks at its own device counters now and then (one look in flight; after its first 32 searches only every 8th:
-// the copy is a launch of its own on the searching stream)
+// the index looks at its own device counters now and then (one look in flight; FilterWatch::due says when: the copy is a launch
+// of its own on the searching stream)
 int after_filter_search(codd_knn_index* ix, int B, bool use8, hipStream_t st) {
-    (use8 ? ix->watch_q8 : ix->watch_q16) += B;
-    if (ix->shadow8_enabled && !ix->watch_pending && ix->dstats && (ix->stat_searches <= 32 || (ix->stat_searches & 7) == 0)) {
+    FilterWatch& w = ix->watch;
+    (use8 ? w.q8 : w.q16) += B;
+    if (ix->knobs.shadow8_enabled && !w.pending && ix->dstats && FilterWatch::due(ix->stat_searches)) {
         if (!ix->watch_host) {
             HIP_TRY(ix->watch_host.reset(4));
             HIP_TRY(ix->watch_copied.ensure());
         }
         HIP_TRY(hipMemcpyAsync(ix->watch_host, ix->dstats, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipEventRecord(ix->watch_copied, st));
-        ix->watch_pending = true;
-        ix->watch_q8_sent = ix->watch_q8;
-        ix->watch_q16_sent = ix->watch_q16;
+        w.sent();
     }
     return CODD_KNN_OK;
 }
 
-// the whole shard-local search: normalise queries, then filter passes or exact scans, keys out.
+// the two asynchronous read-backs a search looks at before it plans: the int8 shadow's worst quantisation error (ensure_shadow8)
+// and the filter watch's counters (after_filter_search).  Neither is waited for.
+void poll_read_backs(codd_knn_index* ix) {
+    if (ix->eps_r_copied) {
+        if (hipEventQuery(ix->eps_r_copied) == hipSuccess) {
+            ix->eps_r_known = ix->eps_r_host[0];
+            ix->wide_blocks_known = (int64_t)reinterpret_cast<const unsigned*>(ix->eps_r_host.get())[1];
+        }
+        else (void)hipGetLastError();  // "not ready" must not surface in a later error check
+    }
+    if (ix->watch.pending && ix->watch_copied) {
+        if (hipEventQuery(ix->watch_copied) == hipSuccess) ix->watch.observe(ix->watch_host[1], ix->watch_host[2], ix->epoch, ix->knobs);
+        else (void)hipGetLastError();
+    }
+}
+
+// the whole shard-local search: validate, look at the read-backs, plan (search_plan.h: plan_search decides the route, nothing below
+// does), make sure of the buffers the plan names, launch the route.
 // deny: the rows no answer may hold — ix->dead_bits, or, `masked`, the ~allow | dead of a masked search's dense route (DESIGN.md
 // §15).  A masked search says nothing about the corpus: it neither feeds the filter watch nor uses up a cooldown.
 int search_impl(codd_knn_index* ix, const float* dev_queries, int B, int k, uint32_t row_base, u64* out_keys,
@@ -1408,125 +1274,82 @@ int search_impl(codd_knn_index* ix, const float* dev_queries, int B, int k, uint
     if (k < 1 || k > CODD_KNN_MAX_K) return fail(CODD_KNN_EINVAL, "k out of range [1,128]%s");
     DeviceGuard guard(ix->device);
     ix->stat_searches++;
-    const int64_t n = ix->count;
     int rc;
     HIP_TRY(ix->qn.ensure((int64_t)B * ix->dpad));
     HIP_TRY(ix->keys_tmp.ensure((int64_t)B * k));
     if ((rc = wait_rows(ix, st)) != 0) return rc;
-    if (n > 0 && space_filter_applies(ix, B, k)) return space_filter_search(ix, dev_queries, B, k, row_base, out_keys, out_dist, out_rows, st, deny);
-    bool use_filter = n > 0 && filter_applies(ix, B, k);
-    if (ix->eps_r_copied) {
-        if (hipEventQuery(ix->eps_r_copied) == hipSuccess) {
-            ix->eps_r_known = ix->eps_r_host[0];
-            ix->wide_blocks_known = (int64_t)reinterpret_cast<const unsigned*>(ix->eps_r_host.get())[1];
-        }
-        else (void)hipGetLastError();  // "not ready" must not surface in a later error check
-    }
-    if (ix->watch_pending && ix->watch_copied) {
-        if (hipEventQuery(ix->watch_copied) == hipSuccess) {
-            ix->watch_pending = false;
-            const unsigned long long surv = ix->watch_host[1], fb = ix->watch_host[2];
-            if (ix->watch_q8_sent > 0 && ix->watch_q16_sent == 0) {  // only int8 passes in the window: the deltas are theirs
-                const double per_q = (double)(surv - ix->watch_surv) / (double)ix->watch_q8_sent;
-                if ((per_q > (double)ix->shadow8_max_surv || (fb - ix->watch_fb) * 20 > (unsigned long long)ix->watch_q8_sent) &&
-                    ix->cooldown_useless_epoch != ix->epoch) {
-                    ix->cooldown_left = ix->shadow8_cooldown;
-                    ix->cooldown_surv8 = per_q;  // what the 2-byte filter has to beat
-                    ix->stat_cooldowns++;
-                }
-            } else if (ix->watch_q16_sent > 0 && ix->watch_q8_sent == 0) {
-                // only bf16 passes (a cooldown): when those leave the re-scoring just as crowded — rows closer to each other than
-                // EITHER slack — the slower bf16 kernel buys nothing: stay on int8 until rows change
-                // (relative, not absolute: the fp16 filter's passes cost about twice an int8 pass, so they pay as soon as they
-                // leave well under half of the exact re-scoring — 7,000 survivors per query are a bargain against 62,000)
-                const double per_q = (double)(surv - ix->watch_surv) / (double)ix->watch_q16_sent;
-                if (per_q > (double)ix->shadow8_max_surv && per_q > 0.5 * ix->cooldown_surv8) {
-                    ix->cooldown_useless_epoch = ix->epoch;
-                    ix->cooldown_left = 0;
-                }
-            }
-            ix->watch_surv = surv;
-            ix->watch_fb = fb;
-            ix->watch_q8 -= ix->watch_q8_sent;
-            ix->watch_q16 -= ix->watch_q16_sent;
-        } else {
-            (void)hipGetLastError();
-        }
-    }
-    const bool cooling = ix->cooldown_left > 0;
-    if (cooling && use_filter && !masked) ix->cooldown_left--;
-    // the int8 filter: every pass of <= 256 queries prepares its own block (a batch above 256 queries is several passes)
-    const bool can8 = use_filter && ix->shadow8_enabled && (B <= ix->shadow8_max_batch || (B > kTileQ && ix->shadow8_max_batch >= kTileQ)) && CODD_MFMA16;
-    // A corpus whose WORST block quantises badly keeps the int8 filter for the batches i8_tile_kernel takes as long as such blocks are
-    // rare (under 1 %): that kernel and finalize evaluate the bound per 32-row block, so only the bad blocks' rows come through
-    // as extra candidates.  The first-generation kernels (other batch sizes, rows under 384 elements) use the device-wide bound.
-    const int nsteps8 = dpad8_of(ix) / 128;
-    const bool per_block = ix->i8v2 != 0 && nsteps8 >= 3 && B > 64 && (B <= 128 ? ix->i8v2_half != 0 : B <= kTileQ) && (ix->i8v2 == 2 || nsteps8 > 4 || !ix->resident_q);
-    const bool eps_ok = ix->eps_r_known <= ix->shadow8_max_eps || (per_block && ix->wide_blocks_known * 100 <= (ix->count + 31) / 32);
-    bool use8 = can8 && !cooling && eps_ok;
-    if (use_filter && !use8) {
-        // the bf16 filter: its shadow is allocated by the first search that needs it.  When HBM cannot hold it the search is
-        // still answered exactly — through the int8 filter where the index may use it (a cooldown or a wide eps_r only make
-        // that one slower), else by the exact scan — and the failed allocation is not retried until rows change.
+
+    poll_read_backs(ix);
+    const bool cooling = ix->watch.cooldown_left > 0;
+    const IndexShape shape = shape_of(ix);
+    SearchPlan plan = plan_search(ix->knobs, shape, B, k, cooling, ix->eps_r_known, ix->wide_blocks_known);
+    if (cooling && plan.filters() && !masked) ix->watch.cooldown_left--;
+
+    // the shadow the plan names (the space filter's route makes sure of its own)
+    if (plan.filters() && !plan.use8) {
+        // the 2-byte filter: its shadow is allocated by the first search that needs it.  When HBM cannot hold it the plan is
+        // downgraded (SearchPlan::without_shadow16) and the failed allocation is not retried until rows change.
         if ((rc = ensure_filter_workspace(ix)) != 0) return rc;
         rc = ensure_shadow(ix, st);
-        if (rc == CODD_KNN_ENOMEM) {
-            if (can8) use8 = true;
-            else use_filter = false;
-        } else if (rc != 0) {
-            return rc;
-        }
+        if (rc == CODD_KNN_ENOMEM) plan.without_shadow16();
+        else if (rc != 0) return rc;
     }
-    const bool fused_prep = use_filter && B <= kTileQ;
-    const int dpad8 = dpad8_of(ix);
-    auto prep8 = [&](int q0, int nq) -> int {
-        hipLaunchKernelGGL(prep_queries8_kernel, dim3(kTileQ / 4), dim3(256), 0, st, dev_queries + (int64_t)q0 * ix->dim, nq, ix->dim, ix->dpad, dpad8,
-                           ix->qn + (int64_t)q0 * ix->dpad, reinterpret_cast<uint32_t*>(ix->qfrag8.get()), ix->qmeta, ix->eps_r_bits,
-                           reinterpret_cast<unsigned*>(ix->ctl.get()), (int)(sizeof(FilterCtl) / 4), ix->exp_slack_scale);
-        HIP_TRY(hipGetLastError());
-        return CODD_KNN_OK;
-    };
-    if (use8) {
+    if (plan.filters() && plan.use8) {
         if ((rc = ensure_filter_workspace(ix)) != 0) return rc;
         if ((rc = ensure_shadow8(ix, st)) != 0) return rc;
-        // a handful of queries: ONE launch streams the int8 shadow, keeps the best approximate scores per wave and re-scores the
-        // survivors exactly in its last workgroup (small_batch_kernel) instead of the six-launch filter chain
-        if (small_batch_applies(ix, B, k)) {
+    }
+
+    // the filter passes write what the caller asked for — packed keys (the shard-local half of a sharded search) and / or
+    // (distance, row) — straight from finalize: no unpack launch behind them
+    const int dpad8 = dpad8_of(shape);
+    switch (plan.route) {
+        case SearchPlan::SPACE_FILTER:  // (ceil(B / 256) passes, each with its own preparation)
+            return space_filter_search(ix, dev_queries, B, k, row_base, out_keys, out_dist, out_rows, st, deny);
+        case SearchPlan::EMPTY: {
+            // nothing stored: all-empty result (chromadb returns {"ids": [[]], ...})
+            if ((rc = prep_exact_queries(ix, dev_queries, B, st)) != 0) return rc;
+            u64* keys_dst = out_keys ? out_keys : ix->keys_tmp;
+            HIP_TRY(hipMemsetAsync(keys_dst, 0, (size_t)B * k * sizeof(u64), st));
+            if (!out_dist && !out_rows) return CODD_KNN_OK;
+            return launch_merge(keys_dst, B, k, k, k, nullptr, out_dist, out_rows, st);
+        }
+        case SearchPlan::EXACT_SCAN:  // small batches: the per-block partials merge straight into the caller's buffers
+            if ((rc = prep_exact_queries(ix, dev_queries, B, st)) != 0) return rc;
+            return exact_scan(ix, ix->qn, B, k, row_base, out_keys, out_dist, out_rows, st, deny);
+        case SearchPlan::SMALL_BATCH:
+            // a handful of queries: ONE launch streams the int8 shadow, keeps the best approximate scores per wave and re-scores the
+            // survivors exactly in its last workgroup (small_batch_kernel) instead of the six-launch filter chain
             HIP_TRY(ix->qn.ensure((int64_t)B * ix->dpad));
             if ((rc = small_batch_search(ix, dev_queries, B, k, row_base, out_keys, out_dist, out_rows, st, deny)) != 0) return rc;
             return masked ? CODD_KNN_OK : after_filter_search(ix, B, true, st);
-        }
+        case SearchPlan::FILTER:
+            break;
+    }
+    if (plan.use8) {
         HIP_TRY(ix->qfrag8.ensure((int64_t)kTileQ * (dpad8 / 16)));
         if (!ix->qmeta) HIP_TRY(ix->qmeta.reset(1024));
-    } else if (fused_prep) {
+    } else if (plan.fused_prep) {
         hipLaunchKernelGGL(prep_queries_kernel, dim3(kTileQ / 4), dim3(256), 0, st, dev_queries, B, ix->dim, ix->dpad, ix->qn,
                            reinterpret_cast<uint2*>(ix->qfrag.get()), reinterpret_cast<unsigned*>(ix->ctl.get()), (int)(sizeof(FilterCtl) / 4));
         HIP_TRY(hipGetLastError());
     } else if ((rc = prep_exact_queries(ix, dev_queries, B, st)) != 0) {
         return rc;
     }
-
-    // the filter passes write what the caller asked for — packed keys (the shard-local half of a sharded search) and / or
-    // (distance, row) — straight from finalize: no unpack launch behind them
-    if (n == 0) {
-        // nothing stored: all-empty result (chromadb returns {"ids": [[]], ...})
-        u64* keys_dst = out_keys ? out_keys : ix->keys_tmp;
-        HIP_TRY(hipMemsetAsync(keys_dst, 0, (size_t)B * k * sizeof(u64), st));
-        if (!out_dist && !out_rows) return CODD_KNN_OK;
-        return launch_merge(keys_dst, B, k, k, k, nullptr, out_dist, out_rows, st);
-    }
-    if (!use_filter)  // small batches: the per-block partials merge straight into the caller's buffers
-        return exact_scan(ix, ix->qn, B, k, row_base, out_keys, out_dist, out_rows, st, deny);
     if ((rc = ensure_filter_workspace(ix)) != 0) return rc;
     for (int q0 = 0; q0 < B; q0 += kTileQ) {
         const int nq = B - q0 < kTileQ ? B - q0 : kTileQ;
-        if (use8 && (rc = prep8(q0, nq)) != 0) return rc;
+        if (plan.use8) {  // the int8 filter: every pass of <= 256 queries prepares its own block
+            hipLaunchKernelGGL(prep_queries8_kernel, dim3(kTileQ / 4), dim3(256), 0, st, dev_queries + (int64_t)q0 * ix->dim, nq, ix->dim, ix->dpad, dpad8,
+                               ix->qn + (int64_t)q0 * ix->dpad, reinterpret_cast<uint32_t*>(ix->qfrag8.get()), ix->qmeta, ix->eps_r_bits,
+                               reinterpret_cast<unsigned*>(ix->ctl.get()), (int)(sizeof(FilterCtl) / 4), ix->exp_slack_scale);
+            HIP_TRY(hipGetLastError());
+        }
         if ((rc = filter_pass(ix, ix->qn + (int64_t)q0 * ix->dpad, nq, k, row_base, out_keys ? out_keys + (int64_t)q0 * k : nullptr,
                               out_dist ? out_dist + (int64_t)q0 * k : nullptr, out_rows ? out_rows + (int64_t)q0 * k : nullptr, st, deny,
-                              fused_prep || use8, use8)) != 0)
+                              plan.fused_prep || plan.use8, plan.use8)) != 0)
             return rc;
     }
-    return masked ? CODD_KNN_OK : after_filter_search(ix, B, use8, st);
+    return masked ? CODD_KNN_OK : after_filter_search(ix, B, plan.use8, st);
 }
 
 // ---- scopes ----------------------------------------------------------------------------------
@@ -1856,7 +1679,7 @@ int codd_knn_approx_scores(codd_knn_index* ix, const float* dev_queries, int B, 
     if (!ix || !dev_queries || !dev_scores || B < 1 || B > kTileQ) return fail(CODD_KNN_EINVAL, "bad debug arguments%s");
     // an ip or l2 index: the values of its int8 filter leg, where that leg exists
     const bool space = !metric_is_cosine(ix);
-    const bool space_ok = space && ix->space_filter && ix->shadow8_enabled && CODD_MFMA16 && B <= 32 && !(ix->metric == CODD_KNN_METRIC_L2 && niter_of(ix) > 4);
+    const bool space_ok = space && ix->knobs.space_filter && ix->knobs.shadow8_enabled && CODD_MFMA16 && B <= 32 && !(ix->metric == CODD_KNN_METRIC_L2 && niter_of(shape_of(ix)) > 4);
     if (space && !space_ok)
         return fail(CODD_KNN_ENOTSUP, "approx_scores: the MFMA filters' scores exist for the cosine metric only (ip, l2: with \"space_filter\" on, B <= 32)%s");
     if (ix->count < 1) return fail(CODD_KNN_EINVAL, "empty index%s");
@@ -1869,8 +1692,8 @@ int codd_knn_approx_scores(codd_knn_index* ix, const float* dev_queries, int B, 
     if (space) {
         if ((rc = ensure_space_filter(ix, st)) != 0) return rc;
         if ((rc = launch_prep_raw(ix, dev_queries, B, ix->qn, st)) != 0) return rc;
-        const int dpad8 = dpad8_of(ix);
-        const int64_t ntiles8 = (ix->count + kTileRows - 1) / kTileRows;
+        const int dpad8 = dpad8_of(shape_of(ix));
+        const int64_t ntiles8 = tiles_of(ix->count);
         const dim3 g8((unsigned)(ntiles8 < ix->num_cus ? ntiles8 : ix->num_cus));
         if (ix->metric == CODD_KNN_METRIC_L2)
             rc = launch_kernel<sqd_filter_kernel<MODE_DUMP, 1>>(g8, dim3(kFilterThreads), filter_lds_bytes(MODE_DUMP), st, ix->shadow8, ix->qfrag8, ix->count, dpad8 / 128,
@@ -1885,16 +1708,16 @@ int codd_knn_approx_scores(codd_knn_index* ix, const float* dev_queries, int B, 
         return CODD_KNN_OK;
     }
     if ((rc = ensure_filter_workspace(ix)) != 0) return rc;
-    if (ix->shadow8_enabled && B <= 32 && CODD_MFMA16) {
+    if (ix->knobs.shadow8_enabled && B <= 32 && CODD_MFMA16) {
         // the int8 filter's scores (what a batch of <= 32 queries is filtered with when "shadow8" is on)
         if ((rc = ensure_shadow8(ix, st)) != 0) return rc;
-        const int dpad8 = dpad8_of(ix);
+        const int dpad8 = dpad8_of(shape_of(ix));
         HIP_TRY(ix->qfrag8.ensure((int64_t)kTileQ * (dpad8 / 16)));
         if (!ix->qmeta) HIP_TRY(ix->qmeta.reset(1024));
         hipLaunchKernelGGL(prep_queries8_kernel, dim3(kTileQ / 4), dim3(256), 0, st, dev_queries, B, ix->dim, ix->dpad, dpad8, ix->qn,
                            reinterpret_cast<uint32_t*>(ix->qfrag8.get()), ix->qmeta, ix->eps_r_bits, reinterpret_cast<unsigned*>(ix->ctl.get()),
                            (int)(sizeof(FilterCtl) / 4), 1.0f);
-        const int64_t ntiles8 = (ix->count + kTileRows - 1) / kTileRows;
+        const int64_t ntiles8 = tiles_of(ix->count);
         const int64_t g8 = ntiles8 < ix->num_cus ? ntiles8 : ix->num_cus;
         if ((rc = launch_kernel<gemm_filter_kernel<MODE_DUMP, 1, 1>>(dim3((unsigned)g8), dim3(kFilterThreads), filter_lds_bytes(MODE_DUMP), st,
                                                                      ix->shadow8, ix->qfrag8, ix->count, dpad8 / 128, ntiles8, (int64_t)1, nullptr, nullptr,
@@ -1907,7 +1730,7 @@ int codd_knn_approx_scores(codd_knn_index* ix, const float* dev_queries, int B, 
     if ((rc = launch_normalize(DT_F32, dev_queries, B, ix->dim, ix->dpad, 1, nullptr, 0, ix->qn, nullptr, st)) != 0) return rc;
     hipLaunchKernelGGL(qfrag_kernel, dim3((kTileQ * (ix->dpad / 8) + 255) / 256), dim3(256), 0, st, ix->qn, B, ix->dpad, ix->qfrag,
                        (unsigned*)nullptr, 0);
-    const int64_t ntiles = (ix->count + kTileRows - 1) / kTileRows;
+    const int64_t ntiles = tiles_of(ix->count);
     const int64_t g = ntiles < ix->num_cus ? ntiles : ix->num_cus;
     if ((rc = launch_kernel<gemm_filter_kernel<MODE_DUMP, 8>>(dim3((unsigned)g), dim3(kFilterThreads), filter_lds_bytes(MODE_DUMP), st, ix->shadow,
                                                               ix->qfrag, ix->count, ix->dpad / 64, ntiles, (int64_t)1, nullptr, nullptr, nullptr, nullptr, 0,
@@ -1920,7 +1743,7 @@ int codd_knn_approx_scores(codd_knn_index* ix, const float* dev_queries, int B, 
 int codd_knn_filter_slack(codd_knn_index* ix, const float* dev_queries, int B, float* dev_slack, void* stream) {
     if (!ix || !dev_queries || !dev_slack || B < 1 || B > kTileQ) return fail(CODD_KNN_EINVAL, "bad debug arguments%s");
     const bool space = !metric_is_cosine(ix);
-    if (!ix->shadow8_enabled || !CODD_MFMA16 || (space && !ix->space_filter) || (space && ix->metric == CODD_KNN_METRIC_L2 && niter_of(ix) > 4))
+    if (!ix->knobs.shadow8_enabled || !CODD_MFMA16 || (space && !ix->knobs.space_filter) || (space && ix->metric == CODD_KNN_METRIC_L2 && niter_of(shape_of(ix)) > 4))
         return fail(CODD_KNN_ENOTSUP, "filter_slack: this index has no int8 filter leg (\"shadow8\"; ip, l2: \"space_filter\")%s");
     if (ix->count < 1) return fail(CODD_KNN_EINVAL, "empty index%s");
     DeviceGuard guard(ix->device);
@@ -1933,7 +1756,7 @@ int codd_knn_filter_slack(codd_knn_index* ix, const float* dev_queries, int B, f
     if (space) {
         if ((rc = launch_prep_raw(ix, dev_queries, B, ix->qn, st)) != 0) return rc;
     } else {
-        hipLaunchKernelGGL(prep_queries8_kernel, dim3(kTileQ / 4), dim3(256), 0, st, dev_queries, B, ix->dim, ix->dpad, dpad8_of(ix), ix->qn,
+        hipLaunchKernelGGL(prep_queries8_kernel, dim3(kTileQ / 4), dim3(256), 0, st, dev_queries, B, ix->dim, ix->dpad, dpad8_of(shape_of(ix)), ix->qn,
                            reinterpret_cast<uint32_t*>(ix->qfrag8.get()), ix->qmeta, ix->eps_r_bits, reinterpret_cast<unsigned*>(ix->ctl.get()),
                            (int)(sizeof(FilterCtl) / 4), ix->exp_slack_scale);
     }
@@ -2076,13 +1899,13 @@ int ivf_search_body(codd_knn_index* ix, const float* dev_queries, int B, int k, 
     const bool sq = ix->metric == CODD_KNN_METRIC_L2;  // the squared-distance list scans (§22); ip runs the dot-product ones on the raw query
     // 1. coarse: the nprobe best lists per query (exact scan of the centroids in the index's space, tiny)
     if ((rc = exact_scan(ix->coarse, ix->qn, B, nprobe, 0u, ix->probe_keys, nullptr, nullptr, st, ix->coarse->dead_bits)) != 0) return rc;
-    const int niter = niter_of(ix);
+    const int niter = niter_of(shape_of(ix));
     // 2a. a batch with enough (query, list) pairs to fill the chip without splitting lists: group the pairs by list on the
     //     device and scan every probed list once per kIvfNB of its queries (ivf_scan_shared_kernel)
     const int64_t npairs = (int64_t)B * nprobe;
     //     (worth it once a list is probed by two queries or more on average: below that every work item holds one pair and the
     //     grouping launches are pure overhead — 12.5M x 1024 fp16, 2,048 lists, B = 256: nprobe 8 5.98 ms per pair vs 7.22 shared)
-    if (ix->ivf_share && npairs >= 1024 && npairs >= 2 * (int64_t)ix->ivf_nlist && !(ix->dtype != DT_F32 && niter == 4)) {
+    if (ix->knobs.ivf_share && npairs >= 1024 && npairs >= 2 * (int64_t)ix->ivf_nlist && !(ix->dtype != DT_F32 && niter == 4)) {
         const int nlist = ix->ivf_nlist;
         ix->stat_ivf_shared++;
         HIP_TRY(ix->ivf_group.ensure(3 * (int64_t)nlist + 2 + npairs));
@@ -2248,38 +2071,13 @@ int codd_knn_search_scoped(codd_knn_index* ix, const float* dev_queries, const u
 
 namespace {
 
-// Which way a masked search of m visible rows goes (time only, both routes give the same bits).  Dense — the
-// ordinary dispatch under ~allow | dead — when the sample's anchors can be expected to hold 4k visible rows and the pass over the
-// whole index costs less than ceil(B / NB) gathered walks of the list; "mask_list_pct" scales the dense side of that comparison.
-bool mask_takes_dense(const codd_knn_index* ix, int B, int k, int64_t m) {
-    if (ix->mask_route == 1) return false;
-    if (ix->mask_route == 2) return true;
-    const int64_t n = ix->count;
-    const int64_t row_bytes = (int64_t)ix->dpad * (int64_t)elem_size(ix->dtype);
-    const int nb = scope_nb(ix->dtype, niter_of(ix) > 4 ? kWideRows : niter_of(ix));
-    const double list_bytes = 2.0 * (double)((B + nb - 1) / nb) * (double)m * (double)row_bytes;
-    double dense_bytes;
-    if (filter_applies(ix, B, k)) {
-        const bool can8 = ix->shadow8_enabled && CODD_MFMA16 && (B <= ix->shadow8_max_batch || (B > kTileQ && ix->shadow8_max_batch >= kTileQ));
-        const int nq = B < kTileQ ? B : kTileQ;
-        const int nbq = nq <= 32 ? 1 : (nq <= 64 ? 2 : (nq <= 128 ? 4 : 8));
-        const int64_t ts = sample_tile_count(ix, (n + kTileRows - 1) / kTileRows, k, can8, nbq);
-        if ((double)m * (double)ts < 4.0 * (double)k * (double)n) return false;   // too few visible anchors: the pass would end in the fallback scan
-        dense_bytes = (double)((B + kTileQ - 1) / kTileQ) * (double)n * (double)(can8 ? dpad8_of(ix) : 2 * ix->dpad);
-    } else {
-        // the exact scan reads the rows once per group of 8 queries, streaming: twice the rate of the gathered walk, as above
-        dense_bytes = (double)((B + 7) / 8) * (double)n * (double)row_bytes;
-    }
-    return list_bytes * 100.0 > dense_bytes * (double)ix->mask_list_pct;
-}
-
 // The body both masked entry points run: the clipped allow words are in ix->mask_allow (written on `st`, or enqueued there) and m > 0,
 // the number of allowed live rows, is known on the host.  Chooses the route and enqueues it.
 int masked_search_body(codd_knn_index* ix, const float* dev_queries, int B, int k, int64_t nwords, int64_t m, uint32_t row_base,
                        uint64_t* dev_keys, float* dev_dist, int64_t* dev_rows, hipStream_t st) {
     const int64_t n = ix->count;
     int rc;
-    if (mask_takes_dense(ix, B, k, m)) {
+    if (mask_takes_dense(ix->knobs, shape_of(ix), B, k, m)) {
         ix->stat_mask_dense++;
         const int64_t total_words = (ix->capacity + 31) / 32;   // (as long as the tombstone bits: every kernel that reads those reads these)
         HIP_TRY(ix->mask_deny.ensure(total_words));
@@ -2894,46 +2692,17 @@ int codd_knn_debug_last_pass(codd_knn_index* ix, void* stream, codd_knn_last_pas
 
 int codd_knn_set_option(codd_knn_index* ix, const char* key, int64_t value) {
     if (!ix || !key) return fail(CODD_KNN_EINVAL, "bad option arguments%s");
-    if (strcmp(key, "scan_blocks_per_cu") == 0) {
-        if (value < 1 || value > 8) return fail(CODD_KNN_EINVAL, "scan_blocks_per_cu must be in [1,8]%s");
-        ix->scan_blocks_per_cu = (int)value;
+    // an integer in [lo, hi] stored into one knob: kKnobTable (search_plan.h)
+    if (const KnobRow* row = find_knob(key)) {
+        if (const char* message = set_knob(ix->knobs, *row, value)) return fail(CODD_KNN_EINVAL, message);
+        if (row->knob == &FilterKnobs::shadow8_cooldown) ix->watch.cooldown_left = 0;
         return CODD_KNN_OK;
     }
-    if (strcmp(key, "filter") == 0) { ix->filter_enabled = value != 0; return CODD_KNN_OK; }
-    if (strcmp(key, "filter_min_rows") == 0) { ix->filter_min_rows = value < 1 ? 1 : value; return CODD_KNN_OK; }
-    if (strcmp(key, "filter_min_rows_small") == 0) { ix->filter_min_rows_small = value < 1 ? 1 : value; return CODD_KNN_OK; }
-    if (strcmp(key, "filter_min_batch") == 0) { ix->filter_min_batch = value < 1 ? 1 : (int)value; return CODD_KNN_OK; }
-    if (strcmp(key, "shadow8") == 0) {
-        if (value != 0 && value != 1) return fail(CODD_KNN_EINVAL, "shadow8 must be 0 or 1%s");
-        ix->shadow8_enabled = (int)value;
-        return CODD_KNN_OK;
-    }
-    if (strcmp(key, "space_filter") == 0) {  // the int8 filter leg of an ip or l2 index; no effect on a cosine index
-        if (value != 0 && value != 1) return fail(CODD_KNN_EINVAL, "space_filter must be 0 or 1%s");
-        ix->space_filter = (int)value;
-        return CODD_KNN_OK;
-    }
-    if (strcmp(key, "space_ivf") == 0) {  // IVF on an ip or l2 index; no effect on a cosine index
-        if (value != 0 && value != 1) return fail(CODD_KNN_EINVAL, "space_ivf must be 0 or 1%s");
-        ix->space_ivf = (int)value;
-        return CODD_KNN_OK;
-    }
-    if (strcmp(key, "shadow8_max_batch") == 0) {
-        if (value < 1 || value > 256) return fail(CODD_KNN_EINVAL, "shadow8_max_batch must be in [1,256]%s");
-        ix->shadow8_max_batch = (int)value;
-        return CODD_KNN_OK;
-    }
-    if (strcmp(key, "shadow8_max_surv") == 0) {
-        if (value < 1 || value > 1000000) return fail(CODD_KNN_EINVAL, "shadow8_max_surv must be in [1,1000000]%s");
-        ix->shadow8_max_surv = (int)value;
-        return CODD_KNN_OK;
-    }
-    if (strcmp(key, "shadow8_cooldown") == 0) {
-        if (value < 0 || value > 1000000) return fail(CODD_KNN_EINVAL, "shadow8_cooldown must be in [0,1000000]%s");
-        ix->shadow8_cooldown = (int)value;
-        ix->cooldown_left = 0;
-        return CODD_KNN_OK;
-    }
+    // ... and the options that clamp, are no plain int or do more than store
+    if (strcmp(key, "filter") == 0) { ix->knobs.filter_enabled = value != 0; return CODD_KNN_OK; }
+    if (strcmp(key, "filter_min_rows") == 0) { ix->knobs.filter_min_rows = value < 1 ? 1 : value; return CODD_KNN_OK; }
+    if (strcmp(key, "filter_min_rows_small") == 0) { ix->knobs.filter_min_rows_small = value < 1 ? 1 : value; return CODD_KNN_OK; }
+    if (strcmp(key, "filter_min_batch") == 0) { ix->knobs.filter_min_batch = value < 1 ? 1 : (int)value; return CODD_KNN_OK; }
 #if CODD_EXPERIMENTS
     if (strcmp(key, "exp_slack_pct") == 0) {  // what-if timing only, experiment builds only: < 100 makes the int8 filter UNSOUND
         if (value < 1 || value > 100) return fail(CODD_KNN_EINVAL, "exp_slack_pct must be in [1,100]%s");
@@ -2941,7 +2710,7 @@ int codd_knn_set_option(codd_knn_index* ix, const char* key, int64_t value) {
         return CODD_KNN_OK;
     }
 #endif
-    if (strcmp(key, "debug_fail_shadow_alloc") == 0) {  // test hook: the bf16 shadow's allocation fails as if HBM were full
+    if (strcmp(key, "debug_fail_shadow_alloc") == 0) {  // test hook: the 2-byte shadow's allocation fails as if HBM were full
         ix->debug_fail_shadow_alloc = value != 0;
         if (!value) ix->shadow_nomem_epoch = -1;
         return CODD_KNN_OK;
@@ -2953,89 +2722,9 @@ int codd_knn_set_option(codd_knn_index* ix, const char* key, int64_t value) {
         ix->all_normalized = false;
         return CODD_KNN_OK;
     }
-    if (strcmp(key, "i8v2") == 0) {
-        if (value < 0 || value > 2) return fail(CODD_KNN_EINVAL, "i8v2 must be 0, 1 or 2%s");
-        ix->i8v2 = (int)value;
-        return CODD_KNN_OK;
-    }
-    if (strcmp(key, "f16_tile") == 0) {
-        if (value != 0 && value != 1) return fail(CODD_KNN_EINVAL, "f16_tile must be 0 or 1%s");
-        ix->f16_tile = (int)value;
-        return CODD_KNN_OK;
-    }
-    if (strcmp(key, "ivf_share") == 0) {
-        if (value != 0 && value != 1) return fail(CODD_KNN_EINVAL, "ivf_share must be 0 or 1%s");
-        ix->ivf_share = (int)value;
-        return CODD_KNN_OK;
-    }
-    if (strcmp(key, "fuse_fallback") == 0) {
-        if (value != 0 && value != 1) return fail(CODD_KNN_EINVAL, "fuse_fallback must be 0 or 1%s");
-        ix->fuse_fallback = (int)value;
-        return CODD_KNN_OK;
-    }
-    if (strcmp(key, "small_batch_max") == 0) {
-        if (value < 0 || value > 1) return fail(CODD_KNN_EINVAL, "small_batch_max must be 0 or 1%s");
-        ix->small_batch_max = (int)value;
-        return CODD_KNN_OK;
-    }
-    if (strcmp(key, "per_block") == 0) {
-        if (value < 0 || value > 7) return fail(CODD_KNN_EINVAL, "per_block must be in [0,7]%s");
-        ix->per_block = (int)value;
-        return CODD_KNN_OK;
-    }
-    if (strcmp(key, "i8_pair") == 0) {
-        if (value < 0 || value > 2) return fail(CODD_KNN_EINVAL, "i8_pair must be 0, 1 or 2%s");
-        ix->i8_pair = (int)value;
-        return CODD_KNN_OK;
-    }
-    if (strcmp(key, "i8v2_half") == 0) {
-        if (value != 0 && value != 1) return fail(CODD_KNN_EINVAL, "i8v2_half must be 0 or 1%s");
-        ix->i8v2_half = (int)value;
-        return CODD_KNN_OK;
-    }
-    if (strcmp(key, "resident_q") == 0) {
-        if (value != 0 && value != 1) return fail(CODD_KNN_EINVAL, "resident_q must be 0 or 1%s");
-        ix->resident_q = (int)value;
-        return CODD_KNN_OK;
-    }
-    if (strcmp(key, "sample_rounds8") == 0) {
-        if (value < 1 || value > 16) return fail(CODD_KNN_EINVAL, "sample_rounds8 must be in [1,16]%s");
-        ix->sample_rounds8 = (int)value;
-        return CODD_KNN_OK;
-    }
-    if (strcmp(key, "sample_div8") == 0) {
-        if (value < 1 || value > 1000) return fail(CODD_KNN_EINVAL, "sample_div8 must be in [1,1000]%s");
-        ix->sample_div8 = (int)value;
-        return CODD_KNN_OK;
-    }
-    if (strcmp(key, "sample_tiles") == 0) {
-        if (value < 1 || value > 65536) return fail(CODD_KNN_EINVAL, "sample_tiles must be in [1,65536]%s");
-        ix->sample_tiles = (int)value;
-        return CODD_KNN_OK;
-    }
-    if (strcmp(key, "sample_div") == 0) {
-        if (value < 1 || value > 4096) return fail(CODD_KNN_EINVAL, "sample_div must be in [1,4096]%s");
-        ix->sample_div = (int)value;
-        return CODD_KNN_OK;
-    }
     if (strcmp(key, "compact_chunk_rows") == 0) {
         if (value < 0 || value > (1ll << 32)) return fail(CODD_KNN_EINVAL, "compact_chunk_rows must be in [0,2^32]%s");
         ix->compact_chunk_rows = value;
-        return CODD_KNN_OK;
-    }
-    if (strcmp(key, "mask_route") == 0) {
-        if (value < 0 || value > 2) return fail(CODD_KNN_EINVAL, "mask_route must be 0 (auto), 1 (list) or 2 (dense)%s");
-        ix->mask_route = (int)value;
-        return CODD_KNN_OK;
-    }
-    if (strcmp(key, "mask_list_pct") == 0) {
-        if (value < 0 || value > 100000) return fail(CODD_KNN_EINVAL, "mask_list_pct must be in [0,100000]%s");
-        ix->mask_list_pct = (int)value;
-        return CODD_KNN_OK;
-    }
-    if (strcmp(key, "hit_cap") == 0) {
-        if (value < 16 || value > (1 << 20)) return fail(CODD_KNN_EINVAL, "hit_cap must be in [16,2^20]%s");
-        ix->hit_cap_q = (int)value;
         return CODD_KNN_OK;
     }
     if (strcmp(key, "profile") == 0) {
@@ -3089,44 +2778,53 @@ int codd_knn_get_stat(const codd_knn_index* ix, const char* key, int64_t* out) {
         *out = want_time ? (int64_t)(total_ms * 1e6) : events;
         return CODD_KNN_OK;
     }
-    if (strcmp(key, "searches") == 0) *out = ix->stat_searches;
-    else if (strcmp(key, "scan_launches") == 0) *out = ix->stat_scan_launches;
-    else if (strcmp(key, "last_scan_blocks") == 0) *out = ix->stat_last_scan_blocks;
-    else if (strcmp(key, "last_scan_group") == 0) *out = ix->stat_last_scan_group;
-    else if (strcmp(key, "last_finalize_parts") == 0) *out = ix->stat_last_finalize_parts;
-    else if (strcmp(key, "ivf_shared_searches") == 0) *out = ix->stat_ivf_shared;
-    else if (strcmp(key, "ivf_masked_searches") == 0) *out = ix->stat_ivf_masked;
-    else if (strcmp(key, "scoped_searches") == 0) *out = ix->stat_scoped_searches;
-    else if (strcmp(key, "scope_builds") == 0) *out = ix->stat_scope_builds;
-    else if (strcmp(key, "scopes") == 0) *out = (int64_t)ix->max_scope;
-    else if (strcmp(key, "masked_searches") == 0) *out = ix->stat_masked_searches;
-    else if (strcmp(key, "mask_list_searches") == 0) *out = ix->stat_mask_list;
-    else if (strcmp(key, "mask_dense_searches") == 0) *out = ix->stat_mask_dense;
-    else if (strcmp(key, "last_mask_rows") == 0) *out = ix->stat_last_mask_rows;
-    else if (strcmp(key, "masked_dev_searches") == 0) *out = ix->stat_masked_dev;
+    // the stats that read one int64 member
+    static const struct { const char* name; int64_t codd_knn_index::*member; } kStatTable[] = {
+        {"searches", &codd_knn_index::stat_searches},
+        {"scan_launches", &codd_knn_index::stat_scan_launches},
+        {"last_scan_blocks", &codd_knn_index::stat_last_scan_blocks},
+        {"last_scan_group", &codd_knn_index::stat_last_scan_group},
+        {"last_finalize_parts", &codd_knn_index::stat_last_finalize_parts},
+        {"ivf_shared_searches", &codd_knn_index::stat_ivf_shared},
+        {"ivf_masked_searches", &codd_knn_index::stat_ivf_masked},
+        {"scoped_searches", &codd_knn_index::stat_scoped_searches},
+        {"scope_builds", &codd_knn_index::stat_scope_builds},
+        {"masked_searches", &codd_knn_index::stat_masked_searches},
+        {"mask_list_searches", &codd_knn_index::stat_mask_list},
+        {"mask_dense_searches", &codd_knn_index::stat_mask_dense},
+        {"last_mask_rows", &codd_knn_index::stat_last_mask_rows},
+        {"masked_dev_searches", &codd_knn_index::stat_masked_dev},
+        {"doc_matches", &codd_knn_index::stat_doc_matches},
+        {"doc_regex_matches", &codd_knn_index::stat_doc_regex_matches},
+        {"dead_rows", &codd_knn_index::dead_count},
+        {"delete_calls", &codd_knn_index::stat_delete_calls},
+        {"compactions", &codd_knn_index::stat_compactions},
+        {"filter_passes", &codd_knn_index::stat_filter_passes},
+        {"shadow8_builds", &codd_knn_index::stat_shadow8_builds},
+        {"shadow16_builds", &codd_knn_index::stat_shadow_builds},
+        {"shadow16_alloc_failures", &codd_knn_index::stat_shadow_nomem},
+        {"shadow8_passes", &codd_knn_index::stat_shadow8_passes},
+        {"i8v2_passes", &codd_knn_index::stat_i8v2_passes},
+        {"f16_tile_passes", &codd_knn_index::stat_f16_tile_passes},
+        {"small_batch_passes", &codd_knn_index::stat_small_batch},
+        {"capacity_rows", &codd_knn_index::capacity},
+    };
+    for (const auto& row : kStatTable)
+        if (strcmp(key, row.name) == 0) {
+            *out = ix->*row.member;
+            return CODD_KNN_OK;
+        }
+    if (strcmp(key, "scopes") == 0) *out = (int64_t)ix->max_scope;
     else if (strcmp(key, "docs_valid") == 0) *out = docs_valid(ix) ? 1 : 0;
     else if (strcmp(key, "doc_bytes") == 0) *out = ix->doc_arena ? ix->doc_bytes : 0;
     else if (strcmp(key, "doc_tile_bytes") == 0) *out = kDocTile;
-    else if (strcmp(key, "doc_matches") == 0) *out = ix->stat_doc_matches;
     else if (strcmp(key, "doc_regex_tile_bytes") == 0) *out = kRegexTile;
     else if (strcmp(key, "doc_regex_run_docs") == 0) *out = kRegexDocs;
-    else if (strcmp(key, "doc_regex_matches") == 0) *out = ix->stat_doc_regex_matches;
-    else if (strcmp(key, "dead_rows") == 0) *out = ix->dead_count;
-    else if (strcmp(key, "delete_calls") == 0) *out = ix->stat_delete_calls;
-    else if (strcmp(key, "compactions") == 0) *out = ix->stat_compactions;
-    else if (strcmp(key, "filter_passes") == 0) *out = ix->stat_filter_passes;
-    else if (strcmp(key, "shadow8_builds") == 0) *out = ix->stat_shadow8_builds;
-    else if (strcmp(key, "shadow16_builds") == 0) *out = ix->stat_shadow_builds;
-    else if (strcmp(key, "shadow16_alloc_failures") == 0) *out = ix->stat_shadow_nomem;
     else if (strcmp(key, "all_normalized") == 0) *out = ix->all_normalized ? 1 : 0;
     else if (strcmp(key, "metric") == 0) *out = ix->metric;
-    else if (strcmp(key, "space_filter") == 0) *out = ix->space_filter;
-    else if (strcmp(key, "space_ivf") == 0) *out = ix->space_ivf;
-    else if (strcmp(key, "shadow8_passes") == 0) *out = ix->stat_shadow8_passes;
-    else if (strcmp(key, "i8v2_passes") == 0) *out = ix->stat_i8v2_passes;
-    else if (strcmp(key, "f16_tile_passes") == 0) *out = ix->stat_f16_tile_passes;
-    else if (strcmp(key, "small_batch_passes") == 0) *out = ix->stat_small_batch;
-    else if (strcmp(key, "shadow8_cooldowns") == 0) *out = ix->stat_cooldowns;
+    else if (strcmp(key, "space_filter") == 0) *out = ix->knobs.space_filter;
+    else if (strcmp(key, "space_ivf") == 0) *out = ix->knobs.space_ivf;
+    else if (strcmp(key, "shadow8_cooldowns") == 0) *out = ix->watch.stat_cooldowns;
     else if (strcmp(key, "shadow8_wide_blocks") == 0) {  // blocks whose error norm exceeds shadow8_max_eps, as last read back
         if (ix->eps_r_copied && hipEventQuery(ix->eps_r_copied) == hipSuccess) *out = (int64_t)reinterpret_cast<const unsigned*>(ix->eps_r_host.get())[1];
         else {
@@ -3161,11 +2859,10 @@ int codd_knn_get_stat(const codd_knn_index* ix, const char* key, int64_t* out) {
         }
         *out = (int64_t)(key[12] == 'h' ? h[0] : (key[12] == 's' ? h[1] : h[2]));
     }
-    else if (strcmp(key, "capacity_rows") == 0) *out = ix->capacity;
     else if (strcmp(key, "num_cus") == 0) *out = ix->num_cus;
     else if (strcmp(key, "device_bytes") == 0) {
         int64_t b = ix->capacity * (int64_t)ix->dpad * (int64_t)elem_size(ix->dtype) + ix->shadow_rows * (int64_t)ix->dpad * 2 +
-                    ix->shadow8_rows * ((int64_t)dpad8_of(ix) + 4) + ix->scope_of.bytes() + ix->scope_perm.bytes() + ix->scope_offsets.bytes() + ix->dead_bits.bytes() +
+                    ix->shadow8_rows * ((int64_t)dpad8_of(shape_of(ix)) + 4) + ix->scope_of.bytes() + ix->scope_perm.bytes() + ix->scope_offsets.bytes() + ix->dead_bits.bytes() +
                     ix->doc_arena.bytes() + ix->doc_offsets.bytes();
         for (const WorkSlot& w : ix->slots)
             b += w.bufs.qn.bytes() + w.bufs.partial.bytes() + w.bufs.keys_tmp.bytes() + w.bufs.hits.bytes() + w.bufs.bucket_max.bytes() +

@@ -27,9 +27,6 @@ int with_dtype(int dtype, F&& f) {
 // the NITER values the wide forms serve: rows of 5 .. 16 chunks per lane (f32: 1,025 .. 4,096 elements; 2-byte: 2,049 .. 4,096)
 constexpr int kMaxNiter = 16;
 
-// chunks of the padded row per lane: the NITER of the exact-score row kernels
-int niter_of(const codd_knn_index* ix) { return (ix->dpad / elems_per_chunk(ix->dtype) + kWave - 1) / kWave; }
-
 // 1 .. 4 chunks per lane: NITER itself; 5 .. kMaxNiter: the wide form (kWideRows); wider: ENOTSUP with `too_wide`
 template <typename F>
 int with_niter(int niter, const char* too_wide, F&& f) {
@@ -59,7 +56,7 @@ int with_nbq(int nbq, F&& f) {
 template <typename F>
 int with_row_form(const codd_knn_index* ix, int k, const char* too_wide, F&& f) {
     return with_dtype(ix->dtype, [&](auto dt) {
-        return with_niter(niter_of(ix), too_wide, [&](auto ni) {
+        return with_niter(niter_of(shape_of(ix)), too_wide, [&](auto ni) {
             return with_slots(k, [&](auto sl) { return f(dt, ni, sl); });
         });
     });

@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "geometry.h"
 #include "row_traits.h"
 #include "wave_topk.h"
 
@@ -147,8 +148,7 @@ __device__ __forceinline__ float score4_one(const float (&w)[4][NITER][E], const
 // the row up to a whole segment.  The row is walked in segments of kSegIt chunks per lane (what NITER 4 holds in registers), the
 // segment's row loads all in flight before its first fmaf, and each lane's accumulators are carried from one segment to the next:
 // chunk j is still lane j % 64's and is visited in increasing j, so the per-lane chains, the butterfly behind them and the scores are
-// exactly the narrow form's.
-constexpr int kWideRows = 0;
+// exactly the narrow form's.  (kWideRows itself: geometry.h)
 constexpr int kSegIt = 4;
 constexpr int kWideMaxFloats = 4096;  // LDS floats of one staged query: dpad <= 4096 rounds up to at most 4,096 (f32: 1,024 chunks; 2-byte: 512)
 __host__ __device__ constexpr int wide_nseg(int nchunks) { return (nchunks + kSegIt * kWave - 1) / (kSegIt * kWave); }

@@ -31,17 +31,13 @@
 #include <type_traits>
 
 #include "exact_score.h"
+#include "geometry.h"
 #include "row_traits.h"
 #include "wave_topk.h"
 
 namespace codd {
 
-#ifndef CODD_SHADOW_F16
-#define CODD_SHADOW_F16 1    // the 2-byte shadow's element type: 1 = fp16 (11-bit significand: eps 0.0011 at 768-d), 0 = bf16 (8 bits: eps 0.0079).
-                             // Same MFMA rate, same bytes; fp16 since round 3: this filter is what an index falls back to when the int8 one (eps ~0.02)
-                             // cannot separate a query's neighbourhood from the rest of a dense cluster, and there a 7x tighter slack is worth more than
-                             // anything else (profiles/r3/clustered_corpora.txt).  Unit-norm operands cannot overflow fp16; its subnormal grid is in the bound.
-#endif
+// (CODD_SHADOW_F16, CODD_MFMA16, kTileRows, kTileQ: geometry.h)
 #if CODD_SHADOW_F16
 typedef __attribute__((ext_vector_type(8))) _Float16 bf16x8;  // "shadow element x8" (name kept for the bf16 default)
 #else
@@ -49,8 +45,6 @@ typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 #endif
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 
-constexpr int kTileRows = 256;
-constexpr int kTileQ = 256;
 constexpr int kStagePieces = 2048;  // 16-byte pieces of one query K-slice (256 q x 64 k bf16 = 32 KiB)
 #ifndef CODD_RB
 #define CODD_RB 1            // 32-row corpus blocks per wave: 1 -> 8 waves x 256 regs, 2 -> 4 waves x 512 regs
@@ -64,9 +58,6 @@ constexpr int kRowGroups = 8 / kRB;                   // row groups of a 256-row
 constexpr int kFilterWaves = kRowGroups * kQSplit;
 constexpr int kFilterThreads = 64 * kFilterWaves;
 constexpr int kQP = kStagePieces / kFilterThreads;  // query-slice pieces each thread stages per K-step
-#ifndef CODD_MFMA16
-#define CODD_MFMA16 1        // 1: v_mfma_f32_16x16x32_bf16 (16-row x 16-query blocks, K 32) instead of 32x32x16
-#endif
 // MFMA block geometry.  32x32x16: a wave's 32 rows are ONE row block, a 64-wide K-step is 4 sub-steps, a
 // 32-query block per accumulator (16 regs).  16x16x32: TWO row blocks of 16, 2 sub-steps, 16-query blocks
 // (4 regs).  Either way a wave-level operand piece is 64 lanes x 16 B = 1 KiB and an accumulator set is 128 regs.

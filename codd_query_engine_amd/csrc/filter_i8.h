@@ -34,6 +34,7 @@
 // LDS: 4 query slices x 32 KiB | 1088 bookkeeping words | 2 row-scale buffers x (256 + 16) floats | hit list.
 #pragma once
 #include "filter_gemm.h"
+#include "geometry.h"
 
 #if !CODD_EXPERIMENTS && (defined(CODD_I8_EXP_NOEPI) || defined(CODD_I8_EXP_NODMA) || defined(CODD_I8_EXP_SAMETILE) || defined(CODD_I8_EXP_NOBARRIER) || \
                           defined(CODD_I8_EXP_NOBREAD) || defined(CODD_I8_EXP_NOHITS) || defined(CODD_I8_EXP_NOAPPEND) || defined(CODD_I8_EXP_NOFLUSH) || defined(CODD_I8_EXP_NOGLOBAL) || \
@@ -154,8 +155,7 @@ constexpr int kAPerIv = 4;
 // SAMPLE: [0..511] = 256 u64 keys.
 constexpr int kI8Words = 1344;   // ... [1088..1343] u_q = B(q) / qscale_q (FILTER)
 
-// does the resident program apply? (nbq: 32-query blocks of the batch: 8 -> NQB = 16, 4 -> NQB = 8)
-__host__ __device__ constexpr bool i8_tile_resident(int nsteps, int nbq) { return nsteps <= (nbq == 8 ? 4 : 8); }
+// (does the resident program apply?  i8_tile_resident(): geometry.h)
 
 __host__ __device__ constexpr size_t i8_lds_bytes(int mode) {
     return (size_t)4 * kI8SliceBytes + kI8Words * 4 + kI8RsBufs * kI8RsStride * 4 + (mode == MODE_FILTER ? (size_t)kHitCap * 12 : 0);

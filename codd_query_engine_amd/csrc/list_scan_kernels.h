@@ -161,7 +161,7 @@ void ivf_scan_sq(const void* __restrict__ rows_, const uint32_t* __restrict__ id
 // The item writes each pair's top-k to the pair's own slot of the partial buffer, so the merge behind it is the same launch
 // as for the unshared scan and the results are the same bits.
 // ---------------------------------------------------------------------------------------------
-constexpr int kIvfNB = 4;  // queries per work item
+// (kIvfNB, the queries per work item: geometry.h)
 __global__ __launch_bounds__(256) void ivf_pair_count_kernel(const u64* __restrict__ probe_keys, int npairs, unsigned* __restrict__ cnt) {
     const int p = (int)blockIdx.x * 256 + (int)threadIdx.x;
     if (p < npairs && probe_keys[p] != 0ull) atomicAdd(&cnt[key_row(probe_keys[p])], 1u);
@@ -483,8 +483,7 @@ __global__ __launch_bounds__(1024) void scope_group_kernel(const uint32_t* __res
     rank[before] = before - lower;
 }
 
-// queries per work item: four, as in ivf_scan_shared_kernel; two for 2-byte rows of 4 chunks per lane (four queries' registers would spill)
-constexpr int scope_nb(int dt, int niter) { return (dt != DT_F32 && niter == 4) ? 2 : 4; }
+// (queries per work item: scope_nb(), geometry.h)
 // rows per part: a whole number of workgroup steps (4 waves x 4 rows)
 __host__ __device__ constexpr int64_t scope_part_rows(int64_t len, int split) { return ((len + split - 1) / split + 15) / 16 * 16; }
 

@@ -3,11 +3,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-namespace codd {
+#include "geometry.h"  // DT_F32, DT_BF16, DT_F16
 
-constexpr int DT_F32 = 0;   // == CODD_KNN_DTYPE_F32
-constexpr int DT_BF16 = 1;  // == CODD_KNN_DTYPE_BF16
-constexpr int DT_F16 = 2;   // == CODD_KNN_DTYPE_F16
+namespace codd {
 
 template <int DT>
 struct RowTraits;

@@ -5,10 +5,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "geometry.h"  // kWave
+
 namespace codd {
 
 typedef unsigned long long u64;
-constexpr int kWave = 64;
 
 __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63u); }
 

@@ -459,7 +459,7 @@ int codd_knn_embed_texts_host(codd_knn_embedder* e, const uint8_t* host_bytes, c
 
 /*
  * Tuning / introspection (never needed for correctness).
- *   options: "scan_blocks_per_cu" (1..8); "filter" (0/1: MFMA filter path for large batches);
+ *   options: "scan_blocks_per_cu" (4; 1..8: workgroups per compute unit of the exact scan, at most); "filter" (0/1: MFMA filter path for large batches);
  *            "filter_min_batch" (9), "filter_min_rows" (1: batches >= filter_min_batch always
  *            filter when the corpus has >= 2k sample tiles), "filter_min_rows_small" (100000:
  *            smaller batches filter when rows * B reaches it): when the filter path is taken;
@@ -472,7 +472,7 @@ int codd_knn_embed_texts_host(codd_knn_embedder* e, const uint8_t* host_bytes, c
  *            "shadow8" (1: batches of <= "shadow8_max_batch" (256) queries are filtered through an
  *            int8 copy of the corpus, 1 byte per element, derived lazily from the stored rows and
  *            kept up to date incrementally; results stay exact; an index whose worst row quantises
- *            badly — error norm above 0.04 — keeps the bf16 filter; so does, for the next
+ *            badly — error norm above 0.04 — keeps the 2-byte (fp16) filter; so does, for the next
  *            "shadow8_cooldown" (256) searches, an index whose int8 passes leave more than
  *            "shadow8_max_surv" (4000) survivors per query or send queries to the fallback: dense
  *            clusters — unless the 2-byte passes are seen to leave at least half as many), "sample_div8" (28:
@@ -487,10 +487,10 @@ int codd_knn_embed_texts_host(codd_knn_embedder* e, const uint8_t* host_bytes, c
  *            "i8_pair" (2: that kernel synchronises once per two K-steps on rows of 768 / 1536 ... elements, and rows of exactly 768 take its static form; 1: without the static form; 0: every
  *            K-step), "per_block" (7, bit mask: the int8 bound uses each 32-row block's own quantisation error instead of
  *            the corpus's worst — bit 0 in the tile kernel, bit 1 in finalize (bit 2 is accepted and ignored: the
- *            tile kernel's filter pass always fetches the block metadata by one LDS-DMA per tile); 0 = the device-wide bound everywhere), "fuse_fallback" (1: batches above 64 queries answer candidate-list
- *            overflows inside the finalize launch; 0: a launch of their own), "small_batch_max" (0; 1: a single query on
- *            <= 2M-row int8 shadows is answered by ONE launch — measured slower than the three-launch chain, see
- *            DESIGN.md §12, hence off), "f16_tile" (1: the 2-byte filter of 129..256 queries on rows of 384 / 768 / 1152 ... elements runs
+ *            tile kernel's filter pass always fetches the block metadata by one LDS-DMA per tile); 0 = the device-wide bound everywhere), "fuse_fallback" (1: every pass of the 2-byte filter and the int8 passes of more than 64 queries, k <= 64,
+ *            answer candidate-list overflows inside the finalize launch; 0: a launch of their own), "small_batch_max" (0; 1: a single query,
+ *            k <= 64, on an index of 4,096 rows or more whose int8 rows are 384, 512, 768 or 1,024 elements wide is answered by ONE
+ *            launch — measured slower than the three-launch chain, see DESIGN.md §12, hence off), "f16_tile" (1: the 2-byte filter of 129..256 queries on rows of 384 / 768 / 1152 ... elements runs
  *            csrc/filter_i8.h's tile program on fp16 operands; 0: the first-generation kernel), "ivf_share" (1: codd_knn_ivf_search scans a probed list once for all queries of the
  *            batch that probe it, from 1,024 (query, list) pairs on; 0: once per pair),
  *            "compact_chunk_rows" (0: codd_knn_compact moves as many source rows per step as 64 MiB hold; N: N rows — tests),
@@ -503,7 +503,8 @@ int codd_knn_embed_texts_host(codd_knn_embedder* e, const uint8_t* host_bytes, c
  *            DESIGN.md §21),
  *            "space_ivf" (0; 1: codd_knn_ivf_install and the IVF searches accept an ip or l2 index — raw centroids, a coarse index
  *            and list scans in the index's own space; 0: they return ENOTSUP there; no effect on a cosine index),
- *            "debug_fail_shadow_alloc" (tests: the next N allocations of the 2-byte shadow fail);
+ *            "debug_fail_shadow_alloc" (tests; a switch, not a count: while it is non-zero every allocation of the 2-byte shadow fails as
+ *            if HBM were full; 0 switches it off and lets the next search try again);
  *            "profile" = N keeps N (start, stop) HIP-event pairs, one per heavy-kernel launch,
  *            recorded on the launch stream (0 = off; resets the log)
  *   stats  : "searches", "scan_launches", "last_scan_blocks", "last_scan_group" (queries per pass over the rows of the
@@ -522,7 +523,7 @@ int codd_knn_embed_texts_host(codd_knn_embedder* e, const uint8_t* host_bytes, c
  *            workgroup of it), "filter_passes",
  *            "fallback_queries", "filter_hits", "filter_survivors", "capacity_rows",
  *            "device_bytes", "num_cus", "workspaces" (stream workspaces in use), "shadow8_builds", "shadow8_passes", "i8v2_passes",
- *            "shadow16_builds" (the bf16 shadow is built lazily, by the first search that needs it), "all_normalized",
+ *            "shadow16_builds" (the 2-byte (fp16) shadow is built lazily, by the first search that needs it), "all_normalized",
  *            "shadow8_cooldowns", "shadow8_eps_r_micro", "shadow8_wide_blocks" (32-row blocks whose quantisation error is above
  *            0.04: tolerated up to 1 % of the blocks), "shadow16_alloc_failures", "small_batch_passes", "f16_tile_passes", "space_filter", "space_ivf" (the options), and per kernel K in {scan, filter, sample, finalize}:
  *            "events:K", "time_ns:K" (sum of the recorded launches; syncs on the last event)
