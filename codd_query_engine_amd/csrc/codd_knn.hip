@@ -82,6 +82,7 @@ struct LastPass {
     int hit_cap = 0;
     float eps = 0.0f;
     int per_block_filter = 0, per_block_finalize = 0;
+    int cascade_d = 0;   // the sample cascade ran with this d: sample_tiles, sample_stride are A0's, whose first tile is 1
 };
 
 // Search workspace.  An index keeps up to kMaxWork of them, one per HIP stream that searches it, so that searches
@@ -254,6 +255,7 @@ struct codd_knn_index : WorkBufs {
     int64_t stat_ivf_shared = 0;            // IVF searches that scanned each probed list once for all its queries (ivf_scan_shared_kernel)
     int64_t stat_ivf_masked = 0;            // IVF searches under a row mask (codd_knn_ivf_search_masked, _masked_dev: DESIGN.md §17)
     int64_t stat_filter_passes = 0;
+    int64_t stat_cascade_passes = 0, stat_last_cascade_d = 0;   // filter passes that took the sample cascade, and the d of the last pass (0: none)
 
     // optional HIP-event timing of the heavy kernels (bench.py's roofline figure): one (start, stop)
     // pair per launch, recorded on the launch stream, read after a sync
@@ -362,9 +364,12 @@ struct EvScope {  // records a (start, stop) pair around one launch when profili
             (void)hipEventRecord(ix->ev[2 * slot], st);
         }
     }
-    ~EvScope() {
+    // the pair ends here instead of at the end of the scope
+    void stop() {
         if (slot >= 0) (void)hipEventRecord(ix->ev[2 * slot + 1], st);
+        slot = -1;
     }
+    ~EvScope() { stop(); }
 };
 
 // Loads the calling stream's workspace into the index for one call (see WorkBufs).  A stream keeps its slot; a new
@@ -908,6 +913,7 @@ struct FilterArgs {
     float eb_scale;
     const float* rnorm2 = nullptr;  // sqd_filter_kernel only: the rows' and the queries' sums of squares
     const float* qn2 = nullptr;
+    int skip_d = 0;                 // i8_tile_kernel only: d of the sample cascade's launch B (0: every run-tile)
 };
 
 // one launch of program `p` in pass MODE (MODE_SAMPLE or MODE_FILTER)
@@ -924,7 +930,7 @@ int launch_filter_program(const FilterProgram& p, dim3 grid, hipStream_t st, con
     auto tile = [&](auto ts, auto nqb, auto res, auto f16) {
         return launch_kernel<i8_tile_kernel<MODE, ts, nqb, res, f16>>(grid, block, i8_lds_bytes(MODE), st, a.shadow, a.qfrag, a.n, a.nsteps,
                                                                       a.ntiles_run, a.tile_stride, a.thr, a.bucket_key, a.hits, a.hit_cnt, a.cap_q,
-                                                                      a.flags, a.rscale, a.qscale, a.bmeta, a.eb_scale);
+                                                                      a.flags, a.rscale, a.qscale, a.bmeta, a.eb_scale, a.skip_d);
     };
     if (p.sqd) {
         return with_nbq(p.nbq, [&](auto nbq) {
@@ -1040,9 +1046,13 @@ int filter_pass(codd_knn_index* ix, const float* qn, int nq, int k, uint32_t row
     const FilterProgram prog = filter_program(knobs, shape, nq, nsteps, use8);
     if (prog.family == FilterProgram::TILE) ix->stat_i8v2_passes++;
     if (prog.family == FilterProgram::TILE_F16) ix->stat_f16_tile_passes++;
-    // sample: every `stride`-th tile
-    const int64_t ts = sample_tile_count(knobs, shape, ntiles, k, use8, prog.nbq);
-    const int64_t stride = ntiles / ts;
+    // sample: every `stride`-th tile; or the sample cascade (search_plan.h: cascade_plan), whose first sample A0 is one round from tile a0_first on
+    const int64_t ts_plain = sample_tile_count(knobs, shape, ntiles, k, use8, prog.nbq);
+    const CascadePlan cas = use8 ? cascade_plan(knobs, shape, prog, ntiles, k, ts_plain) : CascadePlan();
+    const int64_t ts = cas.on ? cas.a0_tiles : ts_plain;
+    const int64_t stride = cas.on ? cas.a0_stride : ntiles / ts;
+    ix->stat_last_cascade_d = cas.on ? cas.d : 0;
+    if (cas.on) ix->stat_cascade_passes++;
     {
         LastPass& lp = ix->last;
         lp.valid = true;
@@ -1051,45 +1061,74 @@ int filter_pass(codd_knn_index* ix, const float* qn, int nq, int k, uint32_t row
         lp.eps = eps;
         lp.per_block_filter = prog.family == FilterProgram::TILE && (ix->knobs.per_block & 1) ? 1 : 0;
         lp.per_block_finalize = slack_q && (ix->knobs.per_block & 2) && cosine ? 1 : 0;
+        lp.cascade_d = cas.on ? cas.d : 0;
     }
-    {
-        EvScope ev(ix, EV_SAMPLE, st);
-        const dim3 g((unsigned)(ts < ix->num_cus ? ts : ix->num_cus));
-        FilterArgs sa{shadow, qfrag, n, nsteps, ts, stride, nullptr, ix->bucket_max, nullptr, nullptr, 0, nullptr, rscale, qscale, nullptr, 1.0f};
-        if (prog.sqd) { sa.rnorm2 = ix->rnorm2; sa.qn2 = ix->qmeta + 512; }
-        if ((rc = launch_filter_program<MODE_SAMPLE>(prog, g, st, sa)) != 0) return rc;
-    }
-    HIP_TRY(hipGetLastError());
-    // thresholds anchored on the exact scores of the k best sampled rows (anchor_thr_kernel)
-    rc = with_row_form(ix, k, "row too wide for the threshold kernel%s", [&](auto dt, auto ni, auto sl) {
-        if constexpr (decltype(ni)::value != kWideRows) {
-            if (prog.sqd)
-                return launch_kernel<sqd_thr_kernel<dt, ni, sl>>(dim3(kTileQ), dim3(kAnchorWaves * kWave), 0, st, ix->bucket_max, ts, nq, k, ix->rows, ix->dpad,
-                                                                        qn, slack_q, ix->thr, deny);
-        }
-        return launch_kernel<anchor_thr_kernel<dt, ni, sl>>(dim3(kTileQ), dim3(kAnchorWaves * kWave), 0, st, ix->bucket_max, ts, nq, k, ix->rows,
-                                                            ix->dpad, qn, eps, slack_q, ix->thr, use8 ? ix->thr + kTileQ : nullptr, deny);
-    });
-    if (rc != 0) return rc;
-    HIP_TRY(hipGetLastError());
-    {
-        EvScope ev(ix, EV_FILTER, st);
-        const dim3 g((unsigned)(ntiles < ix->num_cus ? ntiles : ix->num_cus));
-        FilterArgs fa{shadow, qfrag, n, nsteps, ntiles, 1, ix->thr, nullptr, ix->hits, ix->ctl->hit_cnt, ix->knobs.hit_cap_q, ix->ctl->flags, rscale, qscale, nullptr, 0.0f};
+    // one launch of the pass's filter program over run-tiles [0, ntiles_run) of stride tile_stride, appending to the pass's hit lists
+    auto filter_launch = [&](int64_t ntiles_run, int64_t tile_stride, int64_t grid, int skip_d) -> int {
+        const dim3 g((unsigned)grid);
+        FilterArgs fa{shadow, qfrag, n, nsteps, ntiles_run, tile_stride, ix->thr, nullptr, ix->hits, ix->ctl->hit_cnt, ix->knobs.hit_cap_q, ix->ctl->flags, rscale, qscale, nullptr, 0.0f};
+        fa.skip_d = skip_d;
         if (prog.sqd) { fa.rnorm2 = ix->rnorm2; fa.qn2 = ix->qmeta + 512; }
         if (prog.family == FilterProgram::TILE) {
             // the per-block bound (per_block & 1): thr0[q] and the blocks' error norms
             fa.thr = (ix->knobs.per_block & 1) ? ix->thr + kTileQ : ix->thr;
             fa.bmeta = ix->bmeta;
             fa.eb_scale = (ix->knobs.per_block & 1) ? 1.0f : 0.0f;
-#ifdef CODD_I8_EXP_STAMPS  // (diagnostic build: the filter pass writes its per-wave phase stamps over the sample's bucket keys, which anchor_thr has consumed)
-            fa.bucket_key = ix->bucket_max;
+#ifdef CODD_I8_EXP_STAMPS  // (diagnostic build: the filter pass writes its per-wave phase stamps over the sample's bucket keys, which the anchor kernels have consumed)
+            if (tile_stride == 1) fa.bucket_key = ix->bucket_max;   // (the main launch; the cascade's A1 runs before the re-anchor has read the keys)
 #endif
         } else if (prog.family == FilterProgram::TILE_F16) {
             // (thr doubles as the 256 readable bytes the kernel's per-tile metadata request needs; fp16 operands carry no scales)
             fa.bmeta = reinterpret_cast<const float2*>(ix->thr.get());
         }
-        if ((rc = launch_filter_program<MODE_FILTER>(prog, g, st, fa)) != 0) return rc;
+        return launch_filter_program<MODE_FILTER>(prog, g, st, fa);
+    };
+    // A0 reads the corpus from row slot `row0` on (cas.a0_first whole tiles in: none of its tiles is one of A1's): the sample program and
+    // anchor_thr_kernel are given every per-row array from there, so their row numbers count from row0 — reanchor_thr_kernel adds it back
+    const int64_t row0 = cas.on ? cas.a0_first * kTileRows : 0;
+    {
+        // (the cascade: one event pair from A0 to the re-anchor, everything that fixes the thresholds; else the sample launch alone, as ever)
+        EvScope ev(ix, EV_SAMPLE, st);
+        {
+            const dim3 g((unsigned)(ts < ix->num_cus ? ts : ix->num_cus));
+            FilterArgs sa{shadow + row0 * (dpad8_of(shape) / 16), qfrag, n - row0, nsteps, ts, stride, nullptr, ix->bucket_max, nullptr, nullptr, 0, nullptr,
+                          rscale ? rscale + row0 : nullptr, qscale, nullptr, 1.0f};
+            if (prog.sqd) { sa.rnorm2 = ix->rnorm2; sa.qn2 = ix->qmeta + 512; }
+            if ((rc = launch_filter_program<MODE_SAMPLE>(prog, g, st, sa)) != 0) return rc;
+        }
+        if (!cas.on) ev.stop();
+        HIP_TRY(hipGetLastError());
+        // thresholds anchored on the exact scores of the k best sampled rows (anchor_thr_kernel)
+        const unsigned char* rows_s = ix->rows.get() + row0 * (int64_t)ix->dpad * (int64_t)elem_size(ix->dtype);
+        const uint32_t* deny_s = deny ? deny + row0 / 32 : nullptr;
+        rc = with_row_form(ix, k, "row too wide for the threshold kernel%s", [&](auto dt, auto ni, auto sl) {
+            if constexpr (decltype(ni)::value != kWideRows) {
+                if (prog.sqd)
+                    return launch_kernel<sqd_thr_kernel<dt, ni, sl>>(dim3(kTileQ), dim3(kAnchorWaves * kWave), 0, st, ix->bucket_max, ts, nq, k, ix->rows, ix->dpad,
+                                                                            qn, slack_q, ix->thr, deny);
+            }
+            return launch_kernel<anchor_thr_kernel<dt, ni, sl>>(dim3(kTileQ), dim3(kAnchorWaves * kWave), 0, st, ix->bucket_max, ts, nq, k, rows_s,
+                                                                ix->dpad, qn, eps, slack_q, ix->thr, use8 ? ix->thr + kTileQ : nullptr, deny_s);
+        });
+        if (rc != 0) return rc;
+        HIP_TRY(hipGetLastError());
+        if (cas.on) {
+            // A1: the filter program over tiles 0, d + 1, ... with the provisional thresholds (timed with the sample: it is what fixes the thresholds)
+            if ((rc = filter_launch(cas.a1_tiles, cas.d + 1, cas.a1_tiles < ix->num_cus ? cas.a1_tiles : ix->num_cus, 0)) != 0) return rc;
+            HIP_TRY(hipGetLastError());
+            rc = with_row_form(ix, k, "row too wide for the threshold kernel%s", [&](auto dt, auto ni, auto sl) {
+                return launch_kernel<reanchor_thr_kernel<dt, ni, sl>>(dim3(nq), dim3(kAnchorWaves * kWave), 0, st, ix->bucket_max, ts, (unsigned)row0, ix->hits,
+                                                                      ix->ctl->hit_cnt, ix->knobs.hit_cap_q, nq, k, ix->rows, ix->dpad, qn, eps, slack_q, ix->thr,
+                                                                      ix->thr + kTileQ, deny);
+            });
+            if (rc != 0) return rc;
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    {
+        // the main launch: every tile, or (the cascade's launch B) every tile that is no multiple of d + 1, on a grid d divides
+        EvScope ev(ix, EV_FILTER, st);
+        if ((rc = filter_launch(ntiles, 1, cas.on ? cas.G : (ntiles < ix->num_cus ? ntiles : ix->num_cus), cas.on ? cas.d : 0)) != 0) return rc;
     }
     HIP_TRY(hipGetLastError());
     const int niter = niter_of(shape);
@@ -2665,6 +2704,7 @@ int codd_knn_debug_last_pass(codd_knn_index* ix, void* stream, codd_knn_last_pas
         info->per_block_filter = lp.per_block_filter; info->per_block_finalize = lp.per_block_finalize;
         info->eps = lp.eps;
         info->n = lp.n; info->sample_tiles = lp.sample_tiles; info->sample_stride = lp.sample_stride;
+        info->cascade_d = (uint32_t)lp.cascade_d;
         for (int i = 0; i < 4; ++i) info->flags[i] = i < FLAG_WORDS ? ctl.flags[i] : 0u;
         info->fb_count = ctl.fb_count;
     }
@@ -2703,6 +2743,22 @@ int codd_knn_set_option(codd_knn_index* ix, const char* key, int64_t value) {
     if (strcmp(key, "filter_min_rows") == 0) { ix->knobs.filter_min_rows = value < 1 ? 1 : value; return CODD_KNN_OK; }
     if (strcmp(key, "filter_min_rows_small") == 0) { ix->knobs.filter_min_rows_small = value < 1 ? 1 : value; return CODD_KNN_OK; }
     if (strcmp(key, "filter_min_batch") == 0) { ix->knobs.filter_min_batch = value < 1 ? 1 : (int)value; return CODD_KNN_OK; }
+    // the sample cascade (search_plan.h: cascade_plan)
+    if (strcmp(key, "sample_cascade") == 0) {
+        if (value < 0 || value > 2) return fail(CODD_KNN_EINVAL, "sample_cascade must be 0, 1 or 2%s");
+        ix->knobs.sample_cascade = (int)value;
+        return CODD_KNN_OK;
+    }
+    if (strcmp(key, "cascade_d") == 0) {
+        if (value < kCascadeDMin || value > kCascadeDMax) return fail(CODD_KNN_EINVAL, "cascade_d must be in [16,64]%s");
+        ix->knobs.cascade_d = (int)value;
+        return CODD_KNN_OK;
+    }
+    if (strcmp(key, "cascade_min_rounds") == 0) {
+        if (value < 1 || value > 64) return fail(CODD_KNN_EINVAL, "cascade_min_rounds must be in [1,64]%s");
+        ix->knobs.cascade_min_rounds = (int)value;
+        return CODD_KNN_OK;
+    }
 #if CODD_EXPERIMENTS
     if (strcmp(key, "exp_slack_pct") == 0) {  // what-if timing only, experiment builds only: < 100 makes the int8 filter UNSOUND
         if (value < 1 || value > 100) return fail(CODD_KNN_EINVAL, "exp_slack_pct must be in [1,100]%s");
@@ -2800,6 +2856,8 @@ int codd_knn_get_stat(const codd_knn_index* ix, const char* key, int64_t* out) {
         {"delete_calls", &codd_knn_index::stat_delete_calls},
         {"compactions", &codd_knn_index::stat_compactions},
         {"filter_passes", &codd_knn_index::stat_filter_passes},
+        {"cascade_passes", &codd_knn_index::stat_cascade_passes},
+        {"last_cascade_d", &codd_knn_index::stat_last_cascade_d},
         {"shadow8_builds", &codd_knn_index::stat_shadow8_builds},
         {"shadow16_builds", &codd_knn_index::stat_shadow_builds},
         {"shadow16_alloc_failures", &codd_knn_index::stat_shadow_nomem},

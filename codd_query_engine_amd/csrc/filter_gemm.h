@@ -577,11 +577,14 @@ __global__ __launch_bounds__(kFinThreads) void sqd_fin_kernel(const void* __rest
 // all of them or, past the candidate capacity, by the exact-scan fallback queue; never a threshold from fewer than k rows.
 // ---------------------------------------------------------------------------------------------
 constexpr int kAnchorWaves = 4;  // waves per query: the bucket scan and the k row reads are shared out (one wave: 19 us of a 430 us shard step)
-template <int DT, int NITER, int SLOTS, int METRIC>
+template <int DT, int NITER, int SLOTS, int METRIC, bool RE = false>
 __device__ __forceinline__ void anchor_thr_body(const u64* __restrict__ bucket_key, int64_t nbuckets, int B, int k,
                                                 const void* __restrict__ rows_, int dpad, const float* __restrict__ qn, float eps,
                                                 const float* __restrict__ two_eps_q, float* __restrict__ thr,
-                                                float* __restrict__ thr0, const uint32_t* __restrict__ dead) {
+                                                float* __restrict__ thr0, const uint32_t* __restrict__ dead,
+                                                const u64* __restrict__ more = nullptr, unsigned nmore = 0u, unsigned bucket_row0 = 0u) {
+    // RE (with more, nmore, bucket_row0): the re-anchor of the sample cascade (reanchor_thr_kernel below); every statement it adds is
+    // compiled for RE alone, so anchor_thr_kernel and sqd_thr_kernel stay the kernels they were
     // thr0 (int8 filter, with two_eps_q = qmeta + 256): L - A(q), the block-independent part of the per-block threshold
     // L - A(q) - B(q) e_block that i8_tile_kernel evaluates (A at two_eps_q[256 + q])
     typedef RowTraits<DT> RT;
@@ -612,8 +615,19 @@ __device__ __forceinline__ void anchor_thr_body(const u64* __restrict__ bucket_k
     for (int64_t i0 = (int64_t)wave * kWave; i0 < nbuckets; i0 += kAnchorWaves * kWave) {
         const int64_t i = i0 + lane;
         u64 key = i < nbuckets ? bucket_key[(int64_t)q * nbuckets + i] : 0ull;
+        if constexpr (RE) {
+            if (key) key = make_key(key_score(key), key_row(key) + bucket_row0);
+        }
         if (dead && key && row_dead(dead, key_row(key))) key = 0ull;
         L.offer_lanes(key, k, lane);
+    }
+    if constexpr (RE) {
+        for (unsigned i0 = (unsigned)wave * kWave; i0 < nmore; i0 += kAnchorWaves * kWave) {
+            const unsigned i = i0 + lane;
+            u64 key = i < nmore ? more[i] : 0ull;
+            if (dead && key && row_dead(dead, key_row(key))) key = 0ull;
+            L.offer_lanes(key, k, lane);
+        }
     }
     store_list(lds_list, wave, 1, 0, lane, L);
     __syncthreads();
@@ -624,6 +638,7 @@ __device__ __forceinline__ void anchor_thr_body(const u64* __restrict__ bucket_k
     }
     __syncthreads();
     if (!lds_full) {  // fewer than k buckets with a row: no threshold can be justified
+        if constexpr (RE) return;   // (the query keeps the thresholds it had)
         if (tid == 0) {
             thr[q] = -INFINITY;
             if (thr0) thr0[q] = -INFINITY;
@@ -671,8 +686,13 @@ __device__ __forceinline__ void anchor_thr_body(const u64* __restrict__ bucket_k
         float wmin = lds_worst[0];
 #pragma unroll
         for (int wv = 1; wv < kAnchorWaves; ++wv) wmin = fminf(wmin, lds_worst[wv]);
-        thr[q] = wmin - (two_eps_q ? 0.5f * two_eps_q[q] : eps);
-        if (thr0) thr0[q] = wmin - two_eps_q[256 + q];
+        if constexpr (RE) {
+            thr[q] = fmaxf(thr[q], wmin - (two_eps_q ? 0.5f * two_eps_q[q] : eps));
+            if (thr0) thr0[q] = fmaxf(thr0[q], wmin - two_eps_q[256 + q]);
+        } else {
+            thr[q] = wmin - (two_eps_q ? 0.5f * two_eps_q[q] : eps);
+            if (thr0) thr0[q] = wmin - two_eps_q[256 + q];
+        }
     }
 }
 
@@ -682,6 +702,27 @@ __global__ __launch_bounds__(kAnchorWaves * kWave) void anchor_thr_kernel(const 
                                                                           const float* __restrict__ two_eps_q, float* __restrict__ thr,
                                                                           float* __restrict__ thr0 = nullptr, const uint32_t* __restrict__ dead = nullptr) {
     anchor_thr_body<DT, NITER, SLOTS, kMetricDot>(bucket_key, nbuckets, B, k, rows_, dpad, qn, eps, two_eps_q, thr, thr0, dead);
+}
+
+// reanchor_thr_kernel: the second anchoring of the sample cascade, one workgroup per query.  The first sample (A0)
+// left its bucket keys — rows numbered from row slot bucket_row0 — and anchor_thr_kernel sound thresholds; the filter program has
+// since listed every row of the tiles 0, d + 1, 2 (d + 1), ... that those thresholds admit (hits, hit_cnt).  The k best approximate
+// keys of (that list U the bucket keys), dead rows dropped first, name k distinct live rows (A0's tiles are none of A1's); L is their
+// smallest canonical score and thr, thr0 follow by anchor_thr_kernel's formulas.  The old threshold and the new one are each a lower
+// bound on the approximate score of every top-k row, so the larger of the two is written: the thresholds only ever tighten, and
+// a query with fewer than k live candidates keeps what it had.  A list that overflowed cap_q lends its first cap_q rows (real rows:
+// sound anchors); finalize sends that query to the exact scan as ever.
+template <int DT, int NITER, int SLOTS>
+__global__ __launch_bounds__(kAnchorWaves * kWave) void reanchor_thr_kernel(const u64* __restrict__ bucket_key, int64_t nbuckets, unsigned bucket_row0,
+                                                                            const u64* __restrict__ hits, const unsigned* __restrict__ hit_cnt, int cap_q, int B,
+                                                                            int k, const void* __restrict__ rows_, int dpad, const float* __restrict__ qn, float eps,
+                                                                            const float* __restrict__ two_eps_q, float* __restrict__ thr,
+                                                                            float* __restrict__ thr0, const uint32_t* __restrict__ dead) {
+    const int q = blockIdx.x;
+    if (q >= B) return;   // (padding queries keep anchor_thr_kernel's +inf)
+    const unsigned cnt = hit_cnt[q * kHitCntStride];
+    anchor_thr_body<DT, NITER, SLOTS, kMetricDot, true>(bucket_key, nbuckets, B, k, rows_, dpad, qn, eps, two_eps_q, thr, thr0, dead, hits + (int64_t)q * cap_q,
+                                                        cnt < (unsigned)cap_q ? cnt : (unsigned)cap_q, bucket_row0);
 }
 
 // anchor_thr_kernel for an l2 index: the anchors' exact scores are 0 - (canonical squared distance), so

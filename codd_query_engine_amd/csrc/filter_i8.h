@@ -182,7 +182,8 @@ __global__ __launch_bounds__(512, 2) void i8_tile_kernel(const uint4* __restrict
                                                          int64_t ntiles_run, int64_t tile_stride, const float* __restrict__ thr,
                                                          u64* __restrict__ bucket_key, u64* __restrict__ hits, unsigned* __restrict__ hit_cnt,
                                                          int cap_q, unsigned* __restrict__ flags, const float* __restrict__ rscale,
-                                                         const float* __restrict__ qscale, const float2* __restrict__ bmeta = nullptr, float eb_scale = 1.0f) {
+                                                         const float* __restrict__ qscale, const float2* __restrict__ bmeta = nullptr, float eb_scale = 1.0f,
+                                                         int skip_d = 0) {
     // FILTER: `thr` holds thr0[q] = L(q) - A(q) and qscale[768 + q] = B(q): the bound is evaluated per 32-row block,
     // eps(q, block) = A(q) + B(q) * e_block with e_block = bmeta[block].y, the block's own quantisation error norm (its scale is
     // bmeta[block].x).  A row of block b is a candidate iff acc * scale_b * qscale_q >= thr0[q] - B(q) e_b, i.e. (in the units
@@ -228,8 +229,16 @@ __global__ __launch_bounds__(512, 2) void i8_tile_kernel(const uint4* __restrict
     // the round-3 additions together pushed the kernel past its 102 scalar registers: hipcc parked the query slices' buffer
     // descriptor in lanes of a vector register and re-read it with four v_readlane in front of EVERY slice DMA (2,300 of them
     // in the unrolled program, 16 per K-step and wave)
-    const int G = (int)gridDim.x;
-    const int first_u = (int)blockIdx.x;
+    // G is the step of every tile cursor below and first_u where they start: the grid and the workgroup's number, or — skip_d = d > 0,
+    // launch B of the sample cascade (search_plan.h: cascade_plan; d divides the grid) — the enumeration of the run-tiles that are NO
+    // multiple of d + 1 (geometry.h: skip_first, skip_step).  Derived once, here: the tile loops keep one cursor and one step (the
+    // static program sits at 106 scalar registers)
+    int G = (int)gridDim.x;
+    int first_u = (int)blockIdx.x;
+    if (skip_d > 0) {
+        first_u = skip_first(first_u, skip_d);
+        G = skip_step(G, skip_d);
+    }
     const int tstride = (int)tile_stride;
     const int my_tiles = (int)ntiles_run > first_u ? ((int)ntiles_run - first_u + G - 1) / G : 0;
     const int T = my_tiles * nsteps;  // K-steps of this workgroup

@@ -33,6 +33,14 @@ constexpr int kTileQ = 256;
 // filter_i8.h: does the resident program apply? (nbq: 32-query blocks of the batch: 8 -> NQB = 16, 4 -> NQB = 8)
 constexpr bool i8_tile_resident(int nsteps, int nbq) { return nsteps <= (nbq == 8 ? 4 : 8); }
 
+// filter_i8.h (the tile programs' cursors) and search_plan.h (cascade_plan): the run-tiles that are NO multiple of d + 1, shared out
+// between `grid` workgroups when d divides the grid.  The m-th such tile is m + 1 + m / d, so workgroup b's tiles b + j grid are
+// skip_first(b, d) + j skip_step(grid, d).  One definition for the kernel and for the plan the CPU tests walk.
+template <typename T>
+constexpr T skip_first(T b, T d) { return b + 1 + b / d; }
+template <typename T>
+constexpr T skip_step(T grid, T d) { return grid + grid / d; }
+
 // list_scan_kernels.h
 constexpr int kIvfNB = 4;  // queries per work item
 // queries per work item: four, as in ivf_scan_shared_kernel; two for 2-byte rows of 4 chunks per lane (four queries' registers would spill)

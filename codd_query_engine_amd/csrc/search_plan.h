@@ -54,6 +54,11 @@ struct FilterKnobs {
     // masked search
     int mask_route = 0;        // "mask_route": 0 = by the routing rule, 1 = always the list route, 2 = always the dense route
     int mask_list_pct = 100;   // "mask_list_pct": the list route's side of the cost comparison, in percent (100 = the derived rule)
+    // the sample cascade (cascade_plan below).  Plain integers in a range like the rows of kKnobTable, but not rows of it:
+    // tests/test_search_plan.py pins that table's length and feeds every row to its host program, so codd_knn_set_option checks these itself
+    int sample_cascade = 1;        // "sample_cascade": 0 = off, 1 = where today's sample has cascade_min_rounds rounds of workgroups, 2 = wherever it applies
+    int cascade_d = 16;            // "cascade_d": the stage that fixes the thresholds scans every (d + 1)-th tile; d is the divisor of the grid in [16, 64] nearest this
+    int cascade_min_rounds = 3;    // "cascade_min_rounds": the size rule of sample_cascade = 1 (3 rounds: from ~5M rows of 768 elements on 256 compute units)
 };
 
 // the options that are "an integer in [lo, hi], stored into one knob"; `message` is the whole fail() format of a value outside
@@ -207,6 +212,79 @@ inline FilterProgram filter_program(const FilterKnobs& kn, const IndexShape& s, 
         p.res = 1;
     }
     return p;
+}
+
+// ---- the sample cascade ------------------------------------------------------------------------------------
+// A pass of the static int8 tile program fixes its thresholds in two steps instead of one, so that the tiles the thresholds come
+// from are scanned ONCE, by the filter program, and not a second time by the main launch:
+//   A0   the sample program over a0_tiles tiles a0_first + u a0_stride: one round of workgroups; anchor_thr_kernel turns its keys
+//        into sound provisional thresholds
+//   A1   the filter program over tiles 0, d + 1, 2 (d + 1), ... with those thresholds: candidates straight into the hit lists;
+//        reanchor_thr_kernel then tightens the thresholds on (A1's candidates U A0's keys)
+//   B    the filter program over every OTHER tile, G workgroups: workgroup u owns tiles cascade_b_first(u) + j b_step — the
+//        (u + j G)-th tile that is no multiple of d + 1, which is u + j G + 1 + (u + j G) / d = first(u) + j (G + G / d) when d divides G
+// No A0 tile is a multiple of d + 1: a0_first = 1 and a0_stride is a multiple of the smallest prime factor of d + 1, so every A0
+// tile is 1 modulo that factor.  (A0's rows and A1's must differ: the re-anchor takes k DISTINCT rows from their union.)
+struct CascadePlan {
+    bool on = false;
+    int d = 0;        // A1 scans every (d + 1)-th tile
+    int G = 0;        // workgroups of launch B (d divides G)
+    int64_t a0_tiles = 0, a0_stride = 0, a0_first = 0;
+    int64_t a1_tiles = 0;   // ceil(ntiles / (d + 1)) run-tiles of stride d + 1
+    int64_t b_step = 0;     // G + G / d
+};
+constexpr int kCascadeDMin = 16, kCascadeDMax = 64;   // the useful range: A1 is 1/17 .. 1/65 of the rows
+inline bool cascade_d_admissible(int G, int d) { return d >= kCascadeDMin && d <= kCascadeDMax && G > 0 && G % d == 0; }
+// the admissible d nearest `want` (the smaller of two equally near); 0: the grid has no divisor in the range
+inline int cascade_pick_d(int G, int want) {
+    int best = 0;
+    for (int d = kCascadeDMin; d <= kCascadeDMax; ++d) {
+        if (!cascade_d_admissible(G, d)) continue;
+        const int dist = d > want ? d - want : want - d, best_dist = best > want ? best - want : want - best;
+        if (best == 0 || dist < best_dist) best = d;
+    }
+    return best;
+}
+inline int smallest_prime_factor(int v) {
+    for (int p = 2; p * p <= v; ++p)
+        if (v % p == 0) return p;
+    return v;
+}
+// launch B's enumeration, as the tile programs derive it from (blockIdx, gridDim, d): first tile, and how many
+inline int64_t cascade_b_first(const CascadePlan& c, int64_t u) { return skip_first<int64_t>(u, c.d); }
+inline int64_t cascade_b_my_tiles(const CascadePlan& c, int64_t u, int64_t ntiles) {
+    const int64_t first = cascade_b_first(c, u);
+    return ntiles > first ? (ntiles - first + c.b_step - 1) / c.b_step : 0;
+}
+// the geometry for a given admissible d (no applicability test)
+// a0_cap: the most tiles A0 may take (the sample's key buffer holds "sample_tiles" tiles per query; never more than one round)
+inline CascadePlan cascade_geometry(int G, int d, int64_t ntiles, int64_t a0_cap) {
+    CascadePlan c;
+    c.d = d;
+    c.G = G;
+    c.b_step = skip_step<int64_t>(G, d);
+    c.a1_tiles = (ntiles + d) / (d + 1);
+    const int64_t g = smallest_prime_factor(d + 1);
+    const int64_t most = ntiles < 2 ? 0 : (ntiles - 2) / g + 1;   // tiles 1, 1 + g, ... below ntiles (a single tile is A1's: no A0, no cascade)
+    c.a0_first = 1;
+    if (a0_cap > G) a0_cap = G;
+    c.a0_tiles = most < a0_cap ? most : a0_cap;
+    c.a0_stride = c.a0_tiles > 1 ? (ntiles - 2) / (c.a0_tiles - 1) / g * g : g;
+    return c;
+}
+// ts_today: what sample_tile_count() gives this pass.  Applies to the static int8 tile program (prog.ts == 3) on a grid with an
+// admissible d, where A0 holds 2k tiles (the condition filter_applies() puts on today's sample); "sample_cascade" = 1 adds the size
+// rule (profiles/cascade/README.md: below it two more launches cost more than the second scan of the sample).
+inline CascadePlan cascade_plan(const FilterKnobs& kn, const IndexShape& s, const FilterProgram& prog, int64_t ntiles, int k, int64_t ts_today) {
+    CascadePlan off;
+    if (kn.sample_cascade == 0 || prog.family != FilterProgram::TILE || prog.ts != 3 || prog.res || prog.sqd || !metric_is_cosine(s)) return off;
+    const int d = cascade_pick_d(s.num_cus, kn.cascade_d);
+    if (d == 0 || ntiles < 2) return off;
+    CascadePlan c = cascade_geometry(s.num_cus, d, ntiles, kn.sample_tiles);   // (A0 obeys "sample_tiles" as the plain sample does: bucket_max is sized by it)
+    if (c.a0_tiles < 2 * (int64_t)k) return off;
+    if (kn.sample_cascade == 1 && ts_today < (int64_t)kn.cascade_min_rounds * s.num_cus) return off;
+    c.on = true;
+    return c;
 }
 
 inline bool filter_applies(const FilterKnobs& kn, const IndexShape& s, int B, int k) {

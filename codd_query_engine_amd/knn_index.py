@@ -471,7 +471,7 @@ class DeviceKnnIndex:
         bmeta = np.zeros((max(nblocks, 1), 2), dtype=np.float32)
         native.check(call(self._h, self._stream(), None, None, None, None, None, ptr(keys), per_q, ptr(buckets), buckets.size, ptr(bmeta) if nblocks else None, nblocks),
                      "codd_knn_debug_last_pass")
-        out = {name: getattr(info, name) for name, _ in native.LastPassInfo._fields_ if name not in ("flags", "reserved_", "family")}
+        out = {name: getattr(info, name) for name, _ in native.LastPassInfo._fields_ if name not in ("flags", "family")}
         out["family"] = native.FILTER_FAMILIES[info.family]
         out["flags"] = list(info.flags)
         out.update(thr=thr[:256].copy(), thr0=thr[256:].copy(), qmeta=qmeta if info.el else None, hit_counts=counts, fb_list=fb_list,

@@ -91,7 +91,7 @@ class LastPassInfo(ctypes.Structure):
         [(name, ctypes.c_int32) for name in ("family", "nbq", "ts", "res", "el", "sqd", "nq", "k", "hit_cap", "per_block_filter", "per_block_finalize")]
         + [("eps", ctypes.c_float)]
         + [(name, ctypes.c_int64) for name in ("n", "sample_tiles", "sample_stride")]
-        + [("flags", ctypes.c_uint32 * 4), ("fb_count", ctypes.c_uint32), ("reserved_", ctypes.c_uint32)]
+        + [("flags", ctypes.c_uint32 * 4), ("fb_count", ctypes.c_uint32), ("cascade_d", ctypes.c_uint32)]
     )
 
 

@@ -479,6 +479,14 @@ int codd_knn_embed_texts_host(codd_knn_embedder* e, const uint8_t* host_bytes, c
  *            the int8 filter's thresholds come from a sample of 1/28 of the row tiles) and
  *            "sample_rounds8" (2: ... of at least that many tiles per compute unit for batches of
  *            more than 32 queries, up to a quarter of the corpus; performance only),
+ *            "sample_cascade" (1: a pass of the static int8 tile program — 65..256 queries, rows of 768 int8 elements — whose sample
+ *            would take "cascade_min_rounds" (3) rounds of workgroups fixes its thresholds in two steps, a one-round sample and then
+ *            the filter program itself over every ("cascade_d" (16) + 1)-th tile, whose candidates are kept and whose tiles the main
+ *            launch skips: those tiles are not scanned a second time; 2: wherever that applies, whatever the size; 0: never.  Same ids
+ *            and distance bits either way), "cascade_d" (16, in [16,64]: d of that pass is the divisor of the number of
+ *            compute units in [16,64] nearest this value; no such divisor: no cascade), "cascade_min_rounds" (3, in [1,64]: the size
+ *            rule of "sample_cascade" = 1; both are measured settings, profiles/cascade/README.md; the first sample takes at most
+ *            "sample_tiles" tiles like the plain one),
  *            "resident_q" (1: rows of <= 512 int8 elements keep the query block in LDS for the
  *            whole launch), "i8v2" (2: batches of 65..256 queries on rows of 384 or
  *            more elements take the second-generation int8 kernel, csrc/filter_i8.h; 1: only rows of
@@ -520,7 +528,8 @@ int codd_knn_embed_texts_host(codd_knn_embedder* e, const uint8_t* host_bytes, c
  *            documents' bytes plus one separator each), "doc_tile_bytes" (arena bytes per workgroup step of doc_match_kernel),
  *            "doc_matches" (codd_knn_match_documents calls that launched), "doc_regex_matches" (codd_knn_match_documents_dfa calls that
  *            launched), "doc_regex_tile_bytes" (arena bytes per segment of doc_regex_kernel), "doc_regex_run_docs" (documents per
- *            workgroup of it), "filter_passes",
+ *            workgroup of it), "filter_passes", "cascade_passes" (the filter passes among them that took the sample cascade), "last_cascade_d"
+ *            (the d of the last filter pass's cascade, 0: it took none),
  *            "fallback_queries", "filter_hits", "filter_survivors", "capacity_rows",
  *            "device_bytes", "num_cus", "workspaces" (stream workspaces in use), "shadow8_builds", "shadow8_passes", "i8v2_passes",
  *            "shadow16_builds" (the 2-byte (fp16) shadow is built lazily, by the first search that needs it), "all_normalized",
@@ -556,6 +565,7 @@ int codd_knn_debug_live_allocations(int64_t* buffers, int64_t* bytes, int64_t* e
  *   keys        [256][keys_per_query]  the first min(counter, hit_cap, keys_per_query) candidate keys of each query (approximate
  *                       score in the high word, 0xFFFFFFFF - local row in the low one); the rest is untouched
  *   bucket_max  [256][info->sample_tiles]  the sample pass's best key per (query, sampled tile); bucket_max_cap: u64 the buffer holds
+ *                       (a cascade pass: its first sample's; info->cascade_d)
  *   bmeta       [min(bmeta_blocks, ceil(n / 32))][2]  int8 passes only: {scale, error norm} of the index's 32-row blocks as they are now
  */
 typedef struct codd_knn_last_pass {
@@ -570,7 +580,8 @@ typedef struct codd_knn_last_pass {
     int64_t sample_tiles, sample_stride;
     uint32_t flags[4];          /* FLAG_* words of the control block: [0] a workgroup hit list filled up, [1] a query was queued */
     uint32_t fb_count;
-    uint32_t reserved_;
+    uint32_t cascade_d;         /* the pass took the sample cascade with this d; then sample_tiles, sample_stride are those of
+                                   its first sample, whose first tile is tile 1 and whose keys count rows from row 256.  0: it did not */
 } codd_knn_last_pass;
 int codd_knn_debug_last_pass(codd_knn_index* index, void* stream, codd_knn_last_pass* info, float* thr, float* qmeta,
                              uint32_t* hit_counts, uint32_t* fb_list, uint64_t* keys, int64_t keys_per_query,

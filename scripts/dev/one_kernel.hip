@@ -19,4 +19,4 @@
 #define ONEK_F16 false
 #endif
 template __global__ void codd::i8_tile_kernel<ONEK_MODE, ONEK_S3, ONEK_NQB, ONEK_RES, ONEK_F16>(const uint4*, const uint4*, int64_t, int, int64_t, int64_t, const float*, codd::u64*,
-                                                                                      codd::u64*, unsigned*, int, unsigned*, const float*, const float*, const float2*, float);
+                                                                                      codd::u64*, unsigned*, int, unsigned*, const float*, const float*, const float2*, float, int);
