@@ -15,7 +15,7 @@
 //                        IVF and masked searches between them
 //
 // The other headers (exact_score.h, wave_topk.h, row_traits.h, filter_gemm.h, filter_i8.h, doc_match.h, doc_regex.h, text_embed.h,
-// device_mem.h) are interfaces in namespace codd and come first.  Two of them take no HIP: geometry.h (the sizes kernels and host
+// where_eval.h, device_mem.h) are interfaces in namespace codd and come first.  Two of them take no HIP: geometry.h (the sizes kernels and host
 // share) and search_plan.h, where the ROUTE of a search is decided — plan_search, filter_program, mask_takes_dense and their helpers,
 // pure functions of (FilterKnobs, IndexShape, batch).  search_impl and filter_pass launch what those name and decide nothing.
 //
@@ -47,6 +47,7 @@
 #include "search_plan.h"
 #include "text_embed.h"
 #include "wave_topk.h"
+#include "where_eval.h"
 
 using namespace codd;
 
@@ -238,6 +239,17 @@ struct codd_knn_index : WorkBufs {
     int64_t doc_count = -1, doc_epoch = -1;
     int64_t stat_doc_matches = 0;
     int64_t stat_doc_regex_matches = 0;   // codd_knn_match_documents_dfa calls that launched
+
+    // metadata columns (optional, derived data): per column a tag and a cell for every row slot, kept like scope_of —
+    // allocated by the first codd_knn_set_column_host that names the column, [capacity], zero = absent, regrown by grow_rows, moved by
+    // codd_knn_compact, dropped by codd_knn_load_rows
+    struct WhereColumn {
+        DevBuf<uint8_t> tags;
+        DevBuf<uint64_t> cells;
+    };
+    WhereColumn columns[CODD_KNN_MAX_COLUMNS];
+    int64_t where_max_blocks = 0;      // "where_max_blocks" option: workgroups of where_eval_kernel at most (0 = eight per compute unit)
+    int64_t stat_where_evals = 0;
 
     // tombstones: one bit per row slot, set = deleted.  Null until the first codd_knn_delete_host — the kernels
     // take a null pointer as "nothing was ever deleted" and load nothing.  The host keeps a mirror: the write paths refuse dead
@@ -442,6 +454,20 @@ int grow_rows(codd_knn_index* ix, int64_t need, bool exact) {
     if (ix->dead_bits) {  // ... and so do the tombstone bits, once they exist
         const int rc = grow_dead_bits(ix, cap);
         if (rc != 0) return rc;
+    }
+    for (auto& col : ix->columns) {  // ... and the metadata columns that exist: new slots read absent
+        if (!col.tags || col.tags.cap() >= cap) continue;
+        DevBuf<uint8_t> tags;
+        DevBuf<uint64_t> cells;
+        e = tags.reset(cap);
+        if (e == hipSuccess) e = cells.reset(cap);
+        if (e == hipSuccess) e = hipMemset(tags, 0, (size_t)cap);
+        if (e == hipSuccess) e = hipMemset(cells, 0, (size_t)cap * sizeof(uint64_t));
+        if (e == hipSuccess) e = hipMemcpy(tags, col.tags, (size_t)col.tags.bytes(), hipMemcpyDeviceToDevice);
+        if (e == hipSuccess) e = hipMemcpy(cells, col.cells, (size_t)col.cells.bytes(), hipMemcpyDeviceToDevice);
+        if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? CODD_KNN_ENOMEM : CODD_KNN_EDEVICE, "growing a metadata column failed: %s", hipGetErrorString(e));
+        col.tags = std::move(tags);
+        col.cells = std::move(cells);
     }
     ix->rows = std::move(fresh);
     ix->capacity = cap;
@@ -1611,6 +1637,10 @@ int codd_knn_load_rows(codd_knn_index* ix, int64_t first_slot, const void* host_
     if (range_has_dead(ix, first_slot, first_slot + n)) return fail(CODD_KNN_EINVAL, "load_rows into a deleted row slot (it stays dead until codd_knn_compact)%s");
     DeviceGuard guard(ix->device);
     HIP_TRY(hipDeviceSynchronize());
+    for (auto& col : ix->columns) {  // the metadata columns described other rows: the caller builds them again (derived data)
+        (void)col.tags.reset();
+        (void)col.cells.reset();
+    }
     int rc = grow_rows(ix, first_slot + n, /*exact=*/false);
     if (rc != 0) return rc;
     const size_t row_bytes = (size_t)ix->dpad * elem_size(ix->dtype);
@@ -2603,6 +2633,15 @@ int codd_knn_compact(codd_knn_index* ix, int64_t* new_count) {
     const int64_t nwords = (n + 31) / 32, nblocks = (nwords + 255) / 256;
     DevBuf<unsigned> sums;   // [nwords] per-word prefix, [nblocks] block totals, [nblocks + 1] block bases
     HIP_TRY(sums.reset(nwords + 2 * nblocks + 1));
+    // the metadata columns move out of place, into zero-filled copies allocated before any row moves (nothing has changed if HBM is short)
+    codd_knn_index::WhereColumn moved_columns[CODD_KNN_MAX_COLUMNS];
+    for (int c = 0; c < CODD_KNN_MAX_COLUMNS; ++c) {
+        if (!ix->columns[c].tags) continue;
+        HIP_TRY(moved_columns[c].tags.reset(ix->capacity));
+        HIP_TRY(moved_columns[c].cells.reset(ix->capacity));
+        HIP_TRY(hipMemsetAsync(moved_columns[c].tags, 0, (size_t)ix->capacity, nullptr));
+        HIP_TRY(hipMemsetAsync(moved_columns[c].cells, 0, (size_t)ix->capacity * sizeof(uint64_t), nullptr));
+    }
     unsigned* prefix = sums;
     unsigned* block_total = prefix + nwords;
     unsigned* block_base = block_total + nblocks;
@@ -2626,6 +2665,21 @@ int codd_knn_compact(codd_knn_index* ix, int64_t* new_count) {
             e = hipMemcpyAsync(ix->scope_of + dbase, bounce_scope, (size_t)moved * sizeof(uint32_t), hipMemcpyDeviceToDevice, nullptr);
         dbase += moved;
     }
+    // the columns by the same mapping, while the tombstone bits still stand: slots below the first dead one stay, the rest go to their ranks
+    for (int c = 0; c < CODD_KNN_MAX_COLUMNS && e == hipSuccess; ++c) {
+        codd_knn_index::WhereColumn& from = ix->columns[c];
+        codd_knn_index::WhereColumn& to = moved_columns[c];
+        if (!from.tags) continue;
+        if (first > 0) {
+            e = hipMemcpyAsync(to.tags, from.tags, (size_t)first, hipMemcpyDeviceToDevice, nullptr);
+            if (e == hipSuccess) e = hipMemcpyAsync(to.cells, from.cells, (size_t)first * sizeof(uint64_t), hipMemcpyDeviceToDevice, nullptr);
+        }
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(column_compact_kernel, dim3((unsigned)((n - first + 255) / 256)), dim3(256), 0, nullptr, ix->dead_bits, n, prefix, block_base,
+                               first, from.tags, from.cells, to.tags, to.cells);
+            e = hipGetLastError();
+        }
+    }
     // the slots past the live rows are new slots again: no label, no tombstone; the int8 shadow's scales there read "no such row"
     // ... and zero rows: a later write past the new count that does not regrow the store brings them back below the count
     if (e == hipSuccess) e = hipMemsetAsync(ix->rows + (size_t)live * row_bytes, 0, (size_t)(n - live) * row_bytes, nullptr);
@@ -2642,6 +2696,8 @@ int codd_knn_compact(codd_knn_index* ix, int64_t* new_count) {
     // then on (destroy it and rebuild the collection), as the header says.  Nothing short of a device error gets here.
     if (e != hipSuccess) return fail(CODD_KNN_EDEVICE, "compaction failed, the index is unusable: %s", hipGetErrorString(e));
     if (dbase != live) return fail(CODD_KNN_EDEVICE, "compaction: the host's row mapping disagrees with its dead count%s");
+    for (int c = 0; c < CODD_KNN_MAX_COLUMNS; ++c)
+        if (ix->columns[c].tags) ix->columns[c] = std::move(moved_columns[c]);
     std::fill(ix->dead_host.begin(), ix->dead_host.end(), 0u);
     ix->count = live;
     ix->dead_count = 0;
@@ -2664,6 +2720,117 @@ int codd_knn_compact(codd_knn_index* ix, int64_t* new_count) {
     ix->scope_gen++;
     ix->stat_compactions++;
     if (new_count) *new_count = live;
+    return CODD_KNN_OK;
+}
+
+int codd_knn_set_column_host(codd_knn_index* ix, int column, const int64_t* host_slots, const uint8_t* host_tags, const uint64_t* host_cells, int64_t n) {
+    if (!ix || n < 0 || (n > 0 && (!host_tags || !host_cells))) return fail(CODD_KNN_EINVAL, "bad set_column arguments%s");
+    if (column < 0 || column >= CODD_KNN_MAX_COLUMNS) return fail(CODD_KNN_EINVAL, "set_column: column outside [0, CODD_KNN_MAX_COLUMNS)%s");
+    if (ix->capacity <= 0 || ix->count <= 0) return fail(CODD_KNN_EINVAL, "set_column: the index holds no row slot%s");
+    if (!host_slots && n > ix->count) return fail(CODD_KNN_EINVAL, "set_column: a full upload holds at most count rows%s");
+    bool increasing = true;
+    for (int64_t i = 0; i < n; ++i) {
+        if (host_tags[i] > CODD_KNN_WHERE_TAG_STR) return fail(CODD_KNN_EINVAL, "set_column: a tag is none of absent, bool, number, str%s");
+        if (!host_slots) continue;
+        if (host_slots[i] < 0 || host_slots[i] >= ix->count) return fail(CODD_KNN_EINVAL, "set_column: row slot outside [0, count)%s");
+        if (slot_dead(ix, host_slots[i])) return fail(CODD_KNN_EINVAL, "set_column: deleted row slot (it stays dead until codd_knn_compact)%s");
+        if (i > 0 && host_slots[i] <= host_slots[i - 1]) increasing = false;
+    }
+    // a slot listed more than once keeps its LAST value (the device writes in no order): the triples are made distinct here
+    std::vector<int64_t> slots;
+    std::vector<uint8_t> tags;
+    std::vector<uint64_t> cells;
+    if (host_slots && !increasing) {
+        try {
+            std::vector<int64_t> order((size_t)n);
+            for (int64_t i = 0; i < n; ++i) order[(size_t)i] = i;
+            std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return host_slots[a] < host_slots[b]; });
+            for (int64_t i = 0; i < n; ++i) {
+                const int64_t at = order[(size_t)i];
+                if (i + 1 < n && host_slots[at] == host_slots[order[(size_t)i + 1]]) continue;
+                slots.push_back(host_slots[at]);
+                tags.push_back(host_tags[at]);
+                cells.push_back(host_cells[at]);
+            }
+        } catch (const std::bad_alloc&) {
+            return fail(CODD_KNN_ENOMEM, "host allocation failed%s");
+        }
+        host_slots = slots.data(); host_tags = tags.data(); host_cells = cells.data();
+        n = (int64_t)slots.size();
+    }
+    DeviceGuard guard(ix->device);
+    HIP_TRY(hipDeviceSynchronize());
+    codd_knn_index::WhereColumn& col = ix->columns[column];
+    if (!col.tags) {   // as long as the row store, absent everywhere; on failure the column stays unset
+        DevBuf<uint8_t> fresh_tags;
+        DevBuf<uint64_t> fresh_cells;
+        HIP_TRY(fresh_tags.reset(ix->capacity));
+        HIP_TRY(fresh_cells.reset(ix->capacity));
+        HIP_TRY(hipMemset(fresh_tags, 0, (size_t)ix->capacity));
+        HIP_TRY(hipMemset(fresh_cells, 0, (size_t)ix->capacity * sizeof(uint64_t)));
+        col.tags = std::move(fresh_tags);
+        col.cells = std::move(fresh_cells);
+    }
+    if (n == 0) return CODD_KNN_OK;
+    if (!host_slots) {
+        HIP_TRY(hipMemcpy(col.tags, host_tags, (size_t)n, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(col.cells, host_cells, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice));
+        return CODD_KNN_OK;
+    }
+    DevBuf<int64_t> dev_slots;
+    DevBuf<uint8_t> dev_tags;
+    DevBuf<uint64_t> dev_cells;
+    HIP_TRY(dev_slots.reset(n));
+    HIP_TRY(dev_tags.reset(n));
+    HIP_TRY(dev_cells.reset(n));
+    HIP_TRY(hipMemcpy(dev_slots, host_slots, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dev_tags, host_tags, (size_t)n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dev_cells, host_cells, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(column_set_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, dev_slots, dev_tags, dev_cells, n, col.tags, col.cells);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());  // (the staging buffers go out of scope, and the call is synchronous by contract)
+    return CODD_KNN_OK;
+}
+
+int codd_knn_drop_columns(codd_knn_index* ix) {
+    if (!ix) return fail(CODD_KNN_EINVAL, "null index%s");
+    DeviceGuard guard(ix->device);
+    HIP_TRY(hipDeviceSynchronize());
+    for (auto& col : ix->columns) {
+        (void)col.tags.reset();
+        (void)col.cells.reset();
+    }
+    return CODD_KNN_OK;
+}
+
+int codd_knn_eval_where(codd_knn_index* ix, const codd_knn_where_program* prog, uint32_t* dev_out_bits, int64_t nwords, void* stream) {
+    if (!ix) return fail(CODD_KNN_EINVAL, "eval_where: null index%s");
+    // the program is checked here, index by index, before anything is enqueued: on the device nothing leads outside it
+    if (const char* why = where_program_error(prog)) return fail(CODD_KNN_EINVAL, why);
+    DeviceGuard guard(ix->device);
+    hipStream_t st = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lock(ix->mu);   // (no workspace: the kernel reads the columns and writes the caller's words)
+    WhereArgs args;
+    memset(&args, 0, sizeof(args));
+    args.prog = *prog;
+    for (int i = 0; i < prog->nleaves; ++i) {
+        const int c = prog->leaves[i].column;
+        if (!ix->columns[c].tags || ix->columns[c].tags.cap() < ix->count) return fail(CODD_KNN_EINVAL, "eval_where: a leaf names a column that has not been set%s");
+        args.tags[c] = ix->columns[c].tags;
+        args.cells[c] = ix->columns[c].cells;
+    }
+    const int64_t n = ix->count;
+    if (nwords != (n + 31) / 32) return fail(CODD_KNN_EINVAL, "eval_where: nwords must be ceil(count / 32)%s");
+    if (nwords == 0) return CODD_KNN_OK;
+    if (!dev_out_bits) return fail(CODD_KNN_EINVAL, "eval_where: null bits%s");
+    int rc;
+    if ((rc = wait_rows(ix, st)) != 0) return rc;
+    const int64_t steps = (n + kWhereBlockRows - 1) / kWhereBlockRows;
+    const int64_t most = ix->where_max_blocks > 0 ? ix->where_max_blocks : (int64_t)ix->num_cus * 8;   // (grid-stride beyond that)
+    rc = launch_kernel<where_eval_kernel>(dim3((unsigned)(steps < most ? steps : most)), dim3(kWhereThreads), 0, st, args, ix->dead_bits, n, nwords, dev_out_bits);
+    if (rc != 0) return rc;
+    HIP_TRY(hipGetLastError());
+    ix->stat_where_evals++;
     return CODD_KNN_OK;
 }
 
@@ -2778,6 +2945,11 @@ int codd_knn_set_option(codd_knn_index* ix, const char* key, int64_t value) {
         ix->all_normalized = false;
         return CODD_KNN_OK;
     }
+    if (strcmp(key, "where_max_blocks") == 0) {
+        if (value < 0 || value > (1ll << 20)) return fail(CODD_KNN_EINVAL, "where_max_blocks must be in [0,2^20]%s");
+        ix->where_max_blocks = value;
+        return CODD_KNN_OK;
+    }
     if (strcmp(key, "compact_chunk_rows") == 0) {
         if (value < 0 || value > (1ll << 32)) return fail(CODD_KNN_EINVAL, "compact_chunk_rows must be in [0,2^32]%s");
         ix->compact_chunk_rows = value;
@@ -2852,6 +3024,7 @@ int codd_knn_get_stat(const codd_knn_index* ix, const char* key, int64_t* out) {
         {"masked_dev_searches", &codd_knn_index::stat_masked_dev},
         {"doc_matches", &codd_knn_index::stat_doc_matches},
         {"doc_regex_matches", &codd_knn_index::stat_doc_regex_matches},
+        {"where_evals", &codd_knn_index::stat_where_evals},
         {"dead_rows", &codd_knn_index::dead_count},
         {"delete_calls", &codd_knn_index::stat_delete_calls},
         {"compactions", &codd_knn_index::stat_compactions},
@@ -2878,6 +3051,14 @@ int codd_knn_get_stat(const codd_knn_index* ix, const char* key, int64_t* out) {
     else if (strcmp(key, "doc_tile_bytes") == 0) *out = kDocTile;
     else if (strcmp(key, "doc_regex_tile_bytes") == 0) *out = kRegexTile;
     else if (strcmp(key, "doc_regex_run_docs") == 0) *out = kRegexDocs;
+    else if (strcmp(key, "where_columns") == 0) {
+        *out = 0;
+        for (const auto& col : ix->columns) *out += col.tags ? 1 : 0;
+    }
+    else if (strcmp(key, "where_column_bytes") == 0) {
+        *out = 0;
+        for (const auto& col : ix->columns) *out += col.tags.bytes() + col.cells.bytes();
+    }
     else if (strcmp(key, "all_normalized") == 0) *out = ix->all_normalized ? 1 : 0;
     else if (strcmp(key, "metric") == 0) *out = ix->metric;
     else if (strcmp(key, "space_filter") == 0) *out = ix->knobs.space_filter;

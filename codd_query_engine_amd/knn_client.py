@@ -51,7 +51,7 @@ from typing import Any, Callable, Optional, Sequence
 
 import numpy as np
 
-from . import regex_dfa
+from . import regex_dfa, where_columns
 from .embedding import EmbeddingFunction, HashingEmbeddingFunction
 
 _DEFAULT_SPACE = "cosine"
@@ -77,6 +77,7 @@ def _factory_spaces(engine_factory) -> tuple:
 _SPACE_FILTER_KEY = "codd:space_filter"
 _SPACE_IVF_KEY = "codd:space_ivf"
 _DOCUMENT_REGEX_KEY = "codd:document_regex"   # collection metadata: 1 = where_document knows $regex / $not_regex
+_DEVICE_WHERE_KEY = "codd:device_where"       # collection metadata: 1 = general `where` filters are evaluated on the engine's device
 
 
 def _space_of(metadata: Optional[dict]) -> str:
@@ -99,9 +100,10 @@ class Collection:
     DEVICE_EMBED_MIN_TEXTS = 2
 
     def __init__(self, name: str, metadata: Optional[dict], embedding_function: EmbeddingFunction,
-                 engine_factory: Callable[[int], Any], document_regex: bool = False):
+                 engine_factory: Callable[[int], Any], document_regex: bool = False, device_where: bool = False):
         self.name = name
         self._client_document_regex = bool(document_regex)   # KnnClient(document_regex=True): the opt-in without the metadata key
+        self._client_device_where = bool(device_where)       # KnnClient(device_where=True): likewise
         self.metadata = dict(metadata or {})
         self._embed = embedding_function
         self._engine_factory = engine_factory
@@ -125,6 +127,10 @@ class Collection:
         self._docs_on_device = False
         self._docs_fit_device: Optional[bool] = None   # no document holds NUL (None: not looked yet; one pass per change)
         self._docs_ascii: Optional[bool] = None        # every document is ASCII (found by the same pass)
+        # `where` on the device (opt-in): the metadata columns built so far — numpy mirrors of the engine's, kept in step
+        # by every write, dropped by a load — and the filters' bitmaps (packed words on the GPU) by canonical filter, dropped by writes
+        self._columns = where_columns.ColumnSet()
+        self._where_bits_cache: dict[str, Any] = {}
 
     # ------------------------------------------------------------------ helpers
     @property
@@ -318,6 +324,7 @@ class Collection:
         return mask
 
     def _forget_where_index(self) -> None:
+        self._where_bits_cache.clear()   # (the columns themselves survive writes: upsert and compact maintain them)
         self._key_index.clear()
         self._mask_cache.clear()
         self._doc_mask_cache.clear()
@@ -325,6 +332,66 @@ class Collection:
         self._docs_on_device = False
         self._docs_fit_device = None
         self._docs_ascii = None
+
+    # ------------------------------------------------------------------ general where -> row bitmap on the device (opt-in)
+    @property
+    def device_where(self) -> bool:
+        """Whether a general `where` is evaluated on the engine's device here: the collection's metadata says so
+        ("codd:device_where": 1), or its client does."""
+        return self._client_device_where or bool(self.metadata.get(_DEVICE_WHERE_KEY))
+
+    def _has_device_where(self) -> bool:
+        return self.device_where and all(hasattr(self._engine, m) for m in ("eval_where", "set_column", "search_masked_dev"))
+
+    def _drop_columns(self) -> None:
+        if len(self._columns) and self._engine is not None and hasattr(self._engine, "drop_columns"):
+            self._engine.drop_columns()
+        self._columns.clear()
+
+    def _where_bits(self, where):
+        """The checked filter as packed words on the engine's device — the live row slots that satisfy it, match_documents' form —
+        from the 32-entry cache or evaluated now by the engine's predicate kernel over the metadata columns; a key's column is built
+        by the first filter that names it (one pass over the records, one upload).  None: this filter runs on the host (a
+        host_only column, a literal without a key, a program beyond the limits; where_columns.compile_where)."""
+        canon = json.dumps(where, sort_keys=True, ensure_ascii=False)
+        bits = self._where_bits_cache.get(canon)
+        if bits is not None:
+            return bits
+        for key in where_columns.filter_keys(where):
+            col = self._columns.get(key)
+            if col is None:
+                col = self._columns.build(key, self._metadatas)
+                if not col.host_only:
+                    try:
+                        self._engine.set_column(col.index, None, col.tags, col.cells)
+                    except Exception:
+                        self._drop_columns()
+                        raise
+            if col.host_only:
+                return None
+        program = where_columns.compile_where(where, self._columns.by_key)
+        if program is None:
+            return None
+        bits = self._engine.eval_where(program)
+        if len(self._where_bits_cache) >= self._MASK_CACHE_SIZE:
+            self._where_bits_cache.pop(next(iter(self._where_bits_cache)))
+        self._where_bits_cache[canon] = bits
+        return bits
+
+    def _write_columns(self, slots: np.ndarray, metadatas: Optional[Sequence[Optional[dict]]]) -> None:
+        """After an upsert that the engine and the host lists have taken: every column built so far learns the written slots'
+        cells — a replaced metadata dict that lacks the key writes "absent"; metadatas=None writes nothing (an existing record
+        keeps its metadata, a fresh slot is absent on both sides already).  The engine first, then the mirror."""
+        self._columns.resize(len(self._ids))
+        if metadatas is None or not len(self._columns):
+            return
+        try:
+            for col, tags, cells in self._columns.encode_slots(metadatas):
+                self._engine.set_column(col.index, slots, tags, cells)
+                self._columns.wrote(col, slots, tags, cells)
+        except Exception:
+            self._drop_columns()   # (derived data: the next device-routed filter builds what it needs again)
+            raise
 
     # ------------------------------------------------------------------ where_document -> row mask
     _WHERE_DOCUMENT_GRAMMAR = ('{"$contains": "text"}, {"$not_contains": "text"}, {"$and": [filters]}, {"$or": [filters]}; '
@@ -577,6 +644,7 @@ class Collection:
             scopes = np.array([self._scope_for(md) for md in metadatas], dtype=np.uint32)
             if scopes.any() or len(fresh) < n:  # (a new slot starts with scope 0; a rewritten one may have to lose its label)
                 engine.set_scopes(slots, scopes)
+        self._write_columns(slots, metadatas)   # (nothing to do unless a device-routed `where` has built columns)
 
     def delete(self, ids: Optional[Sequence[str]] = None, where=None) -> None:
         """chromadb Collection.delete: forget records by id and / or by namespace.
@@ -626,6 +694,7 @@ class Collection:
         self._metadatas = [self._metadatas[s] for s in keep]
         self._slot_of = {doc_id: i for i, doc_id in enumerate(self._ids)}
         self._forget_where_index()
+        self._columns.compacted(keep)   # (the engine has moved its copy of the columns with the rows)
         return new_count
 
     def add(self, ids: Sequence[str], embeddings=None, metadatas=None, documents=None) -> None:
@@ -694,7 +763,15 @@ class Collection:
         document) finds something, Python's semantics; a record without a document fails $regex and passes $not_regex.  On the
         device path a pattern inside the device subset runs as a byte DFA (match_documents_dfa), plain text as a needle, and
         anything else (back-references, look-around, \\b, flags, Unicode classes on non-ASCII documents) is evaluated here by re
-        and uploaded as a mask.  Without the opt-in the two operators are unknown operators, as before."""
+        and uploaded as a mask.  Without the opt-in the two operators are unknown operators, as before.
+
+        On a collection that opted in — metadata "codd:device_where": 1, or KnnClient(device_where=True) — and an engine with
+        eval_where, set_column and search_masked_dev, a general `where` is evaluated on the device: the metadata
+        of each key a filter names lives there as a column (built by the first such filter, kept up to date by upsert and
+        compact, dropped by a load), the filter runs as a predicate program (eval_where), its bitmap is cached (32 entries, until
+        the next write), is ANDed with the document bitmap there, and search_masked_dev answers.  The same ids and distances.  A
+        filter the device cannot take — a value or literal that is NaN or an int float64 does not hold, more than 32 leaves, 256
+        literals or 32 keys — runs on the host as before."""
         if (query_texts is None) == (query_embeddings is None):
             raise ValueError("give exactly one of query_texts / query_embeddings")
         if where_document is not None:
@@ -806,6 +883,11 @@ class Collection:
             if w is not None and not self._is_namespace_form(w):
                 groups.setdefault(json.dumps(w, sort_keys=True, ensure_ascii=False), []).append(b)
         for members in groups.values():
+            # opted in: the filter's bitmap is made, and stays, on the device; search_masked_dev counts it there
+            bits = self._where_bits(per_query[members[0]]) if self._has_device_where() else None
+            if bits is not None:
+                dist[members], rows[members] = self._engine.search_masked_dev(self._rows_of(q, members), bits, k)
+                continue
             mask = self._where_mask(per_query[members[0]])
             if mask.any():
                 dist[members], rows[members] = self._engine.search_masked(self._rows_of(q, members), mask, k)
@@ -834,6 +916,11 @@ class Collection:
         on_device = self._has_device_documents() and self._documents_fit_device()
         for members in groups.values():
             w = per_query[members[0]]
+            where_bits = self._where_bits(w) if w is not None and on_device and self._has_device_where() else None
+            if where_bits is not None:   # (opted in, DESIGN.md §26: both bitmaps are on the device already, nothing is uploaded)
+                bits = self._where_document_bits(where_document) & where_bits
+                dist[members], rows[members] = self._engine.search_masked_dev(self._rows_of(q, members), bits, k)
+                continue
             by_where = None if w is None else self._where_mask(w)
             if by_where is not None and not by_where.any():
                 continue
@@ -931,6 +1018,7 @@ class Collection:
         self._engine = engine
         if old is not None and hasattr(old, "close"):
             old.close()
+        self._columns.clear()   # (derived data of the rows that were: the new engine holds no column, nothing of them is on disk)
         self.metadata = dict(manifest.get("metadata") or {})
         self._ids, self._metadatas, self._documents = ids, metadatas, documents
         self._slot_of = {doc_id: i for i, doc_id in enumerate(ids)}
@@ -954,12 +1042,17 @@ class KnnClient:
         engine_factory: test seam, see module docstring.
         document_regex: every collection of this client answers `where_document` {"$regex": ...} / {"$not_regex": ...} (DESIGN.md
             §24); without it only a collection whose metadata carries "codd:document_regex": 1 does.
+        device_where: every collection of this client evaluates a general `where` on the engine's device (metadata
+            columns and a predicate kernel; the same answers); without it only a collection whose metadata carries
+            "codd:device_where": 1 does.
     """
 
     def __init__(self, device: str = "cuda:0", dtype: str = "f32", embedding_function: Optional[EmbeddingFunction] = None,
-                 engine_factory: Optional[Callable[[int], Any]] = None, path: Optional[str] = None, document_regex: bool = False):
+                 engine_factory: Optional[Callable[[int], Any]] = None, path: Optional[str] = None, document_regex: bool = False,
+                 device_where: bool = False):
         self.device = device
         self.document_regex = bool(document_regex)
+        self.device_where = bool(device_where)
         self.dtype = dtype
         self.path = path
         self._embed = embedding_function or HashingEmbeddingFunction()
@@ -971,7 +1064,7 @@ class KnnClient:
                 cdir = os.path.join(path, entry)
                 gen = Collection._current_generation(cdir) if os.path.isdir(cdir) else None
                 if gen:
-                    col = Collection(entry, None, self._embed, self._engine_factory, self.document_regex)
+                    col = Collection(entry, None, self._embed, self._engine_factory, self.document_regex, self.device_where)
                     col._load_generation(cdir, gen)
                     self._collections[col.name] = col
 
@@ -1006,7 +1099,7 @@ class KnnClient:
                 continue
             col = self._collections.get(entry)
             if col is None:
-                col = Collection(entry, None, self._embed, self._engine_factory, self.document_regex)
+                col = Collection(entry, None, self._embed, self._engine_factory, self.document_regex, self.device_where)
                 self._collections[entry] = col
             if int(gen.split("-")[1]) > col._generation:
                 col._load_generation(cdir, gen)
@@ -1027,7 +1120,7 @@ class KnnClient:
         space = _space_of(metadata)
         if space not in _factory_spaces(self._engine_factory):
             raise ValueError(f"hnsw:space={space!r} is not on this path (supported: {_factory_spaces(self._engine_factory)})")
-        col = Collection(name, metadata, embedding_function or self._embed, self._engine_factory, self.document_regex)
+        col = Collection(name, metadata, embedding_function or self._embed, self._engine_factory, self.document_regex, self.device_where)
         self._collections[name] = col
         return col
 

@@ -38,7 +38,8 @@ class DeviceKnnIndex:
     Engine protocol consumed by knn_client.Collection:
         count() / upsert(slots, vecs) / search(queries, k) -> (dist, rows) as numpy;
         optionally set_scopes / search_scoped (`where=` by namespace), search_masked (any other `where=`), set_documents /
-        match_documents / match_documents_dfa / search_masked_dev (`where_document=` on the device) and delete / live_count / compact (`Collection.delete`).
+        match_documents / match_documents_dfa / search_masked_dev (`where_document=` on the device), set_column / drop_columns /
+        eval_where (`where=` on the device, opt-in: DESIGN.md §26) and delete / live_count / compact (`Collection.delete`).
     The ivf_search_*masked* methods are the same masks under an installed IVF layout (ivf.py), slice_mask cuts a shard's words
     out of a mask over global rows (sharded.py).
     """
@@ -333,6 +334,39 @@ class DeviceKnnIndex:
                                                    int(dfa.accept), bits.data_ptr() if nwords else None, nwords, self._stream()),
             "codd_knn_match_documents_dfa",
         )
+        return bits
+
+    # ------------------------------------------------------------------ metadata columns (where= on the device)
+    def set_column(self, column: int, slots, tags, cells) -> None:
+        """Tag (uint8: 0 absent, 1 bool, 2 number, 3 str) and cell (uint64) of the given row slots of metadata column `column`
+        (< native.MAX_COLUMNS); slots None: the rows 0 .. len(tags) - 1, a full upload.  The column lives beside the rows: it grows
+        with them, compact() moves it, load_rows drops it (where_columns.py encodes the cells)."""
+        tags = np.ascontiguousarray(tags, dtype=np.uint8)
+        cells = np.ascontiguousarray(cells, dtype=np.uint64)
+        if tags.ndim != 1 or cells.shape != tags.shape:
+            raise ValueError(f"expected tags [n] and cells [n], got {tags.shape} / {cells.shape}")
+        if slots is not None:
+            slots = np.ascontiguousarray(slots, dtype=np.int64)
+            if slots.shape != tags.shape:
+                raise ValueError(f"expected slots [n] like the tags, got {slots.shape} / {tags.shape}")
+        native.check(self._lib.codd_knn_set_column_host(self._h, int(column), None if slots is None else slots.ctypes.data, tags.ctypes.data,
+                                                        cells.ctypes.data, tags.shape[0]), "codd_knn_set_column_host")
+
+    def drop_columns(self) -> None:
+        """Forget every metadata column."""
+        native.check(self._lib.codd_knn_drop_columns(self._h), "codd_knn_drop_columns")
+
+    def eval_where(self, program):
+        """The live row slots a predicate program accepts (where_columns.compile_where's, or anything native.where_program takes):
+        packed words in match_documents' form, an int32 CUDA tensor of ceil(count() / 32) words — what search_masked_dev,
+        ivf_search_masked_dev_tensors, slice_mask and ShardedSearcher.search(allow=) take.  The engine checks the program on the
+        host before it launches anything; a malformed one is EINVAL.  Asynchronous on the current stream."""
+        torch = _torch()
+        prog = native.where_program(program)
+        nwords = (self.count() + 31) // 32
+        bits = torch.empty((nwords,), dtype=torch.int32, device=self.device)
+        native.check(self._lib.codd_knn_eval_where(self._h, ctypes.byref(prog), bits.data_ptr() if nwords else None, nwords, self._stream()),
+                     "codd_knn_eval_where")
         return bits
 
     def _allow_words_tensor(self, allow_bits):

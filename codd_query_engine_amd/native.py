@@ -74,6 +74,9 @@ ABI = [
     ("codd_knn_embedder_create", ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int, ctypes.c_float]),
     ("codd_knn_embedder_destroy", ctypes.c_int, [ctypes.c_void_p]),
     ("codd_knn_embed_texts_host", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
+    ("codd_knn_set_column_host", ctypes.c_int, [_c_idx, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]),
+    ("codd_knn_drop_columns", ctypes.c_int, [_c_idx]),
+    ("codd_knn_eval_where", ctypes.c_int, [_c_idx, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
     ("codd_knn_delete_host", ctypes.c_int, [_c_idx, ctypes.c_void_p, ctypes.c_int64]),
     ("codd_knn_live_count", ctypes.c_int, [_c_idx, _i64p]),
     ("codd_knn_compact", ctypes.c_int, [_c_idx, _i64p]),
@@ -96,6 +99,51 @@ class LastPassInfo(ctypes.Structure):
 
 
 FILTER_FAMILIES = ("GEMM", "TILE", "TILE_F16")
+
+# codd_knn_eval_where: the limits of include/codd_knn.h; where_columns.py states the same numbers without ctypes
+MAX_COLUMNS = 32          # CODD_KNN_MAX_COLUMNS
+WHERE_MAX_LEAVES = 32     # CODD_KNN_WHERE_MAX_LEAVES
+WHERE_MAX_LITERALS = 256  # CODD_KNN_WHERE_MAX_LITERALS
+WHERE_MAX_OPS = 64        # CODD_KNN_WHERE_MAX_OPS
+
+
+class WhereLeaf(ctypes.Structure):
+    """codd_knn_where_leaf of include/codd_knn.h"""
+
+    _fields_ = [(name, ctypes.c_uint8) for name in ("column", "tag", "kind", "negate")] + [("lit_first", ctypes.c_uint16), ("lit_count", ctypes.c_uint16)]
+
+
+class WhereProgram(ctypes.Structure):
+    """codd_knn_where_program of include/codd_knn.h"""
+
+    _fields_ = [(name, ctypes.c_int32) for name in ("nleaves", "nliterals", "nops", "reserved")] + [
+        ("leaves", WhereLeaf * WHERE_MAX_LEAVES), ("ops", ctypes.c_uint8 * WHERE_MAX_OPS), ("literals", ctypes.c_uint64 * WHERE_MAX_LITERALS)]
+
+
+def where_program(program) -> WhereProgram:
+    """The C form of a program: anything with `leaves` ((column, tag, kind, negate, lit_first, lit_count) each), `literals` (uint64
+    values) and `ops` (bytes), as where_columns.compile_where returns it.  ValueError for what the struct cannot hold — more entries
+    than its arrays have, a field outside its integer type; everything else is the library's own host check (EINVAL)."""
+    leaves, literals, ops = list(program.leaves), list(program.literals), list(program.ops)
+    if len(leaves) > WHERE_MAX_LEAVES or len(literals) > WHERE_MAX_LITERALS or len(ops) > WHERE_MAX_OPS:
+        raise ValueError(f"a where program holds at most {WHERE_MAX_LEAVES} leaves, {WHERE_MAX_LITERALS} literals and {WHERE_MAX_OPS} operators, "
+                         f"got {len(leaves)} / {len(literals)} / {len(ops)}")
+    out = WhereProgram()
+    out.nleaves, out.nliterals, out.nops = len(leaves), len(literals), len(ops)
+    for i, leaf in enumerate(leaves):
+        fields = [int(v) for v in leaf]
+        if len(fields) != 6 or any(not 0 <= v <= 0xFF for v in fields[:4]) or any(not 0 <= v <= 0xFFFF for v in fields[4:]):
+            raise ValueError(f"leaf {i} is not (column, tag, kind, negate, lit_first, lit_count) in range: {leaf!r}")
+        out.leaves[i] = WhereLeaf(*fields)
+    for i, lit in enumerate(literals):
+        if not 0 <= int(lit) < 1 << 64:
+            raise ValueError(f"literal {i} is no uint64: {lit!r}")
+        out.literals[i] = int(lit)
+    for i, op in enumerate(ops):
+        if not 0 <= int(op) <= 0xFF:
+            raise ValueError(f"operator {i} is no byte: {op!r}")
+        out.ops[i] = int(op)
+    return out
 
 
 class NativeLibraryError(RuntimeError):

@@ -21,12 +21,12 @@
  *   - `stream` is a hipStream_t passed as void* (NULL = the null stream).  Calls
  *     are asynchronous with respect to the host unless stated otherwise.
  *   - thread-safety: the search entry points (codd_knn_search, _search_keys, _search_scoped,
- *     _search_masked, _search_masked_dev, _match_documents, _match_documents_dfa, _ivf_search, _ivf_search_masked, _ivf_search_masked_dev, _approx_scores) may be called from several host threads and on
+ *     _search_masked, _search_masked_dev, _match_documents, _match_documents_dfa, _eval_where, _ivf_search, _ivf_search_masked, _ivf_search_masked_dev, _approx_scores) may be called from several host threads and on
  *     several streams of one index: the index keeps one workspace per stream (up to
  *     4; a fifth stream takes over the least recently used one, ordered behind its
  *     previous owner on the device) and serialises only the enqueueing.  Searches on
  *     different streams then overlap on the GPU.  upsert/reserve/load/ivf_install/set_scopes/
- *     delete/compact/set_documents are exclusive: no other call on the index may be in flight.
+ *     delete/compact/set_documents/set_column/drop_columns are exclusive: no other call on the index may be in flight.
  *   - rows are stored L2-normalised, zero padded to a multiple of 64 elements.  Normalisation
  *     (rows and queries alike) holds for every finite non-zero fp32 vector, whatever its scale:
  *     where the fp32 sum of squares leaves [2^-100, 2^100] the vector is first scaled by an exact
@@ -458,6 +458,72 @@ int codd_knn_embed_texts_host(codd_knn_embedder* e, const uint8_t* host_bytes, c
                               void* stream);
 
 /*
+ * Replaces: the general `where` of collection.query once more — this time the filter itself runs on the device.
+ *           Strings still stay on the host: what crosses this boundary is, per metadata key, a COLUMN — for every row slot a tag
+ *           (CODD_KNN_WHERE_TAG_*: absent, bool, number, str) and a 64-bit cell — and, per filter, a PROGRAM over the columns; the
+ *           answer is a row bitmap on the device, in the form codd_knn_match_documents produces, that codd_knn_search_masked_dev,
+ *           codd_knn_ivf_search_masked_dev and codd_knn_slice_mask take.  A C caller has a metadata filter without building bitmaps.
+ *           Cells: bool 0 / 1; number the order-preserving key of the float64 x: the bits of x + 0.0 (so that -0.0 and +0.0 agree),
+ *           all of them flipped for a negative x, else the sign bit alone — unsigned comparison of keys is numeric comparison, and
+ *           the device performs no floating-point operation; str a code of the caller's own dictionary.  An absent cell is ignored.
+ * set_column_host: writes tag and cell of n row slots of column `column` (< CODD_KNN_MAX_COLUMNS).  host_slots == NULL: the rows
+ *           0 .. n-1, a full upload (n <= count).  Otherwise each slot must lie in [0, count) and be live, else EINVAL and nothing
+ *           changes; a slot listed more than once keeps the last value.  A tag above CODD_KNN_WHERE_TAG_STR: EINVAL.  A column's
+ *           storage follows the scope labels': allocated by the first call that names it, as long as the row store and zero (absent)
+ *           wherever nothing was written; it grows with the row store, codd_knn_compact moves it with the rows by the same stable
+ *           mapping (the vacated slots read absent again), codd_knn_load_rows drops every column, and a slot keeps its cell when its
+ *           vector is overwritten.  Derived data: never persisted.  Exclusive like upsert, synchronous.  An index without a row slot:
+ *           EINVAL.
+ * drop_columns: frees every column.  Exclusive, synchronous.
+ * eval_where: sets bit (r & 31) of dev_out_bits[r >> 5] iff r < count, row slot r is not a tombstone and the program accepts it;
+ *           every other bit of the nwords == ceil(count / 32) words (else EINVAL) is zero.  The program: leaf i passes for a row iff
+ *           the row's tag in column leaves[i].column equals leaves[i].tag AND, kind CODD_KNN_WHERE_IN, the cell equals one of
+ *           literals[lit_first .. lit_first + lit_count) (no literal: nothing passes), or, kinds _LT _LE _GT _GE, the cell compares so,
+ *           unsigned, with the one literal; with `negate` the leaf passes iff that fails — an absent cell then passes, ChromaDB's $ne
+ *           and $nin.  ops[0 .. nops) is a postfix expression: a value below CODD_KNN_WHERE_AND pushes that leaf's result,
+ *           CODD_KNN_WHERE_AND and _OR replace the two top entries by their conjunction / disjunction; the one value left is the row's
+ *           verdict.  (p pushes need p - 1 operators: a well-formed program has an odd nops, 63 at the most.)
+ *           THE PROGRAM IS VALIDATED ON THE HOST before anything is enqueued; a failed check is EINVAL with a message, no launch and
+ *           no change: nleaves in [1, CODD_KNN_WHERE_MAX_LEAVES], nliterals in [0, CODD_KNN_WHERE_MAX_LITERALS], nops in
+ *           [1, CODD_KNN_WHERE_MAX_OPS]; every leaf's column below CODD_KNN_MAX_COLUMNS and SET on this index, its tag one of bool /
+ *           number / str, its kind known, negate 0 or 1, its literal range inside the literals; a comparison leaf on class number with
+ *           exactly one literal; every pushed leaf below nleaves; the expression never underflows, needs at most 32 stack entries and
+ *           leaves exactly one value.  `prog` is host memory, consumed before the call returns: it travels to the device as a kernel
+ *           argument.  Asynchronous on `stream`, ordered against upserts like a search, nothing read back: one launch of
+ *           where_eval_kernel (csrc/where_eval.h), a stream of 9 bytes per row and distinct column that writes every output word
+ *           once — no memset, no atomics.  May be called from several host threads and streams, like a search.
+ */
+#define CODD_KNN_MAX_COLUMNS 32            /* columns per index */
+#define CODD_KNN_WHERE_MAX_LEAVES 32
+#define CODD_KNN_WHERE_MAX_LITERALS 256
+#define CODD_KNN_WHERE_MAX_OPS 64
+#define CODD_KNN_WHERE_TAG_ABSENT 0
+#define CODD_KNN_WHERE_TAG_BOOL 1
+#define CODD_KNN_WHERE_TAG_NUMBER 2
+#define CODD_KNN_WHERE_TAG_STR 3
+#define CODD_KNN_WHERE_IN 0
+#define CODD_KNN_WHERE_LT 1
+#define CODD_KNN_WHERE_LE 2
+#define CODD_KNN_WHERE_GT 3
+#define CODD_KNN_WHERE_GE 4
+#define CODD_KNN_WHERE_AND 0xFE            /* postfix operators; a value below these pushes that leaf */
+#define CODD_KNN_WHERE_OR 0xFF
+typedef struct codd_knn_where_leaf {
+    uint8_t column, tag, kind, negate;
+    uint16_t lit_first, lit_count;
+} codd_knn_where_leaf;
+typedef struct codd_knn_where_program {
+    int32_t nleaves, nliterals, nops, reserved;
+    codd_knn_where_leaf leaves[CODD_KNN_WHERE_MAX_LEAVES];
+    uint8_t ops[CODD_KNN_WHERE_MAX_OPS];
+    uint64_t literals[CODD_KNN_WHERE_MAX_LITERALS];
+} codd_knn_where_program;
+int codd_knn_set_column_host(codd_knn_index* index, int column, const int64_t* host_slots, const uint8_t* host_tags, const uint64_t* host_cells,
+                             int64_t n);
+int codd_knn_drop_columns(codd_knn_index* index);
+int codd_knn_eval_where(codd_knn_index* index, const codd_knn_where_program* prog, uint32_t* dev_out_bits, int64_t nwords, void* stream);
+
+/*
  * Tuning / introspection (never needed for correctness).
  *   options: "scan_blocks_per_cu" (4; 1..8: workgroups per compute unit of the exact scan, at most); "filter" (0/1: MFMA filter path for large batches);
  *            "filter_min_batch" (9), "filter_min_rows" (1: batches >= filter_min_batch always
@@ -505,6 +571,8 @@ int codd_knn_embed_texts_host(codd_knn_embedder* e, const uint8_t* host_bytes, c
  *            "mask_route" (0: codd_knn_search_masked chooses its route by the rule of DESIGN.md §15; 1: always the list route; 2: always the
  *            dense route), "mask_list_pct" (100: the weight of the dense side in that rule's cost comparison, in percent — above 100 more
  *            searches take the list route, 0 none that the rule decides by cost),
+ *            "where_max_blocks" (0: codd_knn_eval_where launches as many workgroups as the rows need, at most eight per compute unit; N: at
+ *            most N — tests: the answer never depends on it),
  *            "space_filter" (0; 1: an ip or l2 index filters batches of "filter_min_batch" queries and more over "filter_min_rows" rows
  *            and more through the int8 MFMA filter with measured norms in its bound, then re-scores exactly — same ids and distance
  *            bits as the scan; needs "filter" and "shadow8" on, l2 rows of at most 4 chunks per lane; no effect on a cosine index;
@@ -528,7 +596,8 @@ int codd_knn_embed_texts_host(codd_knn_embedder* e, const uint8_t* host_bytes, c
  *            documents' bytes plus one separator each), "doc_tile_bytes" (arena bytes per workgroup step of doc_match_kernel),
  *            "doc_matches" (codd_knn_match_documents calls that launched), "doc_regex_matches" (codd_knn_match_documents_dfa calls that
  *            launched), "doc_regex_tile_bytes" (arena bytes per segment of doc_regex_kernel), "doc_regex_run_docs" (documents per
- *            workgroup of it), "filter_passes", "cascade_passes" (the filter passes among them that took the sample cascade), "last_cascade_d"
+ *            workgroup of it), "where_evals" (codd_knn_eval_where calls that launched), "where_columns" (columns set), "where_column_bytes"
+ *            (their device bytes: 9 per row slot of the capacity and column), "filter_passes", "cascade_passes" (the filter passes among them that took the sample cascade), "last_cascade_d"
  *            (the d of the last filter pass's cascade, 0: it took none),
  *            "fallback_queries", "filter_hits", "filter_survivors", "capacity_rows",
  *            "device_bytes", "num_cus", "workspaces" (stream workspaces in use), "shadow8_builds", "shadow8_passes", "i8v2_passes",
