@@ -9,14 +9,15 @@
 //   scan_kernels.h       the exact scan of the whole row store (dot product and squared L2), finalize + fallback, the key merges
 //   shadow8_kernels.h    the int8 shadow, the int8 filter leg's query preparation and bounds, small_batch_kernel
 //   list_scan_kernels.h  scans of row lists and what builds the lists: IVF, scopes, tombstones and compaction, masks
+//   ivf_follow_kernels.h an IVF layout that follows writes: the pending bitmap, the delta scan, the fold's kernels
 //   (here)               host side: the index object (its option knobs and filter watch are search_plan.h's), its workspaces and guards
 //   dispatch.h           with_* (run-time value -> template argument), Lds, launch_kernel, launch_by_metric
 //   (here)               the exact pass, the filter pass, search_impl, scopes, then the extern "C" entry points with the bodies of the
 //                        IVF and masked searches between them
 //
 // The other headers (exact_score.h, wave_topk.h, row_traits.h, filter_gemm.h, filter_i8.h, doc_match.h, doc_regex.h, text_embed.h,
-// where_eval.h, device_mem.h) are interfaces in namespace codd and come first.  Two of them take no HIP: geometry.h (the sizes kernels and host
-// share) and search_plan.h, where the ROUTE of a search is decided — plan_search, filter_program, mask_takes_dense and their helpers,
+// where_eval.h, device_mem.h) are interfaces in namespace codd and come first.  Three of them take no HIP: geometry.h (the sizes kernels and host
+// share), ivf_follow.h (the pending-row bookkeeping of a layout that follows writes) and search_plan.h, where the ROUTE of a search is decided — plan_search, filter_program, mask_takes_dense and their helpers,
 // pure functions of (FilterKnobs, IndexShape, batch).  search_impl and filter_pass launch what those name and decide nothing.
 //
 // HBM-bound byte streaming throughout: the corpus is read once per pass, each row by exactly one
@@ -43,6 +44,7 @@
 #include "exact_score.h"
 #include "filter_gemm.h"
 #include "filter_i8.h"
+#include "ivf_follow.h"
 #include "row_traits.h"
 #include "search_plan.h"
 #include "text_embed.h"
@@ -55,6 +57,7 @@ using namespace codd;
 #include "scan_kernels.h"
 #include "shadow8_kernels.h"
 #include "list_scan_kernels.h"
+#include "ivf_follow_kernels.h"
 
 // =============================================================================================
 // host side: the index object and the C ABI
@@ -108,6 +111,7 @@ struct WorkBufs {
     DevBuf<u64> probe_keys;       // IVF: [B][nprobe] coarse keys
     DevBuf<u64> ivf_partial;
     DevBuf<unsigned> ivf_group;   // IVF at batch: [nlist] counters, [nlist+1] pair starts, [nlist+1] item starts, [B*nprobe] pairs by list
+    DevBuf<uint32_t> ivf_deny;    // IVF with rows pending: [ceil(count / 32)] the call's deny bits | the pending bits
     DevBuf<unsigned> scope_group; // scoped search: [B] queries in (scope, query) order, [B] their ranks inside the scope
     // masked search: the call's allow bits, and what the two routes derive from them
     PinnedBuf<uint32_t> mask_host;  // pinned staging of the allow words; mask_uploaded: its last copy to the device
@@ -213,6 +217,22 @@ struct codd_knn_index : WorkBufs {
     int64_t ivf_count = 0;             // rows covered by the IVF layout (must equal count to be fresh)
     int ivf_nlist = 0;
     int64_t ivf_epoch = -1, epoch = 0;  // epoch bumps on every row write; search requires ivf_epoch == epoch
+    // ... a layout that follows writes ("ivf_follow", off by default): a write through upsert_host, upsert_device or
+    // load_rows marks its slots pending and keeps ivf_epoch at the epoch; the searches scan the lists under deny | pending and the
+    // pending rows from the row store; a fold (codd_knn_ivf_refresh, or the write that crosses "ivf_fold_rows") rebuilds the layout
+    int ivf_follow = 0;
+    int64_t ivf_fold_rows = 0;         // "ivf_fold_rows": fold when more rows than this are pending (0 = one mean list)
+    PendingRows pend;                  // host mirror of pend_bits and the number of distinct pending slots (ivf_follow.h)
+    DevBuf<uint32_t> pend_bits;        // [ceil(capacity / 32)] device words, null until the first pending row
+    DevBuf<uint32_t> pend_list;        // [>= pend.count] the distinct pending slots, in the order they became pending
+    PinnedBuf<uint32_t> pend_stage;    // staging of the slots a write appends to pend_list; pend_staged: its last copy to the device
+    Event pend_staged; bool pend_stage_pending = false;
+    DevBuf<uint32_t> list_of;          // [>= count] the list of every row slot, built from ivf_ids / ivf_offsets by the first fold after an install
+    bool list_of_valid = false;
+    DevBuf<float> fold_q;              // the fold: [<= CODD_KNN_MAX_BATCH][dim] stored rows widened to fp32 (the coarse index's queries)
+    DevBuf<unsigned> fold_cnt;         // ... [nlist] rows per list, then the scatter's fill counters
+    DevBuf<int64_t> fold_perm;         // ... [count] slots by list position (gather_rows_kernel's permutation)
+    int64_t stat_ivf_refreshes = 0, stat_ivf_delta = 0;   // folds; searches that ran a delta scan
 
     // scopes (optional): a label per row slot and, derived from it like the shadows, the row slots grouped by label
     DevBuf<uint32_t> scope_of;         // [capacity], 0 = no label; allocated by the first call that needs it
@@ -427,6 +447,7 @@ struct WorkScope {
 };
 
 int grow_dead_bits(codd_knn_index* ix, int64_t slots);
+int grow_pend_bits(codd_knn_index* ix, int64_t slots);
 
 // (re)allocate row storage for at least `need` slots, preserving contents (the shadows are derived data with their own
 // allocations: ensure_shadow / ensure_shadow8)
@@ -453,6 +474,10 @@ int grow_rows(codd_knn_index* ix, int64_t need, bool exact) {
     }
     if (ix->dead_bits) {  // ... and so do the tombstone bits, once they exist
         const int rc = grow_dead_bits(ix, cap);
+        if (rc != 0) return rc;
+    }
+    if (ix->pend_bits) {  // ... and the pending bits of an IVF layout that follows writes
+        const int rc = grow_pend_bits(ix, cap);
         if (rc != 0) return rc;
     }
     for (auto& col : ix->columns) {  // ... and the metadata columns that exist: new slots read absent
@@ -489,6 +514,21 @@ int grow_dead_bits(codd_knn_index* ix, int64_t slots) {
     if (e == hipSuccess && ix->dead_bits) e = hipMemcpy(fresh, ix->dead_bits, (size_t)ix->dead_bits.bytes(), hipMemcpyDeviceToDevice);
     if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? CODD_KNN_ENOMEM : CODD_KNN_EDEVICE, "growing the tombstone bits failed: %s", hipGetErrorString(e));
     ix->dead_bits = std::move(fresh);
+    return CODD_KNN_OK;
+}
+
+// the pending bits cover `slots` row slots (device words only: the mirror grows where it is marked; contents kept, new words zero).
+// Exclusive callers with the device drained only (grow_rows); the device is idle again when it returns.
+int grow_pend_bits(codd_knn_index* ix, int64_t slots) {
+    const int64_t words = (slots + 31) / 32;
+    if (words <= ix->pend_bits.cap()) return CODD_KNN_OK;
+    DevBuf<uint32_t> fresh;
+    hipError_t e = fresh.reset(words);
+    if (e == hipSuccess) e = hipMemset(fresh, 0, (size_t)words * sizeof(uint32_t));
+    if (e == hipSuccess && ix->pend_bits) e = hipMemcpy(fresh, ix->pend_bits, (size_t)ix->pend_bits.bytes(), hipMemcpyDeviceToDevice);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? CODD_KNN_ENOMEM : CODD_KNN_EDEVICE, "growing the pending bits failed: %s", hipGetErrorString(e));
+    ix->pend_bits = std::move(fresh);
     return CODD_KNN_OK;
 }
 
@@ -1484,6 +1524,175 @@ void drop_ivf(codd_knn_index* ix) {
     (void)codd_knn_destroy(ix->coarse);
     ix->coarse = nullptr;
     ix->ivf_epoch = -1;
+    ix->pend.clear();   // (the device bits are cleared by the install that follows; no search reads them without a layout)
+    ix->list_of_valid = false;
+}
+
+// ---- an IVF layout that follows writes ----------------------------------------
+
+bool ivf_layout_fresh(const codd_knn_index* ix) { return ix->coarse && ix->ivf_epoch == ix->epoch; }
+
+// The slots a write made newly pending (`fresh`, the tail of the host's view of the list: positions [at, at + fresh.size())) go to
+// the device on `st`, the write's stream: appended to pend_list through the pinned staging buffer, their bits set in pend_bits.
+// Exclusive callers (a write); the searching streams are ordered behind `st` by the write itself.
+int pend_mark_device(codd_knn_index* ix, const std::vector<uint32_t>& fresh, int64_t at, hipStream_t st) {
+    const int64_t n = (int64_t)fresh.size();
+    if (n == 0) return CODD_KNN_OK;
+    if (!ix->pend_bits) {
+        const int64_t words = (ix->capacity + 31) / 32;
+        HIP_TRY(ix->pend_bits.reset(words));
+        HIP_TRY(hipMemsetAsync(ix->pend_bits, 0, (size_t)words * sizeof(uint32_t), st));
+    }
+    if (at + n > ix->pend_list.cap()) {  // (growth blocks, as every growth here does: searches in flight may read the old list)
+        DevBuf<uint32_t> grown;
+        HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(grown.reset(pending_list_capacity(ix->pend_list.cap(), at + n)));
+        if (at > 0) HIP_TRY(hipMemcpy(grown, ix->pend_list, (size_t)at * sizeof(uint32_t), hipMemcpyDeviceToDevice));
+        HIP_TRY(hipDeviceSynchronize());
+        ix->pend_list = std::move(grown);
+    }
+    if (ix->pend_stage_pending) HIP_TRY(hipEventSynchronize(ix->pend_staged));   // the staging buffer's previous copy
+    ix->pend_stage_pending = false;
+    if (n > ix->pend_stage.cap()) HIP_TRY(ix->pend_stage.reset(n + n / 2 + 64));
+    HIP_TRY(ix->pend_staged.ensure());
+    memcpy(ix->pend_stage.get(), fresh.data(), (size_t)n * sizeof(uint32_t));
+    HIP_TRY(hipMemcpyAsync(ix->pend_list + at, ix->pend_stage, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(ix->pend_staged, st));
+    ix->pend_stage_pending = true;
+    hipLaunchKernelGGL(pend_set_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ix->pend_list + at, n, ix->pend_bits);
+    HIP_TRY(hipGetLastError());
+    return CODD_KNN_OK;
+}
+
+// The end of every write of row slots through the C ABI: slots_written, and for a layout that follows writes the pending marks —
+// the slots the write names (`slots`, n of them; null: the range [lo, hi)) and the gap below it — on `st`, the stream the rows
+// were written on.  A failure here leaves the rows written and the layout stale.
+int finish_write(codd_knn_index* ix, const int64_t* slots, int64_t n, int64_t lo, int64_t hi, hipStream_t st) {
+    const bool following = ix->ivf_follow && ivf_layout_fresh(ix);
+    const int64_t count_before = ix->count;
+    slots_written(ix, lo, hi);
+    if (!following) return CODD_KNN_OK;
+    const int64_t at = ix->pend.count;
+    std::vector<uint32_t> fresh;
+    int rc;
+    try {
+        mark_written(ix->pend, count_before, slots, n, lo, hi, fresh);
+        rc = pend_mark_device(ix, fresh, at, st);
+    } catch (const std::bad_alloc&) {
+        rc = fail(CODD_KNN_ENOMEM, "host allocation failed%s");
+    }
+    if (rc != 0) return rc;   // (ivf_epoch stays behind: the layout is stale)
+    ix->ivf_epoch = ix->epoch;
+    return CODD_KNN_OK;
+}
+
+// The fold: every pending slot is assigned its list — the top-1 of the coarse index's exact scan with the STORED row, widened to
+// fp32, as the query — and the layout is rebuilt on the device from list_of: count, 64-bit prefix sums, scatter, then
+// gather_rows_kernel from the main row store.  All sizes are known on the host: nothing is read back.  Ordered like an upsert on
+// `st`: behind what the searching streams have enqueued, and later searches on other streams wait for rows_ready.
+int ivf_fold_body(codd_knn_index* ix, hipStream_t st) {
+    const int64_t n = ix->count, m = ix->pend.count;
+    const int nlist = ix->ivf_nlist;
+    const size_t row_bytes = (size_t)ix->dpad * elem_size(ix->dtype);
+    WorkScope work(ix, st), work_coarse(ix->coarse, st);
+    int rc;
+    for (WorkSlot& w : ix->slots) {
+        if (!w.used || w.stream == st) continue;
+        HIP_TRY(w.handover.ensure());
+        if (hipEventRecord(w.handover, w.stream) == hipSuccess) HIP_TRY(hipStreamWaitEvent(st, w.handover, 0));
+        else (void)hipGetLastError();  // (a stream that no longer exists has nothing in flight)
+    }
+    if (ix->rows_event_set && ix->rows_stream != st) HIP_TRY(hipStreamWaitEvent(st, ix->rows_ready, 0));
+    if (ix->reader_event_set && ix->reader_stream != st) HIP_TRY(hipStreamWaitEvent(st, ix->reader_done, 0));
+    // appended rows: the layout's buffers and list_of grow.  (Growth is the one place where the fold blocks: what the searching
+    // streams have enqueued may still read the old allocations.)
+    const bool grows = n * (int64_t)row_bytes > ix->rows_ivf.cap() || n > ix->ivf_ids.cap() || (ix->list_of_valid && n > ix->list_of.cap());
+    if (grows) {
+        if ((rc = wait_searching_streams(ix)) != 0) return rc;
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    const int64_t labels = ix->capacity > n ? ix->capacity : n;
+    if (!ix->list_of_valid) {
+        if (ix->list_of.cap() < n) HIP_TRY(ix->list_of.ensure(labels));
+        HIP_TRY(hipMemsetAsync(ix->list_of, 0, (size_t)ix->list_of.bytes(), st));
+        hipLaunchKernelGGL(list_of_build_kernel, dim3((unsigned)((ix->ivf_count + 255) / 256)), dim3(256), 0, st, ix->ivf_ids, ix->ivf_offsets, nlist,
+                           ix->ivf_count, ix->list_of);
+        HIP_TRY(hipGetLastError());
+        ix->list_of_valid = true;
+    } else if (ix->list_of.cap() < n) {
+        DevBuf<uint32_t> grown;
+        HIP_TRY(grown.reset(labels));
+        HIP_TRY(hipMemsetAsync(grown, 0, (size_t)grown.bytes(), st));
+        HIP_TRY(hipMemcpyAsync(grown, ix->list_of, (size_t)ix->ivf_count * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        ix->list_of = std::move(grown);
+    }
+    // 1. the pending rows' lists, in chunks of at most CODD_KNN_MAX_BATCH queries
+    const int64_t chunk = m < CODD_KNN_MAX_BATCH ? m : CODD_KNN_MAX_BATCH;
+    HIP_TRY(ix->fold_q.ensure(chunk * ix->dim));
+    HIP_TRY(ix->qn.ensure(chunk * ix->dpad));
+    HIP_TRY(ix->keys_tmp.ensure(chunk));
+    for (int64_t c0 = 0; c0 < m; c0 += chunk) {
+        const int nb = (int)(m - c0 < chunk ? m - c0 : chunk);
+        const uint32_t* slots = ix->pend_list + c0;
+        rc = with_dtype(ix->dtype, [&](auto dt) {
+            return launch_kernel<widen_listed_rows_kernel<dt>>(dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, st, ix->rows, slots, (int64_t)nb, ix->dim, ix->dpad,
+                                                               ix->fold_q);
+        });
+        if (rc != 0) return rc;
+        HIP_TRY(hipGetLastError());
+        if ((rc = prep_exact_queries(ix, ix->fold_q, nb, st)) != 0) return rc;
+        if ((rc = exact_scan(ix->coarse, ix->qn, nb, 1, 0u, ix->keys_tmp, nullptr, nullptr, st, ix->coarse->dead_bits)) != 0) return rc;
+        hipLaunchKernelGGL(list_assign_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, ix->keys_tmp, slots, (int64_t)nb, nlist, ix->list_of);
+        HIP_TRY(hipGetLastError());
+    }
+    // 2. the layout from list_of
+    HIP_TRY(ix->fold_cnt.ensure(nlist));
+    HIP_TRY(ix->fold_perm.ensure(n));
+    if (n * (int64_t)row_bytes > ix->rows_ivf.cap()) HIP_TRY(ix->rows_ivf.reset(n * (int64_t)row_bytes));
+    if (n > ix->ivf_ids.cap()) HIP_TRY(ix->ivf_ids.reset(n));
+    HIP_TRY(hipMemsetAsync(ix->fold_cnt, 0, (size_t)nlist * sizeof(unsigned), st));
+    const unsigned rb = (unsigned)((n + 255) / 256);
+    hipLaunchKernelGGL(ivf_list_count_kernel, dim3(rb), dim3(256), 0, st, ix->list_of, n, nlist, ix->fold_cnt);
+    hipLaunchKernelGGL(ivf_list_offsets_kernel, dim3(1), dim3(1024), 0, st, ix->fold_cnt, nlist, ix->ivf_offsets);
+    hipLaunchKernelGGL(ivf_list_scatter_kernel, dim3(rb), dim3(256), 0, st, ix->list_of, n, nlist, ix->ivf_offsets, ix->fold_cnt, ix->fold_perm);
+    hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, reinterpret_cast<const uint4*>(ix->rows.get()), ix->fold_perm, n,
+                       (int)(row_bytes / 16), reinterpret_cast<uint4*>(ix->rows_ivf.get()), ix->ivf_ids);
+    HIP_TRY(hipGetLastError());
+    // 3. nothing is pending
+    HIP_TRY(hipMemsetAsync(ix->pend_bits, 0, (size_t)ix->pend_bits.bytes(), st));
+    ix->pend.clear();
+    ix->ivf_count = n;
+    ix->stat_ivf_refreshes++;
+    HIP_TRY(ix->rows_ready.ensure());
+    HIP_TRY(hipEventRecord(ix->rows_ready, st));
+    ix->rows_stream = st;
+    ix->rows_event_set = true;
+    return CODD_KNN_OK;
+}
+// (a fold that fails half way leaves no layout to search: it is stale, and codd_knn_ivf_install is the remedy)
+int ivf_fold(codd_knn_index* ix, hipStream_t st) {
+    const int rc = ivf_fold_body(ix, st);
+    if (rc != 0) ix->ivf_epoch = -1;
+    return rc;
+}
+
+// what a write does last: fold when more rows are pending than "ivf_fold_rows" allows
+int fold_if_due(codd_knn_index* ix, hipStream_t st) {
+    if (!ix->ivf_follow || !ivf_layout_fresh(ix)) return CODD_KNN_OK;
+    if (!fold_due(ix->pend.count, fold_threshold(ix->ivf_fold_rows, ix->ivf_count, ix->ivf_nlist))) return CODD_KNN_OK;
+    return ivf_fold(ix, st);
+}
+
+// the end of a synchronous write (upsert_host, load_rows: the rows are on the device): finish_write and the fold when it is due on
+// the null stream, complete on return like the rows themselves
+int finish_sync_write(codd_knn_index* ix, const int64_t* slots, int64_t n, int64_t lo, int64_t hi) {
+    const bool following = ix->ivf_follow && ivf_layout_fresh(ix);
+    int rc = finish_write(ix, slots, n, lo, hi, nullptr);
+    if (rc == 0) rc = fold_if_due(ix, nullptr);
+    if (following && hipDeviceSynchronize() != hipSuccess && rc == 0) rc = fail(CODD_KNN_EDEVICE, "marking the written rows pending failed%s");
+    ix->rows_event_set = false;  // (everything is complete on the device)
+    return rc;
 }
 
 }  // namespace
@@ -1587,8 +1796,8 @@ int codd_knn_upsert_host(codd_knn_index* ix, const int64_t* host_slots, const fl
     ix->rows_event_set = false;  // (everything is complete on the device)
     ix->reader_event_set = false;
     if (rc == 0) {
-        slots_written(ix, min_slot, max_slot + 1);
         if (!normalize) ix->all_normalized = false;
+        rc = finish_sync_write(ix, host_slots, n, min_slot, max_slot + 1);
     }
     return rc;
 }
@@ -1620,14 +1829,16 @@ int codd_knn_upsert_device(codd_knn_index* ix, int64_t first_slot, const float* 
     if (ix->reader_event_set && ix->reader_stream != wst) HIP_TRY(hipStreamWaitEvent(wst, ix->reader_done, 0));
     int rc = launch_ingest(ix, dev_vecs, n, normalize, nullptr, first_slot, wst);
     if (rc != 0) return rc;
+    if (!normalize) ix->all_normalized = false;
+    // (a layout that follows writes: the pending marks go onto the writing stream behind the rows, in front of rows_ready)
+    const int mark_rc = finish_write(ix, nullptr, n, first_slot, first_slot + n, wst);
     // ... and searches on other streams wait for this write (wait_rows)
     HIP_TRY(ix->rows_ready.ensure());
     HIP_TRY(hipEventRecord(ix->rows_ready, wst));
     ix->rows_stream = wst;
     ix->rows_event_set = true;
-    slots_written(ix, first_slot, first_slot + n);
-    if (!normalize) ix->all_normalized = false;
-    return CODD_KNN_OK;
+    if (mark_rc != 0) return mark_rc;
+    return fold_if_due(ix, wst);
 }
 
 int codd_knn_load_rows(codd_knn_index* ix, int64_t first_slot, const void* host_rows, int64_t n) {
@@ -1646,9 +1857,7 @@ int codd_knn_load_rows(codd_knn_index* ix, int64_t first_slot, const void* host_
     const size_t row_bytes = (size_t)ix->dpad * elem_size(ix->dtype);
     HIP_TRY(hipMemcpy(ix->rows + (size_t)first_slot * row_bytes, host_rows, (size_t)n * row_bytes, hipMemcpyHostToDevice));
     if (!metric_is_cosine(ix)) {   // (ip, l2: rows of any norm, and no filter to keep on)
-        ix->rows_event_set = false;
-        slots_written(ix, first_slot, first_slot + n);
-        return CODD_KNN_OK;
+        return finish_sync_write(ix, nullptr, n, first_slot, first_slot + n);
     }
     // the loaded rows are taken as they are, so their norms are checked: the filters stay on only for unit rows
     // (tolerance = the storage type's rounding of a unit vector)
@@ -1667,9 +1876,7 @@ int codd_knn_load_rows(codd_knn_index* ix, int64_t first_slot, const void* host_
     if (e != hipSuccess) return fail(CODD_KNN_EDEVICE, "norm check of the loaded rows failed: %s", hipGetErrorString(e));
     const float tol = ix->dtype == DT_F32 ? 1e-4f : (ix->dtype == DT_BF16 ? 4e-3f : 6e-4f);
     if (!(worst <= tol)) ix->all_normalized = false;
-    ix->rows_event_set = false;
-    slots_written(ix, first_slot, first_slot + n);
-    return CODD_KNN_OK;
+    return finish_sync_write(ix, nullptr, n, first_slot, first_slot + n);
 }
 
 int codd_knn_count(const codd_knn_index* ix, int64_t* out) {
@@ -1867,6 +2074,7 @@ int codd_knn_ivf_install(codd_knn_index* ix, const float* dev_centroids, int nli
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(hipDeviceSynchronize());
     drop_ivf(ix);  // a previous layout
+    if (ix->pend_bits) HIP_TRY(hipMemsetAsync(ix->pend_bits, 0, (size_t)ix->pend_bits.bytes(), st));  // ... and what was pending under it
 
     const size_t row_bytes = (size_t)ix->dpad * elem_size(ix->dtype);
     const int64_t n = ix->count;
@@ -1948,7 +2156,9 @@ int ivf_check_args(const codd_knn_index* ix, const float* dev_queries, int B, in
     int rc;
     if ((rc = search_check_args(ix, dev_queries, B, k, row_base)) != 0) return rc;
     if (!ivf_allowed(ix)) return fail(CODD_KNN_ENOTSUP, "IVF search exists for the cosine metric only%s");
-    if (!ix->coarse || ix->ivf_epoch != ix->epoch) return fail(CODD_KNN_EINVAL, "no IVF layout, or rows changed since codd_knn_ivf_install%s");
+    // (a layout that follows writes keeps ivf_epoch at the epoch; rows left pending when "ivf_follow" was switched off make it stale)
+    if (!ivf_layout_fresh(ix) || (ix->pend.count > 0 && !ix->ivf_follow))
+        return fail(CODD_KNN_EINVAL, "no IVF layout, or rows changed since codd_knn_ivf_install%s");
     if (*nprobe < 1) return fail(CODD_KNN_EINVAL, "nprobe must be >= 1%s");
     if (*nprobe > ix->ivf_nlist) *nprobe = ix->ivf_nlist;
     if (*nprobe > CODD_KNN_MAX_K) return fail(CODD_KNN_ENOTSUP, "nprobe above 128 is not supported (probe the whole index with codd_knn_search)%s");
@@ -1968,6 +2178,40 @@ int ivf_search_body(codd_knn_index* ix, const float* dev_queries, int B, int k, 
     const bool sq = ix->metric == CODD_KNN_METRIC_L2;  // the squared-distance list scans (§22); ip runs the dot-product ones on the raw query
     // 1. coarse: the nprobe best lists per query (exact scan of the centroids in the index's space, tiny)
     if ((rc = exact_scan(ix->coarse, ix->qn, B, nprobe, 0u, ix->probe_keys, nullptr, nullptr, st, ix->coarse->dead_bits)) != 0) return rc;
+    // Rows pending (a layout that follows writes): the layout's copy of them is stale, so the list scans run under
+    // deny | pending, and the delta scan scores every pending slot from the row store under the call's own deny.  Its partial keys go
+    // behind the lists' — query b's at [B * m1 + b * m1, ...), m1 the lists' keys per query — and ONE merge reads both runs.
+    // Nothing pending: a host branch, and the launches below are what they always were.
+    const int64_t npend = ix->pend.count;
+    const uint32_t* deny_lists = deny;
+    if (npend > 0) {
+        const int64_t nwords = (ix->count + 31) / 32;
+        HIP_TRY(ix->ivf_deny.ensure(nwords));
+        hipLaunchKernelGGL(pend_or_kernel, dim3((unsigned)((nwords + 255) / 256)), dim3(256), 0, st, deny, ix->pend_bits, nwords, ix->ivf_deny);
+        HIP_TRY(hipGetLastError());
+        deny_lists = ix->ivf_deny;
+        ix->stat_ivf_delta++;
+    }
+    // m1: the lists' partial keys per query, list_parts = m1 / k of them; the caller has made room for 2 * B * m1 keys
+    auto delta_then_merge = [&](int64_t m1, int64_t list_parts) -> int {
+        if (npend == 0) return launch_merge_of(ix, ix->ivf_partial, B, m1, k, (u64*)dev_keys, dev_dist, dev_rows, st);
+        const int dsplit = delta_split(ix->num_cus, B, npend, list_parts);
+        u64* delta = ix->ivf_partial + (int64_t)B * m1;
+        int drc;
+        {
+            EvScope ev(ix, EV_SCAN, st);
+            drc = with_row_form(ix, k, "row too wide for the IVF scan%s", [&](auto dt, auto ni, auto sl) {
+                constexpr int NB = scope_nb(decltype(dt)::value, decltype(ni)::value);
+                return launch_by_metric<ivf_delta_sq<dt, ni, sl>, ivf_delta_kernel<dt, ni, sl>>(kernel_metric(ix->metric), dim3((unsigned)((B + NB - 1) / NB), (unsigned)dsplit),
+                                                                                                dim3(256), 0, st, ix->rows, ix->pend_list, npend, B, dsplit, ix->dpad, ix->qn, k,
+                                                                                                row_base, deny, delta, m1);
+            });
+        }
+        if (drc != 0) return drc;
+        HIP_TRY(hipGetLastError());
+        return launch_merge(ix->ivf_partial, B, m1 + (int64_t)dsplit * k, m1, k, (u64*)dev_keys, dev_dist, dev_rows, st, nullptr, nullptr, nullptr, m1, (int64_t)B * m1,
+                            kernel_metric(ix->metric));
+    };
     const int niter = niter_of(shape_of(ix));
     // 2a. a batch with enough (query, list) pairs to fill the chip without splitting lists: group the pairs by list on the
     //     device and scan every probed list once per kIvfNB of its queries (ivf_scan_shared_kernel)
@@ -1978,7 +2222,7 @@ int ivf_search_body(codd_knn_index* ix, const float* dev_queries, int B, int k, 
         const int nlist = ix->ivf_nlist;
         ix->stat_ivf_shared++;
         HIP_TRY(ix->ivf_group.ensure(3 * (int64_t)nlist + 2 + npairs));
-        HIP_TRY(ix->ivf_partial.ensure(npairs * k));
+        HIP_TRY(ix->ivf_partial.ensure((npend > 0 ? 2 : 1) * npairs * k));
         unsigned* cnt = ix->ivf_group;
         unsigned* pair_start = cnt + nlist;
         unsigned* item_start = pair_start + nlist + 1;
@@ -2000,37 +2244,37 @@ int ivf_search_body(codd_knn_index* ix, const float* dev_queries, int B, int k, 
                     return fail(CODD_KNN_EINVAL, "the shared squared-distance scan takes no 2-byte rows of 4 chunks per lane%s");
                 } else {
                     return launch_kernel<ivf_shared_sq<dt, ni, sl>>(dim3((unsigned)bound), dim3(256), 0, st, ix->rows_ivf, ix->ivf_ids, ix->ivf_offsets, pair_start,
-                                                                    item_start, sorted_pairs, nlist, nprobe, ix->dpad, ix->qn, k, row_base, ix->ivf_partial, deny);
+                                                                    item_start, sorted_pairs, nlist, nprobe, ix->dpad, ix->qn, k, row_base, ix->ivf_partial, deny_lists);
                 }
             }
             return launch_kernel<ivf_scan_shared_kernel<dt, ni, sl>>(dim3((unsigned)bound), dim3(256), 0, st, ix->rows_ivf, ix->ivf_ids, ix->ivf_offsets,
                                                                      pair_start, item_start, sorted_pairs, nlist, nprobe, ix->dpad, ix->qn, k, row_base,
-                                                                     ix->ivf_partial, deny);
+                                                                     ix->ivf_partial, deny_lists);
         });
         if (rc != 0) return rc;
         HIP_TRY(hipGetLastError());
         }
         const int64_t ms = (int64_t)nprobe * k;
-        return launch_merge_of(ix, ix->ivf_partial, B, ms, k, (u64*)dev_keys, dev_dist, dev_rows, st);
+        return delta_then_merge(ms, nprobe);
     }
     // 2. scan the probed lists; split each list over several blocks when the batch alone cannot fill the chip
     int split = (int)((4 * (int64_t)ix->num_cus + (int64_t)B * nprobe - 1) / ((int64_t)B * nprobe));
     split = split < 1 ? 1 : (split > 16 ? 16 : split);
     const int64_t m = (int64_t)nprobe * split * k;
-    HIP_TRY(ix->ivf_partial.ensure((int64_t)B * m));
+    HIP_TRY(ix->ivf_partial.ensure((npend > 0 ? 2 : 1) * (int64_t)B * m));
     const dim3 grid((unsigned)(nprobe * split), (unsigned)B), block(256);
     {
         EvScope ev(ix, EV_SCAN, st);
         rc = with_row_form(ix, k, "row too wide for the IVF scan%s", [&](auto dt, auto ni, auto sl) {
             return launch_by_metric<ivf_scan_sq<dt, ni, sl>, ivf_scan_kernel<dt, ni, sl>>(sq ? kMetricL2 : kMetricDot, grid, block, 0, st, ix->rows_ivf, ix->ivf_ids,
                                                                                           ix->ivf_offsets, ix->probe_keys, nprobe, split, ix->dpad, ix->qn, k, row_base,
-                                                                                          ix->ivf_partial, deny);
+                                                                                          ix->ivf_partial, deny_lists);
         });
     }
     if (rc != 0) return rc;
     HIP_TRY(hipGetLastError());
     // 3. top-k of the nprobe*split partial lists
-    return launch_merge_of(ix, ix->ivf_partial, B, m, k, (u64*)dev_keys, dev_dist, dev_rows, st);
+    return delta_then_merge(m, (int64_t)nprobe * split);
 }
 
 }  // namespace
@@ -2045,6 +2289,15 @@ int codd_knn_ivf_search(codd_knn_index* ix, const float* dev_queries, int B, int
     hipStream_t st = (hipStream_t)stream;
     WorkScope work(ix, st), work_coarse(ix->coarse, st);
     return ivf_search_body(ix, dev_queries, B, k, nprobe, row_base, dev_keys, dev_dist, dev_rows, st, ix->dead_bits);
+}
+
+int codd_knn_ivf_refresh(codd_knn_index* ix, void* stream) {
+    if (!ix) return fail(CODD_KNN_EINVAL, "null index%s");
+    if (!ix->ivf_follow) return fail(CODD_KNN_EINVAL, "ivf_refresh: option \"ivf_follow\" is off%s");
+    if (!ivf_layout_fresh(ix)) return fail(CODD_KNN_EINVAL, "ivf_refresh: no IVF layout, or rows changed since codd_knn_ivf_install%s");
+    if (ix->pend.count == 0) return CODD_KNN_OK;   // nothing pending: nothing enqueued
+    DeviceGuard guard(ix->device);
+    return ivf_fold(ix, (hipStream_t)stream);
 }
 
 int codd_knn_set_scopes_host(codd_knn_index* ix, const int64_t* host_slots, const uint32_t* host_scopes, int64_t n) {
@@ -2910,6 +3163,17 @@ int codd_knn_set_option(codd_knn_index* ix, const char* key, int64_t value) {
     if (strcmp(key, "filter_min_rows") == 0) { ix->knobs.filter_min_rows = value < 1 ? 1 : value; return CODD_KNN_OK; }
     if (strcmp(key, "filter_min_rows_small") == 0) { ix->knobs.filter_min_rows_small = value < 1 ? 1 : value; return CODD_KNN_OK; }
     if (strcmp(key, "filter_min_batch") == 0) { ix->knobs.filter_min_batch = value < 1 ? 1 : (int)value; return CODD_KNN_OK; }
+    // an IVF layout that follows writes (plain integers in a range, checked here like the cascade's: kKnobTable's length is pinned)
+    if (strcmp(key, "ivf_follow") == 0) {
+        if (value < 0 || value > 1) return fail(CODD_KNN_EINVAL, "ivf_follow must be 0 or 1%s");
+        ix->ivf_follow = (int)value;
+        return CODD_KNN_OK;
+    }
+    if (strcmp(key, "ivf_fold_rows") == 0) {
+        if (value < 0 || value > (1ll << 32)) return fail(CODD_KNN_EINVAL, "ivf_fold_rows must be in [0,2^32]%s");
+        ix->ivf_fold_rows = value;
+        return CODD_KNN_OK;
+    }
     // the sample cascade (search_plan.h: cascade_plan)
     if (strcmp(key, "sample_cascade") == 0) {
         if (value < 0 || value > 2) return fail(CODD_KNN_EINVAL, "sample_cascade must be 0, 1 or 2%s");
@@ -3015,6 +3279,10 @@ int codd_knn_get_stat(const codd_knn_index* ix, const char* key, int64_t* out) {
         {"last_finalize_parts", &codd_knn_index::stat_last_finalize_parts},
         {"ivf_shared_searches", &codd_knn_index::stat_ivf_shared},
         {"ivf_masked_searches", &codd_knn_index::stat_ivf_masked},
+        {"ivf_refreshes", &codd_knn_index::stat_ivf_refreshes},
+        {"ivf_delta_searches", &codd_knn_index::stat_ivf_delta},
+        {"ivf_fold_rows", &codd_knn_index::ivf_fold_rows},
+        {"ivf_rows", &codd_knn_index::ivf_count},
         {"scoped_searches", &codd_knn_index::stat_scoped_searches},
         {"scope_builds", &codd_knn_index::stat_scope_builds},
         {"masked_searches", &codd_knn_index::stat_masked_searches},
@@ -3063,6 +3331,9 @@ int codd_knn_get_stat(const codd_knn_index* ix, const char* key, int64_t* out) {
     else if (strcmp(key, "metric") == 0) *out = ix->metric;
     else if (strcmp(key, "space_filter") == 0) *out = ix->knobs.space_filter;
     else if (strcmp(key, "space_ivf") == 0) *out = ix->knobs.space_ivf;
+    else if (strcmp(key, "ivf_follow") == 0) *out = ix->ivf_follow;
+    else if (strcmp(key, "ivf_pending_rows") == 0) *out = ix->pend.count;
+    else if (strcmp(key, "ivf_fold_threshold") == 0) *out = ix->coarse ? fold_threshold(ix->ivf_fold_rows, ix->ivf_count, ix->ivf_nlist) : 0;
     else if (strcmp(key, "shadow8_cooldowns") == 0) *out = ix->watch.stat_cooldowns;
     else if (strcmp(key, "shadow8_wide_blocks") == 0) {  // blocks whose error norm exceeds shadow8_max_eps, as last read back
         if (ix->eps_r_copied && hipEventQuery(ix->eps_r_copied) == hipSuccess) *out = (int64_t)reinterpret_cast<const unsigned*>(ix->eps_r_host.get())[1];

@@ -11,6 +11,9 @@ mean of its members, and every assignment is the exact search of a centroid inde
 distance for l2 — Lloyd's algorithm — and largest inner product for ip, the usual inner-product IVF).
 Search: `codd_knn_ivf_search` (HIP): exact top-nprobe lists per query, canonical exact scores over
 those lists, original row slots; `nprobe == nlist` reproduces the flat search bit for bit.
+Writes: by default any upsert makes the layout stale and `build_ivf` is the remedy.  With `follow_writes(index)` (engine option
+"ivf_follow") written rows are pending instead — every IVF search scores them exactly from the row store beside the
+probed lists — until `refresh_ivf(index)`, or a write that crosses "ivf_fold_rows", folds them into their lists on the device.
 
 The reference has no counterpart (ChromaDB answers with HNSW, store.py:63-68); results are
 approximate by design and reported as recall@k against this engine's exact search.
@@ -54,15 +57,35 @@ def _assign_exact(torch, centroid_index: DeviceKnnIndex, vecs) -> "torch.Tensor"
     return out
 
 
+def follow_writes(index: DeviceKnnIndex, on: bool = True, fold_rows: Optional[int] = None) -> None:
+    """Let an installed layout follow writes: with `on`, rows written by upsert, upsert_device and load_rows are
+    pending — scanned exactly from the row store by every IVF search — until a fold puts them into their lists.  fold_rows: a
+    write folds when more rows than this are pending (None leaves the option alone; 0 = one mean list, the default).  With
+    `on` False the next write makes the layout stale again, and so do rows that are still pending."""
+    index.set_option("ivf_follow", 1 if on else 0)
+    if fold_rows is not None:
+        index.set_option("ivf_fold_rows", int(fold_rows))
+
+
+def refresh_ivf(index: DeviceKnnIndex) -> None:
+    """Fold the pending rows into the layout now (codd_knn_ivf_refresh): each is assigned the list of its best centroid by the
+    coarse index's exact search, the others keep theirs, and the layout is rebuilt on the device.  Centroids stay as they are."""
+    index.ivf_refresh()
+
+
 def build_ivf(index: DeviceKnnIndex, nlist: int, iters: int = 8, sample: Optional[int] = None, seed: int = 7,
-              chunk_rows: int = 262_144) -> dict:
+              chunk_rows: int = 262_144, follow_writes: bool = False) -> dict:
     """Cluster the stored rows into `nlist` lists and install the layout on `index`.
 
     sample: rows used for training (default min(count, 64 * nlist)).  Returns list-size statistics.
+    follow_writes: switch option "ivf_follow" on before the install, so that the layout survives later upserts (see
+    follow_writes() above; off by default, and False leaves the option as it is).
     """
     import torch
 
     _require_cosine(index)
+    if follow_writes:
+        index.set_option("ivf_follow", 1)
     lib = native.load()
     n, dim, dev = index.count(), index.dim, index.device
     if n < nlist:

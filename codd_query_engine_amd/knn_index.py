@@ -448,6 +448,12 @@ class DeviceKnnIndex:
         """ivf.search_ivf_keys among the rows the device mask names."""
         return self._ivf_search_masked(queries, allow_bits, k, nprobe, row_base, True, True)[0]
 
+    def ivf_refresh(self) -> None:
+        """Fold the pending rows of an IVF layout that follows writes (option "ivf_follow", ivf.follow_writes) into the layout:
+        codd_knn_ivf_refresh on the current stream.  A no-op with nothing pending; NativeLibraryError with the option off, or
+        with no layout or a stale one."""
+        native.check(self._lib.codd_knn_ivf_refresh(self._h, self._stream()), "codd_knn_ivf_refresh")
+
     def slice_mask(self, global_bits, global_rows: int, row_base: int):
         """This shard's words of a mask over GLOBAL rows: bit r of the result = global bit row_base + r, for r < count()."""
         return slice_mask(global_bits, global_rows, row_base, self.count(), self.device)

@@ -227,7 +227,8 @@ int codd_knn_filter_slack(codd_knn_index* index, const float* dev_queries, int B
  *   dev_centroids [nlist][dim] fp32, dev_perm [count] (row slots grouped by list),
  *   dev_offsets [nlist+1] (list l = perm[offsets[l] .. offsets[l+1])).
  * install copies the rows into list order (HBM: one more copy of the rows) and builds the coarse
- * index; any later upsert makes the layout stale (ivf_search then fails with EINVAL).
+ * index; any later upsert makes the layout stale (ivf_search then fails with EINVAL) — except on an
+ * index whose option "ivf_follow" is 1, see codd_knn_ivf_refresh below.
  * ivf_search: nprobe (<= 128) best lists per query by exact centroid score, canonical exact scores
  * over those lists, top-k with ORIGINAL row slots; with nprobe == nlist the result is bit-identical
  * to codd_knn_search.  Any of dev_keys / dev_dist / dev_rows may be NULL.
@@ -249,6 +250,33 @@ int codd_knn_ivf_install(codd_knn_index* index, const float* dev_centroids, int 
 int codd_knn_ivf_search(codd_knn_index* index, const float* dev_queries, int B, int k, int nprobe,
                         uint32_t row_base, uint64_t* dev_keys, float* dev_dist, int64_t* dev_rows,
                         void* stream);
+
+/*
+ * An IVF layout that follows writes (opt-in, option "ivf_follow" = 1, default 0: nothing changes).
+ * With the option on, an installed layout stays searchable across codd_knn_upsert_host, _upsert_device and _load_rows:
+ * every slot such a call writes, and every slot that comes into existence below a write that starts above the count,
+ * is marked PENDING (a device bitmap with a host mirror, and a device list of the distinct pending slots; a slot
+ * written twice is pending once).  The layout's own copy of a pending row is stale from then on.  All four IVF
+ * entry points then scan the probed lists under deny | pending and score every pending slot from the main row store
+ * with the canonical exact score under the call's own deny bits (tombstones, or ~allow | dead), one merge over both.
+ * The contract is the IVF contract word for word with the pending rows counting as a list every query probes: the exact
+ * canonical top-k among the allowed live rows of {rows of the probed lists that are not pending} U {pending rows};
+ * nprobe >= nlist is codd_knn_search bit for bit.  Probe selection is unchanged, the device-mask form stays free of
+ * host synchronisation, and with nothing pending a search enqueues exactly what it enqueues with the option off.
+ * codd_knn_delete_host is followed as it always was (tombstones by original slot); codd_knn_compact still makes the
+ * layout stale, and so do rows left pending when the option is switched off.
+ * ivf_refresh: the FOLD.  Every pending slot is assigned its list — the top-1 of the coarse index's exact scan with the
+ *           STORED row, widened to fp32, as the query: largest canonical dot product (cosine, ip), smallest canonical
+ *           squared distance (l2), ties to the lower list — rows that are not pending keep theirs, and the layout is rebuilt
+ *           on the device from the main row store (count per list, 64-bit prefix sums, scatter, gather); centroids and the
+ *           coarse index are untouched.  Appended rows join the layout here; afterwards nothing is pending.  Asynchronous on
+ *           `stream` and ordered like an upsert: searches enqueued earlier on any stream finish before the layout is replaced,
+ *           later ones wait for it; nothing is read back (it blocks only where appended rows make the layout's buffers grow).
+ *           Nothing pending: a no-op, nothing enqueued.  Option "ivf_follow" off, no layout or a stale one: EINVAL, nothing
+ *           enqueued.  A search never folds; a write folds before it returns when more rows are pending than option
+ *           "ivf_fold_rows" allows (0, the default: one mean list, ceil(rows of the layout / nlist)).
+ */
+int codd_knn_ivf_refresh(codd_knn_index* index, void* stream);
 
 /*
  * Replaces: the `where={"namespace": ...}` of collection.query(query_texts=..., n_results=..., where=...) — the metadata
@@ -579,6 +607,9 @@ int codd_knn_eval_where(codd_knn_index* index, const codd_knn_where_program* pro
  *            DESIGN.md §21),
  *            "space_ivf" (0; 1: codd_knn_ivf_install and the IVF searches accept an ip or l2 index — raw centroids, a coarse index
  *            and list scans in the index's own space; 0: they return ENOTSUP there; no effect on a cosine index),
+ *            "ivf_follow" (0; 1: an installed IVF layout follows upsert_host, upsert_device and load_rows — written rows are pending
+ *            until a fold, see codd_knn_ivf_refresh), "ivf_fold_rows" (0; a write folds when more rows than this are
+ *            pending; 0 = one mean list of the layout; at most 2^32),
  *            "debug_fail_shadow_alloc" (tests; a switch, not a count: while it is non-zero every allocation of the 2-byte shadow fails as
  *            if HBM were full; 0 switches it off and lets the next search try again);
  *            "profile" = N keeps N (start, stop) HIP-event pairs, one per heavy-kernel launch,
@@ -586,7 +617,10 @@ int codd_knn_eval_where(codd_knn_index* index, const codd_knn_where_program* pro
  *   stats  : "searches", "scan_launches", "last_scan_blocks", "last_scan_group" (queries per pass over the rows of the
  *            last exact scan), "last_finalize_parts" (workgroups per query of the last filter pass's finalize),
  *            "ivf_shared_searches" (IVF searches that scanned each probed list once for all its queries), "ivf_masked_searches" (IVF searches
- *            under a row mask, host or device words), "scoped_searches",
+ *            under a row mask, host or device words), "ivf_pending_rows" (distinct row slots pending under a layout that follows
+ *            writes), "ivf_refreshes" (folds, by codd_knn_ivf_refresh or by a write), "ivf_delta_searches" (IVF searches that ran a
+ *            delta scan over pending rows), "ivf_rows" (rows the layout holds), "ivf_fold_threshold" (pending rows above which a write
+ *            folds), "ivf_follow", "ivf_fold_rows" (the options), "scoped_searches",
  *            "scope_builds" (times the scope lists were rebuilt), "scopes" (highest scope label ever set), "dead_rows" (tombstones below count),
  *            "delete_calls", "compactions" (codd_knn_compact calls that moved rows), "masked_searches", "mask_list_searches",
  *            "mask_dense_searches" (masked searches by route), "last_mask_rows" (allowed live rows of the last masked search),
