@@ -162,6 +162,7 @@ struct codd_knn_index : WorkBufs {
     int64_t shadow_nomem_epoch = -1;   // row epoch at which allocating the bf16 shadow failed: not retried until rows change
     int64_t stat_shadow_nomem = 0;
     int debug_fail_shadow_alloc = 0;   // test hook ("debug_fail_shadow_alloc"): the next bf16-shadow allocation reports out of memory
+    int debug_num_cus = 0;             // test hook ("debug_num_cus"): > 0 = the filter passes plan and launch as if the device had this many compute units
     // stored rows written on a caller's stream (upsert_device): searches on other streams wait for this on the device
     Event rows_ready;
     hipStream_t rows_stream = nullptr;
@@ -287,6 +288,7 @@ struct codd_knn_index : WorkBufs {
     int64_t stat_ivf_shared = 0;            // IVF searches that scanned each probed list once for all its queries (ivf_scan_shared_kernel)
     int64_t stat_ivf_masked = 0;            // IVF searches under a row mask (codd_knn_ivf_search_masked, _masked_dev: DESIGN.md §17)
     int64_t stat_filter_passes = 0;
+    int64_t stat_sweep_passes = 0, stat_last_sweep = 0;   // filter passes whose filter launches ran i8_sweep_kernel, and whether the last pass was one
     int64_t stat_cascade_passes = 0, stat_last_cascade_d = 0;   // filter passes that took the sample cascade, and the d of the last pass (0: none)
 
     // optional HIP-event timing of the heavy kernels (bench.py's roofline figure): one (start, stop)
@@ -1012,6 +1014,13 @@ int launch_filter_program(const FilterProgram& p, dim3 grid, hipStream_t st, con
                 // (the sample pass keeps the generic program: its tile-structured instantiations — the static six-step one too, tried in round 3 —
                 //  spill inside the loop: the fold's registers on top of two corpus ring slots in flight)
                 return p.res ? tile(IntC<0>{}, nqb, Yes{}, No{}) : tile(IntC<0>{}, nqb, No{}, No{});
+            } else if (p.sweep) {  // (filter_program: ts = 3, 16 query blocks of 16, staged)
+                if constexpr (decltype(nqb)::value == 16) {
+                    return launch_kernel<i8_sweep_kernel<16>>(grid, block, i8_lds_bytes(MODE), st, a.shadow, a.qfrag, a.n, a.nsteps, a.ntiles_run, a.tile_stride, a.thr,
+                                                              a.bucket_key, a.hits, a.hit_cnt, a.cap_q, a.flags, a.rscale, a.qscale, a.bmeta, a.eb_scale, a.skip_d);
+                } else {
+                    return fail(CODD_KNN_EINVAL, "bad tile program%s");
+                }
             } else if (p.res) {  // (the pair programs stage the query block)
                 return with_int<0, 1>(p.ts, "bad tile program%s", [&](auto ts) { return tile(ts, nqb, Yes{}, No{}); });
             } else {
@@ -1087,7 +1096,10 @@ int listed_fallback(codd_knn_index* ix, const float* qn, int k, uint32_t row_bas
 int filter_pass(codd_knn_index* ix, const float* qn, int nq, int k, uint32_t row_base, u64* keys_out, float* dist_out, int64_t* rows_out,
                 hipStream_t st, const uint32_t* deny, bool prepared = false, bool use8 = false) {
     const int64_t n = ix->count;
-    const IndexShape shape = shape_of(ix);
+    IndexShape shape = shape_of(ix);
+    // ("debug_num_cus": the pass's plan and its sample and filter launches count this many compute units — a small corpus then gives a workgroup several tiles)
+    const int num_cus = ix->debug_num_cus > 0 ? ix->debug_num_cus : ix->num_cus;
+    shape.num_cus = num_cus;
     const FilterKnobs& knobs = ix->knobs;
     const int nsteps = use8 ? dpad8_of(shape) / 128 : ix->dpad / 64;
     const uint4* shadow = use8 ? ix->shadow8 : ix->shadow;
@@ -1118,6 +1130,8 @@ int filter_pass(codd_knn_index* ix, const float* qn, int nq, int k, uint32_t row
     const int64_t ts = cas.on ? cas.a0_tiles : ts_plain;
     const int64_t stride = cas.on ? cas.a0_stride : ntiles / ts;
     ix->stat_last_cascade_d = cas.on ? cas.d : 0;
+    ix->stat_last_sweep = prog.sweep ? 1 : 0;
+    if (prog.sweep) ix->stat_sweep_passes++;
     if (cas.on) ix->stat_cascade_passes++;
     {
         LastPass& lp = ix->last;
@@ -1156,7 +1170,7 @@ int filter_pass(codd_knn_index* ix, const float* qn, int nq, int k, uint32_t row
         // (the cascade: one event pair from A0 to the re-anchor, everything that fixes the thresholds; else the sample launch alone, as ever)
         EvScope ev(ix, EV_SAMPLE, st);
         {
-            const dim3 g((unsigned)(ts < ix->num_cus ? ts : ix->num_cus));
+            const dim3 g((unsigned)(ts < num_cus ? ts : num_cus));
             FilterArgs sa{shadow + row0 * (dpad8_of(shape) / 16), qfrag, n - row0, nsteps, ts, stride, nullptr, ix->bucket_max, nullptr, nullptr, 0, nullptr,
                           rscale ? rscale + row0 : nullptr, qscale, nullptr, 1.0f};
             if (prog.sqd) { sa.rnorm2 = ix->rnorm2; sa.qn2 = ix->qmeta + 512; }
@@ -1180,7 +1194,7 @@ int filter_pass(codd_knn_index* ix, const float* qn, int nq, int k, uint32_t row
         HIP_TRY(hipGetLastError());
         if (cas.on) {
             // A1: the filter program over tiles 0, d + 1, ... with the provisional thresholds (timed with the sample: it is what fixes the thresholds)
-            if ((rc = filter_launch(cas.a1_tiles, cas.d + 1, cas.a1_tiles < ix->num_cus ? cas.a1_tiles : ix->num_cus, 0)) != 0) return rc;
+            if ((rc = filter_launch(cas.a1_tiles, cas.d + 1, cas.a1_tiles < num_cus ? cas.a1_tiles : num_cus, 0)) != 0) return rc;
             HIP_TRY(hipGetLastError());
             rc = with_row_form(ix, k, "row too wide for the threshold kernel%s", [&](auto dt, auto ni, auto sl) {
                 return launch_kernel<reanchor_thr_kernel<dt, ni, sl>>(dim3(nq), dim3(kAnchorWaves * kWave), 0, st, ix->bucket_max, ts, (unsigned)row0, ix->hits,
@@ -1194,7 +1208,7 @@ int filter_pass(codd_knn_index* ix, const float* qn, int nq, int k, uint32_t row
     {
         // the main launch: every tile, or (the cascade's launch B) every tile that is no multiple of d + 1, on a grid d divides
         EvScope ev(ix, EV_FILTER, st);
-        if ((rc = filter_launch(ntiles, 1, cas.on ? cas.G : (ntiles < ix->num_cus ? ntiles : ix->num_cus), cas.on ? cas.d : 0)) != 0) return rc;
+        if ((rc = filter_launch(ntiles, 1, cas.on ? cas.G : (ntiles < num_cus ? ntiles : num_cus), cas.on ? cas.d : 0)) != 0) return rc;
     }
     HIP_TRY(hipGetLastError());
     const int niter = niter_of(shape);
@@ -3185,6 +3199,11 @@ int codd_knn_set_option(codd_knn_index* ix, const char* key, int64_t value) {
         ix->knobs.cascade_d = (int)value;
         return CODD_KNN_OK;
     }
+    if (strcmp(key, "i8_sweep") == 0) {  // the sweep form of the static int8 tile program (search_plan.h: filter_program)
+        if (value < 0 || value > 1) return fail(CODD_KNN_EINVAL, "i8_sweep must be 0 or 1%s");
+        ix->knobs.i8_sweep = (int)value;
+        return CODD_KNN_OK;
+    }
     if (strcmp(key, "cascade_min_rounds") == 0) {
         if (value < 1 || value > 64) return fail(CODD_KNN_EINVAL, "cascade_min_rounds must be in [1,64]%s");
         ix->knobs.cascade_min_rounds = (int)value;
@@ -3200,6 +3219,11 @@ int codd_knn_set_option(codd_knn_index* ix, const char* key, int64_t value) {
     if (strcmp(key, "debug_fail_shadow_alloc") == 0) {  // test hook: the 2-byte shadow's allocation fails as if HBM were full
         ix->debug_fail_shadow_alloc = value != 0;
         if (!value) ix->shadow_nomem_epoch = -1;
+        return CODD_KNN_OK;
+    }
+    if (strcmp(key, "debug_num_cus") == 0) {  // test hook: the filter passes count this many compute units (0: the device's)
+        if (value < 0 || value > ix->num_cus) return fail(CODD_KNN_EINVAL, "debug_num_cus must be 0 or in [1, the device's compute units]%s");
+        ix->debug_num_cus = (int)value;
         return CODD_KNN_OK;
     }
     if (strcmp(key, "all_normalized") == 0) {
@@ -3299,6 +3323,8 @@ int codd_knn_get_stat(const codd_knn_index* ix, const char* key, int64_t* out) {
         {"filter_passes", &codd_knn_index::stat_filter_passes},
         {"cascade_passes", &codd_knn_index::stat_cascade_passes},
         {"last_cascade_d", &codd_knn_index::stat_last_cascade_d},
+        {"sweep_passes", &codd_knn_index::stat_sweep_passes},
+        {"last_sweep", &codd_knn_index::stat_last_sweep},
         {"shadow8_builds", &codd_knn_index::stat_shadow8_builds},
         {"shadow16_builds", &codd_knn_index::stat_shadow_builds},
         {"shadow16_alloc_failures", &codd_knn_index::stat_shadow_nomem},

@@ -59,6 +59,8 @@ struct FilterKnobs {
     int sample_cascade = 1;        // "sample_cascade": 0 = off, 1 = where today's sample has cascade_min_rounds rounds of workgroups, 2 = wherever it applies
     int cascade_d = 16;            // "cascade_d": the stage that fixes the thresholds scans every (d + 1)-th tile; d is the divisor of the grid in [16, 64] nearest this
     int cascade_min_rounds = 3;    // "cascade_min_rounds": the size rule of sample_cascade = 1 (3 rounds: from ~5M rows of 768 elements on 256 compute units)
+    // the sweep form of the static int8 tile program (checked by codd_knn_set_option like the cascade's)
+    int i8_sweep = 1;              // "i8_sweep": 1 = 129..256 queries on rows of exactly 6 K-steps run i8_sweep_kernel (two query slices staged per tile); 0 = i8_tile_kernel<., 3> (six)
 };
 
 // the options that are "an integer in [lo, hi], stored into one knob"; `message` is the whole fail() format of a value outside
@@ -161,7 +163,8 @@ inline int64_t sample_tile_count(const FilterKnobs& kn, const IndexShape& s, int
 //   GEMM      gemm_filter_kernel<MODE, nbq, el, res>: el = 1 int8 operands; res = 1 the whole int8 query block resident in LDS,
 //             res = 2 two of its six slices (768 elements, 4 query blocks)
 //   TILE      i8_tile_kernel<MODE, ts, 2 * nbq, res> (filter_i8.h: the int8 tile program, 16-query blocks; res: the query block
-//             resident in LDS); the sample pass runs ts = 0
+//             resident in LDS); the sample pass runs ts = 0.  sweep: the filter launches of ts = 3, nbq = 8 run i8_sweep_kernel<16>
+//             instead, the same program walking K back and forth
 //   TILE_F16  i8_tile_kernel<MODE_FILTER, ts, 16, false, true>: the same program on fp16 operands; the sample pass is GEMM's
 //             gemm_filter_kernel<MODE_SAMPLE, 8>
 struct FilterProgram {
@@ -170,6 +173,7 @@ struct FilterProgram {
     int nbq = 8;  // 32-query blocks the GEMM multiplies
     int ts = 0, res = 0, el = 0;
     bool sqd = false;  // sqd_filter_kernel<MODE, nbq>: the squared-distance epilogue of an l2 index
+    bool sweep = false;
 };
 
 inline FilterProgram filter_program(const FilterKnobs& kn, const IndexShape& s, int nq, int nsteps, bool use8) {
@@ -206,6 +210,7 @@ inline FilterProgram filter_program(const FilterKnobs& kn, const IndexShape& s, 
         else if (static6) p.ts = 3;
         else if (pair) p.ts = 2;
         else p.ts = nsteps % 3 == 0 ? 1 : 0;
+        p.sweep = p.ts == 3 && p.nbq == 8 && !p.res && kn.i8_sweep != 0;
     } else if (partial6) {  // 768 int8 elements: two of the six query slices stay in LDS
         p.res = 2;
     } else if (resident) {  // the whole int8 query block fits the LDS slices: loaded once per workgroup

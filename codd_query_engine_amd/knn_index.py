@@ -489,7 +489,7 @@ class DeviceKnnIndex:
 
     def last_pass(self, keys_per_query: int | None = None, want_bmeta: bool = True) -> dict:
         """What the last filter pass on this stream's workspace left behind (diagnostics; codd_knn_debug_last_pass): a dict of
-        the program and shape fields of codd_knn_last_pass ("family" as its name), "flags", "fb_count", and numpy arrays "thr" [256],
+        the program and shape fields of codd_knn_last_pass ("family" as its name), "flags", "fb_count", "sweep" (1: the index's last pass ran the sweep form of the static int8 tile program), and numpy arrays "thr" [256],
         "thr0" [256], "qmeta" [1024] (int8 passes, else None), "hit_counts" [256], "fb_list" [256], "keys" (a list of 256 u64
         arrays: each query's first min(counter, hit_cap, keys_per_query) candidate keys), "bucket_max" [256, sample_tiles] and
         "bmeta" [ceil(n / 32), 2] (int8 passes, else None).  keys_per_query: None = the largest list the pass left."""
@@ -513,6 +513,7 @@ class DeviceKnnIndex:
                      "codd_knn_debug_last_pass")
         out = {name: getattr(info, name) for name, _ in native.LastPassInfo._fields_ if name not in ("flags", "family")}
         out["family"] = native.FILTER_FAMILIES[info.family]
+        out["sweep"] = int(self.stat("last_sweep"))   # the filter launches ran i8_sweep_kernel (the index's last pass: the struct has no room for it)
         out["flags"] = list(info.flags)
         out.update(thr=thr[:256].copy(), thr0=thr[256:].copy(), qmeta=qmeta if info.el else None, hit_counts=counts, fb_list=fb_list,
                    keys=[keys[q, : kept[q]].copy() for q in range(256)], bucket_max=buckets, bmeta=bmeta[:nblocks] if nblocks else None)

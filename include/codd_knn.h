@@ -581,6 +581,9 @@ int codd_knn_eval_where(codd_knn_index* index, const codd_knn_where_program* pro
  *            compute units in [16,64] nearest this value; no such divisor: no cascade), "cascade_min_rounds" (3, in [1,64]: the size
  *            rule of "sample_cascade" = 1; both are measured settings, profiles/cascade/README.md; the first sample takes at most
  *            "sample_tiles" tiles like the plain one),
+ *            "i8_sweep" (1: a filter pass of 129..256 queries over rows of 768 int8 elements runs the static tile program in its sweep
+ *            form — tiles of odd ordinal walk the K-steps the other way round, so a tile stages two query slices instead of six; same
+ *            candidates, same ids and distance bits; 0: i8_tile_kernel's static program),
  *            "resident_q" (1: rows of <= 512 int8 elements keep the query block in LDS for the
  *            whole launch), "i8v2" (2: batches of 65..256 queries on rows of 384 or
  *            more elements take the second-generation int8 kernel, csrc/filter_i8.h; 1: only rows of
@@ -611,7 +614,10 @@ int codd_knn_eval_where(codd_knn_index* index, const codd_knn_where_program* pro
  *            until a fold, see codd_knn_ivf_refresh), "ivf_fold_rows" (0; a write folds when more rows than this are
  *            pending; 0 = one mean list of the layout; at most 2^32),
  *            "debug_fail_shadow_alloc" (tests; a switch, not a count: while it is non-zero every allocation of the 2-byte shadow fails as
- *            if HBM were full; 0 switches it off and lets the next search try again);
+ *            if HBM were full; 0 switches it off and lets the next search try again),
+ *            "debug_num_cus" (tests; 0: off; N in [1, the device's compute units]: the filter passes plan and launch their sample and
+ *            filter programs as if the device had N compute units, so that a small corpus gives a workgroup several tiles; the answer
+ *            never depends on it);
  *            "profile" = N keeps N (start, stop) HIP-event pairs, one per heavy-kernel launch,
  *            recorded on the launch stream (0 = off; resets the log)
  *   stats  : "searches", "scan_launches", "last_scan_blocks", "last_scan_group" (queries per pass over the rows of the
@@ -632,7 +638,8 @@ int codd_knn_eval_where(codd_knn_index* index, const codd_knn_where_program* pro
  *            launched), "doc_regex_tile_bytes" (arena bytes per segment of doc_regex_kernel), "doc_regex_run_docs" (documents per
  *            workgroup of it), "where_evals" (codd_knn_eval_where calls that launched), "where_columns" (columns set), "where_column_bytes"
  *            (their device bytes: 9 per row slot of the capacity and column), "filter_passes", "cascade_passes" (the filter passes among them that took the sample cascade), "last_cascade_d"
- *            (the d of the last filter pass's cascade, 0: it took none),
+ *            (the d of the last filter pass's cascade, 0: it took none), "sweep_passes" (the filter passes whose filter launches ran
+ *            i8_sweep_kernel), "last_sweep" (1: the last filter pass was one of them; family TILE and ts 3 either way),
  *            "fallback_queries", "filter_hits", "filter_survivors", "capacity_rows",
  *            "device_bytes", "num_cus", "workspaces" (stream workspaces in use), "shadow8_builds", "shadow8_passes", "i8v2_passes",
  *            "shadow16_builds" (the 2-byte (fp16) shadow is built lazily, by the first search that needs it), "all_normalized",
@@ -672,7 +679,7 @@ int codd_knn_debug_live_allocations(int64_t* buffers, int64_t* bytes, int64_t* e
  *   bmeta       [min(bmeta_blocks, ceil(n / 32))][2]  int8 passes only: {scale, error norm} of the index's 32-row blocks as they are now
  */
 typedef struct codd_knn_last_pass {
-    int32_t family;             /* 0 GEMM (gemm_filter_kernel, sqd_filter_kernel), 1 TILE (i8_tile_kernel), 2 TILE_F16 */
+    int32_t family;             /* 0 GEMM (gemm_filter_kernel, sqd_filter_kernel), 1 TILE (i8_tile_kernel, i8_sweep_kernel), 2 TILE_F16 */
     int32_t nbq, ts, res, el, sqd;
     int32_t nq, k;
     int32_t hit_cap;
